@@ -9,7 +9,10 @@ hot lines of /root/reference/src/train.py:86-105 — on configs[1] of BASELINE.j
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP event pairs attached to every conv / wgrad
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline figures (`value`,
+`ms_per_step`, `loss`); `--dump-outputs DIR` also writes what the last timed step computed (dump_outputs).  `--full` adds the
+secondary measurements and checks below: the data-parallel self-validation (`ddp_check`), `roofline` / `kernels`, the serial
+steps, `alt_modes` and `cpu_baseline`.  `roofline` is measured live with HIP event pairs attached to every conv / wgrad
 dispatch (hipExtLaunchKernelGGL, on the stream the kernel is launched on) during the timed region (uwm_prof_*);
 `roofline.frac` is ALGORITHMIC conv FLOP/s of the dominant kernel class over the dense peak of the matrix instruction it
 issues (`roofline.mfma_util` = the FLOPs the pipe executed, 3x for the fp16x3 split products); `cpu_baseline` times
@@ -195,6 +198,30 @@ def collect_prof(L, steps):
     return ents
 
 
+DUMP_SAMPLE = 1 << 22      # floats per dumped array at most: params + grads samples = 32 MB, under the 64 MB a dump may take
+
+
+def dump_outputs(path, model, loss):
+    """--dump-outputs: what the timed train step hands its caller after the LAST timed step, as .npy files in `path`:
+    loss.npy (float64: total, dice, bce of that step), params.npy / grads.npy (float32: every parameter after the optimizer
+    step / its gradient, each flattened in torch (N,C,H,W) order, concatenated in the library's parameter order) and
+    bn_stats.npy (float32: every BatchNorm running_mean / running_var, concatenated).  An array longer than DUMP_SAMPLE is
+    replaced by a fixed sample: the elements at a seeded set of indices, ascending, the same for the same arguments."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    g = model.flat_grads()
+    views = [(model.flat_parameters().as_strided(shape, stride, off), g.as_strided(shape, stride, off)) for off, shape, stride in model._pinfo]
+    arrays = {"params": torch.cat([p.reshape(-1) for p, _ in views]), "grads": torch.cat([q.reshape(-1) for _, q in views]),
+              "bn_stats": torch.cat([b.reshape(-1) for n_, b in model.named_buffers() if n_.endswith(("running_mean", "running_var"))])}
+    for name, a in arrays.items():
+        if a.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(1234))[:DUMP_SAMPLE].sort().values
+            a = a[idx.to(a.device)]
+        np.save(os.path.join(path, name + ".npy"), a.detach().float().cpu().numpy())
+    np.save(os.path.join(path, "loss.npy"), loss.detach().double().cpu().numpy())
+
+
 def ddp_verdict(local, real_step, stages, world, rank, dev):
     """The collective half of validate_ddp, free of the model so that tests/test_ddp_gloo.py can drive it over gloo with fabricated
     arenas at world 8: `local` = this rank's local gradient arena; `real_step()` runs the step under test and returns (exchanged
@@ -329,6 +356,13 @@ def main():
     ap.add_argument("--serial-steps", type=int, default=3,
                     help="extra UNTIMED steps after the timed region with the wgrad side stream off, to report the "
                          "dominant kernel alone next to its in-step (co-resident) figure (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements and checks: ddp_check, the profiled steps (roofline / kernels), the serial "
+                         "steps, alt_modes and cpu_baseline (the --no-ddp-check / --prof-steps / --serial-steps / --alt-steps / "
+                         "--no-cpu-baseline options tune them).  Without it only the headline steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, parameters, gradients, BatchNorm "
+                         "statistics) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     import torch
@@ -384,14 +418,14 @@ def main():
         torch.cuda.synchronize(dev)
 
     ddp_check = None
-    if (world > 1 or force_ddp) and trainer.ddp and not args.no_ddp_check:
+    if args.full and (world > 1 or force_ddp) and trainer.ddp and not args.no_ddp_check:
         ddp_check = validate_ddp(trainer, model, x, t, world, rank, dev)        # exits non-zero on every rank if it fails
     for _ in range(args.warmup):
         loss = trainer.step(x, t)
     barrier()
     # profiled launches go through hipExtLaunchKernelGGL with an event pair each (a little host work per launch), so only
     # the LAST `prof_steps` steps of the timed region carry them; `kernels` / `roofline` come from those
-    prof_steps = min(args.prof_steps, args.steps)
+    prof_steps = min(args.prof_steps, args.steps) if args.full else 0
     t0 = time.perf_counter()
     for i in range(args.steps):
         if i == args.steps - prof_steps:
@@ -401,12 +435,14 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     L.lib().uwm_prof_enable(0)
-    ents = collect_prof(L, prof_steps)
+    ents = collect_prof(L, prof_steps) if prof_steps > 0 else {}
     loss_val = float(loss[0].item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)
     # kernel routing of the benched step (one extra UNTIMED step with the library's routing record on): the parity sample of
     # cpu_baseline must take the same kernels layer by layer
     routing_ref = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         model.routing(enable=True)
         ug = trainer.use_graph
         trainer.use_graph = False
@@ -416,7 +452,7 @@ def main():
         model.routing(enable=False)
     # the dominant kernel ALONE (not part of `value`): the same step with the wgrad side stream switched off
     ents_s = None
-    if args.serial_steps > 0 and rank == 0 and world == 1:
+    if args.full and args.serial_steps > 0 and rank == 0 and world == 1:
         L.lib().uwm_set_side_stream(model._h, 0)
         trainer.step(x, t); torch.cuda.synchronize(dev)
         L.lib().uwm_prof_enable(1)
@@ -429,7 +465,7 @@ def main():
 
     # the other precision modes (NOT part of `value`): the same step with uwm_set_precision(...)
     alt_modes = None
-    if args.alt_steps > 0 and rank == 0 and world == 1:
+    if args.full and args.alt_steps > 0 and rank == 0 and world == 1:
         alt_modes = {}
         for mode in [m_ for m_ in ("f32", "f16x3_all", "bf16x3", "f16x3_bwd2", "f16x1") if m_ != args.precision]:
             model.set_precision(mode)
@@ -563,7 +599,7 @@ def main():
             out["kernels"] = [{k: v for k, v in e.items() if not k.startswith("_")} for e in kernels]
         if alt_modes is not None:
             out["alt_modes"] = alt_modes
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.encoder, s, arch=args.arch, batch=n, decoder_channels=dec, precision=args.precision,
                                                routing_ref=routing_ref)
             if alt_modes is not None:

@@ -167,10 +167,12 @@ def test_config_yaml_and_checkpoint_roundtrip(U, tmp_path):
     assert load_checkpoint(str(tmp_path / "bare.pth"), m2)["epoch"] == 0
 
 
-def test_cli_parses_reference_flags(U):
+def test_cli_parses_reference_flags(U, monkeypatch):
     from unet_watermark_amd import cli
     import pytest as _pt
-    with _pt.raises(SystemExit):
+    # the flags parse, then the command fails loudly without a GPU: the device is hidden so that this holds on a GPU machine too
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    with _pt.raises(SystemExit, match="needs a HIP device"):
         cli.main(["train", "--epochs", "1", "--batch-size", "2", "--lr", "0.001", "--no-early-stopping", "--synthetic", "8"])
 
 

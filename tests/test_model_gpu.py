@@ -750,7 +750,7 @@ def test_bench_ddp_path_single_rank_rccl(cuda):
     backward) run through torch.distributed.run with ONE rank: same loss as the plain single-GPU step."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--steps", "3", "--warmup", "1", "--batch", "2", "--size", "128", "--encoder", "resnet18", "--no-cpu-baseline"]
+    common = ["--steps", "3", "--warmup", "1", "--batch", "2", "--size", "128", "--encoder", "resnet18", "--no-cpu-baseline", "--full"]
     env = dict(os.environ, UWM_FORCE_DDP="1")
     ddp = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", "29611", os.path.join(root, "bench.py"), "--gpus", "1"] + common,
@@ -769,6 +769,32 @@ def test_bench_ddp_path_single_rank_rccl(cuda):
     bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2"] + common, capture_output=True, text=True, timeout=600)
     assert bad.returncode != 0 and "WORLD_SIZE" in bad.stderr          # --gpus N without N ranks fails loudly
     assert abs(a["loss"] - b["loss"]) < 1e-4 and a["value"] > 0
+
+
+def test_bench_plain_run_dumps_last_step(cuda, tmp_path):
+    """A plain bench run (no --full) times the steps and nothing else; --dump-outputs writes the last timed step's loss, parameters,
+    gradients and BatchNorm statistics as float .npy files (under 64 MB), and the same arguments give the same loss."""
+    import json, os, subprocess, sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2", "--size", "128",
+           "--encoder", "resnet18", "--dump-outputs"]
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run(cmd + [str(tmp_path / d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    j = lines[0]
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0 and j["roofline"] is None and j["ddp_check"] is None
+    assert "cpu_baseline" not in j and "alt_modes" not in j and "kernels" not in j
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["bn_stats.npy", "grads.npy", "loss.npy", "params.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    out = {f[:-len(".npy")]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in out.values())
+    assert out["loss"].shape == (3,) and abs(float(out["loss"][0]) - j["loss"]) < 1e-6
+    assert np.abs(out["grads"]).max() > 0 and out["params"].shape == out["grads"].shape
+    assert abs(lines[1]["loss"] - j["loss"]) < 1e-6 and np.allclose(np.load(tmp_path / "b" / "params.npy"), out["params"], rtol=0, atol=1e-6)
 
 
 @pytest.mark.parametrize("arch,enc,n,h,w,train", [
