@@ -306,6 +306,14 @@ int  uwm_op_maxpool_backward(const float* gout, const uint8_t* idx, const float*
  * dy = gamma*rstd*(g - mean(g) - yhat*mean(g*yhat)), dgamma = sum g*yhat, dbeta = sum g */
 int  uwm_op_bn_backward(const float* g, const float* y, const float* mean, const float* rstd, const float* gamma,
                         double* scratch2c, float* dy, float* dgamma, float* dbeta, long long npix, int C, uwm_stream stream);
+/* BatchNorm backward behind swish [and the squeeze-and-excitation product] (EfficientNet MBConv): y = BN input [N][hw][C],
+ * scale / shift = gamma*rstd / beta - mean*gamma*rstd (the forward's swish(y*scale + shift)); g = grad wrt the swish output or,
+ * with se_s / gpool ([N][C] each, both or neither), wrt swish(.) * se_s, the pooled branch contributing gpool / hw.
+ * Writes dy = grad wrt y, dgamma, dbeta; scratch2c: 2*C doubles; xmax (optional, 32 floats): max over its slots = max|dy|, the
+ * value the fp16x3 dgrad / wgrad that reads dy scales by */
+int  uwm_op_bn_backward_act(const float* g, const float* y, const float* mean, const float* rstd, const float* gamma,
+                            const float* scale, const float* shift, const float* se_s, const float* gpool, int N, long long hw,
+                            int C, double* scratch2c, float* dy, float* dgamma, float* dbeta, float* xmax, uwm_stream stream);
 /* gradient of cat(nearest_x2(prev), skip): gprev[N][H/2][W/2][C0] = mask(sum 2x2 dcat[..., :C0]), gskip = dcat[..., C0:] */
 /* decoder block conv1 dgrad with the concat split fused (Winograd epilogue): gprev [N][H/2][W/2][C0] = ReLU-masked
  * 2x2 sums of the first C0 gradient channels, gskip [N][H][W][C1] the rest; wd = uwm_op_pack_dgrad output */

@@ -27,7 +27,8 @@ def _grad_check(model, ref, l2_rel=3e-2, cos_min=0.9995):
     Dice gradient, amplifying fp32 rounding to ~1-2e-3 relative L2 everywhere upstream of the first
     BatchNorm; (b) a ReLU mask flips where a pre-activation is within rounding of 0 — ONE flip in a
     layer4 feature map moves every upstream gradient by ~1e-2.  Each backward kernel is exact (1e-6)
-    given its inputs: tests/test_ops_gpu.py and tests/test_backward_steps_gpu.py.  So the end-to-end
+    given its inputs: tests/test_ops_gpu.py; the whole backward's range scaling (fp16x3 max|dY| producers and
+    consumers) at tiny and huge gradients: tests/test_grad_scale_gpu.py.  So the end-to-end
     bar is cosine >= 0.9995 and relative L2 <= 3e-2 per tensor."""
     gref = dict(ref.named_parameters())
     for n, p in model.named_parameters():

@@ -749,6 +749,55 @@ def test_bn_backward_matches_autograd(cuda, c, n, h, w):
     assert torch.allclose(dbet.cpu(), beta.grad.float(), rtol=1e-5, atol=1e-5 * float(beta.grad.abs().max()))
 
 
+@pytest.mark.parametrize("se", [False, True], ids=["swish", "swish-se"])
+@pytest.mark.parametrize("c,n,h,w", [(32, 2, 24, 40), (192, 3, 8, 12), (2688, 2, 6, 10)])
+def test_bn_backward_act_matches_autograd(cuda, c, n, h, w, se):
+    """bn_bwd_reduce_act + bn_bwd_apply_act (mbconv.hip: the EfficientNet MBConv BatchNorm backward behind swish [and the
+    squeeze-and-excitation product]) == autograd of batch_norm -> swish [-> x SE scale, + the pooled branch] in fp64.  Upstream
+    gradient with a non-zero mean; C = 2688 > 1024 splits the channels over grid.y (pick_cw).  The optional max|dy| output
+    must equal max|dy| of the written dy bit for bit: the fp16x3 dgrad / wgrad that reads dy scales by it."""
+    L = lib()
+    g = torch.Generator().manual_seed(c + 7 * se)
+    y = (torch.randn(n, c, h, w, generator=g) * 2 + 0.7).double().requires_grad_()
+    gamma = (torch.rand(c, generator=g) + 0.5).double().requires_grad_()
+    beta = (torch.randn(c, generator=g) * 0.5).double().requires_grad_()
+    z = F.batch_norm(y, None, None, gamma, beta, True, 0.1, 1e-3)
+    a = z * torch.sigmoid(z)
+    go = torch.randn(n, c, h, w, generator=g).double() + 0.5          # non-zero mean: exercises the cancellation
+    if se:
+        s = torch.rand(n, c, generator=g).double() + 0.25               # the SE channel scale (a constant of this backward)
+        gpool = torch.randn(n, c, generator=g).double() * h * w * 0.3   # gradient wrt the squeeze pooling mean_hw(a): non-zero
+        obj = (a * s[:, :, None, None] * go).sum() + (a.mean((2, 3)) * gpool).sum()
+    else:
+        obj = (a * go).sum()
+    obj.backward()
+    mean = y.detach().mean((0, 2, 3)); var = y.detach().var((0, 2, 3), unbiased=False)
+    rstd = 1.0 / torch.sqrt(var + 1e-3)
+    scale = gamma.detach() * rstd; shift = beta.detach() - mean * scale
+    dev = lambda t: t.float().contiguous().to(cuda)
+    gd, yd = nhwc(go.float()).to(cuda), nhwc(y.detach().float()).to(cuda)
+    dy = torch.full_like(gd, float("nan")); dgam = torch.empty(c, device=cuda); dbet = torch.empty(c, device=cuda)
+    scr = torch.empty(2 * c, dtype=torch.float64, device=cuda)
+    xmax = torch.full((32,), float("nan"), device=cuda)
+    t = [dev(mean), dev(rstd), dev(gamma.detach()), dev(scale), dev(shift)]
+    sd, gpd = (dev(s), dev(gpool)) if se else (None, None)
+    L.check(L.lib().uwm_op_bn_backward_act(P(gd), P(yd), P(t[0]), P(t[1]), P(t[2]), P(t[3]), P(t[4]), P(sd), P(gpd), n, h * w, c,
+                                           P(scr), P(dy), P(dgam), P(dbet), P(xmax), stream()))
+    torch.cuda.synchronize()
+    ref = y.grad.float()
+    assert (nchw(dy.cpu()) - ref).abs().max() < 3e-5 * float(ref.abs().max()) + 1e-6
+    assert torch.allclose(dgam.cpu(), gamma.grad.float(), rtol=1e-4, atol=1e-4 * float(gamma.grad.abs().max()))
+    assert torch.allclose(dbet.cpu(), beta.grad.float(), rtol=1e-4, atol=1e-4 * float(beta.grad.abs().max()))
+    assert float(xmax.max()) == float(dy.abs().max()), (float(xmax.max()), float(dy.abs().max()))
+    assert bool((xmax >= 0).all())                                       # every slot zeroed, then only maxima of |dy|
+    # without the xmax output: the same dy
+    dy2 = torch.full_like(gd, float("nan"))
+    L.check(L.lib().uwm_op_bn_backward_act(P(gd), P(yd), P(t[0]), P(t[1]), P(t[2]), P(t[3]), P(t[4]), P(sd), P(gpd), n, h * w, c,
+                                           P(scr), P(dy2), P(dgam), P(dbet), None, stream()))
+    torch.cuda.synchronize()
+    assert torch.equal(dy2, dy) or (dy2 - dy).abs().max() <= 1e-6 * float(dy.abs().max())
+
+
 def test_upsplit_matches_autograd(cuda):
     L = lib()
     g = torch.Generator().manual_seed(12)

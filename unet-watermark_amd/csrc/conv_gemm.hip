@@ -327,6 +327,7 @@ static hipError_t launch_gemm_(const ConvArgs& a, hipStream_t st, int cls) {
   static DevOnce lds_attr;
   { hipError_t e = lds_attr.set_max_lds((const void*)conv_gemm_kernel<BN, F16>, lds); if (e != hipSuccess) return e; }
   UWM_LAUNCH(F16 ? (BN == 128 ? 51 : 52) : cls, a.flops, a.bytes, (conv_gemm_kernel<BN, F16>), dim3((unsigned)nwg), dim3(256), lds, st, a, tilesM, ntiles);
+  if (F16) route_note("(conv_gemm_kernel<BN, true>)");        // (the routing record names the fp16x3 form)
   return hipGetLastError();
 }
 template <int BN>

@@ -385,37 +385,58 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_act_kernel(const float* __r
   }
 }
 template <bool SE>
-__global__ void bn_bwd_apply_act_kernel(const float* __restrict__ g, const float* __restrict__ y, const float* __restrict__ mean,
+__global__ __launch_bounds__(256) void bn_bwd_apply_act_kernel(const float* __restrict__ g, const float* __restrict__ y, const float* __restrict__ mean,
                                         const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ scale,
                                         const float* __restrict__ shift, const float* __restrict__ se_s, const float* __restrict__ gpool,
                                         float inv_hw, size_t per_img4, const double* __restrict__ dgamma, const double* __restrict__ dbeta,
-                                        float* __restrict__ dy, float* gamma_grad, float* beta_grad, size_t n4, int C, float invM) {
+                                        float* __restrict__ dy, float* gamma_grad, float* beta_grad, size_t n4, int C, float invM,
+                                        float* xmax) {
+  __shared__ float wmax[4];
   if (blockIdx.x == 0 && gamma_grad)
     for (int c = threadIdx.x; c < C; c += blockDim.x) { gamma_grad[c] = (float)dgamma[c]; beta_grad[c] = (float)dbeta[c]; }
   const size_t stride = (size_t)gridDim.x * blockDim.x;       // a multiple of C/4: a thread stays on one channel quad
   size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-  if (i >= n4) return;
-  const int c = (int)((i * 4) % (size_t)C);
-  const f4 mu = *(const f4*)(mean + c), rs = *(const f4*)(rstd + c), gm = *(const f4*)(gamma + c), sc = *(const f4*)(scale + c), sf = *(const f4*)(shift + c);
-  f4 dg, db;
-  dg.x = (float)dgamma[c] * invM; dg.y = (float)dgamma[c + 1] * invM; dg.z = (float)dgamma[c + 2] * invM; dg.w = (float)dgamma[c + 3] * invM;
-  db.x = (float)dbeta[c] * invM; db.y = (float)dbeta[c + 1] * invM; db.z = (float)dbeta[c + 2] * invM; db.w = (float)dbeta[c + 3] * invM;
-  const f4 A = gm * rs, B = -(gm * rs * rs * dg), K = -(A * db) - B * mu;
-  for (; i + stride < n4; i += 2 * stride) {
-    const f4 g0 = *(const f4*)(g + i * 4), g1 = *(const f4*)(g + (i + stride) * 4);
-    const f4 y0 = *(const f4*)(y + i * 4), y1 = *(const f4*)(y + (i + stride) * 4);
-    *(f4*)(dy + i * 4) = A * act_grad<SE>(g0, y0, sc, sf, se_s, gpool, inv_hw, SE ? (i / per_img4) * C + c : 0) + B * y0 + K;
-    *(f4*)(dy + (i + stride) * 4) = A * act_grad<SE>(g1, y1, sc, sf, se_s, gpool, inv_hw, SE ? ((i + stride) / per_img4) * C + c : 0) + B * y1 + K;
+  if (i >= n4 && !xmax) return;
+  float amax = 0.f;                                           // max |dy| of this thread's outputs (xmax != nullptr)
+  auto amax4 = [&](const f4& v) { amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w))); };
+  if (i < n4) {
+    const int c = (int)((i * 4) % (size_t)C);
+    const f4 mu = *(const f4*)(mean + c), rs = *(const f4*)(rstd + c), gm = *(const f4*)(gamma + c), sc = *(const f4*)(scale + c), sf = *(const f4*)(shift + c);
+    f4 dg, db;
+    dg.x = (float)dgamma[c] * invM; dg.y = (float)dgamma[c + 1] * invM; dg.z = (float)dgamma[c + 2] * invM; dg.w = (float)dgamma[c + 3] * invM;
+    db.x = (float)dbeta[c] * invM; db.y = (float)dbeta[c + 1] * invM; db.z = (float)dbeta[c + 2] * invM; db.w = (float)dbeta[c + 3] * invM;
+    const f4 A = gm * rs, B = -(gm * rs * rs * dg), K = -(A * db) - B * mu;
+    for (; i + stride < n4; i += 2 * stride) {
+      const f4 g0 = *(const f4*)(g + i * 4), g1 = *(const f4*)(g + (i + stride) * 4);
+      const f4 y0 = *(const f4*)(y + i * 4), y1 = *(const f4*)(y + (i + stride) * 4);
+      const f4 o0 = A * act_grad<SE>(g0, y0, sc, sf, se_s, gpool, inv_hw, SE ? (i / per_img4) * C + c : 0) + B * y0 + K;
+      const f4 o1 = A * act_grad<SE>(g1, y1, sc, sf, se_s, gpool, inv_hw, SE ? ((i + stride) / per_img4) * C + c : 0) + B * y1 + K;
+      if (xmax) { amax4(o0); amax4(o1); }
+      *(f4*)(dy + i * 4) = o0;
+      *(f4*)(dy + (i + stride) * 4) = o1;
+    }
+    for (; i < n4; i += stride) {
+      const f4 yv = *(const f4*)(y + i * 4);
+      const f4 o = A * act_grad<SE>(*(const f4*)(g + i * 4), yv, sc, sf, se_s, gpool, inv_hw, SE ? (i / per_img4) * C + c : 0) + B * yv + K;
+      if (xmax) amax4(o);
+      *(f4*)(dy + i * 4) = o;
+    }
   }
-  for (; i < n4; i += stride) {
-    const f4 yv = *(const f4*)(y + i * 4);
-    *(f4*)(dy + i * 4) = A * act_grad<SE>(*(const f4*)(g + i * 4), yv, sc, sf, se_s, gpool, inv_hw, SE ? (i / per_img4) * C + c : 0) + B * yv + K;
+  if (xmax) {                                                 // wave max -> workgroup max -> one atomic on one of 32 slots, as bn_bwd_apply_kernel
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) amax = fmaxf(amax, __shfl_xor(amax, d));
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = amax;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const float mx = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+      if (mx > 0.f) atomicMax((unsigned*)xmax + (blockIdx.x & 31), __float_as_uint(mx));
+    }
   }
 }
 // BatchNorm backward of y -> swish (-> SE product): g = gradient wrt the swish output (SE: wrt the SE-scaled tensor)
 hipError_t launch_bn_bwd_act(const float* g, const float* y, const float* mean, const float* rstd, const float* gamma, const float* scale,
                              const float* shift, const float* se_s, const float* gpool, int N, size_t hw, double* dgamma, double* dbeta,
-                             float* dy, float* gamma_grad, float* beta_grad, int C, hipStream_t st) {
+                             float* dy, float* gamma_grad, float* beta_grad, int C, hipStream_t st, float* xmax) {
   const size_t npix = (size_t)N * hw;
   const int CW = pick_cw(C);
   if (!CW || npix >= (1ull << 32)) return hipErrorInvalidValue;
@@ -432,8 +453,8 @@ hipError_t launch_bn_bwd_act(const float* g, const float* y, const float* mean, 
   nbk = ((nbk + unit - 1) / unit) * unit;
   const size_t per_img4 = hw * (size_t)C / 4;
   const float invM = (float)(1.0 / (double)npix);
-  if (se_s) hipLaunchKernelGGL((bn_bwd_apply_act_kernel<true>), dim3(nbk), dim3(256), 0, st, g, y, mean, rstd, gamma, scale, shift, se_s, gpool, inv_hw, per_img4, dgamma, dbeta, dy, gamma_grad, beta_grad, n4, C, invM);
-  else hipLaunchKernelGGL((bn_bwd_apply_act_kernel<false>), dim3(nbk), dim3(256), 0, st, g, y, mean, rstd, gamma, scale, shift, se_s, gpool, inv_hw, per_img4, dgamma, dbeta, dy, gamma_grad, beta_grad, n4, C, invM);
+  if (se_s) hipLaunchKernelGGL((bn_bwd_apply_act_kernel<true>), dim3(nbk), dim3(256), 0, st, g, y, mean, rstd, gamma, scale, shift, se_s, gpool, inv_hw, per_img4, dgamma, dbeta, dy, gamma_grad, beta_grad, n4, C, invM, xmax);
+  else hipLaunchKernelGGL((bn_bwd_apply_act_kernel<false>), dim3(nbk), dim3(256), 0, st, g, y, mean, rstd, gamma, scale, shift, se_s, gpool, inv_hw, per_img4, dgamma, dbeta, dy, gamma_grad, beta_grad, n4, C, invM, xmax);
   return hipGetLastError();
 }
 

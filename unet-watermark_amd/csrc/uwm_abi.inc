@@ -584,6 +584,19 @@ int uwm_op_bn_backward(const float* g, const float* y, const float* mean, const 
   LCHK(launch_bn_bwd_apply(g, y, mean, rstd, gamma, scratch2c, scratch2c + C, dy, dgamma, dbeta, (size_t)npix, C, st));
   return 0;
 }
+int uwm_op_bn_backward_act(const float* g, const float* y, const float* mean, const float* rstd, const float* gamma,
+                           const float* scale, const float* shift, const float* se_s, const float* gpool, int N, long long hw,
+                           int C, double* scratch2c, float* dy, float* dgamma, float* dbeta, float* xmax, uwm_stream stream) {
+  if (!g || !y || !mean || !rstd || !gamma || !scale || !shift || !scratch2c || !dy || !dgamma || !dbeta || N < 1 || hw < 1 ||
+      C < 4 || (C & 3) || (!se_s != !gpool))
+    return fail("uwm_op_bn_backward_act: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipMemsetAsync(scratch2c, 0, 2 * (size_t)C * sizeof(double), st));
+  if (xmax) HIPCHK(hipMemsetAsync(xmax, 0, 32 * sizeof(float), st));
+  LCHK(launch_bn_bwd_act(g, y, mean, rstd, gamma, scale, shift, se_s, gpool, N, (size_t)hw, scratch2c, scratch2c + C, dy, dgamma,
+                         dbeta, C, st, xmax));
+  return 0;
+}
 int uwm_op_upsplit(const float* dcat, int N, int H, int W, int C0, int C1, float* gprev, const float* pmask,
                    const float* pscale, const float* pshift, float* gskip, uwm_stream stream) {
   if (!dcat || !gprev) return fail("uwm_op_upsplit: null argument");

@@ -21,6 +21,7 @@ static int do_backward(uwm_model* m, const float* dlogits, float* ws, int sb, in
 
   std::vector<char>& out_sums = m->out_sums;
   if (sb <= 0 || out_sums.size() != first_blk[3] + m->stages[3].size()) out_sums.assign(first_blk[3] + m->stages[3].size(), 0);
+  if (sb <= 0 || m->dy_max_made.size() != m->bns.size()) m->dy_max_made.assign(m->bns.size(), 0);     // (the slots are zeroed below)
   m->disp_cov.clear();
   if (sb <= 0) m->rq = ReduceQueue();                   // (a failed earlier call may have left jobs behind)
   if (sb <= 0 && se > 0) {

@@ -342,7 +342,8 @@ hipError_t launch_dw_wgrad(const float* x, const float* dy, int k, int stride, i
 // BatchNorm backward behind swish [and the SE product]: swish_bwd fused into both BatchNorm-backward passes
 hipError_t launch_bn_bwd_act(const float* g, const float* y, const float* mean, const float* rstd, const float* gamma, const float* scale,
                              const float* shift, const float* se_s, const float* gpool, int N, size_t hw, double* dgamma, double* dbeta,
-                             float* dy, float* gamma_grad, float* beta_grad, int C, hipStream_t st);
+                             float* dy, float* gamma_grad, float* beta_grad, int C, hipStream_t st,
+                             float* xmax = nullptr);   // xmax: as launch_bn_bwd_apply's (32 zero-initialised floats <- max|dy|)
 hipError_t launch_colstats(const float* y, size_t npix, int C, double* ssum, double* ssq, hipStream_t st);
 // out[n][c] = scale * sum_hw a[n][hw][c] (* b[n][hw][c]); deterministic two-stage sum, part: se_reduce_scratch_floats(N, C) floats
 size_t se_reduce_scratch_floats(int N, int C);

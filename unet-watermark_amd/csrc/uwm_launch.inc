@@ -16,6 +16,34 @@ static Src lazy_src(const Ctx& c, int conv, int H, int W, int relu = 1, int up =
   return mk_src(c.F(c.m->plan.y[conv]), cv.CoutP, H, W, c.F(b.f_off) + 2 * b.C, c.F(b.f_off) + 3 * b.C, relu, up);
 }
 
+// a launch helper that found a contract violation of its own: the message is set here and LCHK passes it on unchanged
+static thread_local bool g_err_own = false;
+static hipError_t fail_launch(const char* fmt, ...) {
+  va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof(g_err), fmt, ap); va_end(ap);
+  g_err_own = true;
+  return hipErrorInvalidValue;
+}
+
+// The max|dY| contract of the fp16x3 backward.  Every fp16x3 dgrad / wgrad of conv ci stages dY times the power of two that
+// puts max|dY| into [2^13, 2^14); it reads that maximum from the 32 slots of the conv's BatchNorm (BNL::xmax_off), which the
+// BatchNorm backward that writes dY fills (run_bn_bwd, run_bn_bwd_act).  An unwritten slot reads 0 and the kernels fall back to
+// scale 1 without a word (dY below ~6e-5 loses mantissa, below ~6e-8 flushes to zero).  This one predicate decides both
+// sides: the producers write the slots of every conv it holds for, and the consumers read them only through dy_max_slot.
+static bool dy_max_needed(const uwm_model* m, size_t ci) {
+  return m->convs[ci].bn >= 0 &&
+         (f3_dgrad_on(m, ci) || f3_wgrad_on(m, ci) || ig16_on(m, ci, true) || up2_f16_on(m, ci, true) || stem_wg16_on(m, ci) ||
+          c16_wg16_on(m, ci) || c16_f16_on(m, ci, true));
+}
+// *slot = the max|dY| slots an fp16x3 dgrad / wgrad of conv ci reads; an error when no producer of this backward wrote them (a
+// new fp16x3 route without a producer fails here instead of silently running on unscaled fp16)
+static hipError_t dy_max_slot(const Ctx& c, int ci, const char* pass, const float** slot) {
+  const ConvL& cv = c.m->convs[ci];
+  if (!dy_max_needed(c.m, (size_t)ci) || cv.bn >= (int)c.m->dy_max_made.size() || !c.m->dy_max_made[cv.bn])
+    return fail_launch("internal: the fp16x3 %s of %s has no max|dY| producer (dy_max_needed / run_bn_bwd*)", pass, cv.name.c_str());
+  *slot = (const float*)c.D(c.m->bns[cv.bn].xmax_off());
+  return hipSuccess;
+}
+
 // routing record (uwm_routing_enable / uwm_routing_dump): "<pass> <layer> <kernel>" per conv-class launch, in launch order
 static hipError_t route_rec(const Ctx& c, const char* pass, int ci, hipError_t e) {
   if (c.m->route_log_on && e == hipSuccess) { c.m->route_log += pass; c.m->route_log += ' '; c.m->route_log += c.m->convs[ci].name; c.m->route_log += ' '; c.m->route_log += route_last(); c.m->route_log += '\n'; }
@@ -90,11 +118,16 @@ static hipError_t run_dgrad(const Ctx& c, int ci, const float* dy, int Ho, int W
     if (f3_dgrad_on(c.m, (size_t)ci) && (!us || (us->C0 & 63) == 0)) {        // fp16x3 direct form: dY scaled by the power of two bn_bwd_apply's max|dy| calls for
       a.prec = 2; a.wu_layout = f3_layout(c.m, (size_t)ci, true); a.nprod = f3_nprod(c.m, true);
       a.wu_ncb = a.wu_layout == 1 ? f16x3v2_nf(cv.CinP) : f16x3_nj(cv.CinP); a.wu_rinv_off = (int)f16x3_rinv_off(cv.CinP, cv.CoutP);
-      a.xmax = (const float*)c.D(c.m->bns[cv.bn].xmax_off());
+      const hipError_t e = dy_max_slot(c, ci, "dgrad", &a.xmax);
+      if (e != hipSuccess) return e;
     }
   }
   a.wino = c.m->plan.wino_mode + 1;
-  if (ig16_on(c.m, (size_t)ci, true) || up2_f16_on(c.m, (size_t)ci, true) || c16_f16_on(c.m, (size_t)ci, true)) { a.ig16 = 1; a.xmax = (const float*)c.D(c.m->bns[cv.bn].xmax_off()); }
+  if (ig16_on(c.m, (size_t)ci, true) || up2_f16_on(c.m, (size_t)ci, true) || c16_f16_on(c.m, (size_t)ci, true)) {
+    a.ig16 = 1;
+    const hipError_t e = dy_max_slot(c, ci, "dgrad", &a.xmax);
+    if (e != hipSuccess) return e;
+  }
   if (us) { a.out_up = us->gprev; a.up_c0 = us->C0; a.up_mask = us->pmask; a.up_mscale = us->pscale; a.up_mshift = us->pshift; a.up_accum = us->accumulate; }
   if (fused) *fused = false;
   static const bool no_fuse = dbg_flag("UWM_NO_BN_FUSE");
@@ -126,9 +159,13 @@ static hipError_t run_wgrad(const Ctx& c, int ci, const Src& s0, const Src* s1, 
   a.bytes = 4.0 * ((double)a.M * cv.CoutP + (double)c.N * s0.H * s0.W * s0.C + (s1 ? (double)c.N * s1->H * s1->W * s1->C : 0.0) +
                    (double)cv.Cout * cv.Kpad);
   a.wino = c.m->plan.wino_mode + 1; a.route_n = c.m->route_n;
-  if (stem_wg16_on(c.m, (size_t)ci) || c16_wg16_on(c.m, (size_t)ci) || up2_f16_on(c.m, (size_t)ci, true)) { a.prec = 2; a.xmax = (const float*)c.D(c.m->bns[cv.bn].xmax_off()); }
-  if (ig16_on(c.m, (size_t)ci, true)) { a.prec = 2; a.xmax = (const float*)c.D(c.m->bns[cv.bn].xmax_off()); }      // stride-2 layers: wgrad_igemm's fp16x3 form
-  if (f3_wgrad_on(c.m, (size_t)ci)) { a.prec = 2; a.nprod = f3_nprod(c.m, true); a.xmax = (const float*)c.D(c.m->bns[cv.bn].xmax_off()); a.cu_share = (c.wst && c.wst != c.st) ? 3 : 0; }
+  if (stem_wg16_on(c.m, (size_t)ci) || c16_wg16_on(c.m, (size_t)ci) || up2_f16_on(c.m, (size_t)ci, true)) a.prec = 2;
+  if (ig16_on(c.m, (size_t)ci, true)) a.prec = 2;      // stride-2 and 1x1 layers: wgrad_igemm's fp16x3 form
+  if (f3_wgrad_on(c.m, (size_t)ci)) { a.prec = 2; a.nprod = f3_nprod(c.m, true); a.cu_share = (c.wst && c.wst != c.st) ? 3 : 0; }
+  if (a.prec == 2) {
+    const hipError_t e = dy_max_slot(c, ci, "wgrad", &a.xmax);
+    if (e != hipSuccess) return e;
+  }
   // partial images of a split launch: the next free slice of the scratch; their reduce is queued and runs with the other layers'
   // in one launch (flush_reduces: when the scratch / queue fills up and at the end of every backward stage)
   static const bool no_defer = dbg_flag("UWM_NO_DEFER_REDUCE");
@@ -179,7 +216,7 @@ static hipError_t run_bn_bwd(const Ctx& c, int ci, const float* g, float* dy, si
     if (cs == hipStreamCaptureStatusNone) done = m->ev_disp;          // (a capturing stream takes the plain record / wait pair: graph edges)
   }
   hipError_t e = hipSuccess;
-  float* xmax = (f3_dgrad_on(m, (size_t)ci) || f3_wgrad_on(m, (size_t)ci) || ig16_on(m, (size_t)ci, true) || up2_f16_on(m, (size_t)ci, true) || stem_wg16_on(m, (size_t)ci) || c16_wg16_on(m, (size_t)ci) || c16_f16_on(m, (size_t)ci, true)) ? (float*)c.D(b.xmax_off()) : nullptr;      // the fp16x3 dgrad / wgrad of this conv scale dy by its maximum
+  float* xmax = dy_max_needed(m, (size_t)ci) ? (float*)c.D(b.xmax_off()) : nullptr;      // the fp16x3 dgrad / wgrad of this conv scale dy by its maximum
   if (sums_fused)
     e = launch_bn_bwd_apply(g, y, f, f + b.C, m->params + b.g_off, nullptr, nullptr, dy, m->grads + b.g_off, m->grads + b.b_off,
                             npix, b.C, c.st, c.D(b.d_off) + 2 * b.C, b.nrep, 2 * b.C, done, xmax);
@@ -190,6 +227,7 @@ static hipError_t run_bn_bwd(const Ctx& c, int ci, const float* g, float* dy, si
                             npix, b.C, c.st, nullptr, 0, 0, done, xmax);
   }
   if (e == hipSuccess && done) m->disp_cov.push_back(dy);
+  if (e == hipSuccess && xmax) m->dy_max_made[cv.bn] = 1;
   return e;
 }
 
@@ -197,13 +235,16 @@ static hipError_t run_bn_bwd(const Ctx& c, int ci, const float* g, float* dy, si
 static hipError_t run_bn_bwd_act(const Ctx& c, int ci, const float* g, float* dy, int N, size_t hw, const float* se_s, const float* gpool) {
   uwm_model* m = c.m; const ConvL& cv = m->convs[ci]; const BNL& b = m->bns[cv.bn];
   const float* f = c.F(b.f_off);
-  return launch_bn_bwd_act(g, c.F(m->plan.y[ci]), f, f + b.C, m->params + b.g_off, f + 2 * b.C, f + 3 * b.C, se_s, gpool, N, hw,
-                           c.D(b.d_off), c.D(b.d_off) + b.C, dy, m->grads + b.g_off, m->grads + b.b_off, b.C, c.st);
+  float* xmax = dy_max_needed(m, (size_t)ci) ? (float*)c.D(b.xmax_off()) : nullptr;      // (the MBConv expand convs: 1x1 fp16x3 forms)
+  const hipError_t e = launch_bn_bwd_act(g, c.F(m->plan.y[ci]), f, f + b.C, m->params + b.g_off, f + 2 * b.C, f + 3 * b.C, se_s, gpool,
+                                         N, hw, c.D(b.d_off), c.D(b.d_off) + b.C, dy, m->grads + b.g_off, m->grads + b.b_off, b.C, c.st, xmax);
+  if (e == hipSuccess && xmax) m->dy_max_made[cv.bn] = 1;
+  return e;
 }
 
 #define LCHK(expr)                                                                                     \
-  do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail("launch failed: %s at %s:%d (%s)",  \
-       hipGetErrorString(e_), __FILE__, __LINE__, #expr); } while (0)
+  do { hipError_t e_ = (expr); if (e_ != hipSuccess) { if (g_err_own) { g_err_own = false; return 1; }     \
+       return fail("launch failed: %s at %s:%d (%s)", hipGetErrorString(e_), __FILE__, __LINE__, #expr); } } while (0)
 
 // Winograd filter transforms of every eligible layer (forward banks, or dgrad banks straight from the forward
 // weights), at most 40 layers per launch

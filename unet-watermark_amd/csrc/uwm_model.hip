@@ -143,6 +143,7 @@ struct uwm_model {
   bool route_log_on = false;         // uwm_routing_enable: record (pass, layer, kernel) of every conv / dgrad / wgrad launch
   std::string route_log;             // text of the record since the last uwm_routing_dump(.., clear)
   bool prec_from_env = false;        // the precision mode came from UWM_PRECISION (logged once at the first forward)
+  std::vector<char> dy_max_made;     // per BatchNorm: a BatchNorm backward of this backward wrote its max|dY| slots (BNL::xmax_off; reset with them at stage 0)
   std::vector<char> out_sums;        // per residual block: the BatchNorm-backward sums of its last BatchNorm were made by the dgrad that wrote its output gradient (run_dgrad bn_y)
 };
 

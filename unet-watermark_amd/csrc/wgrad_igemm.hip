@@ -290,6 +290,7 @@ static hipError_t launch_w(const WgradArgs& a, hipStream_t st, int cls) {
   static DevOnce lds_attr;                  // hipFuncSetAttribute is per device
   { hipError_t e = lds_attr.set_max_lds((const void*)wgrad_igemm_kernel<TA, TB, WA, WB, F16>, lds); if (e != hipSuccess) return e; }
   UWM_LAUNCH(cls, a.flops, a.bytes, (wgrad_igemm_kernel<TA, TB, WA, WB, F16>), dim3((unsigned)(tilesA * tilesB * a.nsplit)), dim3(256), lds, st, a);
+  if (F16) route_note("(wgrad_igemm_kernel<TA, TB, WA, WB, true>)");        // (the routing record names the fp16x3 form)
   if (a.nsplit > 1) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
