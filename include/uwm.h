@@ -1,7 +1,7 @@
 /* libuwm — C ABI of the MI355X-native U-Net watermark-segmentation hot path.
  *
  * This is the drop-in boundary for ONE path of Dave-he/unet-watermark: the forward / backward of
- * smp.Unet | smp.UnetPlusPlus (encoders resnet18 | resnet34 | resnet50 | efficientnet-b4; UnetPlusPlus is the
+ * smp.Unet | smp.UnetPlusPlus (encoders resnet18 | resnet34 | resnet50 | efficientnet-b0 .. b7; UnetPlusPlus is the
  * reference's default MODEL.NAME, src/configs/config.py:15) and its Dice + BCE loss, which the reference reaches through
  *   model = smp.Unet(**kwargs)                /root/reference/src/models/unet_model.py:17-27,64-71,93-120
  *   outputs = model(images)                    /root/reference/src/train.py:91,100,142 ; src/predict.py:339,611
@@ -43,7 +43,11 @@ typedef struct uwm_model* uwm_handle;
 typedef void* uwm_stream;              /* hipStream_t */
 
 enum { UWM_ENC_RESNET18 = 18, UWM_ENC_RESNET34 = 34, UWM_ENC_RESNET50 = 50,     /* 50: Bottleneck blocks (unet_watermark_large.yaml) */
-       UWM_ENC_EFFICIENTNET_B4 = 104 };   /* MBConv blocks (README.md:173-176 / BASELINE config 4) */
+       /* MBConv blocks: efficientnet_pytorch's compound-scaled family; b4 = README.md:173-176 / BASELINE config 4, b3 = the
+        * text-watermark config (unet_text_watermark.yaml) */
+       UWM_ENC_EFFICIENTNET_B0 = 100, UWM_ENC_EFFICIENTNET_B1 = 101, UWM_ENC_EFFICIENTNET_B2 = 102,
+       UWM_ENC_EFFICIENTNET_B3 = 103, UWM_ENC_EFFICIENTNET_B4 = 104, UWM_ENC_EFFICIENTNET_B5 = 105,
+       UWM_ENC_EFFICIENTNET_B6 = 106, UWM_ENC_EFFICIENTNET_B7 = 107 };
 enum { UWM_ARCH_UNET = 0, UWM_ARCH_UNETPLUSPLUS = 1 };   /* smp.Unet | smp.UnetPlusPlus (the reference's default MODEL.NAME, src/configs/config.py:15) */
 enum { UWM_T_F32 = 0, UWM_T_I64 = 1, UWM_T_U8 = 2, UWM_T_I32 = 3 };          /* target dtypes */
 enum { UWM_KIND_CONV_W = 0, UWM_KIND_BIAS = 1, UWM_KIND_BN_GAMMA = 2, UWM_KIND_BN_BETA = 3,
@@ -151,6 +155,15 @@ int  uwm_adam_clip(float* p, const float* g, float* m, float* v, long long n, fl
  * and fills the two bias-correction slots itself.  clip_scratch != NULL (>= 8 bytes): global-norm clipping to hyper[6]. */
 int  uwm_adam_graph(float* p, const float* g, float* m, float* v, long long n, float* hyper, void* clip_scratch,
                     uwm_stream stream);
+/* torch.optim.AdamW (decoupled weight decay): the same arguments and hyper layout as uwm_adam / uwm_adam_clip /
+ * uwm_adam_graph; p *= 1 - lr*weight_decay, then the Adam moments of the (scaled, clipped) gradient without an L2 term */
+int  uwm_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
+               float eps, float weight_decay, long long step, float grad_scale, uwm_stream stream);
+int  uwm_adamw_clip(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
+                    float eps, float weight_decay, long long step, float grad_scale, float max_norm, void* scratch,
+                    uwm_stream stream);
+int  uwm_adamw_graph(float* p, const float* g, float* m, float* v, long long n, float* hyper, void* clip_scratch,
+                     uwm_stream stream);
 /* torch.optim.SGD(lr, momentum, weight_decay) (coupled L2, dampening 0; the reference's OPTIMIZER.NAME == "SGD" branch,
  * /root/reference/src/train.py:272-278) over a flat range: buf = step == 1 ? g' : momentum*buf + g', p -= lr*buf with
  * g' = grad_scale*g + weight_decay*p; max_norm > 0 adds global-norm clipping as uwm_adam_clip (scratch >= 8 bytes). */

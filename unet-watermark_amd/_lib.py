@@ -46,7 +46,7 @@ class uwm_src(C.Structure):
 
 KIND_CONV_W, KIND_BIAS, KIND_BN_GAMMA, KIND_BN_BETA, KIND_BN_MEAN, KIND_BN_VAR = range(6)
 ARENA_PARAM, ARENA_BUFFER = 0, 1
-ENC = {"resnet18": 18, "resnet34": 34, "resnet50": 50, "efficientnet-b4": 104}
+ENC = {"resnet18": 18, "resnet34": 34, "resnet50": 50, **{f"efficientnet-b{i}": 100 + i for i in range(8)}}
 ARCH = {"Unet": 0, "UnetPlusPlus": 1}
 PREC = {"f32": 0, "bf16x3": 1, "bf16x3_all": 2, "f16x3": 3, "f16x3_all": 4, "f16x1": 5, "f16x3_bwd2": 6}
 P, I, L, F, Z = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t
@@ -78,6 +78,9 @@ SIGNATURES = {
     "uwm_adam": (I, [P, P, P, P, L, F, F, F, F, F, L, F, P]),
     "uwm_adam_clip": (I, [P, P, P, P, L, F, F, F, F, F, L, F, F, P, P]),
     "uwm_adam_graph": (I, [P, P, P, P, L, P, P, P]),
+    "uwm_adamw": (I, [P, P, P, P, L, F, F, F, F, F, L, F, P]),
+    "uwm_adamw_clip": (I, [P, P, P, P, L, F, F, F, F, F, L, F, F, P, P]),
+    "uwm_adamw_graph": (I, [P, P, P, P, L, P, P, P]),
     "uwm_sgd": (I, [P, P, P, L, F, F, F, L, F, F, P, P]),
     "uwm_scale": (I, [P, L, F, P]),
     "uwm_set_winograd": (I, [I]),

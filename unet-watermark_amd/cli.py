@@ -107,6 +107,12 @@ def _make_scheduler(cfg, opt):
                                                           patience=int(cfg.OPTIMIZER.SCHEDULER_PATIENCE))
     if name == "CosineAnnealingLR":
         return torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=int(cfg.TRAIN.EPOCHS))
+    if name == "CosineAnnealingWarmRestarts":          # the text-watermark trainer (src/text/train_text_watermark.py:85-91)
+        o = cfg.OPTIMIZER
+        if o.get("SCHEDULER_T_0") is None:
+            raise ValueError("OPTIMIZER.LR_SCHEDULER=CosineAnnealingWarmRestarts needs OPTIMIZER.SCHEDULER_T_0")
+        return torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(
+            opt, T_0=int(o.SCHEDULER_T_0), T_mult=int(o.get("SCHEDULER_T_MULT", 1)), eta_min=float(o.get("SCHEDULER_ETA_MIN", 0.0)))
     return None
 
 
@@ -134,7 +140,7 @@ def train_command(args):
         cfg.TRAIN.CHECKPOINT_DIR = args.checkpoint_dir
     if cfg.MODEL.NAME not in ("Unet", "UnetPlusPlus"):
         raise ValueError(f"MODEL.NAME={cfg.MODEL.NAME!r}: this build serves 'Unet' and 'UnetPlusPlus'")
-    if cfg.OPTIMIZER.NAME not in ("Adam", "SGD"):
+    if cfg.OPTIMIZER.NAME not in ("Adam", "AdamW", "SGD"):
         raise ValueError(f"unsupported optimizer: {cfg.OPTIMIZER.NAME}")           # /root/reference/src/train.py:279
     if cfg.MODEL.ENCODER_WEIGHTS is not None:
         print(f"note: ENCODER_WEIGHTS={cfg.MODEL.ENCODER_WEIGHTS!r} needs a download; training from seeded init")
@@ -286,10 +292,11 @@ def main(argv=None):
     tp.add_argument("--workers", type=int, default=2)
     tp.add_argument("--model", choices=["Unet", "UnetPlusPlus"], default=None, help="MODEL.NAME (reference default: UnetPlusPlus)")
     tp.add_argument("--grad-clip", action="store_true", help="honour TRAIN.GRADIENT_CLIP (the reference defines but never applies it)")
-    tp.add_argument("--optimizer", choices=["Adam", "SGD"], default=None, help="OPTIMIZER.NAME")
+    tp.add_argument("--optimizer", choices=["Adam", "AdamW", "SGD"], default=None, help="OPTIMIZER.NAME")
     tp.add_argument("--global-dice", action="store_true",
                     help="data-parallel runs: Dice of the GLOBAL batch (loss sums all-reduced) instead of the mean of per-rank Dice losses")
-    tp.add_argument("--lr-scheduler", choices=["ReduceLROnPlateau", "CosineAnnealingLR", "none"], default=None, help="OPTIMIZER.LR_SCHEDULER")
+    tp.add_argument("--lr-scheduler", choices=["ReduceLROnPlateau", "CosineAnnealingLR", "CosineAnnealingWarmRestarts", "none"],
+                    default=None, help="OPTIMIZER.LR_SCHEDULER")
     tp.add_argument("--checkpoint-dir", type=str, default=None, help="TRAIN.CHECKPOINT_DIR")
     pp = sub.add_parser("predict")
     pp.add_argument("--input", type=str, required=True); pp.add_argument("--output", type=str, required=True)

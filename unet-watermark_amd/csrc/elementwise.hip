@@ -639,7 +639,7 @@ hipError_t launch_colsum(const float* g, size_t npix, int C, float* out, double*
   return hipGetLastError();
 }
 
-// ------------------------------------------------------------------ Adam (torch.optim.Adam, coupled L2)
+// ------------------------------------------------------------------ Adam (torch.optim.Adam, coupled L2) and AdamW (decoupled decay)
 // hyp != nullptr (hipGraph-captured train step, uwm_adam_graph): every hyper-parameter comes from DEVICE memory, so one captured
 // launch serves every step — hyp = {lr, beta1, beta2, eps, weight_decay, grad_scale, max_norm, step, bc1, sqrt(bc2)}; the
 // step counter and the two bias corrections are advanced by adam_hyper_kernel (one thread) in front of every adam launch
@@ -649,6 +649,8 @@ __global__ void adam_hyper_kernel(float* hyp) {
   hyp[8] = 1.f - powf(hyp[1], step);
   hyp[9] = sqrtf(1.f - powf(hyp[2], step));
 }
+// DECOUPLED (torch.optim.AdamW): p *= 1 - lr*wd first, then the moments of the scaled / clipped gradient with no L2 term
+template <bool DECOUPLED>
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             size_t n4, size_t n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2s,
                             float gscale, const double* sumsq, float max_norm, const float* __restrict__ hyp) {
@@ -661,7 +663,8 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
     const size_t o = i * 4;
     if (o + 4 <= n) {
       f4 pv = *(f4*)(p + o), gv = *(const f4*)(g + o) * gscale, mv = *(f4*)(m + o), vv = *(f4*)(v + o);
-      gv += wd * pv;
+      if (DECOUPLED) pv *= 1.f - lr * wd;
+      else gv += wd * pv;
       mv = mv + (1.f - b1) * (gv - mv);          // torch: m.lerp_(g, 1-b1)
       vv = b2 * vv + (1.f - b2) * gv * gv;
       f4 den;
@@ -670,27 +673,38 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
       *(f4*)(p + o) = pv; *(f4*)(m + o) = mv; *(f4*)(v + o) = vv;
     } else {
       for (size_t j = o; j < n; ++j) {
-        float gj = g[j] * gscale + wd * p[j];
+        float pj = p[j], gj = g[j] * gscale;
+        if (DECOUPLED) pj *= 1.f - lr * wd;
+        else gj += wd * pj;
         float mj = m[j] + (1.f - b1) * (gj - m[j]);
         float vj = b2 * v[j] + (1.f - b2) * gj * gj;
-        p[j] -= (lr / bc1) * (mj / (sqrtf(vj) / bc2s + eps));
+        p[j] = pj - (lr / bc1) * (mj / (sqrtf(vj) / bc2s + eps));
         m[j] = mj; v[j] = vj;
       }
     }
   }
 }
 hipError_t launch_adam(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps,
-                       float wd, float bc1, float bc2, float gscale, hipStream_t st, const double* sumsq, float max_norm) {
+                       float wd, float bc1, float bc2, float gscale, hipStream_t st, const double* sumsq, float max_norm, bool decoupled) {
   const size_t n4 = (n + 3) / 4;
-  hipLaunchKernelGGL(adam_kernel, dim3(nblocks(n4, 256)), dim3(256), 0, st, p, g, m, v, n4, n, lr, b1, b2, eps, wd, bc1,
-                     sqrtf(bc2), gscale, sumsq, max_norm, (const float*)nullptr);
+  if (decoupled)
+    hipLaunchKernelGGL(adam_kernel<true>, dim3(nblocks(n4, 256)), dim3(256), 0, st, p, g, m, v, n4, n, lr, b1, b2, eps, wd, bc1,
+                       sqrtf(bc2), gscale, sumsq, max_norm, (const float*)nullptr);
+  else
+    hipLaunchKernelGGL(adam_kernel<false>, dim3(nblocks(n4, 256)), dim3(256), 0, st, p, g, m, v, n4, n, lr, b1, b2, eps, wd, bc1,
+                       sqrtf(bc2), gscale, sumsq, max_norm, (const float*)nullptr);
   return hipGetLastError();
 }
-hipError_t launch_adam_graph(float* p, const float* g, float* m, float* v, size_t n, float* hyp, const double* sumsq, hipStream_t st) {
+hipError_t launch_adam_graph(float* p, const float* g, float* m, float* v, size_t n, float* hyp, const double* sumsq, hipStream_t st,
+                             bool decoupled) {
   const size_t n4 = (n + 3) / 4;
   hipLaunchKernelGGL(adam_hyper_kernel, dim3(1), dim3(1), 0, st, hyp);
-  hipLaunchKernelGGL(adam_kernel, dim3(nblocks(n4, 256)), dim3(256), 0, st, p, g, m, v, n4, n, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f,
-                     sumsq, 0.f, (const float*)hyp);
+  if (decoupled)
+    hipLaunchKernelGGL(adam_kernel<true>, dim3(nblocks(n4, 256)), dim3(256), 0, st, p, g, m, v, n4, n, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f,
+                       sumsq, 0.f, (const float*)hyp);
+  else
+    hipLaunchKernelGGL(adam_kernel<false>, dim3(nblocks(n4, 256)), dim3(256), 0, st, p, g, m, v, n4, n, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f,
+                       sumsq, 0.f, (const float*)hyp);
   return hipGetLastError();
 }
 

@@ -228,6 +228,27 @@ int uwm_adam_graph(float* p, const float* g, float* m, float* v, long long n, fl
   LCHK(launch_adam_graph(p, g, m, v, (size_t)n, hyper, (const double*)clip_scratch, (hipStream_t)stream));
   return 0;
 }
+int uwm_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float wd,
+              long long step, float gscale, uwm_stream stream) {
+  if (!p || !g || !m || !v || n < 1 || step < 1) return fail("uwm_adamw: bad argument");
+  const float bc1 = 1.f - powf(b1, (float)step), bc2 = 1.f - powf(b2, (float)step);
+  LCHK(launch_adam(p, g, m, v, (size_t)n, lr, b1, b2, eps, wd, bc1, bc2, gscale, (hipStream_t)stream, nullptr, 0.f, true));
+  return 0;
+}
+int uwm_adamw_clip(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float wd,
+                   long long step, float gscale, float max_norm, void* scratch, uwm_stream stream) {
+  if (!p || !g || !m || !v || !scratch || n < 1 || step < 1 || max_norm <= 0.f) return fail("uwm_adamw_clip: bad argument");
+  const float bc1 = 1.f - powf(b1, (float)step), bc2 = 1.f - powf(b2, (float)step);
+  LCHK(launch_sumsq(g, (size_t)n, (double*)scratch, (hipStream_t)stream));
+  LCHK(launch_adam(p, g, m, v, (size_t)n, lr, b1, b2, eps, wd, bc1, bc2, gscale, (hipStream_t)stream, (const double*)scratch, max_norm, true));
+  return 0;
+}
+int uwm_adamw_graph(float* p, const float* g, float* m, float* v, long long n, float* hyper, void* clip_scratch, uwm_stream stream) {
+  if (!p || !g || !m || !v || !hyper || n < 1) return fail("uwm_adamw_graph: bad argument");
+  if (clip_scratch) LCHK(launch_sumsq(g, (size_t)n, (double*)clip_scratch, (hipStream_t)stream));
+  LCHK(launch_adam_graph(p, g, m, v, (size_t)n, hyper, (const double*)clip_scratch, (hipStream_t)stream, true));
+  return 0;
+}
 int uwm_sgd(float* p, const float* g, float* buf, long long n, float lr, float momentum, float wd, long long step, float gscale,
             float max_norm, void* scratch, uwm_stream stream) {
   if (!p || !g || !buf || n < 1 || step < 1 || (max_norm > 0.f && !scratch)) return fail("uwm_sgd: bad argument");

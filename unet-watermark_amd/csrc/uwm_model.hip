@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 #include <algorithm>
+#include <cmath>
 
 using namespace uwm;
 
@@ -174,11 +175,11 @@ static void push_info(uwm_model* m, const std::string& name, int kind, int arena
 static int build_model(uwm_model* m) {
   const uwm_unet_desc& d = m->desc;
   int nb[4] = {0, 0, 0, 0}; int expn = 1;
-  const bool effnet = d.encoder == UWM_ENC_EFFICIENTNET_B4;
+  const bool effnet = d.encoder >= UWM_ENC_EFFICIENTNET_B0 && d.encoder <= UWM_ENC_EFFICIENTNET_B7;
   if (d.encoder == UWM_ENC_RESNET18) { nb[0] = 2; nb[1] = 2; nb[2] = 2; nb[3] = 2; }
   else if (d.encoder == UWM_ENC_RESNET34) { nb[0] = 3; nb[1] = 4; nb[2] = 6; nb[3] = 3; }
   else if (d.encoder == UWM_ENC_RESNET50) { nb[0] = 3; nb[1] = 4; nb[2] = 6; nb[3] = 3; expn = 4; }
-  else if (!effnet) return fail("unsupported encoder %d (supported: resnet18, resnet34, resnet50, efficientnet-b4)", d.encoder);
+  else if (!effnet) return fail("unsupported encoder %d (supported: resnet18, resnet34, resnet50, efficientnet-b0 .. efficientnet-b7)", d.encoder);
   if (d.in_channels < 1 || d.in_channels > 4) return fail("in_channels must be 1..4, got %d", d.in_channels);
   if (d.classes < 1 || d.classes > 4) return fail("classes must be 1..4, got %d", d.classes);
   for (int i = 0; i < 5; ++i)
@@ -214,24 +215,42 @@ static int build_model(uwm_model* m) {
       }
     }
   } else {
-    // efficientnet_pytorch "efficientnet-b4" as smp wraps it: width 1.4 / depth 1.8 scaling of the b0
-    // stage table; BatchNorm eps 1e-3, momentum 0.01; Conv2dStaticSamePadding pads computed along the 380-pixel size chain
-    // (asymmetric: begin = total / 2); SE ratio 0.25 of the block INPUT channels; drop-connect 0.2 * idx / 32.
+    // efficientnet_pytorch "efficientnet-b0".."b7" as smp wraps them: the b0 stage table scaled by the
+    // variant's width / depth coefficients (round_filters / round_repeats); BatchNorm eps 1e-3, momentum 0.01;
+    // Conv2dStaticSamePadding pads computed along the variant's own image-size chain (asymmetric: begin = total / 2); SE ratio
+    // 0.25 of the block INPUT channels; drop-connect 0.2 * idx / (number of blocks).
     struct St { int rep, k, stride, expand, cin, cout; };
-    const St stg[7] = {{2, 3, 1, 1, 48, 24}, {4, 3, 2, 6, 24, 32}, {4, 5, 2, 6, 32, 56}, {6, 3, 2, 6, 56, 112},
-                       {6, 5, 1, 6, 112, 160}, {8, 5, 2, 6, 160, 272}, {2, 3, 1, 6, 272, 448}};
+    const St base[7] = {{1, 3, 1, 1, 32, 16}, {2, 3, 2, 6, 16, 24}, {2, 5, 2, 6, 24, 40}, {3, 3, 2, 6, 40, 80},
+                        {3, 5, 1, 6, 80, 112}, {4, 5, 2, 6, 112, 192}, {1, 3, 1, 6, 192, 320}};
+    struct Coef { double w, dep; int image; };
+    const Coef coef[8] = {{1.0, 1.0, 224}, {1.0, 1.1, 240}, {1.1, 1.2, 260}, {1.2, 1.4, 300},
+                          {1.4, 1.8, 380}, {1.6, 2.2, 456}, {1.8, 2.6, 528}, {2.0, 3.1, 600}};
+    const Coef& cf = coef[d.encoder - UWM_ENC_EFFICIENTNET_B0];
+    auto round_filters = [&](int f) {
+      const double x = f * cf.w; int n = std::max(8, (int)(x + 4.0) / 8 * 8);
+      if (n < 0.9 * x) n += 8;
+      return n;
+    };
+    auto round_repeats = [&](int r) { return (int)std::ceil(cf.dep * r); };
+    St stg[7]; int nblocks = 0, cum[7];
+    for (int sg = 0; sg < 7; ++sg) {
+      stg[sg] = base[sg];
+      stg[sg].rep = round_repeats(base[sg].rep); stg[sg].cin = round_filters(base[sg].cin); stg[sg].cout = round_filters(base[sg].cout);
+      nblocks += stg[sg].rep; cum[sg] = nblocks;
+    }
+    const int stemC = round_filters(32);
     const float be = 1e-3f, bm = 0.01f;
     auto same_pad = [](int size, int k, int st, int* out) { const int o = (size + st - 1) / st; int t = (o - 1) * st + k - size; if (t < 0) t = 0; *out = o; return t / 2; };
-    int size = 380, osz = 0;
+    int size = cf.image, osz = 0;
     const int spb = same_pad(size, 3, 2, &osz); size = osz;
-    m->stem = add_conv(m, "encoder._conv_stem", d.in_channels, 48, 3, 2, spb, 4, false, "encoder._bn0", false, be, bm);
-    const int feat_after[4] = {6, 10, 22, 32};             // smp: features after blocks[:6], [:10], [:22], [:32]
+    m->stem = add_conv(m, "encoder._conv_stem", d.in_channels, stemC, 3, 2, spb, 4, false, "encoder._bn0", false, be, bm);
+    const int feat_after[4] = {cum[1], cum[2], cum[4], cum[6]};      // smp: features after the blocks of stages 1, 2, 4 and 6
     int idx = 0;
     for (int sg = 0; sg < 7; ++sg)
       for (int r = 0; r < stg[sg].rep; ++r, ++idx) {
         MBL b; b.Cin = r == 0 ? stg[sg].cin : stg[sg].cout; b.Cout = stg[sg].cout; b.k = stg[sg].k;
         b.stride = r == 0 ? stg[sg].stride : 1; b.mid = b.Cin * stg[sg].expand; b.nsq = std::max(1, b.Cin / 4);
-        b.skip = b.stride == 1 && b.Cin == b.Cout; b.drop = 0.2f * (float)idx / 32.f;
+        b.skip = b.stride == 1 && b.Cin == b.Cout; b.drop = 0.2f * (float)idx / (float)nblocks;
         int fs = 0; while (idx >= feat_after[fs]) ++fs;     // feature stage this block belongs to (0..3)
         const int stage = 4 - fs;
         char pre[64]; snprintf(pre, sizeof(pre), "encoder._blocks.%d", idx);
@@ -246,7 +265,7 @@ static int build_model(uwm_model* m) {
         m->mb.push_back(b);
         if (idx + 1 == feat_after[fs]) m->feat_blk[fs] = idx;
       }
-    encc[0] = 448; encc[1] = 160; encc[2] = 56; encc[3] = 32; encc[4] = 48;
+    encc[0] = stg[6].cout; encc[1] = stg[4].cout; encc[2] = stg[2].cout; encc[3] = stg[1].cout; encc[4] = stemC;
   }
   m->f1C = encc[4];
   for (int j = 0; j < 4; ++j) m->featC[j] = encc[3 - j];            // f2..f5

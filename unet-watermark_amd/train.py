@@ -202,6 +202,7 @@ class FusedAdam(_FusedFlatOptimizer):
     over the model's flat parameter arena (/root/reference/src/train.py:266-270 builds optim.Adam)."""
 
     _SLOTS = ("exp_avg", "exp_avg_sq")
+    _ABI = "uwm_adam"                   # entry points: _ABI, _ABI + "_clip", _ABI + "_graph" (same arguments for both optimizers)
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
                  materialize_grads=False):
@@ -246,9 +247,10 @@ class FusedAdam(_FusedFlatOptimizer):
         if getattr(self, "_hyper", None) is None:
             raise RuntimeError("FusedAdam.step_graph: call sync_hyper() first (outside the capture)")
         with L.on_device(p):
-            L.check(L.lib().uwm_adam_graph(C.c_void_p(p.data_ptr()), C.c_void_p(gr.data_ptr()), C.c_void_p(self._bufs[0].data_ptr()),
-                                           C.c_void_p(self._bufs[1].data_ptr()), p.numel(), C.c_void_p(self._hyper.data_ptr()),
-                                           self._clip_ptr(p), C.c_void_p(L.stream_ptr(p.device))))
+            L.check(getattr(L.lib(), self._ABI + "_graph")(
+                C.c_void_p(p.data_ptr()), C.c_void_p(gr.data_ptr()), C.c_void_p(self._bufs[0].data_ptr()),
+                C.c_void_p(self._bufs[1].data_ptr()), p.numel(), C.c_void_p(self._hyper.data_ptr()),
+                self._clip_ptr(p), C.c_void_p(L.stream_ptr(p.device))))
 
     def note_graph_step(self):
         """Host mirror of the device step counter after one replay / eager step_graph()."""
@@ -270,11 +272,26 @@ class FusedAdam(_FusedFlatOptimizer):
                 float(g["eps"]), float(g["weight_decay"]), self._step, float(grad_scale))
         with L.on_device(p):
             if self.max_grad_norm:
-                L.check(L.lib().uwm_adam_clip(*args, float(self.max_grad_norm), self._clip_ptr(p),
-                                              C.c_void_p(L.stream_ptr(p.device))))
+                L.check(getattr(L.lib(), self._ABI + "_clip")(*args, float(self.max_grad_norm), self._clip_ptr(p),
+                                                              C.c_void_p(L.stream_ptr(p.device))))
             else:
-                L.check(L.lib().uwm_adam(*args, C.c_void_p(L.stream_ptr(p.device))))
+                L.check(getattr(L.lib(), self._ABI)(*args, C.c_void_p(L.stream_ptr(p.device))))
         return loss
+
+
+class FusedAdamW(FusedAdam):
+    """torch.optim.AdamW(lr, betas, eps, weight_decay) semantics (decoupled weight decay: p *= 1 - lr*wd, then Adam on the
+    gradient alone) as ONE kernel launch over the flat arena — the optimizer of the reference's text-watermark trainer
+    (/root/reference/src/text/train_text_watermark.py:78).  Same state layout as torch.optim.AdamW (exp_avg, exp_avg_sq)."""
+
+    _ABI = "uwm_adamw"
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, max_grad_norm=None,
+                 materialize_grads=False):
+        if amsgrad:
+            raise ValueError("FusedAdamW: amsgrad=True is not supported")
+        super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                         materialize_grads=materialize_grads)
 
 
 class FusedSGD(_FusedFlatOptimizer):
@@ -327,10 +344,12 @@ class Trainer:
         self.w_dice, self.w_bce, self.smooth, self.eps = float(w_dice), float(w_bce), float(smooth), float(eps)
         if optimizer == "Adam":          # cfg.OPTIMIZER.NAME (/root/reference/src/train.py:266-279)
             self.opt = FusedAdam(model, lr=lr, betas=betas, eps=adam_eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        elif optimizer == "AdamW":      # the text-watermark trainer (/root/reference/src/text/train_text_watermark.py:78)
+            self.opt = FusedAdamW(model, lr=lr, betas=betas, eps=adam_eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
         elif optimizer == "SGD":
             self.opt = FusedSGD(model, lr=lr, momentum=momentum, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
         else:
-            raise ValueError(f"unsupported optimizer: {optimizer!r} (Adam | SGD)")
+            raise ValueError(f"unsupported optimizer: {optimizer!r} (Adam | AdamW | SGD)")
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         self.overlap = overlap_comm
