@@ -14,28 +14,43 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--precision", default="f16x3", choices=["f32", "f16x3"],
                     help="f16x3 (default): fp16x3 split products on the 3x3 convolutions, fp32-class accuracy; f32: exact-fp32 matrix instruction")
+    ap.add_argument("--freeze", action="store_true", help="freeze the weights (WatermarkPredictor(freeze=True)): BatchNorm scale / shift and filter banks made once")
+    ap.add_argument("--u8", action="store_true", help="time uint8 images -> masks through uwm_predict_u8 (predict_mask_u8) instead of fp32 NCHW input -> masks")
     a = ap.parse_args()
-    from unet_watermark_amd.predict import WatermarkPredictor
+    from unet_watermark_amd.predict import WatermarkPredictor, IMAGENET_MEAN, IMAGENET_STD
     from unet_watermark_amd.config import get_cfg_defaults
     cfg = get_cfg_defaults(); cfg.MODEL.NAME = "Unet"; cfg.MODEL.ENCODER_NAME = a.encoder      # BASELINE configs[4] names Unet
     torch.manual_seed(42)
-    pred = WatermarkPredictor(config=cfg, device="cuda", precision=a.precision)
-    x = torch.randn(a.batch, 3, a.size, a.size, device="cuda")
+    pred = WatermarkPredictor(config=cfg, device="cuda", precision=a.precision, **({"freeze": True} if a.freeze else {}))
+    if a.u8:
+        xu = torch.randint(0, 256, (a.batch, a.size, a.size, 3), dtype=torch.uint8, device="cuda")
+        x = pred.preprocess(xu)
+        step = lambda: pred.predict_mask_u8(xu, use_graph=not a.no_graph)
+    else:
+        x = torch.randn(a.batch, 3, a.size, a.size, device="cuda")
+        step = lambda: pred.predict_mask(x, use_graph=not a.no_graph)
     for _ in range(2):
-        m = pred.predict_mask(x, use_graph=not a.no_graph)
+        m = step()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.batches):
-        m = pred.predict_mask(x, use_graph=not a.no_graph)
+        m = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     fwd, _ = pred.model.conv_flops(a.size, a.size)
     n = a.batch * a.batches
     # per-image equality of the batched, graph-replayed path with the batch-1 eager path
-    lb = pred.logits(x, use_graph=not a.no_graph).clone()
+    # (--u8: the logits uwm_predict_u8 itself computes from the bytes, against the batch-1 preprocess -> forward path)
+    lb = pred.model.predict_u8(xu, IMAGENET_MEAN, IMAGENET_STD, pred.threshold, return_logits=True)[1].clone() if a.u8 else pred.logits(x, use_graph=not a.no_graph).clone()
     eq = True
     for i in (0, a.batch // 2, a.batch - 1):
         eq = eq and bool(torch.equal(pred.logits(x[i:i + 1], use_graph=False)[0], lb[i]))
+    extra = {}
+    if a.freeze or a.u8:
+        # weight-preparation launches one forward of this batch enqueues (a replayed graph holds the same kernels): 0 when frozen
+        p0 = pred.model.prep_launches()
+        pred.logits(x, use_graph=False)
+        extra = {"frozen": bool(pred.model.frozen), "prep_launches_per_batch": pred.model.prep_launches() - p0, "input": "u8" if a.u8 else "f32"}
     print(json.dumps({"metric": "predict_images_per_sec", "value": round(n / dt, 2), "unit": "images/s", "n_gpus": 1,
                       "images": n, "batch": a.batch, "ms_per_batch": round(1e3 * dt / a.batches, 3),
                       "dtype": "f32" if a.precision == "f32" else "f32 storage / accumulation, 3x3 conv products as fp16x3 splits (22-bit operands) on v_mfma_f32_16x16x32_f16",
@@ -43,7 +58,7 @@ def main():
                       "data": "synthetic", "hipgraph": not a.no_graph,
                       "config": {"workload": f"Unet-{a.encoder} {a.size}x{a.size} eval forward + logit threshold, bs{a.batch} (BASELINE configs[4])"},
                       "model_tflops": round(n * fwd / dt / 1e12, 2), "mask_positive_frac": round(float((m > 0).float().mean()), 4),
-                      "bitwise_equal_to_batch1_path": eq}))
+                      "bitwise_equal_to_batch1_path": eq, **extra}))
 
 
 if __name__ == "__main__":

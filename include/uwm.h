@@ -109,6 +109,55 @@ int  uwm_conv_flops(uwm_handle h, int H, int W, double* fwd, double* fwd_bwd);
 int  uwm_forward(uwm_handle h, const float* x_nchw, float* logits, void* workspace, size_t workspace_bytes,
                  int N, int H, int W, int training, uwm_stream stream);
 
+/* ---- Frozen-weight inference.  An eval forward derives three things from the parameters and buffers alone: the scale / shift of
+ * every BatchNorm (from gamma, beta and the running statistics), the forward filter bank of every layer that has one (fp32
+ * Winograd, bf16x3 Winograd or fp16x3, as the modes ask) and the stem's fp16x3 bank.  An unfrozen handle recomputes them in every
+ * uwm_forward(training = 0).  A FROZEN handle computed them once, in uwm_freeze, into a caller-owned device arena; its eval
+ * forwards read the arena and launch no weight-preparation kernel.  The results do not change: the same convolution kernels
+ * run on banks with the same bits and on the same scale / shift values, so frozen logits equal unfrozen ones bit for bit.
+ *
+ * uwm_frozen_bytes: size of the arena = 2 floats per BatchNorm channel + one forward bank slot per layer that has one (stem
+ * included); it follows from the model alone, not from a shape.  No dgrad banks, no repacks: the backward has no part in this.
+ *
+ * uwm_freeze fills `frozen` (16-byte aligned, >= uwm_frozen_bytes) from the bound arenas under the handle's CURRENT precision
+ * mode, Winograd mode, fill threshold and routing batch, for the bank forms an eval forward of shape (N, H, W) selects.
+ * Asynchronous on `stream`; forwards that use the arena must be ordered behind it.  The library writes the arena nowhere else:
+ * it is immutable until uwm_unfreeze or the next uwm_freeze, so a hipGraph captured from a frozen forward stays valid while
+ * eager forwards of other shapes run between its replays (the workspace's own copy of these items offers no such promise).
+ *
+ * uwm_forward(training = 0) and uwm_predict_u8 on a frozen handle: if every layer's bank form for the call's (N, H, W) under the
+ * current modes equals the frozen one (uwm_frozen_serves tells in advance), scale / shift and banks come from the arena.
+ * Otherwise the call takes the unfrozen path, in the workspace, and leaves the arena alone: same result, just not faster.
+ * With the routing pinned (uwm_set_precision_fill(h, 1) or a routing batch) the forms no longer depend on N, and an arena
+ * frozen at one batch serves every batch of that image size.
+ *
+ * What unfreezes: uwm_unfreeze; uwm_bind; uwm_forward(training = 1) (the running statistics move).  A caller that changes the
+ * parameters or buffers in ANY other way (an optimizer step, a copy into the arenas, ...) must call uwm_unfreeze or uwm_freeze
+ * again itself: the library cannot see such writes, and a frozen forward would go on using the old values.
+ *
+ * uwm_prep_launches: host-side counter (like the routing record: no device work, no effect on results) of the weight-preparation
+ * launches this handle has enqueued since uwm_create: one per BatchNorm scale / shift launch (per layer in an unfrozen eval
+ * forward, one bn_eval_multi launch per 128 BatchNorms in uwm_freeze), one per batch of forward bank builders, one per stem
+ * bank builder; uwm_freeze's own launches count.  It stands still across forwards served from the arena. */
+size_t uwm_frozen_bytes(uwm_handle h);
+int  uwm_freeze(uwm_handle h, void* frozen, size_t bytes, int N, int H, int W, uwm_stream stream);
+int  uwm_unfreeze(uwm_handle h);
+int  uwm_is_frozen(uwm_handle h);
+int  uwm_frozen_serves(uwm_handle h, int N, int H, int W);     /* 1: an eval forward of this shape would read the arena now */
+long long uwm_prep_launches(uwm_handle h);
+
+/* Image bytes to mask bytes in one call: images uint8 [N][H][W][C] (C = the model's in_channels, 4-byte aligned) are normalised
+ * ((v / 255 - mean) / std, mean / std host pointers) straight into the forward's NHWC4 input buffer, the eval forward runs
+ * (frozen or not), and the logit plane of class 0 is resized to out_h x out_w and thresholded as uwm_resize_threshold does:
+ * mask uint8 [N][out_h][out_w] in {0, 255}.  logits (may be NULL): [N][H][W][CP] as uwm_forward writes them; with NULL they
+ * live behind the plan in the workspace, which must then hold uwm_predict_workspace_bytes(h, N, H, W, 1) bytes (else
+ * uwm_workspace_bytes(h, N, H, W, 0) = uwm_predict_workspace_bytes(.., 0)).  Masks and logits equal, bit for bit, the sequence
+ * uwm_preprocess_u8(flags = NULL) -> uwm_forward(training = 0) -> uwm_resize_threshold.  Capturable in a hipGraph like uwm_forward. */
+size_t uwm_predict_workspace_bytes(uwm_handle h, int N, int H, int W, int with_logits);
+int  uwm_predict_u8(uwm_handle h, const uint8_t* images, const float* mean, const float* std, float threshold,
+                    int apply_sigmoid, int out_h, int out_w, uint8_t* mask, float* logits, void* workspace,
+                    size_t workspace_bytes, int N, int H, int W, uwm_stream stream);
+
 /* Backward of the last training forward held in `workspace`; writes (overwrites) the gradient arena
  * ranges of stages [stage_begin, stage_end).  Call with (0, uwm_num_stages) for everything, or stage
  * by stage to overlap gradient all-reduce with the rest of the backward. */
@@ -282,7 +331,10 @@ const char* uwm_prof_class_name(int cls);
 /* Workspace introspection for parity tests: element offset (in floats from the workspace base) and
  * element count of a planned intermediate.  Keys: "y:<conv>", "g:<conv>" (raw conv output / its
  * gradient; <conv> = state_dict prefix such as "encoder.layer1.0.conv1"), "xn:<i>", "gx:<i>"
- * (encoder block i output / masked gradient), "pool", "g_pool", "x4", "dcat:<i>", "gskip:<i>". */
+ * (encoder block i output / masked gradient), "pool", "g_pool", "x4", "dcat:<i>", "gskip:<i>".
+ * The fixed (shape-independent) region needs no plan: "fixed" (all of it, offset 0), "bnf:<bn>" (a BatchNorm's {scale[C],
+ * shift[C]}; <bn> = state_dict prefix such as "encoder.bn1"), "wu:<conv>" / "wud:<conv>" / "wd:<conv>" (a conv's forward bank
+ * slot / dgrad bank slot / dgrad repack; count 0 where the layer has none). */
 int  uwm_debug_lookup(uwm_handle h, const char* key, long long* offset, long long* count);
 
 /* ---- single-operator entry points (used by the parity tests) ---- */
@@ -297,6 +349,10 @@ typedef struct {
  * kernel; 700 sub-pixel kernel for a 3x3 over a nearest-x2 upsampled 32-channel source with 16 outputs (conv_up2.hip);
  * 800 (+64 | +128 = channel tile) persistent LDS-DMA GEMM for 1x1 / stride-1 layers with Cin % 32 == 0 (conv_gemm.hip)
  * (tests / timing). */
+/* preprocess_u8_nhwc4 alone (uwm_predict_u8's input kernel): uint8 [npix][C] (4-byte aligned, C 1..4) -> Normalize as fp32 [npix][4]
+ * (16-byte aligned), padding channels zero; any pixel count */
+int  uwm_op_preprocess_u8_nhwc4(const uint8_t* images, long long npix, int C, const float* mean, const float* std, float* out,
+                                uwm_stream stream);
 int  uwm_op_set_igemm_f16x3(int on);   /* tests / kernel timing: uwm_op_conv / uwm_op_dgrad launches that end on the implicit GEMM (stride 2, 1x1) use its fp16x3 split-product form (what the model does for the stride-2 layers in the fp16x3 precision modes) */
 int  uwm_op_conv(const uwm_src* s0, const uwm_src* s1, const float* w, int wrows, int Kpad, int kh, int kw, int stride,
                  int pad, int N, int Cout, const float* bias, float* y, double* stats, int cfg, uwm_stream stream);

@@ -70,6 +70,15 @@ SIGNATURES = {
     "uwm_conv_flops": (I, [P, I, I, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "uwm_forward": (I, [P, P, P, P, Z, I, I, I, I, P]),
     "uwm_backward": (I, [P, P, P, I, I, P]),
+    "uwm_frozen_bytes": (Z, [P]),
+    "uwm_freeze": (I, [P, P, Z, I, I, I, P]),
+    "uwm_unfreeze": (I, [P]),
+    "uwm_is_frozen": (I, [P]),
+    "uwm_frozen_serves": (I, [P, I, I, I]),
+    "uwm_prep_launches": (L, [P]),
+    "uwm_predict_workspace_bytes": (Z, [P, I, I, I, I]),
+    "uwm_predict_u8": (I, [P, P, C.POINTER(C.c_float), C.POINTER(C.c_float), F, I, I, I, P, P, P, Z, I, I, I, P]),
+    "uwm_op_preprocess_u8_nhwc4": (I, [P, L, I, C.POINTER(C.c_float), C.POINTER(C.c_float), P, P]),
     "uwm_loss": (I, [P, I, P, I, L, F, F, F, F, P, P, P, I, F, P]),
     "uwm_loss_sums": (I, [P, I, P, I, L, P, P]),
     "uwm_loss_apply": (I, [P, I, P, I, L, L, F, F, F, F, P, P, P, I, F, P]),

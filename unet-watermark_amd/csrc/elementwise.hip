@@ -88,13 +88,36 @@ hipError_t launch_bn_finalize(const double* ssum, const double* ssq, const float
   return hipGetLastError();
 }
 
+// eval-mode scale / shift of one channel.  ONE function for bn_eval_kernel and bn_eval_multi_kernel, with the fused multiply-add
+// written out (what the plain expression beta - rm * gamma * rs contracts to), so that both produce the same bits
+__device__ __forceinline__ void bn_eval_one(float gamma, float beta, float rm, float rv, float eps, float* scale, float* shift) {
+  const double rs = 1.0 / sqrt((double)rv + (double)eps);
+  *scale = (float)((double)gamma * rs);
+  *shift = (float)fma(-rs, (double)rm * (double)gamma, (double)beta);
+}
 __global__ void bn_eval_kernel(const float* gamma, const float* beta, const float* rm, const float* rv, float* scale,
                                float* shift, int C, float eps) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const double rs = 1.0 / sqrt((double)rv[c] + (double)eps);
-  scale[c] = (float)((double)gamma[c] * rs);
-  shift[c] = (float)((double)beta[c] - (double)rm[c] * (double)gamma[c] * rs);
+  bn_eval_one(gamma[c], beta[c], rm[c], rv[c], eps, scale + c, shift + c);
+}
+// every BatchNorm of a model in one launch (uwm_freeze): blockIdx.y = job, blockIdx.x = 64-channel chunk of it
+__global__ void bn_eval_multi_kernel(const float* __restrict__ params, const float* __restrict__ buffers, float* __restrict__ out,
+                                     const BnEvalJobs jobs) {
+  const BnEvalJob j = jobs.j[blockIdx.y];
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= j.C) return;
+  const float* g = params + j.g_off; const float* r = buffers + j.rm_off;
+  float* o = out + j.out_off;
+  bn_eval_one(g[c], g[j.C + c], r[c], r[j.C + c], j.eps, o + c, o + j.C + c);
+}
+hipError_t launch_bn_eval_multi(const float* params, const float* buffers, float* out, const BnEvalJobs& jobs, hipStream_t st) {
+  if (jobs.n <= 0) return hipSuccess;
+  if (jobs.n > BnEvalJobs::kMax) return hipErrorInvalidValue;
+  int mc = 0;
+  for (int i = 0; i < jobs.n; ++i) mc = jobs.j[i].C > mc ? jobs.j[i].C : mc;
+  hipLaunchKernelGGL(bn_eval_multi_kernel, dim3((unsigned)((mc + 63) / 64), (unsigned)jobs.n), dim3(64), 0, st, params, buffers, out, jobs);
+  return hipGetLastError();
 }
 hipError_t launch_bn_eval(const float* gamma, const float* beta, const float* run_mean, const float* run_var,
                           float* scale, float* shift, int C, float eps, hipStream_t st) {
@@ -475,6 +498,15 @@ hipError_t launch_upsplit(const float* dcat, int N, int H, int W, int C0, int C1
 // bits 2-3 = k of rot90 (counter-clockwise, numpy/torch convention; needs H == W), applied in albumentations'
 // pipeline order: flips first, then the rotation.
 struct PreArgs { float mul[4], add[4]; };
+// Normalize of one byte: ONE function (explicit fused multiply-add) for preprocess_u8_kernel and preprocess_u8_nhwc4_kernel, so that
+// the stem sees the same bits on either path
+__device__ __forceinline__ float pre_norm(uint32_t b, float mul, float add) { return fmaf((float)b, mul, add); }
+static PreArgs make_pre_args(int C, const float* mean, const float* std) {
+  PreArgs pa;
+  for (int c = 0; c < 4; ++c) { pa.mul[c] = 0.f; pa.add[c] = 0.f; }
+  for (int c = 0; c < C; ++c) { pa.mul[c] = 1.f / (255.f * std[c]); pa.add[c] = -mean[c] / std[c]; }
+  return pa;
+}
 __device__ __forceinline__ void aug_src(int flags, int H, int W, int y, int x, int& sy, int& sx) {
   // output (y, x) of rot90^k(flip(img)) -> coordinates in the flipped image, then undo the flips
   const int k = (flags >> 2) & 3;
@@ -493,7 +525,44 @@ __global__ void preprocess_u8_kernel(const uint8_t* __restrict__ img, int H, int
     const int y = (int)(r % H); const int n = (int)(r / H);
     int sy, sx; aug_src(flags ? flags[n] : 0, H, W, y, x, sy, sx);
     const uint8_t* p = img + (((size_t)n * H + sy) * W + sx) * C;
-    for (int c = 0; c < C; ++c) out[(((size_t)n * C + c) * H + y) * W + x] = (float)p[c] * pa.mul[c] + pa.add[c];
+    for (int c = 0; c < C; ++c) out[(((size_t)n * C + c) * H + y) * W + x] = pre_norm(p[c], pa.mul[c], pa.add[c]);
+  }
+}
+// uint8 [npix][C] -> normalised fp32 [npix][4] (padding channels zero): the forward's NHWC4 input without the NCHW fp32 round trip
+// (uwm_predict_u8).  A workgroup takes 1024 pixels: their 1024 * C bytes are 256 * C aligned dwords, read one per lane (coalesced)
+// into LDS; then lane t converts pixels t, t + 256, t + 512, t + 768, so that every store instruction of a wave writes 64
+// consecutive pixels = 1 KB of whole lines.  (First form: 4 consecutive pixels per thread straight from registers — each store
+// instruction then touched 64 different lines, 16 bytes of each: 42 us for 8 x 512 x 512, under 1 TB/s.)  The last dword of an
+// image buffer whose byte count is no multiple of 4 is read byte by byte.
+template <int C>
+__global__ __launch_bounds__(256) void preprocess_u8_nhwc4_kernel(const uint8_t* __restrict__ img, PreArgs pa, float* __restrict__ out,
+                                                                  size_t npix) {
+  __shared__ uint32_t raw[256 * C];
+  const int t = threadIdx.x;
+  const size_t p0 = (size_t)blockIdx.x * 1024, nbytes = npix * C, b0 = p0 * C;      // (b0 % 4 == 0)
+  const uint32_t* src = (const uint32_t*)(img + b0);
+#pragma unroll
+  for (int i = 0; i < C; ++i) {
+    const int d = t + 256 * i;
+    const size_t b = b0 + 4 * (size_t)d;
+    uint32_t v = 0u;
+    if (b + 4 <= nbytes) v = __builtin_nontemporal_load(src + d);
+    else
+      for (int k = 0; k < 4; ++k) if (b + k < nbytes) v |= (uint32_t)img[b + k] << (8 * k);
+    raw[d] = v;
+  }
+  __syncthreads();
+  const uint8_t* rb = (const uint8_t*)raw;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int p = t + 256 * k;
+    if (p0 + p < npix) {
+      float v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < C; ++c) v[c] = pre_norm(rb[p * C + c], pa.mul[c], pa.add[c]);
+      f4 o; o.x = v[0]; o.y = v[1]; o.z = v[2]; o.w = v[3];
+      __builtin_nontemporal_store(o, (f4*)(out + (p0 + p) * 4));
+    }
   }
 }
 __global__ void preprocess_mask_kernel(const uint8_t* __restrict__ m, int H, int W, int thr, const int* __restrict__ flags,
@@ -508,11 +577,22 @@ __global__ void preprocess_mask_kernel(const uint8_t* __restrict__ m, int H, int
 hipError_t launch_preprocess_u8(const uint8_t* img, int N, int H, int W, int C, const float* mean, const float* std,
                                 const int* flags, float* out, hipStream_t st) {
   if (C < 1 || C > 4) return hipErrorInvalidValue;
-  PreArgs pa;
-  for (int c = 0; c < 4; ++c) { pa.mul[c] = 0.f; pa.add[c] = 0.f; }
-  for (int c = 0; c < C; ++c) { pa.mul[c] = 1.f / (255.f * std[c]); pa.add[c] = -mean[c] / std[c]; }
+  const PreArgs pa = make_pre_args(C, mean, std);
   const size_t total = (size_t)N * H * W;
   hipLaunchKernelGGL(preprocess_u8_kernel, dim3(nblocks(total, 256)), dim3(256), 0, st, img, H, W, C, pa, flags, out, total);
+  return hipGetLastError();
+}
+hipError_t launch_preprocess_u8_nhwc4(const uint8_t* img, size_t npix, int C, const float* mean, const float* std, float* out,
+                                      hipStream_t st) {
+  if (C < 1 || C > 4 || npix < 1 || ((uintptr_t)img & 3) || ((uintptr_t)out & 15)) return hipErrorInvalidValue;
+  const PreArgs pa = make_pre_args(C, mean, std);
+  const dim3 grid((unsigned)((npix + 1023) / 1024)), block(256);
+  switch (C) {
+    case 1: hipLaunchKernelGGL(preprocess_u8_nhwc4_kernel<1>, grid, block, 0, st, img, pa, out, npix); break;
+    case 2: hipLaunchKernelGGL(preprocess_u8_nhwc4_kernel<2>, grid, block, 0, st, img, pa, out, npix); break;
+    case 3: hipLaunchKernelGGL(preprocess_u8_nhwc4_kernel<3>, grid, block, 0, st, img, pa, out, npix); break;
+    default: hipLaunchKernelGGL(preprocess_u8_nhwc4_kernel<4>, grid, block, 0, st, img, pa, out, npix); break;
+  }
   return hipGetLastError();
 }
 hipError_t launch_preprocess_mask(const uint8_t* m, int N, int H, int W, int thr, const int* flags, uint8_t* out, hipStream_t st) {

@@ -79,6 +79,7 @@ int uwm_bind(uwm_handle h, float* params, float* grads, float* buffers) {
   }
   h->device = dev;
   h->params = params; h->grads = grads; h->buffers = buffers;
+  h->frozen = nullptr;                  // other arenas: whatever was frozen no longer describes them
   DeviceGuard guard(dev);
   if (h->use_side && !h->side) {        // created on the device the arenas live on
     // LOWEST queue priority: the weight gradients are off the critical path, the dgrad / BatchNorm-backward chain on the caller's
@@ -157,6 +158,92 @@ int uwm_forward(uwm_handle h, const float* x, float* logits, void* ws, size_t ws
   DeviceGuard guard(h->device);
   if (do_forward(h, x, logits, (float*)ws, N, H, W, training ? 1 : 0, (hipStream_t)stream)) return 1;
   h->have_fwd = training != 0;
+  return 0;
+}
+
+// ---- frozen-weight inference: the parameter-derived items of the eval forward, made once into a caller-owned arena
+size_t uwm_frozen_bytes(uwm_handle h) { return h ? h->frozen_floats * sizeof(float) : 0; }
+int uwm_is_frozen(uwm_handle h) { return h && h->frozen ? 1 : 0; }
+int uwm_unfreeze(uwm_handle h) {
+  if (!h) return fail("uwm_unfreeze: null handle");
+  h->frozen = nullptr; return 0;
+}
+long long uwm_prep_launches(uwm_handle h) { return h ? h->prep_launches : 0; }
+// the plan of an eval forward of (N, H, W) for the time of one call that only needs its routing (the held plan — a training forward
+// waiting for its backward, say — comes back afterwards)
+struct PlanScope {
+  uwm_model* m; Plan keep; bool have_fwd;
+  PlanScope(uwm_model* m_, int N, int H, int W) : m(m_), keep(m_->plan), have_fwd(m_->have_fwd) { make_plan(m, N, H, W, 0); }
+  ~PlanScope() { m->plan = keep; m->have_fwd = have_fwd; }
+};
+int uwm_freeze(uwm_handle h, void* frozen, size_t bytes, int N, int H, int W, uwm_stream stream) {
+  if (!h || !frozen) return fail("uwm_freeze: null argument");
+  if (check_shape(N, H, W)) return 1;
+  if ((uintptr_t)frozen & 15) return fail("uwm_freeze: the arena must be 16-byte aligned");
+  if (bytes < uwm_frozen_bytes(h)) return fail("uwm_freeze: arena too small (%zu < %zu bytes)", bytes, uwm_frozen_bytes(h));
+  if (!h->params || !h->buffers) return fail("uwm_freeze: call uwm_bind first");
+  if (h->param_floats >= (1LL << 32) || h->buffer_floats >= (1LL << 32) || h->frozen_floats >= ((size_t)1 << 32))
+    return fail("uwm_freeze: arena offsets do not fit the 32 bits of a BnEvalJob");
+  h->frozen = nullptr;
+  DeviceGuard guard(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  PlanScope scope(h, N, H, W);
+  Ctx c{h, nullptr, st, N};
+  c.fz = (float*)frozen;
+  BnEvalJobs jobs; jobs.n = 0;
+  auto flush = [&]() -> hipError_t { if (jobs.n == 0) return hipSuccess; ++h->prep_launches; hipError_t e = launch_bn_eval_multi(h->params, h->buffers, c.fz, jobs, st); jobs.n = 0; return e; };
+  for (auto& b : h->bns) {
+    BnEvalJob& j = jobs.j[jobs.n++];
+    j.g_off = (unsigned)b.g_off; j.rm_off = (unsigned)b.rm_off; j.out_off = (unsigned)b.fz_off; j.C = b.C;
+    j.eps = b.eps > 0.f ? b.eps : h->desc.bn_eps;
+    if (b.b_off != b.g_off + b.C || b.rv_off != b.rm_off + b.C) return fail("internal: uwm_freeze expects beta behind gamma and the running variance behind the mean");
+    if (jobs.n == BnEvalJobs::kMax) LCHK(flush());
+  }
+  LCHK(flush());
+  LCHK(wino_jobs(c, false, st));
+  if (stem_bank_job(c, st)) return 1;
+  h->fz_form.assign(h->convs.size(), 0);
+  for (size_t ci = 0; ci < h->convs.size(); ++ci) h->fz_form[ci] = (signed char)fwd_bank_form(h, ci);
+  h->frozen = (float*)frozen;
+  return 0;
+}
+int uwm_frozen_serves(uwm_handle h, int N, int H, int W) {
+  if (!h || !h->frozen || check_shape(N, H, W)) return 0;
+  PlanScope scope(h, N, H, W);
+  return frozen_serves(h) ? 1 : 0;
+}
+size_t uwm_predict_workspace_bytes(uwm_handle h, int N, int H, int W, int with_logits) {
+  const size_t need = uwm_workspace_bytes(h, N, H, W, 0);
+  return need && with_logits ? need + (size_t)N * H * W * h->CP * sizeof(float) : need;
+}
+int uwm_predict_u8(uwm_handle h, const uint8_t* images, const float* mean, const float* std, float threshold, int apply_sigmoid,
+                   int out_h, int out_w, uint8_t* mask, float* logits, void* ws, size_t ws_bytes, int N, int H, int W,
+                   uwm_stream stream) {
+  if (!h || !images || !mean || !std || !mask || !ws) return fail("uwm_predict_u8: null argument");
+  if (!h->params || !h->buffers) return fail("uwm_predict_u8: call uwm_bind first");
+  if (check_shape(N, H, W)) return 1;
+  if (out_h < 1 || out_w < 1) return fail("uwm_predict_u8: bad output size %d x %d", out_h, out_w);
+  const int C = h->desc.in_channels;
+  for (int c = 0; c < C; ++c) if (!(std[c] > 0.f)) return fail("uwm_predict_u8: std[%d] must be positive", c);
+  if ((uintptr_t)images & 3) return fail("uwm_predict_u8: images must be 4-byte aligned");
+  if (((uintptr_t)logits | (uintptr_t)ws) & 15) return fail("uwm_predict_u8: logits and workspace must be 16-byte aligned");
+  const size_t need = uwm_predict_workspace_bytes(h, N, H, W, logits ? 0 : 1);
+  if (ws_bytes < need) return fail("uwm_predict_u8: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+  float* lg = logits ? logits : (float*)ws + h->plan.bytes / sizeof(float);      // (no caller buffer: behind the plan)
+  h->have_fwd = false;
+  DeviceGuard guard(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  LCHK(launch_preprocess_u8_nhwc4(images, (size_t)N * H * W, C, mean, std, (float*)ws + h->plan.x4, st));
+  if (do_forward(h, nullptr, lg, (float*)ws, N, H, W, 0, st)) return 1;
+  LCHK(launch_resize_threshold(lg, h->CP, N, H, W, out_h, out_w, threshold, apply_sigmoid, mask, nullptr, st));
+  return 0;
+}
+int uwm_op_preprocess_u8_nhwc4(const uint8_t* images, long long npix, int C, const float* mean, const float* std, float* out,
+                               uwm_stream stream) {
+  if (!images || !mean || !std || !out || npix < 1 || C < 1 || C > 4) return fail("uwm_op_preprocess_u8_nhwc4: bad argument");
+  if (((uintptr_t)images & 3) || ((uintptr_t)out & 15)) return fail("uwm_op_preprocess_u8_nhwc4: images must be 4-byte, out 16-byte aligned");
+  for (int c = 0; c < C; ++c) if (!(std[c] > 0.f)) return fail("uwm_op_preprocess_u8_nhwc4: std[%d] must be positive", c);
+  LCHK(launch_preprocess_u8_nhwc4(images, (size_t)npix, C, mean, std, out, (hipStream_t)stream));
   return 0;
 }
 
@@ -302,8 +389,25 @@ const char* uwm_prof_class_name(int cls) { return prof_class_name(cls); }
 int uwm_debug_lookup(uwm_handle h, const char* key, long long* off, long long* count) {
   if (!h || !key || !off || !count) return fail("uwm_debug_lookup: null argument");
   const Plan& p = h->plan;
-  if (p.N == 0) return fail("uwm_debug_lookup: no plan yet");
   const std::string k(key);
+  // the fixed region (shape-independent): "fixed" = all of it; "bnf:<bn>" = a BatchNorm's {scale, shift}; "wu:<conv>" / "wud:<conv>" /
+  // "wd:<conv>" = a conv's forward bank slot / dgrad bank slot / dgrad repack (count 0 where the layer has none)
+  if (k == "fixed") { *off = 0; *count = (long long)h->fixed_floats; return 0; }
+  if (k.rfind("bnf:", 0) == 0) {
+    for (auto& b : h->bns) if (b.name == k.substr(4)) { *off = (long long)(b.f_off + 2 * (size_t)b.C); *count = 2LL * b.C; return 0; }
+    return fail("uwm_debug_lookup: unknown BatchNorm %s", k.c_str() + 4);
+  }
+  if (k.rfind("wu:", 0) == 0 || k.rfind("wud:", 0) == 0 || k.rfind("wd:", 0) == 0) {
+    const std::string name = k.substr(k.find(':') + 1);
+    for (auto& cv : h->convs) if (cv.name == name) {
+      if (k[1] == 'd') { *off = (long long)cv.wd_off; *count = cv.dgrad ? (long long)cv.CinP * cv.KpadD : 0; }
+      else if (k[2] == 'd') { *off = (long long)cv.wud_off; *count = cv.wud_off ? (long long)std::max(wino_weights_floats(cv.CinP, cv.CoutP), cv.f3_d() ? f16x3_bank_floats(cv.CinP, cv.CoutP) : 0) : 0; }
+      else { *off = (long long)cv.wu_off; *count = (long long)cv.wu_floats; }
+      return 0;
+    }
+    return fail("uwm_debug_lookup: unknown conv %s", name.c_str());
+  }
+  if (p.N == 0) return fail("uwm_debug_lookup: no plan yet");
   const int N = p.N, H = p.H, W = p.W;
   auto conv_geo = [&](int ci, long long* cnt) { *cnt = (long long)N * p.oh[ci] * p.ow[ci] * h->convs[ci].CoutP; };
   if (k.rfind("y:", 0) == 0 || k.rfind("g:", 0) == 0) {

@@ -1,9 +1,24 @@
 // libuwm, part of uwm_model.hip (one translation unit; included from there): uwm_forward: the encoder / decoder walk.
 // ------------------------------------------------------------------------------ forward
+// the stem bank builder where the handle's modes put the stem on conv_stem_f16x3 (into Ctx::wu: workspace, or the frozen arena from uwm_freeze)
+static int stem_bank_job(const Ctx& c, hipStream_t st) {
+  uwm_model* m = c.m;
+  if (!stem_f3_on(m)) return 0;
+  const ConvL& sv = m->convs[m->stem];
+  ++m->prep_launches;
+  LCHK(launch_stem_f16x3_weights(m->params + sv.w_off, sv.Kpad, sv.CinP, c.wu(sv), st));
+  return 0;
+}
+// x == nullptr: the caller has filled plan.x4 (the NHWC4 input) itself (uwm_predict_u8)
 static int do_forward(uwm_model* m, const float* x, float* logits, float* ws, int N, int H, int W, int training,
                       hipStream_t st) {
   const Plan& p = m->plan;
   Ctx c{m, ws, st, N};
+  if (training) m->frozen = nullptr;          // the running statistics move: what the arena holds is stale after this call
+  // frozen handle, and every layer's bank form for this shape is the frozen one: scale / shift and banks come from the arena and no
+  // preparation kernel is launched; else today's path, in the workspace (the arena is written by uwm_freeze alone)
+  const bool fz = !training && frozen_serves(m);
+  if (fz) c.fz = m->frozen;
   if (m->prec_from_env) {               // say once which arithmetic a process default switched on (a stray variable must not go unnoticed)
     static const char* names[7] = {"f32", "bf16x3", "bf16x3_all", "f16x3", "f16x3_all", "f16x1", "f16x3_bwd2"};
     fprintf(stderr, "libuwm: precision mode %s for this handle comes from UWM_PRECISION (uwm_set_precision overrides it)\n", names[m->prec]);
@@ -30,11 +45,10 @@ static int do_forward(uwm_model* m, const float* x, float* logits, float* ws, in
     HIPCHK(hipEventRecord(m->ev_pack, m->side));
     m->packed_in_fwd = true; m->pack_mode = pack_key(m);
   }
-  LCHK(wino_jobs(c, false, st));
-  if (stem_f3_on(m)) { const ConvL& sv = m->convs[m->stem]; LCHK(launch_stem_f16x3_weights(m->params + sv.w_off, sv.Kpad, sv.CinP, c.F(sv.wu_off), st)); }
-  LCHK(launch_nchw_to_nhwc4(x, c.F(p.x4), N, m->desc.in_channels, H, W, m->CinP, st));
+  if (!fz) { LCHK(wino_jobs(c, false, st)); if (stem_bank_job(c, st)) return 1; }
+  if (x) LCHK(launch_nchw_to_nhwc4(x, c.F(p.x4), N, m->desc.in_channels, H, W, m->CinP, st));
   // eval: all BN scale/shift come from running stats and are known up front
-  if (!training) for (size_t i = 0; i < m->bns.size(); ++i) LCHK(run_bn_finalize(c, (int)i, 1, 0));
+  if (!training && !fz) for (size_t i = 0; i < m->bns.size(); ++i) LCHK(run_bn_finalize(c, (int)i, 1, 0));
   auto conv_bn_on = [&](const Ctx& cc, int ci, const Src& s0, const Src* s1, int Ho, int Wo) -> int {
     LCHK(run_conv_fwd(cc, ci, s0, s1, Ho, Wo, cc.F(p.y[ci]), training != 0));
     if (training) LCHK(run_bn_finalize(cc, m->convs[ci].bn, (size_t)N * Ho * Wo, 1));
@@ -87,9 +101,9 @@ static int do_forward(uwm_model* m, const float* x, float* logits, float* ws, in
         if (cd_aside) HIPCHK(hipStreamWaitEvent(st, m->ev_join, 0));
         else if (conv_bn(bl.cd, cur, nullptr, ho, wo)) return 1;
         const BNL& bdn = m->bns[m->convs[bl.cd].bn];
-        idp = c.F(p.y[bl.cd]); sd = c.F(bdn.f_off) + 2 * bdn.C; bd = c.F(bdn.f_off) + 3 * bdn.C;
+        idp = c.F(p.y[bl.cd]); sd = c.bn_ss(bdn); bd = sd + bdn.C;
       }
-      LCHK(launch_residual(c.F(p.y[lc]), c.F(b2.f_off) + 2 * b2.C, c.F(b2.f_off) + 3 * b2.C, idp, sd, bd,
+      LCHK(launch_residual(c.F(p.y[lc]), c.bn_ss(b2), c.bn_ss(b2) + b2.C, idp, sd, bd,
                            c.F(p.xn[bi]), (size_t)N * ho * wo, bl.Cout, st));
       h = ho; w = wo;
       cur = mk_src(c.F(p.xn[bi]), bl.Cout, h, w);
@@ -99,7 +113,7 @@ static int do_forward(uwm_model* m, const float* x, float* logits, float* ws, in
   }
   } else {
     // ---- EfficientNet encoder: every stage of an MBConv block materialised (round-1 correctness-first path)
-    auto bn_ss = [&](int ci, const float** sc, const float** sh_) { const BNL& b = m->bns[m->convs[ci].bn]; *sc = c.F(b.f_off) + 2 * b.C; *sh_ = c.F(b.f_off) + 3 * b.C; };
+    auto bn_ss = [&](int ci, const float** sc, const float** sh_) { const BNL& b = m->bns[m->convs[ci].bn]; *sc = c.bn_ss(b); *sh_ = *sc + b.C; };
     const float *sc, *sf;
     bn_ss(m->stem, &sc, &sf);
     LCHK(launch_swish_fwd(c.F(p.y[m->stem]), sc, sf, m->f1C, c.F(p.stem_a), (size_t)N * h * w, st));

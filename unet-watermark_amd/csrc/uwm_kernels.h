@@ -284,6 +284,11 @@ hipError_t launch_bn_finalize(const double* ssum, const double* ssq, const float
                               int nrep = 1, int rep_stride = 0);
 hipError_t launch_bn_eval(const float* gamma, const float* beta, const float* run_mean, const float* run_var,
                           float* scale, float* shift, int C, float eps, hipStream_t st);
+// eval scale / shift of many BatchNorms in one launch (uwm_freeze).  Job: gamma at params + g_off, beta behind it; running mean at
+// buffers + rm_off, running variance behind it; scale to out + out_off, shift behind it (C floats each).  Same arithmetic as launch_bn_eval.
+struct BnEvalJob { unsigned g_off, rm_off, out_off; int C; float eps; };
+struct BnEvalJobs { static constexpr int kMax = 128; BnEvalJob j[kMax]; int n; };
+hipError_t launch_bn_eval_multi(const float* params, const float* buffers, float* out, const BnEvalJobs& jobs, hipStream_t st);
 // xn = relu(y*s2+b2 + idn), idn = id (materialised) or id*sd+bd (lazy)
 hipError_t launch_residual(const float* y, const float* s2, const float* b2, const float* id, const float* sd,
                            const float* bd, float* out, size_t npix, int C, hipStream_t st);
@@ -327,6 +332,9 @@ hipError_t launch_scale(float* p, size_t n, float s, hipStream_t st);
 hipError_t launch_absmax32(const float* x, size_t n, float* out32, hipStream_t st);      // out32[0..31] <- max|x| (slot workgroup & 31; zeroed first): the xmax contract of the fp16x3 kernels
 hipError_t launch_preprocess_u8(const uint8_t* img, int N, int H, int W, int C, const float* mean, const float* std,
                                 const int* flags, float* out, hipStream_t st);
+// uint8 [npix][C] (4-byte aligned) -> Normalize as fp32 [npix][4], padding channels zero: launch_preprocess_u8's values in the forward's input layout
+hipError_t launch_preprocess_u8_nhwc4(const uint8_t* img, size_t npix, int C, const float* mean, const float* std, float* out,
+                                      hipStream_t st);
 hipError_t launch_preprocess_mask(const uint8_t* m, int N, int H, int W, int thr, const int* flags, uint8_t* out, hipStream_t st);
 
 // EfficientNet MBConv pieces (mbconv.hip): swish, depthwise k x k conv (weights tap-major [k*k][C]) with static "same"

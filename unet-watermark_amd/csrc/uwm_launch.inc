@@ -3,7 +3,11 @@
 struct Ctx {
   uwm_model* m; float* ws; hipStream_t st; int N;
   hipStream_t wst = nullptr;          // stream for wgrad launches (== st when the side stream is off)
+  float* fz = nullptr;                // frozen arena, when this (eval) forward reads it (frozen_serves); null = everything in the workspace
   float* F(size_t off) const { return ws + off; }
+  // the one place that decides "arena or workspace": a BatchNorm's {scale[C], shift[C]} and a conv's forward bank
+  const float* bn_ss(const BNL& b) const { return fz ? fz + b.fz_off : ws + b.f_off + 2 * b.C; }
+  float* wu(const ConvL& cv) const { return fz ? fz + cv.fz_wu : ws + cv.wu_off; }
   double* D(size_t doff) const { return (double*)ws + doff; }
 };
 static Src mk_src(const float* ptr, int C, int H, int W, const float* scale = nullptr, const float* shift = nullptr,
@@ -13,7 +17,7 @@ static Src mk_src(const float* ptr, int C, int H, int W, const float* scale = nu
 static Src lazy_src(const Ctx& c, int conv, int H, int W, int relu = 1, int up = 0) {
   const ConvL& cv = c.m->convs[conv];
   const BNL& b = c.m->bns[cv.bn];
-  return mk_src(c.F(c.m->plan.y[conv]), cv.CoutP, H, W, c.F(b.f_off) + 2 * b.C, c.F(b.f_off) + 3 * b.C, relu, up);
+  return mk_src(c.F(c.m->plan.y[conv]), cv.CoutP, H, W, c.bn_ss(b), c.bn_ss(b) + b.C, relu, up);
 }
 
 // a launch helper that found a contract violation of its own: the message is set here and LCHK passes it on unchanged
@@ -70,12 +74,12 @@ static hipError_t run_conv_fwd(const Ctx& c, int ci, const Src& s0, const Src* s
   a.bytes = 4.0 * ((double)c.N * s0.H * s0.W * s0.C + (s1 ? (double)c.N * s1->H * s1->W * s1->C : 0.0) + (double)cv.Cout * cv.Kpad +
                    (double)a.M * cv.CoutP);
   if (ci == c.m->stem && cfg < 0 && stem_f3_on(c.m)) {
-    a.wu = c.F(cv.wu_off);
+    a.wu = c.wu(cv);
     if (conv_stem_f16x3_applicable(a)) return route_rec(c, "fwd", ci, launch_conv_stem_f16x3(a, c.st));
     a.wu = nullptr;
   }
   if (cv.wu_off && !cv.stem7() && a.Ctot == cv.CinP && c.m->plan.wino_ok((size_t)ci)) {
-    a.wu = c.F(cv.wu_off); a.wu_ncb = wino_ncb(cv.Cout);
+    a.wu = c.wu(cv); a.wu_ncb = wino_ncb(cv.Cout);
     if (c.m->plan.prec == UWM_PREC_BF16X3_ALL && cv.x3()) {
       if (a.C0 != cv.c0 && a.C0 != a.Ctot) return hipErrorInvalidValue;       // the bank was split for this concat boundary
       a.prec = 1;
@@ -198,6 +202,7 @@ static hipError_t run_bn_finalize(const Ctx& c, int bi, size_t count, int traini
     return launch_bn_finalize(c.D(b.d_off) + 2 * b.C, c.D(b.d_off) + 3 * b.C, m->params + b.g_off, m->params + b.b_off,
                               m->buffers + b.rm_off, m->buffers + b.rv_off, f, f + b.C, f + 2 * b.C, f + 3 * b.C, b.C,
                               (double)count, eps, mom, 1, c.st, b.nrep, 2 * b.C);
+  ++m->prep_launches;
   return launch_bn_eval(m->params + b.g_off, m->params + b.b_off, m->buffers + b.rm_off, m->buffers + b.rv_off,
                         f + 2 * b.C, f + 3 * b.C, b.C, eps, c.st);
 }
@@ -248,16 +253,17 @@ static hipError_t run_bn_bwd_act(const Ctx& c, int ci, const float* g, float* dy
 
 // Winograd filter transforms of every eligible layer (forward banks, or dgrad banks straight from the forward
 // weights), at most 40 layers per launch
+// (forward banks go where Ctx::wu points: the workspace, or the frozen arena when uwm_freeze fills it)
 static hipError_t wino_jobs(const Ctx& c, bool dgrad, hipStream_t st) {
   if (c.m->plan.wino_mode == 0) return hipSuccess;
-  const uwm_model* m = c.m;
+  uwm_model* m = c.m;
   // three passes: fp32 banks, then (bf16x3 modes) the split-bf16 banks of the layers that run on conv_wino_x3, then (fp16x3
   // modes) the split-fp16 banks of the layers that run on conv_f16x3
   const int prec = m->plan.prec;
   const bool bf = prec == UWM_PREC_BF16X3 || prec == UWM_PREC_BF16X3_ALL;
   for (int x3 = 0; x3 <= 2; ++x3) {
     WinoJobs jobs; jobs.n = 0;
-    auto flush = [&]() { hipError_t e = x3 == 2 ? launch_f16x3_weights_multi(jobs, st) : (x3 ? launch_wino_weights_x3_multi(jobs, st) : launch_wino_weights_multi(jobs, st)); jobs.n = 0; return e; };
+    auto flush = [&]() { if (jobs.n > 0 && !dgrad) ++m->prep_launches; hipError_t e = x3 == 2 ? launch_f16x3_weights_multi(jobs, st) : (x3 ? launch_wino_weights_x3_multi(jobs, st) : launch_wino_weights_multi(jobs, st)); jobs.n = 0; return e; };
     for (size_t ci = 0; ci < m->convs.size(); ++ci) {
       const ConvL& cv = m->convs[ci];
       if (!m->plan.wino_ok(ci) || !(dgrad ? cv.wud_off : cv.wu_off) || cv.stem7()) continue;      // (the stem's slot holds conv_stem_f16x3's bank, built by its own kernel)
@@ -268,7 +274,7 @@ static hipError_t wino_jobs(const Ctx& c, bool dgrad, hipStream_t st) {
       WinoJob& j = jobs.j[jobs.n++];
       j.w = m->params + cv.w_off; j.Kpad = cv.Kpad; j.pad_ = kind == 2 ? f3_layout(m, ci, dgrad) : 0;
       if (dgrad) { j.ut = c.F(cv.wud_off); j.rows = cv.CinP; j.chans = cv.CoutP; j.mode = 2; j.src_rows = cv.Cout; }
-      else { j.ut = c.F(cv.wu_off); j.rows = cv.Cout; j.chans = cv.CinP; j.mode = 0; j.src_rows = cv.Cout; }
+      else { j.ut = c.wu(cv); j.rows = cv.Cout; j.chans = cv.CinP; j.mode = 0; j.src_rows = cv.Cout; }
       if (jobs.n == 40) { hipError_t e = flush(); if (e != hipSuccess) return e; }
     }
     hipError_t e = flush();

@@ -41,6 +41,7 @@ struct BNL {
   size_t dcount() const { return 2 * (size_t)C + (size_t)nrep * 2 * C + 16; }     // (+ 16 doubles = the 32 float slots of max|dy|: fp16x3 dgrad scaling, zeroed with the sums)
   size_t xmax_off() const { return d_off + dcount() - 16; }                         // in doubles
   size_t f_off;                    // workspace floats: mean, rstd, scale, shift (4*C)
+  size_t fz_off = 0;               // frozen arena floats (uwm_freeze): scale, shift (2*C)
   float eps = 0.f, mom = 0.f;      // 0 = the descriptor's bn_eps / bn_momentum (EfficientNet encoder layers carry their own)
 };
 struct ConvL {
@@ -50,6 +51,7 @@ struct ConvL {
   long long wfloats() const { return dw ? (long long)k * k * CoutP : (long long)Cout * Kpad; }
   size_t wd_off;                   // workspace floats: [CinP][KpadD] dgrad repack
   size_t wu_off, wud_off;          // workspace floats: Winograd-transformed weights (forward / dgrad); 0 = none
+  size_t wu_floats = 0, fz_wu = 0; // size of the forward slot; its place in the frozen arena (uwm_freeze), in floats
   bool wino() const { return k == 3 && stride == 1 && pad == 1 && (CinP & 7) == 0; }
   bool wino_d() const { return dgrad && k == 3 && stride == 1 && pad == 1 && (CoutP & 7) == 0; }
   int c0 = 0;                      // channels of the FIRST source of this conv's input (decoder conv1: the up-sampled tensor; else CinP)
@@ -145,6 +147,11 @@ struct uwm_model {
   std::string route_log;             // text of the record since the last uwm_routing_dump(.., clear)
   bool prec_from_env = false;        // the precision mode came from UWM_PRECISION (logged once at the first forward)
   std::vector<char> dy_max_made;     // per BatchNorm: a BatchNorm backward of this backward wrote its max|dY| slots (BNL::xmax_off; reset with them at stage 0)
+  // frozen state (uwm_freeze): the eval forward's parameter-derived items, made once into a caller-owned arena
+  float* frozen = nullptr;           // the arena (null = not frozen): per BatchNorm {scale, shift} at BNL::fz_off, per forward bank slot the bank at ConvL::fz_wu
+  size_t frozen_floats = 0;          // its size; follows from the model alone
+  std::vector<signed char> fz_form;  // per conv: the bank form the arena holds (fwd_bank_form)
+  long long prep_launches = 0;       // uwm_prep_launches: weight-preparation launches enqueued so far (BatchNorm eval scale / shift, forward bank builders, stem bank builder)
   std::vector<char> out_sums;        // per residual block: the BatchNorm-backward sums of its last BatchNorm were made by the dgrad that wrote its output gradient (run_dgrad bn_y)
 };
 
@@ -349,11 +356,17 @@ static int build_model(uwm_model* m) {
   for (auto& c : m->convs) if (c.dgrad) { c.wd_off = f; f += (size_t)c.CinP * c.KpadD; f = (size_t)rup((long long)f, 64); }
   for (auto& c : m->convs) {
     // (one slot per direction holds whichever bank the precision mode asks for: fp32 Winograd, bf16x3 Winograd or fp16x3 direct)
-    if (c.wino()) { c.wu_off = f; f += std::max(wino_weights_floats(c.Cout, c.CinP), c.f3() ? f16x3_bank_floats(c.Cout, c.CinP) : 0); f = (size_t)rup((long long)f, 64); }
-    if (c.stem7()) { c.wu_off = f; f += stem_f16x3_bank_floats(); f = (size_t)rup((long long)f, 64); }
+    if (c.wino()) { c.wu_off = f; c.wu_floats = std::max(wino_weights_floats(c.Cout, c.CinP), c.f3() ? f16x3_bank_floats(c.Cout, c.CinP) : 0); f += c.wu_floats; f = (size_t)rup((long long)f, 64); }
+    if (c.stem7()) { c.wu_off = f; c.wu_floats = stem_f16x3_bank_floats(); f += c.wu_floats; f = (size_t)rup((long long)f, 64); }
     if (c.wino_d()) { c.wud_off = f; f += std::max(wino_weights_floats(c.CinP, c.CoutP), c.f3_d() ? f16x3_bank_floats(c.CinP, c.CoutP) : 0); f = (size_t)rup((long long)f, 64); }
   }
   m->fixed_floats = f;
+  // ---- frozen arena (uwm_freeze): {scale, shift} of every BatchNorm, then one slot per forward bank (no statistics, no dgrad items)
+  size_t z = 0;
+  for (auto& b : m->bns) { b.fz_off = z; z += 2 * (size_t)b.C; }
+  z = (size_t)rup((long long)z, 64);
+  for (auto& c : m->convs) if (c.wu_off) { c.fz_wu = z; z += (size_t)rup((long long)c.wu_floats, 64); }
+  m->frozen_floats = z;
 
   // ---- tensor infos in smp state_dict order
   m->param_count = 0;

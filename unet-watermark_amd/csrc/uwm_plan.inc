@@ -245,3 +245,21 @@ static int f3_layout(const uwm_model* m, size_t ci, bool dgrad) {
 static int pack_key(const uwm_model* m) {
   return ((m->plan.wino_mode * 8 + m->plan.prec) * 4099 + (m->f3_min_wgs & 0xfff)) * 257 + (m->route_n & 0xff);
 }
+// The FORM of the bank conv ci's forward slot holds under the current plan and modes; 0 = the slot is not used.  It mirrors what
+// wino_jobs(dgrad = false) and the stem bank builder of do_forward make: 1 fp32 Winograd, 2 bf16x3 Winograd, 3 / 4 fp16x3 in conv_f16x3 /
+// conv_f16x3v2 layout, 5 the stem's fp16x3 bank.  uwm_freeze records it per layer; an eval forward reads the frozen arena only when
+// every layer's form is the recorded one.
+static int fwd_bank_form(const uwm_model* m, size_t ci) {
+  const ConvL& cv = m->convs[ci];
+  if (!cv.wu_off) return 0;
+  if (cv.stem7()) return stem_f3_on(m) ? 5 : 0;
+  if (!m->plan.wino_ok(ci)) return 0;
+  if (f3_fwd_on(m, ci)) return 3 + f3_layout(m, ci, false);
+  return m->plan.prec == UWM_PREC_BF16X3_ALL && cv.x3() ? 2 : 1;
+}
+// this eval forward may take its BatchNorm scale / shift and banks from the frozen arena
+static bool frozen_serves(const uwm_model* m) {
+  if (!m->frozen || m->fz_form.size() != m->convs.size()) return false;
+  for (size_t ci = 0; ci < m->convs.size(); ++ci) if (fwd_bank_form(m, ci) != m->fz_form[ci]) return false;
+  return true;
+}

@@ -151,6 +151,8 @@ class Unet(nn.Module):
         self._fused_opt_ref = None        # weakref to the fused flat optimizer that consumes the gradient arena itself (train.py)
         self._keep_override = None        # tests: {0,1} keep masks [n_blocks, N] instead of a random draw
         self._rowscale = None
+        self._frozen = False              # freeze(): eval forwards read the frozen arena
+        self._fz_arena = None             # the arena tensor (uint8), owned here
         self.reset_parameters()
 
     # ------------------------------------------------------------------ init
@@ -185,6 +187,7 @@ class Unet(nn.Module):
 
     # ------------------------------------------------------------------ device movement keeps the arena aliasing
     def _apply(self, fn, recurse=True):
+        self.unfreeze()
         new_p = fn(self._param_arena)
         new_b = fn(self._buffer_arena)
         if new_p.dtype != torch.float32 or new_b.dtype != torch.float32:
@@ -240,6 +243,7 @@ class Unet(nn.Module):
         as well (fp16 autocast + GradScaler, /root/reference/src/train.py:75,89-98)."""
         if mode not in L.PREC:
             raise ValueError(f"unsupported precision {mode!r} (supported: {list(L.PREC)})")
+        self.unfreeze()                      # the bank forms follow the precision mode and the routing: freeze again afterwards
         L.check(L.lib().uwm_set_precision(self._h, L.PREC[mode]), ValueError)
         if min_workgroups is not None:       # fp16x3 modes: smallest launch the fp16x3 kernels take (default: one workgroup per two CUs)
             L.check(L.lib().uwm_set_precision_fill(self._h, int(min_workgroups)), ValueError)
@@ -247,6 +251,69 @@ class Unet(nn.Module):
             L.check(L.lib().uwm_set_routing_batch(self._h, int(routing_batch)), ValueError)
         self.precision = mode
         return self
+
+    # ------------------------------------------------------------------ frozen-weight inference
+    @property
+    def frozen(self) -> bool:
+        return bool(getattr(self, "_frozen", False))
+
+    def freeze(self, batch_shape: Optional[Sequence[int]] = None):
+        """Freeze the weights for inference (uwm_freeze): everything the eval forward derives from parameters and buffers alone —
+        every BatchNorm's scale / shift, every forward filter bank, the stem bank — is computed ONCE into an arena this model owns,
+        and eval forwards then launch no weight-preparation kernel.  Logits stay bit-identical to the unfrozen eval forward.
+
+        Needs eval mode and a HIP device.  `batch_shape` = (N, H, W) fixes the bank forms now; with None the first eval forward
+        after freeze() fixes them for its own shape.  A later forward whose shape selects other forms still gives the same
+        logits, through the unfrozen path, without touching the arena (call freeze(batch_shape=...) again to serve it from the
+        arena; `frozen_serves` tells).  With the routing pinned (set_precision(..., min_workgroups=1) or a routing batch)
+        the forms do not depend on the batch size.
+
+        train(True), load_state_dict, .to() / .float() (`_apply`) and set_precision (precision, min_workgroups, routing_batch)
+        unfreeze: call freeze() again afterwards.  Parameters or buffers changed in any OTHER way (an optimizer step on a
+        model left in eval mode, in-place writes) are not seen: unfreeze() / freeze() by hand then.  unfreeze() releases the
+        arena, so a hipGraph captured from a frozen forward must not be replayed after it."""
+        if self.training:
+            raise RuntimeError("freeze() needs eval mode (call .eval() first): a training forward moves the running statistics")
+        self._require_gpu()
+        L.check(L.lib().uwm_unfreeze(self._h))
+        self._frozen = True
+        if batch_shape is not None:
+            n, h, w = (int(v) for v in batch_shape)
+            self._ensure_bound()
+            self._freeze_now(n, h, w)
+        return self
+
+    def unfreeze(self):
+        if getattr(self, "_h", None) is not None and getattr(self, "_frozen", False):
+            L.check(L.lib().uwm_unfreeze(self._h))
+        self._frozen = False
+        self._fz_arena = None
+        return self
+
+    def _freeze_now(self, n: int, h: int, w: int):
+        need = int(L.lib().uwm_frozen_bytes(self._h))
+        if self._fz_arena is None or self._fz_arena.numel() < need or self._fz_arena.device != self.device:
+            self._fz_arena = torch.empty(need, dtype=torch.uint8, device=self.device)
+        with L.on_device(self._fz_arena):
+            L.check(L.lib().uwm_freeze(self._h, C.c_void_p(self._fz_arena.data_ptr()), self._fz_arena.numel(), n, h, w,
+                                       C.c_void_p(L.stream_ptr(self.device))), SegmentationModelError)
+
+    def frozen_serves(self, n: int, h: int, w: int) -> bool:
+        """True when an eval forward of (n, h, w) would read the frozen arena right now (uwm_frozen_serves)."""
+        return bool(self.frozen and L.lib().uwm_frozen_serves(self._h, int(n), int(h), int(w)))
+
+    def prep_launches(self) -> int:
+        """Weight-preparation launches enqueued by this model so far (uwm_prep_launches): stands still across frozen forwards."""
+        return int(L.lib().uwm_prep_launches(self._h))
+
+    def train(self, mode: bool = True):
+        if mode:
+            self.unfreeze()
+        return super().train(mode)
+
+    def load_state_dict(self, *args, **kwargs):
+        self.unfreeze()
+        return super().load_state_dict(*args, **kwargs)
 
     def routing(self, enable: Optional[bool] = None, clear: bool = True):
         """Routing record of the library (uwm_routing_enable / uwm_routing_dump): with `enable` switch the record on / off; otherwise
@@ -289,9 +356,12 @@ class Unet(nn.Module):
             L.check(L.lib().uwm_bind(self._h, C.c_void_p(key[0]), C.c_void_p(key[1]), C.c_void_p(key[2])))
             self._bound = key
 
-    def _workspace(self, n, h, w, training):
+    def _workspace(self, n, h, w, training, logits_inside=None):
         key = (n, h, w, bool(training))
-        need = L.lib().uwm_workspace_bytes(self._h, n, h, w, int(training))
+        if logits_inside is None:
+            need = L.lib().uwm_workspace_bytes(self._h, n, h, w, int(training))
+        else:                                 # predict_u8: the eval plan [+ the logits behind it]
+            need = L.lib().uwm_predict_workspace_bytes(self._h, n, h, w, int(logits_inside))
         if need == 0:
             raise SegmentationModelError(L.lib().uwm_last_error().decode())
         if self._ws is None or self._ws.numel() < need or self._ws.device != self.device:
@@ -319,6 +389,8 @@ class Unet(nn.Module):
         x = x.contiguous()
         n, _, h, w = x.shape
         self._ensure_bound()
+        if self._frozen and not training and not L.lib().uwm_is_frozen(self._h):
+            self._freeze_now(n, h, w)        # freeze(batch_shape=None): this forward fixes the forms (also after a re-bind)
         ws = self._workspace(n, h, w, training)
         logits = torch.empty((n, h, w, self._cp), dtype=torch.float32, device=x.device)
         self._fwd_gen += 1
@@ -330,6 +402,39 @@ class Unet(nn.Module):
         if training:
             self._nbt_arena += 1
         return logits
+
+    @torch.no_grad()
+    def predict_u8(self, images_u8: torch.Tensor, mean, std, threshold: float = 0.5, apply_sigmoid: bool = False,
+                   out_size=None, return_logits: bool = False):
+        """uint8 (N,H,W,C) images on the HIP device -> uint8 {0,255} masks (N,out_h,out_w) in ONE library call (uwm_predict_u8):
+        Normalize(mean, std) of x/255 written straight into the forward's input layout, eval forward (frozen or not), bilinear
+        resize to `out_size` (default: the input size) + threshold.  Bit-identical to device_preprocess -> forward ->
+        resize_threshold.  return_logits: also the logits (N,classes,H,W)."""
+        if self.training:
+            raise RuntimeError("predict_u8 is an eval-mode path: call .eval() first")
+        self._require_gpu(images_u8)
+        if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[3] != self.in_channels:
+            raise RuntimeError(f"expected uint8 images of shape (N,H,W,{self.in_channels}), got {images_u8.dtype} {tuple(images_u8.shape)}")
+        x = images_u8.contiguous()
+        n, h, w, c = x.shape
+        self.check_input_shape(x.permute(0, 3, 1, 2))
+        oh, ow = (h, w) if out_size is None else (int(out_size[0]), int(out_size[1]))
+        self._ensure_bound()
+        if self._frozen and not L.lib().uwm_is_frozen(self._h):
+            self._freeze_now(n, h, w)
+        ws = self._workspace(n, h, w, False, logits_inside=not return_logits)
+        mask = torch.empty((n, oh, ow), dtype=torch.uint8, device=x.device)
+        logits = torch.empty((n, h, w, self._cp), dtype=torch.float32, device=x.device) if return_logits else None
+        self._fwd_gen += 1
+        if self._n_mb:
+            self._set_drop_connect(n, False, x.device)
+        mean_c = (C.c_float * c)(*[float(v) for v in mean[:c]]); std_c = (C.c_float * c)(*[float(v) for v in std[:c]])
+        with L.on_device(x):
+            L.check(L.lib().uwm_predict_u8(self._h, C.c_void_p(x.data_ptr()), mean_c, std_c, float(threshold), int(apply_sigmoid),
+                                           oh, ow, C.c_void_p(mask.data_ptr()), C.c_void_p(logits.data_ptr() if logits is not None else 0),
+                                           C.c_void_p(ws.data_ptr()), ws.numel(), n, h, w, C.c_void_p(L.stream_ptr(x.device))),
+                    SegmentationModelError)
+        return (mask, self._logits_view(logits)) if return_logits else mask
 
     def _set_drop_connect(self, n: int, training: bool, device):
         """Draw this step's per-block, per-sample keep masks (efficientnet_pytorch utils.drop_connect: floor(keep_prob +

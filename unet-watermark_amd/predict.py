@@ -20,7 +20,10 @@ IMAGENET_STD = (0.229, 0.224, 0.225)
 
 class WatermarkPredictor:
     def __init__(self, model_path: Optional[str] = None, config_path: Optional[str] = None, config=None,
-                 device: str = "cuda", model=None, precision: Optional[str] = None):
+                 device: str = "cuda", model=None, precision: Optional[str] = None, freeze: bool = False):
+        """freeze=True: the weights are frozen after loading (model.freeze): BatchNorm scale / shift and filter banks are made once
+        instead of in every forward, logits unchanged bit for bit; the arena is re-made when a new graph shape selects other bank
+        forms."""
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("WatermarkPredictor runs only on a HIP device (no CPU fallback)")
@@ -38,7 +41,13 @@ class WatermarkPredictor:
         self.threshold = float(self.cfg.PREDICT.THRESHOLD)
         self._graph = None
         self._gkey = None
-        self._gin = self._gout = None
+        self._gin = self._gout = self._gws = None
+        self._ugraph = None
+        self._ukey = None
+        self._uin = self._uout = self._uws = None
+        self.freeze = bool(freeze)
+        if self.freeze:
+            self.model.freeze()               # the first forward fixes the bank forms
 
     # --- input contract of dataset.get_val_transform: Resize -> Normalize(ImageNet) -> NCHW fp32
     def preprocess(self, images_u8_nhwc: torch.Tensor) -> torch.Tensor:
@@ -53,13 +62,14 @@ class WatermarkPredictor:
             return self.model(x)
         key = tuple(x.shape)
         if self._gkey != key:
+            self._refreeze_for(x.shape[0], x.shape[2], x.shape[3])
             self._gin = x.clone()
             self.model(self._gin)                     # eager warm-up: plans the workspace, sets kernel attributes
             torch.cuda.synchronize(self.device)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 self._gout = self.model(self._gin)
-            self._graph, self._gkey = g, key
+            self._graph, self._gkey, self._gws = g, key, self.model._ws      # (the graph's workspace stays alive with it)
         self._gin.copy_(x)
         self._graph.replay()
         return self._gout
@@ -68,3 +78,34 @@ class WatermarkPredictor:
     def predict_mask(self, x: torch.Tensor, apply_sigmoid: bool = False, use_graph: bool = True) -> torch.Tensor:
         """-> uint8 {0,255} (N,H,W); default reproduces predict.py:624 (raw logits > THRESHOLD)."""
         return threshold_mask(self.logits(x, use_graph), self.threshold, apply_sigmoid)
+
+    def _refreeze_for(self, n: int, h: int, w: int):
+        """freeze=True: a new graph shape whose bank forms differ from the frozen ones gets the arena re-made for it; the graphs
+        captured on the old arena contents go."""
+        if self.freeze and not self.model.frozen_serves(n, h, w):
+            self.model.freeze(batch_shape=(n, h, w))
+            self._graph = self._gkey = self._ugraph = self._ukey = None
+
+    @torch.no_grad()
+    def predict_mask_u8(self, images_u8_nhwc: torch.Tensor, out_size=None, apply_sigmoid: bool = False,
+                        use_graph: bool = True) -> torch.Tensor:
+        """uint8 (N,H,W,3) images -> uint8 {0,255} masks (N,out_h,out_w) through ONE library call (uwm_predict_u8): ImageNet
+        Normalize written straight into the forward's input layout, eval forward, resize to `out_size` (default: the input
+        size) + threshold.  Same masks as preprocess -> predict_mask / resize_threshold, bit for bit."""
+        x = images_u8_nhwc.to(self.device, non_blocking=True)
+        run = lambda t: self.model.predict_u8(t, IMAGENET_MEAN, IMAGENET_STD, self.threshold, apply_sigmoid, out_size)
+        if not use_graph:
+            return run(x)
+        key = (tuple(x.shape), None if out_size is None else tuple(out_size), bool(apply_sigmoid))
+        if self._ukey != key:
+            self._refreeze_for(x.shape[0], x.shape[1], x.shape[2])
+            self._uin = x.clone()
+            run(self._uin)                            # eager warm-up
+            torch.cuda.synchronize(self.device)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._uout = run(self._uin)
+            self._ugraph, self._ukey, self._uws = g, key, self.model._ws
+        self._uin.copy_(x)
+        self._ugraph.replay()
+        return self._uout
