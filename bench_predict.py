@@ -16,7 +16,12 @@ def main():
                     help="f16x3 (default): fp16x3 split products on the 3x3 convolutions, fp32-class accuracy; f32: exact-fp32 matrix instruction")
     ap.add_argument("--freeze", action="store_true", help="freeze the weights (WatermarkPredictor(freeze=True)): BatchNorm scale / shift and filter banks made once")
     ap.add_argument("--u8", action="store_true", help="time uint8 images -> masks through uwm_predict_u8 (predict_mask_u8) instead of fp32 NCHW input -> masks")
+    ap.add_argument("--mask-type", choices=["watermark", "text", "mixed"], default=None,
+                    help="with --u8: post-process the masks on the device (predict_mask_u8(mask_type=...)); adds mask_type / out_size to the line")
+    ap.add_argument("--out-size", type=int, nargs=2, metavar=("H", "W"), default=None, help="with --u8: resize the masks to H x W (default: the input size)")
     a = ap.parse_args()
+    if (a.mask_type or a.out_size) and not a.u8:
+        ap.error("--mask-type / --out-size need --u8")
     from unet_watermark_amd.predict import WatermarkPredictor, IMAGENET_MEAN, IMAGENET_STD
     from unet_watermark_amd.config import get_cfg_defaults
     cfg = get_cfg_defaults(); cfg.MODEL.NAME = "Unet"; cfg.MODEL.ENCODER_NAME = a.encoder      # BASELINE configs[4] names Unet
@@ -25,7 +30,8 @@ def main():
     if a.u8:
         xu = torch.randint(0, 256, (a.batch, a.size, a.size, 3), dtype=torch.uint8, device="cuda")
         x = pred.preprocess(xu)
-        step = lambda: pred.predict_mask_u8(xu, use_graph=not a.no_graph)
+        post = {k: v for k, v in (("mask_type", a.mask_type), ("out_size", tuple(a.out_size) if a.out_size else None)) if v}
+        step = lambda: pred.predict_mask_u8(xu, use_graph=not a.no_graph, **post)
     else:
         x = torch.randn(a.batch, 3, a.size, a.size, device="cuda")
         step = lambda: pred.predict_mask(x, use_graph=not a.no_graph)
@@ -51,6 +57,10 @@ def main():
         p0 = pred.model.prep_launches()
         pred.logits(x, use_graph=False)
         extra = {"frozen": bool(pred.model.frozen), "prep_launches_per_batch": pred.model.prep_launches() - p0, "input": "u8" if a.u8 else "f32"}
+    if a.mask_type:
+        extra["mask_type"] = a.mask_type
+    if a.out_size:
+        extra["out_size"] = list(a.out_size)
     print(json.dumps({"metric": "predict_images_per_sec", "value": round(n / dt, 2), "unit": "images/s", "n_gpus": 1,
                       "images": n, "batch": a.batch, "ms_per_batch": round(1e3 * dt / a.batches, 3),
                       "dtype": "f32" if a.precision == "f32" else "f32 storage / accumulation, 3x3 conv products as fp16x3 splits (22-bit operands) on v_mfma_f32_16x16x32_f16",

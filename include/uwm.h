@@ -315,6 +315,38 @@ float uwm_mbconv_drop_rate(uwm_handle h, int block);
 int  uwm_resize_threshold(const float* logits, int ld, int N, int h, int w, int H, int W, float threshold,
                           int apply_sigmoid, uint8_t* mask, float* resized, uwm_stream stream);
 
+/* Mask post-processing on the device: the reference's WatermarkPredictor._optimize_mask (src/predict.py:161-301), which every
+ * mask passes before it is returned or written.  Masks are uint8 [N][H][W], any H, W >= 1 with H*W < 2^31 - 1, N <= 65535;
+ * foreground = value > 127, results in {0, 255}.  Integer work only: results are exact and the same on every run.
+ *   elements    cv2.getStructuringElement: RECT all ones; ELLIPSE (w,h) with r = h/2, c = w/2: row i (dy = i - r) has ones in
+ *               columns [max(c - dx, 0), min(c + dx + 1, w)), dx = round_half_even(c * sqrt((r*r - dy*dy) / (r*r)))
+ *   morphology  anchor (w/2, h/2), no reflection: dilate dst(y,x) = OR over element(i,j) != 0 of src(y+i-ay, x+j-ax), erode the
+ *               same with AND; pixels outside the image are ignored (0 for dilate, 1 for erode); open(k,n) = erode n times then
+ *               dilate n times, close(k,n) the other way round
+ *   components  8-connected; a component's id is the linear index y*W + x of its first pixel in raster order; "largest" =
+ *               greatest area, ties to the smallest id
+ *   pipelines   WATERMARK: open E(3,3)x1, close E(7,7)x3, close E(11,11)x2, dilate E(9,9)x2; keep the largest component, or, when
+ *               its area is below 500, every component with area > 200.  TEXT: open E(2,2)x1, close E(3,3)x2, close R(5,1)x1 OR
+ *               close R(1,5)x1 (same input), dilate E(4,4)x1; keep area > 50.  MIXED: open E(2,2)x1, close E(5,5)x2, dilate
+ *               E(6,6)x1; keep area > 100.  (The reference's trailing 3x3 blur + threshold is the identity on {0,255} images.)
+ * Caller-owned buffers, work enqueued on the caller's stream, no host synchronisation: capturable behind uwm_predict_u8.  Every
+ * argument is checked before any launch.  workspace: uwm_mask_workspace_bytes(N, H, W) bytes (0 on a bad shape), 16-byte aligned. */
+enum { UWM_MASK_WATERMARK = 0, UWM_MASK_TEXT = 1, UWM_MASK_MIXED = 2 };
+enum { UWM_MORPH_RECT = 0, UWM_MORPH_ELLIPSE = 2 };              /* cv2's values */
+/* host only, no device: the element as kh*kw bytes of 0/1 (1 <= kw, kh <= 15) */
+int    uwm_mask_element(int shape, int kw, int kh, uint8_t* out);
+size_t uwm_mask_workspace_bytes(int N, int H, int W);
+/* the whole pipeline; out may alias in.  summary (device, may be NULL): long long [N][4] =
+ * {components found, area of the largest (0 if none), foreground pixels of the output, id of the largest or -1} */
+int    uwm_optimize_mask(const uint8_t* in, uint8_t* out, int N, int H, int W, int mask_type, long long* summary,
+                         void* workspace, size_t workspace_bytes, uwm_stream stream);
+/* building blocks, for tests and other callers; out may alias in */
+int    uwm_op_morph(const uint8_t* in, uint8_t* out, int N, int H, int W, int dilate, int shape, int kw, int kh,
+                    int iterations, void* workspace, size_t workspace_bytes, uwm_stream stream);
+int    uwm_op_components(const uint8_t* in, int32_t* labels /* [N][H][W]: id+1, 0 = background */,
+                         int32_t* areas /* [N][H][W]: area at the id pixel, 0 elsewhere */, int N, int H, int W,
+                         void* workspace, size_t workspace_bytes, uwm_stream stream);
+
 /* Weight-gradient kernels run on an internal side stream (forked from / joined to the caller's stream with events,
  * per backward stage) so they overlap the dgrad chain; this switches that off/on at run time (default on). */
 int  uwm_set_side_stream(uwm_handle h, int on);

@@ -268,8 +268,12 @@ def predict_command(args):
         arr = np.stack([np.asarray(im.resize((s, s), Image.BILINEAR), dtype=np.uint8) for im in ims])
         logits = pred.logits(pred.preprocess(torch.from_numpy(arr)), use_graph=len(chunk) == bs)
         from .metrics import resize_threshold
+        from .postprocess import optimize_mask
         for k, (f, im) in enumerate(zip(chunk, ims)):          # bilinear resize of the raw logits to the original size, then threshold
-            m = resize_threshold(logits[k:k + 1], (im.size[1], im.size[0]), pred.threshold, args.sigmoid)[0].cpu().numpy()
+            m = resize_threshold(logits[k:k + 1], (im.size[1], im.size[0]), pred.threshold, args.sigmoid)
+            if args.mask_type:                                 # the reference's _optimize_mask, per image at its original size
+                m = optimize_mask(m, args.mask_type)
+            m = m[0].cpu().numpy()
             Image.fromarray(m).save(os.path.join(args.output, os.path.splitext(f)[0] + "_mask.png"))
     print(f"wrote {len(files)} masks to {args.output}")
 
@@ -303,6 +307,8 @@ def main(argv=None):
     pp.add_argument("--model", type=str, required=True); pp.add_argument("--config", type=str, default=None)
     pp.add_argument("--encoder", type=str); pp.add_argument("--threshold", type=float)
     pp.add_argument("--batch-size", type=int); pp.add_argument("--sigmoid", action="store_true")
+    pp.add_argument("--mask-type", choices=["watermark", "text", "mixed"], default=None,
+                    help="post-process every mask as the reference's _optimize_mask does for this watermark type (absent: raw thresholded masks)")
     args = ap.parse_args(argv)
     if args.command == "train":
         return train_command(args)

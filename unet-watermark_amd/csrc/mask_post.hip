@@ -1,0 +1,427 @@
+// Mask post-processing on the device: the reference's WatermarkPredictor._optimize_mask (binary morphology, 8-connected
+// components, selection by area) for uint8 {0,255} masks [N][H][W].  DESIGN.md §8b is the specification; every result is
+// exact (integer operations only) and independent of the schedule.
+//
+// Morphology runs on bit planes: a mask is packed to 1 bit per pixel (bit b of word k of a row = pixel x = 64k + b, row pitch
+// WP = ceil(W / 64) words, padding bits always 0), so a 768x1024 mask is 96 KB and every pass of a pipeline stays in L2.  A
+// structuring element row is a horizontal run, so a pass is, per output word, an OR / AND over the element's rows of the
+// run-dilated (run-eroded) neighbour words.  Pixels outside the image are ignored: 0 for a dilation, 1 for an erosion.
+//
+// Components: union-find over the pixels with integer atomicMin.  A label array holds parent + 1 (0 = background); a parent is
+// never greater than its child, so every find / union chain strictly descends and ends by its own progress, and the root of a
+// finished tree is the component's smallest linear index — its first pixel in raster order, the id the specification defines.
+// The phases that need a global order are separate launches (init, merge, compress + areas, largest, select + write): no
+// grid-wide barrier, no wait on another workgroup.
+#include "uwm_kernels.h"
+
+namespace uwm {
+
+typedef unsigned long long u64;
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kPer = 8;                    // pixels per thread of the kernels that end in an atomic sum (mp_cc_compress, mp_select)
+constexpr int kPix = kPer * kThreads;
+constexpr int kCtr = 16;                   // u64 counters per image: one 128-byte line each, so images do not share an atomic's line
+
+__device__ __forceinline__ u64 valid_bits(int k, int W) {
+  const int rem = W - 64 * k;
+  return rem >= 64 ? ~0ull : ((1ull << rem) - 1ull);
+}
+
+// ---------------------------------------------------------------- pack / unpack
+// one wave per group of 4 words: lane l reads pixel 64k + l, the ballot is the word
+__global__ void __launch_bounds__(kThreads) mp_pack(const uint8_t* __restrict__ in, u64* __restrict__ bits, int H, int W, int WP) {
+  const int lane = threadIdx.x & 63;
+  const unsigned nwords = (unsigned)H * WP;
+  const unsigned w0 = (blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6)) * 4u;
+  const uint8_t* img = in + (size_t)blockIdx.y * H * W;
+  u64* out = bits + (size_t)blockIdx.y * nwords;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned w = w0 + i;
+    if (w >= nwords) break;                       // uniform in the wave
+    const int y = w / WP, k = w % WP, x = 64 * k + lane;
+    const bool fg = x < W && img[(size_t)y * W + x] > 127;
+    const u64 word = __ballot(fg);
+    if (lane == 0) out[w] = word;
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) mp_unpack(const u64* __restrict__ bits, uint8_t* __restrict__ out, int H, int W, int WP) {
+  const unsigned p = blockIdx.x * kThreads + threadIdx.x;
+  if (p >= (unsigned)H * W) return;
+  const int y = p / W, x = p % W;
+  const u64 word = bits[((size_t)blockIdx.y * H + y) * WP + (x >> 6)];
+  out[(size_t)blockIdx.y * H * W + p] = (word >> (x & 63)) & 1 ? 255 : 0;
+}
+
+// ---------------------------------------------------------------- one morphology pass on bit planes
+struct MorphEl {               // element rows as runs of column offsets [lo, hi] from the anchor (lo > hi: empty row)
+  int kh, ay;
+  signed char lo[15], hi[15];
+};
+
+template <bool DIL>
+__global__ void __launch_bounds__(kThreads) mp_morph(const u64* __restrict__ src, u64* __restrict__ dst, const u64* __restrict__ orw,
+                                                     int H, int W, int WP, MorphEl el) {
+  const unsigned idx = blockIdx.x * kThreads + threadIdx.x;
+  const unsigned nwords = (unsigned)H * WP;
+  if (idx >= nwords) return;
+  const int y = idx / WP, k = idx % WP;
+  const u64* plane = src + (size_t)blockIdx.y * nwords;
+  const u64 outside = DIL ? 0ull : ~0ull;
+  u64 acc = outside;
+  for (int i = 0; i < el.kh; ++i) {
+    const int yy = y + i - el.ay, lo = el.lo[i], hi = el.hi[i];
+    if (lo > hi || yy < 0 || yy >= H) continue;          // a row outside the image is ignored
+    const u64* row = plane + (size_t)yy * WP;
+    u64 cur = row[k], prev = outside, next = outside;
+    if (k > 0) prev = row[k - 1];
+    if (k + 1 < WP) next = row[k + 1];
+    if (!DIL) {                                          // the padding bits of a row's last word lie outside the image
+      cur |= ~valid_bits(k, W);
+      if (k + 1 < WP) next |= ~valid_bits(k + 1, W);
+    }
+    u64 r = outside;
+    for (int dx = lo; dx <= hi; ++dx) {                  // bit b of v = source pixel 64k + b + dx
+      u64 v = cur;
+      if (dx > 0) v = (cur >> dx) | (next << (64 - dx));
+      else if (dx < 0) v = (cur << -dx) | (prev >> (64 + dx));
+      r = DIL ? (r | v) : (r & v);
+    }
+    acc = DIL ? (acc | r) : (acc & r);
+  }
+  acc &= valid_bits(k, W);
+  if (orw) acc |= orw[(size_t)blockIdx.y * nwords + idx];
+  dst[(size_t)blockIdx.y * nwords + idx] = acc;
+}
+
+// ---------------------------------------------------------------- components
+__device__ __forceinline__ int ld_label(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_label(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// root of p: parents never exceed their children, so the walk strictly descends
+__device__ __forceinline__ int mp_find(const int* lab, int p) {
+  for (;;) {
+    const int q = ld_label(lab + p) - 1;
+    if (q == p) return p;
+    p = q;
+  }
+}
+// join the sets of a and b.  Every turn either ends or continues with max(a, b) strictly smaller.
+__device__ __forceinline__ void mp_union(int* lab, int a, int b) {
+  for (;;) {
+    a = mp_find(lab, a);
+    b = mp_find(lab, b);
+    if (a == b) return;
+    if (a < b) { const int t = a; a = b; b = t; }
+    const int old = atomicMin(lab + a, b + 1) - 1;       // a's parent as it was
+    if (old == a) return;                                // a was a root and now hangs below b
+    a = old;                                             // a had got a parent meanwhile: that set still has to meet b's
+  }
+}
+
+__device__ __forceinline__ bool bit_at(const u64* plane, int WP, int y, int x) {
+  return (plane[(size_t)y * WP + (x >> 6)] >> (x & 63)) & 1;
+}
+
+// labels = start of the pixel's run inside its 64-pixel word (+ 1), areas = 0; the per-image counters are cleared
+__global__ void __launch_bounds__(kThreads) mp_cc_init(const u64* __restrict__ bits, int* __restrict__ labels, int* __restrict__ areas,
+                                                       u64* __restrict__ counters, int H, int W, int WP) {
+  const unsigned p = blockIdx.x * kThreads + threadIdx.x;
+  if (p < 4) counters[(size_t)blockIdx.y * kCtr + p] = 0;
+  if (p >= (unsigned)H * W) return;
+  const int y = p / W, x = p % W, b = x & 63;
+  const u64 word = bits[((size_t)blockIdx.y * H + y) * WP + (x >> 6)];
+  int l = 0;
+  if ((word >> b) & 1) {
+    const u64 gaps = ~word & ((1ull << b) - 1ull);       // background bits below b; the run starts above the highest
+    const int start = gaps ? 64 - __clzll((long long)gaps) : 0;
+    l = (int)p - b + start + 1;
+  }
+  const size_t g = (size_t)blockIdx.y * H * W + p;
+  labels[g] = l;
+  areas[g] = 0;
+}
+
+// joins across word boundaries and between rows.  A pixel whose left neighbour is foreground with foreground above it leaves
+// the join with the row above to that neighbour (they share a run), so each stretch of vertical contact joins once.
+__global__ void __launch_bounds__(kThreads) mp_cc_merge(const u64* __restrict__ bits, int* __restrict__ labels, int H, int W, int WP) {
+  const unsigned p = blockIdx.x * kThreads + threadIdx.x;
+  if (p >= (unsigned)H * W) return;
+  const int y = p / W, x = p % W;
+  const u64* plane = bits + (size_t)blockIdx.y * H * WP;
+  if (!bit_at(plane, WP, y, x)) return;
+  int* lab = labels + (size_t)blockIdx.y * H * W;
+  const bool left = x > 0 && bit_at(plane, WP, y, x - 1);
+  if (left && (x & 63) == 0) mp_union(lab, (int)p, (int)p - 1);
+  if (y == 0) return;
+  const bool up = bit_at(plane, WP, y - 1, x);
+  const bool upl = x > 0 && bit_at(plane, WP, y - 1, x - 1);
+  const bool upr = x + 1 < W && bit_at(plane, WP, y - 1, x + 1);
+  if (up) {
+    if (!(left && upl)) mp_union(lab, (int)p, (int)p - W);
+  } else {
+    if (upl && !left) mp_union(lab, (int)p, (int)p - W - 1);      // (with `left`, the left pixel has `up` = upl and joins)
+    if (upr) mp_union(lab, (int)p, (int)p - W + 1);
+  }
+}
+
+// labels <- root + 1, areas[root] += pixel count.  A workgroup covers kPix consecutive pixels; each wave sums the lanes that share
+// the root of its first foreground lane, the workgroup merges equal roots in LDS, so a large component costs one atomic add per
+// workgroup, not one per pixel (a single address takes only so many atomics per microsecond).
+__global__ void __launch_bounds__(kThreads) mp_cc_compress(int* __restrict__ labels, int* __restrict__ areas, int H, int W) {
+  __shared__ int s_root[kPer * kThreads / 64], s_cnt[kPer * kThreads / 64];
+  int* lab = labels + (size_t)blockIdx.y * H * W;
+  int* ar = areas + (size_t)blockIdx.y * H * W;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < kPer; ++i) {
+    const unsigned p = blockIdx.x * kPix + i * kThreads + threadIdx.x;
+    int r = -1;
+    if (p < (unsigned)H * W && ld_label(lab + p) != 0) {
+      r = mp_find(lab, (int)p);
+      st_label(lab + p, r + 1);
+    }
+    const u64 fg = __ballot(r >= 0);
+    int r0 = -1, cnt = 0;
+    if (fg) {                                            // uniform in the wave
+      r0 = __shfl(r, __ffsll((long long)fg) - 1);
+      cnt = __popcll(__ballot(r == r0));
+      if (r >= 0 && r != r0) atomicAdd(ar + r, 1);       // the lanes of other components (borders between components are short)
+    }
+    if (lane == 0) { s_root[i * (kThreads / 64) + wave] = r0; s_cnt[i * (kThreads / 64) + wave] = cnt; }
+  }
+  __syncthreads();
+  const int j = threadIdx.x;
+  if (j < kPer * kThreads / 64 && s_root[j] >= 0) {      // the first entry of each root adds the sum of all its entries
+    int total = 0;
+    bool first = true;
+    for (int k = 0; k < kPer * kThreads / 64; ++k)
+      if (s_root[k] == s_root[j]) { if (k < j) first = false; total += s_cnt[k]; }
+    if (first) atomicAdd(ar + s_root[j], total);
+  }
+}
+
+// counters[n][kCtr] = {components, max of (area << 32 | ~id), foreground of the output, unused ...}
+__global__ void __launch_bounds__(kThreads) mp_cc_largest(const int* __restrict__ labels, const int* __restrict__ areas,
+                                                          u64* __restrict__ counters, int H, int W) {
+  const unsigned p = blockIdx.x * kThreads + threadIdx.x;
+  if (p >= (unsigned)H * W) return;
+  const size_t g = (size_t)blockIdx.y * H * W + p;
+  if (labels[g] != (int)p + 1) return;                   // roots only
+  u64* c = counters + (size_t)blockIdx.y * kCtr;
+  atomicAdd(c, 1ull);
+  atomicMax(c + 1, ((u64)(unsigned)areas[g] << 32) | (unsigned)~p);
+}
+
+__global__ void __launch_bounds__(kThreads) mp_select(const int* __restrict__ labels, const int* __restrict__ areas, u64* __restrict__ counters,
+                                                      uint8_t* __restrict__ out, int H, int W, int mask_type) {
+  __shared__ int s_kept[kThreads / 64];
+  const size_t base = (size_t)blockIdx.y * H * W;
+  const u64 best = counters[(size_t)blockIdx.y * kCtr + 1];
+  int kept = 0;
+#pragma unroll
+  for (int i = 0; i < kPer; ++i) {
+    const unsigned p = blockIdx.x * kPix + i * kThreads + threadIdx.x;
+    bool keep = false;
+    if (p < (unsigned)H * W) {
+      const int l = labels[base + p];
+      if (l) {
+        const int area = areas[base + l - 1];
+        if (mask_type == 0)                              // watermark: the largest, or everything above 200 when it is below 500
+          keep = (int)(best >> 32) < 500 ? area > 200 : (unsigned)(l - 1) == ~(unsigned)best;
+        else
+          keep = area > (mask_type == 1 ? 50 : 100);     // text | mixed
+      }
+      out[base + p] = keep ? 255 : 0;
+    }
+    kept += __popcll(__ballot(keep));                    // (the same sum in every lane of the wave)
+  }
+  if ((threadIdx.x & 63) == 0) s_kept[threadIdx.x >> 6] = kept;
+  __syncthreads();
+  if (threadIdx.x == 0) {                                // one add per workgroup
+    int total = 0;
+    for (int k = 0; k < kThreads / 64; ++k) total += s_kept[k];
+    if (total) atomicAdd(counters + (size_t)blockIdx.y * kCtr + 2, (u64)total);
+  }
+}
+
+__global__ void mp_summary(const u64* __restrict__ counters, long long* __restrict__ summary, int N) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  const u64 ncomp = counters[(size_t)n * kCtr], best = counters[(size_t)n * kCtr + 1];
+  summary[(size_t)n * 4 + 0] = (long long)ncomp;
+  summary[(size_t)n * 4 + 1] = (long long)(best >> 32);
+  summary[(size_t)n * 4 + 2] = (long long)counters[(size_t)n * kCtr + 2];
+  summary[(size_t)n * 4 + 3] = ncomp ? (long long)~(unsigned)best : -1ll;
+}
+
+// ---------------------------------------------------------------- host side
+size_t rup256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+struct Layout {                // workspace: three bit planes, labels, areas, per-image counters (each 256-byte aligned)
+  size_t plane, labels, areas, counters, total;
+};
+Layout layout(int N, int H, int W) {
+  Layout l;
+  const size_t WP = ((size_t)W + 63) / 64;
+  l.plane = rup256((size_t)N * H * WP * 8);
+  l.labels = 3 * l.plane;
+  l.areas = l.labels + rup256((size_t)N * H * W * 4);
+  l.counters = l.areas + rup256((size_t)N * H * W * 4);
+  l.total = l.counters + rup256((size_t)N * kCtr * 8);
+  return l;
+}
+
+bool make_el(int shape, int kw, int kh, MorphEl* el) {
+  uint8_t k[15 * 15];
+  if (mask_element(shape, kw, kh, k)) return false;
+  el->kh = kh; el->ay = kh / 2;
+  const int ax = kw / 2;
+  for (int i = 0; i < kh; ++i) {
+    int lo = 1, hi = 0;
+    for (int j = 0; j < kw; ++j) if (k[i * kw + j]) { if (lo > hi) lo = j - ax; hi = j - ax; }
+    el->lo[i] = (signed char)lo; el->hi[i] = (signed char)hi;
+  }
+  return true;
+}
+
+dim3 grid_for(size_t per_image, int N) { return dim3((unsigned)((per_image + kThreads - 1) / kThreads), (unsigned)N); }
+
+hipError_t morph_pass(const u64* src, u64* dst, const u64* orw, int N, int H, int W, bool dil, const MorphEl& el, hipStream_t st) {
+  const int WP = (W + 63) / 64;
+  const dim3 g = grid_for((size_t)H * WP, N);
+  if (dil) hipLaunchKernelGGL(mp_morph<true>, g, dim3(kThreads), 0, st, src, dst, orw, H, W, WP, el);
+  else hipLaunchKernelGGL(mp_morph<false>, g, dim3(kThreads), 0, st, src, dst, orw, H, W, WP, el);
+  return hipGetLastError();
+}
+
+// `it` passes of one operation, ping-pong between *cur and *tmp; the result is in *cur afterwards
+hipError_t morph_n(u64** cur, u64** tmp, int N, int H, int W, bool dil, const MorphEl& el, int it, hipStream_t st) {
+  for (int i = 0; i < it; ++i) {
+    hipError_t e = morph_pass(*cur, *tmp, nullptr, N, H, W, dil, el, st);
+    if (e != hipSuccess) return e;
+    u64* t = *cur; *cur = *tmp; *tmp = t;
+  }
+  return hipSuccess;
+}
+hipError_t open_close(u64** cur, u64** tmp, int N, int H, int W, bool close, int shape, int kw, int kh, int it, hipStream_t st) {
+  MorphEl el;
+  if (!make_el(shape, kw, kh, &el)) return hipErrorInvalidValue;
+  hipError_t e = morph_n(cur, tmp, N, H, W, close, el, it, st);
+  if (e != hipSuccess) return e;
+  return morph_n(cur, tmp, N, H, W, !close, el, it, st);
+}
+
+hipError_t pack(const uint8_t* in, u64* bits, int N, int H, int W, hipStream_t st) {
+  const int WP = (W + 63) / 64;
+  const size_t groups = ((size_t)H * WP + 3) / 4;                    // 4 words per wave, 4 waves per workgroup
+  hipLaunchKernelGGL(mp_pack, dim3((unsigned)((groups + 3) / 4), (unsigned)N), dim3(kThreads), 0, st, in, bits, H, W, WP);
+  return hipGetLastError();
+}
+
+hipError_t components(const u64* bits, int* labels, int* areas, u64* counters, int N, int H, int W, hipStream_t st) {
+  const int WP = (W + 63) / 64;
+  const dim3 g = grid_for((size_t)H * W, N);
+  hipLaunchKernelGGL(mp_cc_init, g, dim3(kThreads), 0, st, bits, labels, areas, counters, H, W, WP);
+  hipLaunchKernelGGL(mp_cc_merge, g, dim3(kThreads), 0, st, bits, labels, H, W, WP);
+  hipLaunchKernelGGL(mp_cc_compress, dim3((unsigned)(((size_t)H * W + kPix - 1) / kPix), (unsigned)N), dim3(kThreads), 0, st, labels, areas, H, W);
+  return hipGetLastError();
+}
+
+#define MP_CHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
+
+}  // namespace
+
+int mask_element(int shape, int kw, int kh, uint8_t* out) {
+  if (!out || kw < 1 || kh < 1 || kw > 15 || kh > 15 || (shape != 0 && shape != 2)) return 1;
+  if (shape == 0) {
+    for (int i = 0; i < kw * kh; ++i) out[i] = 1;
+    return 0;
+  }
+  // cv2.getStructuringElement(MORPH_ELLIPSE): row i covers c +- round_half_even(c * sqrt((r^2 - dy^2) / r^2))
+  const int r = kh / 2, c = kw / 2;
+  const double inv_r2 = r ? 1.0 / ((double)r * r) : 0.0;
+  for (int i = 0; i < kh; ++i) {
+    const int dy = i - r;
+    int j1 = 0, j2 = 0;
+    if (dy >= -r && dy <= r) {
+      const int dx = (int)__builtin_rint(c * __builtin_sqrt((r * r - dy * dy) * inv_r2));     // (default rounding mode: half to even)
+      j1 = c - dx > 0 ? c - dx : 0;
+      j2 = c + dx + 1 < kw ? c + dx + 1 : kw;
+    }
+    for (int j = 0; j < kw; ++j) out[i * kw + j] = j >= j1 && j < j2;
+  }
+  return 0;
+}
+
+size_t mask_workspace_bytes(int N, int H, int W) { return layout(N, H, W).total; }
+
+hipError_t launch_mask_morph(const uint8_t* in, uint8_t* out, int N, int H, int W, int dilate, int shape, int kw, int kh,
+                             int iterations, void* ws, hipStream_t st) {
+  const Layout l = layout(N, H, W);
+  u64* cur = (u64*)ws;
+  u64* tmp = (u64*)((char*)ws + l.plane);
+  MorphEl el;
+  if (!make_el(shape, kw, kh, &el)) return hipErrorInvalidValue;
+  MP_CHK(pack(in, cur, N, H, W, st));
+  MP_CHK(morph_n(&cur, &tmp, N, H, W, dilate != 0, el, iterations, st));
+  hipLaunchKernelGGL(mp_unpack, grid_for((size_t)H * W, N), dim3(kThreads), 0, st, cur, out, H, W, (W + 63) / 64);
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_components(const uint8_t* in, int* labels, int* areas, int N, int H, int W, void* ws, hipStream_t st) {
+  const Layout l = layout(N, H, W);
+  MP_CHK(pack(in, (u64*)ws, N, H, W, st));
+  return components((u64*)ws, labels, areas, (u64*)((char*)ws + l.counters), N, H, W, st);
+}
+
+hipError_t launch_optimize_mask(const uint8_t* in, uint8_t* out, int N, int H, int W, int mask_type, long long* summary, void* ws,
+                                hipStream_t st) {
+  const Layout l = layout(N, H, W);
+  u64* a = (u64*)ws;
+  u64* b = (u64*)((char*)ws + l.plane);
+  u64* c = (u64*)((char*)ws + 2 * l.plane);
+  int* labels = (int*)((char*)ws + l.labels);
+  int* areas = (int*)((char*)ws + l.areas);
+  u64* counters = (u64*)((char*)ws + l.counters);
+  const int E = 2, R = 0;
+  MorphEl el;
+  MP_CHK(pack(in, a, N, H, W, st));
+  if (mask_type == 0) {                                   // watermark
+    MP_CHK(open_close(&a, &b, N, H, W, false, E, 3, 3, 1, st));
+    MP_CHK(open_close(&a, &b, N, H, W, true, E, 7, 7, 3, st));
+    MP_CHK(open_close(&a, &b, N, H, W, true, E, 11, 11, 2, st));
+    make_el(E, 9, 9, &el);
+    MP_CHK(morph_n(&a, &b, N, H, W, true, el, 2, st));
+  } else if (mask_type == 1) {                            // text
+    MP_CHK(open_close(&a, &b, N, H, W, false, E, 2, 2, 1, st));
+    MP_CHK(open_close(&a, &b, N, H, W, true, E, 3, 3, 2, st));
+    // the two line closings read the same input (a): c = close(a, 5x1); a = close(a, 1x5) | c
+    make_el(R, 5, 1, &el);
+    MP_CHK(morph_pass(a, b, nullptr, N, H, W, true, el, st));
+    MP_CHK(morph_pass(b, c, nullptr, N, H, W, false, el, st));
+    make_el(R, 1, 5, &el);
+    MP_CHK(morph_pass(a, b, nullptr, N, H, W, true, el, st));
+    MP_CHK(morph_pass(b, a, c, N, H, W, false, el, st));
+    make_el(E, 4, 4, &el);
+    MP_CHK(morph_n(&a, &b, N, H, W, true, el, 1, st));
+  } else {                                                // mixed
+    MP_CHK(open_close(&a, &b, N, H, W, false, E, 2, 2, 1, st));
+    MP_CHK(open_close(&a, &b, N, H, W, true, E, 5, 5, 2, st));
+    make_el(E, 6, 6, &el);
+    MP_CHK(morph_n(&a, &b, N, H, W, true, el, 1, st));
+  }
+  MP_CHK(components(a, labels, areas, counters, N, H, W, st));
+  const dim3 g = grid_for((size_t)H * W, N);
+  hipLaunchKernelGGL(mp_cc_largest, g, dim3(kThreads), 0, st, labels, areas, counters, H, W);
+  hipLaunchKernelGGL(mp_select, dim3((unsigned)(((size_t)H * W + kPix - 1) / kPix), (unsigned)N), dim3(kThreads), 0, st, labels, areas, counters, out, H, W,
+                     mask_type);
+  if (summary) hipLaunchKernelGGL(mp_summary, dim3((N + 63) / 64), dim3(64), 0, st, counters, summary, N);
+  return hipGetLastError();
+}
+
+}  // namespace uwm

@@ -350,6 +350,56 @@ int uwm_resize_threshold(const float* logits, int ld, int N, int h, int w, int H
   LCHK(launch_resize_threshold(logits, ld, N, h, w, H, W, threshold, apply_sigmoid, mask, resized, (hipStream_t)stream));
   return 0;
 }
+// ---- mask post-processing (mask_post.hip): every argument is checked here, before any launch
+static int mask_shape_check(const char* fn, int N, int H, int W, const void* ws, size_t ws_bytes) {
+  if (N < 1 || H < 1 || W < 1) return fail("%s: N, H, W must be >= 1 (got %d, %d, %d)", fn, N, H, W);
+  if (N > 65535) return fail("%s: at most 65535 masks per call (got %d)", fn, N);
+  if ((long long)H * W >= 2147483647ll) return fail("%s: H*W must be below 2^31 - 1 (got %d x %d)", fn, H, W);
+  if (!ws) return fail("%s: null workspace", fn);
+  if ((uintptr_t)ws & 15) return fail("%s: workspace must be 16-byte aligned", fn);
+  const size_t need = mask_workspace_bytes(N, H, W);
+  if (ws_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", fn, ws_bytes, need);
+  return 0;
+}
+int uwm_mask_element(int shape, int kw, int kh, uint8_t* out) {
+  if (!out) return fail("uwm_mask_element: null argument");
+  if (shape != UWM_MORPH_RECT && shape != UWM_MORPH_ELLIPSE) return fail("uwm_mask_element: unknown shape %d (UWM_MORPH_RECT = 0 | UWM_MORPH_ELLIPSE = 2)", shape);
+  if (kw < 1 || kh < 1 || kw > 15 || kh > 15) return fail("uwm_mask_element: element size %d x %d outside 1..15", kw, kh);
+  if (mask_element(shape, kw, kh, out)) return fail("uwm_mask_element: bad argument");
+  return 0;
+}
+size_t uwm_mask_workspace_bytes(int N, int H, int W) {
+  if (N < 1 || H < 1 || W < 1 || (long long)H * W >= 2147483647ll) { fail("uwm_mask_workspace_bytes: bad shape %d x %d x %d", N, H, W); return 0; }
+  return mask_workspace_bytes(N, H, W);
+}
+int uwm_optimize_mask(const uint8_t* in, uint8_t* out, int N, int H, int W, int mask_type, long long* summary, void* ws,
+                      size_t ws_bytes, uwm_stream stream) {
+  if (!in || !out) return fail("uwm_optimize_mask: null argument");
+  if (mask_type != UWM_MASK_WATERMARK && mask_type != UWM_MASK_TEXT && mask_type != UWM_MASK_MIXED)
+    return fail("uwm_optimize_mask: unknown mask type %d (UWM_MASK_WATERMARK = 0 | UWM_MASK_TEXT = 1 | UWM_MASK_MIXED = 2)", mask_type);
+  if ((uintptr_t)summary & 7) return fail("uwm_optimize_mask: summary must be 8-byte aligned");
+  if (mask_shape_check("uwm_optimize_mask", N, H, W, ws, ws_bytes)) return 1;
+  LCHK(launch_optimize_mask(in, out, N, H, W, mask_type, summary, ws, (hipStream_t)stream));
+  return 0;
+}
+int uwm_op_morph(const uint8_t* in, uint8_t* out, int N, int H, int W, int dilate, int shape, int kw, int kh, int iterations,
+                 void* ws, size_t ws_bytes, uwm_stream stream) {
+  if (!in || !out) return fail("uwm_op_morph: null argument");
+  if (shape != UWM_MORPH_RECT && shape != UWM_MORPH_ELLIPSE) return fail("uwm_op_morph: unknown shape %d (UWM_MORPH_RECT = 0 | UWM_MORPH_ELLIPSE = 2)", shape);
+  if (kw < 1 || kh < 1 || kw > 15 || kh > 15) return fail("uwm_op_morph: element size %d x %d outside 1..15", kw, kh);
+  if (iterations < 1) return fail("uwm_op_morph: iterations must be >= 1 (got %d)", iterations);
+  if (mask_shape_check("uwm_op_morph", N, H, W, ws, ws_bytes)) return 1;
+  LCHK(launch_mask_morph(in, out, N, H, W, dilate, shape, kw, kh, iterations, ws, (hipStream_t)stream));
+  return 0;
+}
+int uwm_op_components(const uint8_t* in, int32_t* labels, int32_t* areas, int N, int H, int W, void* ws, size_t ws_bytes,
+                      uwm_stream stream) {
+  if (!in || !labels || !areas) return fail("uwm_op_components: null argument");
+  if (((uintptr_t)labels | (uintptr_t)areas) & 3) return fail("uwm_op_components: labels and areas must be 4-byte aligned");
+  if (mask_shape_check("uwm_op_components", N, H, W, ws, ws_bytes)) return 1;
+  LCHK(launch_mask_components(in, labels, areas, N, H, W, ws, (hipStream_t)stream));
+  return 0;
+}
 int uwm_preprocess_u8(const uint8_t* images, int N, int H, int W, int C, const float* mean, const float* std, const int* flags,
                       float* out_nchw, uwm_stream stream) {
   if (!images || !mean || !std || !out_nchw || N < 1 || H < 1 || W < 1 || C < 1 || C > 4) return fail("uwm_preprocess_u8: bad argument");

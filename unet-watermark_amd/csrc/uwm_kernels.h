@@ -384,4 +384,14 @@ hipError_t launch_stats(const float* logits, int ld, const void* target, int tdt
 hipError_t launch_threshold(const float* logits, int ld, size_t npix, float thr, int apply_sigmoid,
                             uint8_t* out, hipStream_t st);
 
+// mask post-processing (mask_post.hip): the reference's _optimize_mask on bit planes + union-find components.  ws holds
+// mask_workspace_bytes(N, H, W) bytes; the callers (uwm_abi.inc) have checked every argument
+int mask_element(int shape, int kw, int kh, uint8_t* out);      // host: kh*kw bytes of 0/1; non-zero on a bad shape / size
+size_t mask_workspace_bytes(int N, int H, int W);
+hipError_t launch_mask_morph(const uint8_t* in, uint8_t* out, int N, int H, int W, int dilate, int shape, int kw, int kh,
+                             int iterations, void* ws, hipStream_t st);
+hipError_t launch_mask_components(const uint8_t* in, int* labels, int* areas, int N, int H, int W, void* ws, hipStream_t st);
+hipError_t launch_optimize_mask(const uint8_t* in, uint8_t* out, int N, int H, int W, int mask_type, long long* summary, void* ws,
+                                hipStream_t st);
+
 }  // namespace uwm

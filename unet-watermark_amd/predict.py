@@ -2,7 +2,8 @@
 step1_batch_predict_watermark_masks (/root/reference/src/predict.py:68-99,303-368,560-664) for the model
 part of that path: checkpoint -> eval() -> logits -> threshold -> uint8 mask.  The reference runs batch 1
 per image; here a whole batch goes through ONE hipGraph replay of the eval forward (BASELINE config 5).
-OpenCV post-processing / IOPaint / OCR stay out of scope."""
+The reference's mask post-processing (_optimize_mask, src/predict.py:161-301) is opt-in through `mask_type` and runs on the
+device inside the same graph (postprocess.py); its automatic type detection, IOPaint and OCR stay out of scope."""
 from __future__ import annotations
 
 from typing import Optional
@@ -13,6 +14,7 @@ from .checkpoint import load_checkpoint
 from .config import get_cfg_defaults, update_config
 from .metrics import threshold_mask
 from .model import create_model_from_config
+from .postprocess import mask_type_code, optimize_mask, workspace as mask_workspace
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -45,6 +47,9 @@ class WatermarkPredictor:
         self._ugraph = None
         self._ukey = None
         self._uin = self._uout = self._uws = None
+        self._pgraph = None                   # predict_mask(mask_type=...): the forward + threshold + post-processing graph
+        self._pkey = None
+        self._pin = self._pout = self._pws = None
         self.freeze = bool(freeze)
         if self.freeze:
             self.model.freeze()               # the first forward fixes the bank forms
@@ -75,28 +80,62 @@ class WatermarkPredictor:
         return self._gout
 
     @torch.no_grad()
-    def predict_mask(self, x: torch.Tensor, apply_sigmoid: bool = False, use_graph: bool = True) -> torch.Tensor:
-        """-> uint8 {0,255} (N,H,W); default reproduces predict.py:624 (raw logits > THRESHOLD)."""
-        return threshold_mask(self.logits(x, use_graph), self.threshold, apply_sigmoid)
+    def predict_mask(self, x: torch.Tensor, apply_sigmoid: bool = False, use_graph: bool = True, mask_type: Optional[str] = None) -> torch.Tensor:
+        """-> uint8 {0,255} (N,H,W); default reproduces predict.py:624 (raw logits > THRESHOLD).  mask_type 'watermark' | 'text' |
+        'mixed': the reference's _optimize_mask on that mask (predict.py:357-362), inside the same captured graph."""
+        if mask_type is None:
+            return threshold_mask(self.logits(x, use_graph), self.threshold, apply_sigmoid)
+        mask_type_code(mask_type)
+        run = lambda t: optimize_mask(threshold_mask(self.model(t), self.threshold, apply_sigmoid), mask_type)
+        if not use_graph:
+            return run(x)
+        key = (tuple(x.shape), bool(apply_sigmoid), mask_type)
+        if self._pkey != key:
+            self._refreeze_for(x.shape[0], x.shape[2], x.shape[3])
+            self._pin = x.clone()
+            run(self._pin)                            # eager warm-up (also allocates the post-processing workspace)
+            torch.cuda.synchronize(self.device)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._pout = run(self._pin)
+            self._pgraph, self._pkey = g, key
+            self._pws = (self.model._ws, mask_workspace(x.device, *self._pout.shape))      # (the graph's workspaces stay alive with it)
+        self._pin.copy_(x)
+        self._pgraph.replay()
+        return self._pout
 
     def _refreeze_for(self, n: int, h: int, w: int):
         """freeze=True: a new graph shape whose bank forms differ from the frozen ones gets the arena re-made for it; the graphs
         captured on the old arena contents go."""
         if self.freeze and not self.model.frozen_serves(n, h, w):
             self.model.freeze(batch_shape=(n, h, w))
-            self._graph = self._gkey = self._ugraph = self._ukey = None
+            self._graph = self._gkey = self._ugraph = self._ukey = self._pgraph = self._pkey = None
 
     @torch.no_grad()
     def predict_mask_u8(self, images_u8_nhwc: torch.Tensor, out_size=None, apply_sigmoid: bool = False,
-                        use_graph: bool = True) -> torch.Tensor:
+                        use_graph: bool = True, mask_type: Optional[str] = None, return_summary: bool = False):
         """uint8 (N,H,W,3) images -> uint8 {0,255} masks (N,out_h,out_w) through ONE library call (uwm_predict_u8): ImageNet
         Normalize written straight into the forward's input layout, eval forward, resize to `out_size` (default: the input
-        size) + threshold.  Same masks as preprocess -> predict_mask / resize_threshold, bit for bit."""
+        size) + threshold.  Same masks as preprocess -> predict_mask / resize_threshold, bit for bit.
+        mask_type 'watermark' | 'text' | 'mixed': the reference's _optimize_mask (uwm_optimize_mask) on the resized, thresholded
+        mask, in place and inside the same captured graph; return_summary then adds the int64 (N,4) device tensor {components,
+        largest area, foreground pixels, id of the largest or -1} (the reference's watermark_ratio / "no watermark found" test,
+        src/predict.py:636-645, without copying the mask back).  mask_type=None: the masks as they were, untouched."""
         x = images_u8_nhwc.to(self.device, non_blocking=True)
-        run = lambda t: self.model.predict_u8(t, IMAGENET_MEAN, IMAGENET_STD, self.threshold, apply_sigmoid, out_size)
+        if mask_type is None:
+            if return_summary:
+                raise ValueError("return_summary needs a mask_type ('watermark', 'text' or 'mixed')")
+            run = lambda t: self.model.predict_u8(t, IMAGENET_MEAN, IMAGENET_STD, self.threshold, apply_sigmoid, out_size)
+        else:
+            mask_type_code(mask_type)
+
+            def run(t):
+                m = self.model.predict_u8(t, IMAGENET_MEAN, IMAGENET_STD, self.threshold, apply_sigmoid, out_size)
+                return optimize_mask(m, mask_type, return_summary=True, out=m)
+        pick = (lambda r: r) if mask_type is None or return_summary else (lambda r: r[0])
         if not use_graph:
-            return run(x)
-        key = (tuple(x.shape), None if out_size is None else tuple(out_size), bool(apply_sigmoid))
+            return pick(run(x))
+        key = (tuple(x.shape), None if out_size is None else tuple(out_size), bool(apply_sigmoid)) + (() if mask_type is None else (mask_type,))
         if self._ukey != key:
             self._refreeze_for(x.shape[0], x.shape[1], x.shape[2])
             self._uin = x.clone()
@@ -106,6 +145,8 @@ class WatermarkPredictor:
             with torch.cuda.graph(g):
                 self._uout = run(self._uin)
             self._ugraph, self._ukey, self._uws = g, key, self.model._ws
+            if mask_type is not None:
+                self._uws = (self._uws, mask_workspace(x.device, *self._uout[0].shape))
         self._uin.copy_(x)
         self._ugraph.replay()
-        return self._uout
+        return pick(self._uout)
