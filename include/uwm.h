@@ -376,11 +376,24 @@ typedef struct {
 } uwm_src;
 /* y[N][Ho][Wo][Cout] = conv(cat(s0,s1), w) ; w [Cout][Kpad] packed (k = tap*Ctot + c).
  * stats (2*Cout doubles: sum, sumsq; pre-zeroed) may be NULL.
- * cfg: -1 = the library's routing; 0..5 implicit-GEMM tile configs; 100+BN direct patch kernel; 200 16-channel patch
- * kernel; 300 (+BN, 308 = 8-wave) Winograd F(2x2,3x3); 400 Winograd in bf16x3 arithmetic; 500 segmentation-head streaming
- * kernel; 700 sub-pixel kernel for a 3x3 over a nearest-x2 upsampled 32-channel source with 16 outputs (conv_up2.hip);
- * 800 (+64 | +128 = channel tile) persistent LDS-DMA GEMM for 1x1 / stride-1 layers with Cin % 32 == 0 (conv_gemm.hip)
- * (tests / timing). */
+ * cfg (tests / timing; every code the library accepts, anything else is an error):
+ *    -1         the library's routing
+ *    0..5       flattened implicit GEMM, tile configuration {BM, BN}: 0 {128,128} 1 {128,64} 2 {128,32} 3 {128,16} 4 {64,64} 5 {64,128}
+ *    100+BN     direct patch kernel, BN = 16 | 32 | 64 | 128 output channels per workgroup (conv_patch.hip)
+ *    200        16-channel patch kernel (conv_patch16.hip)
+ *    300, 300+BN  Winograd F(2x2,3x3): 300 auto tile, BN = 16 | 32 | 64; 308 = the 8-wave variant (conv_wino8.hip)
+ *    400        Winograd in bf16x3 arithmetic (conv_wino_x3.hip)
+ *    500        segmentation-head streaming kernel (conv_head.hip)
+ *    600..603   fp16x3 direct form: 600 = the kernel the model would take (conv_f16x3.hip or conv_f16x3v2.hip by shape); conv_f16x3.hip's
+ *               601 four-wave kernel | 602 eight-wave kernel | 603 four-wave kernel, 32-channel tiles
+ *    607, 605   conv_f16x3v2.hip (whole 8 x 32-pixel tiles, Cout % 32 == 0, 32-channel tiles): 607 = its kernel (8 waves), 605 = the 4-wave
+ *               kernel no routing takes.  604 and 606 named removed forms: rejected
+ *    1600..1603, 1605, 1607  = 6xx without re-packing the filter bank (kernel-only timing: the previous call must have been the same layer and code)
+ *    610        the 7x7 / stride-2 ResNet stem in fp16x3 arithmetic (conv_stem_f16x3.hip; 4 stored input channels, 64 outputs)
+ *    700        sub-pixel kernel for a 3x3 over a nearest-x2 upsampled 32-channel source with 16 outputs (conv_up2.hip; with
+ *               uwm_op_set_igemm_f16x3(1): conv_up2_f16.hip)
+ *    710, 711   3x3 16 -> 16 / 32 -> 32 at full resolution in fp16x3 arithmetic (conv_c16_f16.hip)
+ *    800, 864, 928  persistent LDS-DMA GEMM for 1x1 / stride-1 layers with Cin % 32 == 0 (conv_gemm.hip): auto | 64 | 128 channel tile */
 /* preprocess_u8_nhwc4 alone (uwm_predict_u8's input kernel): uint8 [npix][C] (4-byte aligned, C 1..4) -> Normalize as fp32 [npix][4]
  * (16-byte aligned), padding channels zero; any pixel count */
 int  uwm_op_preprocess_u8_nhwc4(const uint8_t* images, long long npix, int C, const float* mean, const float* std, float* out,
@@ -392,9 +405,11 @@ int  uwm_op_conv(const uwm_src* s0, const uwm_src* s1, const float* w, int wrows
 int  uwm_op_dgrad(const float* dy, int N, int Ho, int Wo, int Cout, const float* wd, int Cin, int KpadD, int kh, int kw,
                   int stride, int pad, int H, int W, const float* addend, const float* mask, const float* mscale,
                   const float* mshift, float* dx, uwm_stream stream);
-/* force_igemm: 0 = the library's routing (Winograd-domain / sub-pixel / 16-channel / stem / 1x1-GEMM kernels where they apply);
- * 1 = flattened implicit GEMM only; 2 = no Winograd; 4 = wgrad_gemm.hip wherever applicable; 6 = the fp16x3 direct weight
- * gradient (wgrad_f16x3.hip: 3x3 stride 1, channels % 32 == 0, Wo % 32 == 0, Ho % 4 == 0) (tests / timing) */
+/* force_igemm (tests / timing), low byte: 0 = the library's routing (Winograd-domain / sub-pixel / 16-channel / stem / 1x1-GEMM /
+ * fp16x3 kernels where they apply); 1 = flattened implicit GEMM only; 2 = none of the dedicated kernels but wgrad_patch.hip; 4 =
+ * wgrad_gemm.hip (an error where it does not apply); 6 = the dedicated fp16x3 kernels (wgrad_f16x3.hip: 3x3 stride 1, channels % 32 == 0,
+ * Wo % 32 == 0, Ho % 4 == 0; the sub-pixel, stem and 16-channel kernels in their fp16x3 forms; an error elsewhere); 7 = the flattened
+ * implicit GEMM in its fp16x3 form.  6 and 7 take max|dy| through a one-off reduction. */
 int  uwm_op_wgrad(const uwm_src* s0, const uwm_src* s1, const float* dy, int N, int Ho, int Wo, int Cout, int wrows,
                   int Kpad, int kh, int kw, int stride, int pad, float* dw, int force_igemm, uwm_stream stream);
 int  uwm_op_pack_dgrad(const float* w, int Cout, int Kpad, int ntaps, int Cin, float* wd, int KpadD, int CoutP,

@@ -20,7 +20,7 @@ def timeit(f, reps=20):
     return e0.elapsed_time(e1) * 1e3 / reps      # us
 
 
-CFGS = [int(v) for v in sys.argv[1:]] or [600]      # 600 auto | 601 / 602 / 603: conv_f16x3.hip variants | 604 / 605: conv_f16x3v2.hip 64- / 32-channel tiles
+CFGS = [int(v) for v in sys.argv[1:]] or [600]      # 600 auto | 601 / 602 / 603: conv_f16x3.hip variants | 607 / 605: conv_f16x3v2.hip, its 8-wave / 4-wave kernel (include/uwm.h)
 for name, cin, cout, h in (("layer1", 64, 64, 128), ("layer2", 128, 128, 64), ("layer3", 256, 256, 32), ("layer4", 512, 512, 16),
                            ("dec2.c2", 64, 64, 128), ("dec1.c1", 384, 128, 64), ("dec0.c1", 768, 256, 32), ("dec3.c1", 128, 32, 256), ("dec3.c2", 32, 32, 256)):
     x = torch.randn(N, h, h, cin, device=dev); y = torch.empty(N, h, h, cout, device=dev)

@@ -799,11 +799,7 @@ static hipError_t launch_f3s(const ConvArgs& a, hipStream_t st, dim3 grid, size_
   return hipGetLastError();
 }
 hipError_t launch_conv_f16x3(const ConvArgs& a, hipStream_t st, int variant) {
-  if (a.wu_layout == 1) return launch_conv_f16x3v2(a, st, variant >= 4 ? variant : 0);      // the bank is a conv_f16x3v2.hip one
-  if (variant >= 4) return hipErrorInvalidValue;
-  if (!conv_f16x3_applicable(a)) return hipErrorInvalidValue;
-  if (a.out_up && (a.addend || a.mask || a.bias || a.bnb_y || (a.ssum && !a.bnb_mean) || (a.up_c0 < a.Cout && !a.out))) return hipErrorInvalidValue;
-  if (a.bnb_mean && (!a.ssum || !a.ssq || !a.bnb_rstd || !(a.out_up ? a.up_mask : (a.bnb_y ? a.bnb_y : a.mask)) || a.up_accum)) return hipErrorInvalidValue;
+  if (a.wu_layout != 0 || variant < 0 || variant > 3 || !conv_f16x3_applicable(a)) return hipErrorInvalidValue;      // (a layout-1 bank is conv_f16x3v2.hip's: conv_route)
   const int tilesN = (a.Cout + 63) / 64;
   const int tilesW = (a.Wo + kFT - 1) / kFT, tilesH = (a.Ho + kFT - 1) / kFT;
   const size_t main_lds = (size_t)2 * kFBuf * sizeof(_Float16) + 6 * 256 * sizeof(int), q_lds = (size_t)4 * 64 * 68 * sizeof(float);

@@ -16,11 +16,12 @@
 //     one v_med3 does ReLU + range clamp + halo zeroing, v_cvt_pk_f16_f32 rounds two values at once, and the low halves come from
 //     v_fma_mixlo/mixhi_f16 (f16(x - hi) in ONE instruction, reading hi straight out of the packed register).
 //
-// Work split: workgroup = 8 x 32 output pixels x 64 (NCF = 2) or 32 (NCF = 1) output channels, 4 waves; wave w = pixel rows
-// 2w, 2w+1 (two 32-pixel B fragments) x NCF 32-channel A fragments = 2 NCF accumulator tiles of 32 x 32 (64 VGPRs at NCF = 2).
-// Filter fragments come from global memory / L1 in MFMA lane order, one tap ahead (f16x3v2 bank: [chunk][tap][fragment][hi | lo]
-// [64 lanes][8 halfs]); the 10 x 34-pixel halo patch of a chunk is staged through registers (double-buffered LDS, one barrier per
-// chunk), its conversion rounds riding between the MFMAs of the previous chunk's taps.  Epilogue contract = conv_f16x3_kernel's.
+// Work split: workgroup = 8 x 32 output pixels x 32 output channels (NCF = 1: one 32-channel A fragment; the 64-channel form, NCF = 2,
+// measured at parity with conv_f16x3.hip and is no longer instantiated); MMA wave w = pixel rows 2w, 2w+1 (two 32-pixel B fragments) x
+// NCF accumulator tiles of 32 x 32.  The kernel the routing takes has 8 waves (four MMA waves, four loader waves: see it below).
+// Filter fragments in MFMA lane order (f16x3v2 bank: [chunk][tap][fragment][hi | lo][64 lanes][8 halfs]); the 10 x 34-pixel halo
+// patch of a chunk is staged through registers (double-buffered LDS, one barrier per chunk).  Epilogue contract = conv_f16x3_kernel's,
+// without the fused concat split.  The layers it takes (f16x3v2_shape): output rows % 64 == 32; the 64-row layers stay on conv_f16x3.hip.
 //
 // Reference semantics replaced: the 3x3 convolutions of smp.Unet's encoder / decoder forward and their input gradients
 // (/root/reference/src/models/unet_model.py:64-71 -> SURVEY.md §8 a5-a8, a10, a14).
@@ -62,13 +63,10 @@ int f16x3v2_nf(int rows) { return f16x3v2_nf_(rows); }
 
 // shapes the second form takes: whole 8 x 32 tiles, 32-channel output fragments (the launcher and whoever packs the bank agree
 // through ConvArgs::wu_layout, which carries this function's verdict)
-bool f16x3v2_shape(int Ho, int Wo, int rows, int chans, int dgrad) {
+bool f16x3v2_shape(int Ho, int Wo, int rows, int chans) {
   static const bool off = dbg_flag("UWM_F16X3_V1");
-  static const int mode = dbg_int("UWM_V2_MODE", 1);      // experiments: 0 never | 1 32-row-fragment layers only | 2 + forward convolutions | 3 wherever the shape allows
-  if (off || mode == 0 || (Wo % kVW) != 0 || (Ho % kVH) != 0 || (chans & 31) != 0 || rows < 32 || (rows & 31) != 0) return false;
-  if (mode == 1) return (rows & 63) != 0;
-  if (mode == 2) return (rows & 63) != 0 || !dgrad;
-  return true;
+  if (off || (Wo % kVW) != 0 || (Ho % kVH) != 0 || (chans & 31) != 0 || rows < 32 || (rows & 31) != 0) return false;
+  return (rows & 63) != 0;      // (the 64-row layers stay on conv_f16x3.hip: parity there)
 }
 
 __global__ __launch_bounds__(256) void f16x3v2_weights_multi_kernel(const WinoJobs jobs) {
@@ -135,7 +133,7 @@ __device__ __forceinline__ void split4(f4 x, u2& hi, u2& lo) {
 // R = one MMA wave's block [64 pixels = 2 image rows x 32][32 NCF + 4 floats] (raw accumulators); this wave finishes pixels
 // [p0, p0 + np) of it with lanes along the channels (whole 128- / 256-byte pixel rows per store): row un-scale, bias, residual
 // addend, ReLU mask, BatchNorm statistics / fused BatchNorm-backward sums — conv_f16x3_kernel's contract.  hb = image row of the
-// block's first row.  The concat-split form (ConvArgs::out_up, NCF = 2 only) sums 2 x 2 pixel blocks and needs np = 64.
+// block's first row.
 template <int NCF>
 __device__ __forceinline__ void v2_epilogue(const ConvArgs& a, const float* R, int p0, int np, int n, int hb, int w0, int n0, int lane,
                                             float ixs, f4& ps_, f4& pq_) {
@@ -145,43 +143,6 @@ __device__ __forceinline__ void v2_epilogue(const ConvArgs& a, const float* R, i
   const int cq = lane & (kCQ - 1), sub = lane / kCQ;
   const int co = n0 + cq * 4;
   const bool cok = co < a.Cout;
-  if (NCF == 2 && a.out_up != nullptr) {
-    f4 rs = {0.f, 0.f, 0.f, 0.f};
-    if (cok) rs = *(const f4*)(rinv + co) * ixs;
-    if (cok) {
-      if (n0 < a.up_c0) {
-        f4 bmu = {0.f, 0.f, 0.f, 0.f}, brs = bmu, msc = {1.f, 1.f, 1.f, 1.f}, msh = bmu;
-        if (bnb) { bmu = *(const f4*)(a.bnb_mean + co); brs = *(const f4*)(a.bnb_rstd + co); }
-        if (a.up_mscale) { msc = *(const f4*)(a.up_mscale + co); msh = *(const f4*)(a.up_mshift + co); }
-#pragma unroll
-        for (int r = 0; r < 16 / kSub; ++r) {
-          const int bx = r * kSub + sub;                   // block column 0..15
-          const float* q = R + (2 * bx) * VQ<NCF>::kLd + cq * 4;
-          f4 v = (*(const f4*)q + *(const f4*)(q + VQ<NCF>::kLd) + *(const f4*)(q + 32 * VQ<NCF>::kLd) + *(const f4*)(q + 33 * VQ<NCF>::kLd)) * rs;
-          const size_t o2 = (((size_t)n * (a.Ho >> 1) + (hb >> 1)) * (a.Wo >> 1) + ((w0 >> 1) + bx)) * a.up_c0 + co;
-          if (a.up_mask) {
-            f4 mk = *(const f4*)(a.up_mask + o2);
-            const f4 yr = mk;
-            if (a.up_mscale) mk = mk * msc + msh;
-            v.x = mk.x > 0.f ? v.x : 0.f; v.y = mk.y > 0.f ? v.y : 0.f;
-            v.z = mk.z > 0.f ? v.z : 0.f; v.w = mk.w > 0.f ? v.w : 0.f;
-            if (bnb) { ps_ += v; pq_ += v * ((yr - bmu) * brs); }
-          }
-          if (a.up_accum) v += *(const f4*)(a.out_up + o2);
-          *(f4*)(a.out_up + o2) = v;
-        }
-      } else {
-        const int c1n = a.Cout - a.up_c0;
-#pragma unroll 4
-        for (int r = 0; r < 64 / kSub; ++r) {
-          const int p = r * kSub + sub;
-          const int ho = hb + (p >> 5), wo = w0 + (p & 31);
-          *(f4*)(a.out + (((size_t)n * a.Ho + ho) * a.Wo + wo) * c1n + (co - a.up_c0)) = *(const f4*)(R + p * VQ<NCF>::kLd + cq * 4) * rs;
-        }
-      }
-    }
-    return;
-  }
   f4 rs = {0.f, 0.f, 0.f, 0.f}, bmu = rs, brs = rs, bia = rs, msc = {1.f, 1.f, 1.f, 1.f}, msh = rs;
   if (cok) rs = *(const f4*)(rinv + co) * ixs;
   if (bnb && cok) { bmu = *(const f4*)(a.bnb_mean + co); brs = *(const f4*)(a.bnb_rstd + co); }
@@ -215,7 +176,7 @@ template <int NCF, int NW>
 __device__ __forceinline__ void v2_stats(const ConvArgs& a, float* red, f4 ps_, f4 pq_, int n0, int tid, int lane, int wave) {
   constexpr int kCo = 32 * NCF, kCQ = kCo / 4;
   const int cq = lane & (kCQ - 1), sub = lane / kCQ;
-  const int stat_c = a.out_up != nullptr ? a.up_c0 : a.Cout;       // channels the statistics cover
+  const int stat_c = a.out_up != nullptr ? a.up_c0 : a.Cout;       // channels the statistics cover (conv_f16x3_kernel's rule; out_up never reaches this file)
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     float sv = ps_[e], qv = pq_[e];
@@ -242,7 +203,10 @@ __device__ __forceinline__ void v2_stats(const ConvArgs& a, float* red, f4 ps_, 
   }
 }
 
-// ---------------------------------------------------------------- main kernel
+// ---------------------------------------------------------------- 4-wave kernel (forced code 605 only: tests / timing)
+// The routing never takes it.  It stays compiled, with 32-channel tiles (NCF = 1), because the 8-wave kernel below shares
+// v2_epilogue<1> with it: with this second caller gone hipcc specialises the epilogue for the one that is left and emits a
+// different instruction stream for the kernel every 32-row-fragment layer runs on (scripts/isa_identity.py shows it).
 // NP = split products per tile (ConvArgs::nprod): 3 = hi*hi' + hi*lo' + lo*hi'; 2 = without the pixel operand's low half; 1 = hi*hi' only
 template <int NCF, int NP = 3>
 __global__ __launch_bounds__(256, 2) void conv_f16x3v2_kernel(const ConvArgs a) {
@@ -509,7 +473,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16x3v2s_kernel(const ConvArgs a)
   constexpr int dbg = UWM_F16V2_ABL;
   constexpr bool kALds = UWM_V2_ALDS != 0;
   constexpr int kAPieces = 9 * NCF * 2;                // 1-KB fragment planes of a chunk's filter block: [tap][fragment][hi | lo][64 lanes][16 B]
-  constexpr int kABuf = kAPieces * 1024;               // 36 864 bytes at NCF = 2
+  constexpr int kABuf = kAPieces * 1024;               // 18 432 bytes at NCF = 1
 
   constexpr int kTrip = (kSD == 4 || kSD == 2) ? (kSD == 4 ? 4 : 2) : (kSD == 3 ? 1 : 0);      // chunks per loop trip: (9 * kTrip) % kSD == 0
   static_assert(kTrip > 0 && (9 * kTrip) % kSD == 0, "UWM_V2_SD must be 2, 3 or 4");
@@ -823,8 +787,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16x3v2s_kernel(const ConvArgs a)
   }
 
   // ---------------- epilogue (the 4-wave kernel's, spread over eight waves): an MMA wave's 64 px x kCo block goes through its LDS
-  // region; waves w and w + 4 finish its first and its second image row (the concat-split form sums 2 x 2 blocks across the two
-  // rows: the MMA waves do it alone)
+  // region; waves w and w + 4 finish its first and its second image row
   if (is_mma) {
     float* const Rw = (float*)vsm + mw * 64 * VQ<NCF>::kLd;
 #pragma unroll
@@ -838,22 +801,20 @@ __global__ __launch_bounds__(512, 1) void conv_f16x3v2s_kernel(const ConvArgs a)
   __syncthreads();
   const float* const R = (const float*)vsm + mw * 64 * VQ<NCF>::kLd;
   f4 ps_ = {0.f, 0.f, 0.f, 0.f}, pq_ = ps_;
-  if (NCF == 2 && a.out_up != nullptr) { if (is_mma) v2_epilogue<NCF>(a, R, 0, 64, n, h0 + 2 * mw, w0, n0, lane, 1.f / xs, ps_, pq_); }
-  else v2_epilogue<NCF>(a, R, (wave >> 2) * 32, 32, n, h0 + 2 * mw, w0, n0, lane, 1.f / xs, ps_, pq_);
+  v2_epilogue<NCF>(a, R, (wave >> 2) * 32, 32, n, h0 + 2 * mw, w0, n0, lane, 1.f / xs, ps_, pq_);
   if (a.ssum != nullptr) v2_stats<NCF, 8>(a, (float*)vsm, ps_, pq_, n0, tid, lane, wave);
 }
 
 // 3x3 / stride 1 / pad 1 over whole 8 x 32-pixel tiles, 16-channel chunks in PAIRS on either side of a concat (the loop is
-// unrolled two chunks per trip), 32-channel output fragments; the fused concat split with the boundary on a 64-channel tile
+// unrolled two chunks per trip), 32-channel output fragments; no fused concat split
 bool conv_f16x3v2_applicable(const ConvArgs& a) {
   return a.wu != nullptr && a.wu_layout == 1 && a.ntaps == 9 && a.kw == 3 && a.smul == 1 && a.sdiv == 1 && (a.rmul == 1 ? a.off == -1 : a.off == 1) &&
          (a.Ctot & 31) == 0 && (a.C0 & 15) == 0 && (a.s0.C & 3) == 0 && (a.s1.C & 3) == 0 && (a.Cout & 31) == 0 && a.Cout >= 32 &&
-         a.Hl == a.Ho && a.Wl == a.Wo && (a.Ho % kVH) == 0 && (a.Wo % kVW) == 0 && a.Hl < 32768 && a.Wl < 32768 &&
-         (!a.out_up || (((a.Ho | a.Wo) & 1) == 0 && (a.up_c0 & 63) == 0 && a.up_c0 <= a.Cout && (a.Cout & 63) == 0)) &&
+         a.Hl == a.Ho && a.Wl == a.Wo && (a.Ho % kVH) == 0 && (a.Wo % kVW) == 0 && a.Hl < 32768 && a.Wl < 32768 && !a.out_up &&
          (size_t)a.N * a.s0.H * a.s0.W * a.s0.C < (1ull << 31) && (size_t)a.N * a.s1.H * a.s1.W * a.s1.C < (1ull << 31);
 }
 
-template <int NCF, int NP>
+template <int NCF, int NP>      // (the routing record names the kernels by these spellings)
 static hipError_t launch_v2(const ConvArgs& a, hipStream_t st, unsigned grid, size_t lds) {
   static DevOnce lds_attr;
   { hipError_t e = lds_attr.set_max_lds((const void*)conv_f16x3v2_kernel<NCF, NP>, lds); if (e != hipSuccess) return e; }
@@ -867,40 +828,22 @@ static hipError_t launch_v2s(const ConvArgs& a, hipStream_t st, unsigned grid, s
   UWM_LAUNCH(42, a.flops, a.bytes, (conv_f16x3v2s_kernel<NCF, NP>), dim3(grid), dim3(512), lds, st, a);
   return hipGetLastError();
 }
-hipError_t launch_conv_f16x3v2(const ConvArgs& a, hipStream_t st, int variant) {      // variant: 0 auto | 4 / 5 = 4-wave kernel, 64- / 32-channel tiles | 6 / 7 = 8-wave kernel, 64- / 32-channel tiles
+// the 8-wave kernel with 32-channel tiles (kernel-alone at 16 x 512^2, 128 -> 32 at 256^2: 260 us against 275 on the 4-wave kernel and
+// 394 on conv_f16x3.hip's); four_wave: forced code 605
+hipError_t launch_conv_f16x3v2(const ConvArgs& a, hipStream_t st, bool four_wave) {
   if (!conv_f16x3v2_applicable(a)) return hipErrorInvalidValue;
-  if (a.out_up && (a.addend || a.mask || a.bias || a.bnb_y || (a.ssum && !a.bnb_mean) || (a.up_c0 < a.Cout && !a.out))) return hipErrorInvalidValue;
-  if (a.bnb_mean && (!a.ssum || !a.ssq || !a.bnb_rstd || !(a.out_up ? a.up_mask : (a.bnb_y ? a.bnb_y : a.mask)) || a.up_accum)) return hipErrorInvalidValue;
   const int tiles = a.N * (a.Ho / kVH) * (a.Wo / kVW);
-  const size_t main_lds = (size_t)2 * kVBuf + (size_t)kVRounds * 256 * sizeof(int);
-  // which kernel (kernel-alone timings at 16 x 512^2, profiles/r04_*): 32-channel tiles -> the 8-wave kernel (128 -> 32 at 256^2: 260 us
-  // against 275 on the 4-wave kernel and 394 on conv_f16x3.hip's); 64-channel tiles -> the 4-wave kernel while the launch gives every
-  // CU two workgroups (they cover each other's prologue and epilogue: 64 -> 64 at 128^2 71 vs 85 us), the 8-wave kernel below that
-  // (256 -> 256 at 32^2: 56 vs 57-69 us)
-  int v = variant;
-  if (v == 0) {
-    const long wgs64 = (long)route_N(a) * (a.Ho / kVH) * (a.Wo / kVW) * ((a.Cout + 63) / 64);
-    if ((a.Cout & 63) != 0) v = 7;
-    else v = (wgs64 >= 2L * device_cu_count() || a.out_up) ? 4 : 6;
-  }
-  if ((v == 4 || v == 6) && (a.Cout & 63)) return hipErrorInvalidValue;
-  if ((v == 5 || v == 7) && a.out_up) return hipErrorInvalidValue;
-  const int ncf = (v == 4 || v == 6) ? 2 : 1;
-  // epilogue blocks: 4 waves x 64 pixels x (32 ncf + 4) floats — 36.9 KB at 32-channel tiles, so the 4-wave kernel's 49.6 KB of
-  // staging LDS (and its 168 VGPRs) admit THREE workgroups per CU there
-  const size_t q_lds = (size_t)4 * 64 * (32 * ncf + 4) * sizeof(float);
-  const size_t lds = main_lds > q_lds ? main_lds : q_lds;
-  const unsigned grid = (unsigned)(tiles * (a.Cout / (32 * ncf)));
+  const size_t q_lds = (size_t)4 * 64 * VQ<1>::kLd * sizeof(float);      // epilogue blocks: 4 MMA waves x 64 pixels x (32 + 4) floats
+  const unsigned grid = (unsigned)(tiles * (a.Cout / 32));
   const int np = (a.nprod >= 1 && a.nprod <= 3) ? a.nprod : 3;
-  if (v == 6 || v == 7) {
-    const size_t s_lds = UWM_V2_ALDS ? (size_t)2 * kVBuf + (size_t)2 * 9 * ncf * 2 * 1024 : 0;      // patch buffers + two filter-fragment blocks
-    const size_t lds8 = s_lds > q_lds ? s_lds : q_lds;
-    if (v == 7) return np == 3 ? launch_v2s<1, 3>(a, st, grid, lds8) : np == 2 ? launch_v2s<1, 2>(a, st, grid, lds8) : launch_v2s<1, 1>(a, st, grid, lds8);
-    return np == 3 ? launch_v2s<2, 3>(a, st, grid, lds8) : np == 2 ? launch_v2s<2, 2>(a, st, grid, lds8) : launch_v2s<2, 1>(a, st, grid, lds8);
+  if (four_wave) {
+    const size_t main_lds = (size_t)2 * kVBuf + (size_t)kVRounds * 256 * sizeof(int);
+    const size_t lds = main_lds > q_lds ? main_lds : q_lds;
+    return np == 3 ? launch_v2<1, 3>(a, st, grid, lds) : np == 2 ? launch_v2<1, 2>(a, st, grid, lds) : launch_v2<1, 1>(a, st, grid, lds);
   }
-  if (v == 5) return np == 3 ? launch_v2<1, 3>(a, st, grid, lds) : np == 2 ? launch_v2<1, 2>(a, st, grid, lds) : launch_v2<1, 1>(a, st, grid, lds);
-  if (v != 4) return hipErrorInvalidValue;
-  return np == 3 ? launch_v2<2, 3>(a, st, grid, lds) : np == 2 ? launch_v2<2, 2>(a, st, grid, lds) : launch_v2<2, 1>(a, st, grid, lds);
+  const size_t s_lds = UWM_V2_ALDS ? (size_t)2 * kVBuf + (size_t)2 * 9 * 2 * 1024 : 0;      // patch buffers + two filter-fragment blocks
+  const size_t lds = s_lds > q_lds ? s_lds : q_lds;
+  return np == 3 ? launch_v2s<1, 3>(a, st, grid, lds) : np == 2 ? launch_v2s<1, 2>(a, st, grid, lds) : launch_v2s<1, 1>(a, st, grid, lds);
 }
 
 }  // namespace uwm

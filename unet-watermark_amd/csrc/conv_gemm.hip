@@ -339,7 +339,6 @@ static hipError_t launch_gemm(const ConvArgs& a, hipStream_t st, int cls) {
 // bn: 0 auto | 128 | 64 output channels per tile
 hipError_t launch_conv_gemm(const ConvArgs& a, hipStream_t st, int bn) {
   if (!conv_gemm_applicable(a)) return hipErrorInvalidValue;
-  if (a.bnb_mean && (!a.ssum || !a.ssq || !a.bnb_rstd || !(a.bnb_y ? a.bnb_y : a.mask))) return hipErrorInvalidValue;
   if (bn <= 0) {
     // 64-channel tiles run three workgroups per CU (148 VGPRs, 48 KB): better latency hiding for the short-K, HBM-bound layers
     // and for launches with few tiles; 128-channel tiles read X half as often: the long-K layers with plenty of tiles

@@ -261,7 +261,6 @@ static hipError_t launch_head_dgrad(const ConvArgs& a, hipStream_t st) {
 }
 hipError_t launch_conv_head_dgrad(const ConvArgs& a, hipStream_t st) {
   if (!conv_head_dgrad_applicable(a)) return hipErrorInvalidValue;
-  if (a.bnb_mean && (!a.ssum || !a.ssq || !a.bnb_rstd || !a.mask)) return hipErrorInvalidValue;
   switch (a.Cout) {
     case 8: return launch_head_dgrad<2>(a, st);
     case 16: return launch_head_dgrad<4>(a, st);
@@ -294,7 +293,7 @@ static hipError_t launch_head(const ConvArgs& a, hipStream_t st) {
 }
 
 hipError_t launch_conv_head(const ConvArgs& a, hipStream_t st) {
-  if (!conv_head_applicable(a) || a.bnb_mean) return hipErrorInvalidValue;      // (the forward head has no BatchNorm-backward epilogue)
+  if (!conv_head_applicable(a)) return hipErrorInvalidValue;
   switch (a.Ctot) {
     case 8: return launch_head<2>(a, st);
     case 16: return launch_head<4>(a, st);

@@ -385,116 +385,13 @@ static hipError_t launch_s2_dgrad_(const ConvArgs& a0, hipStream_t st, int cls) 
   return hipGetLastError();
 }
 
-static int g_winograd = -1;
-bool winograd_enabled() {
-  if (g_winograd < 0) { const char* e = getenv("UWM_WINOGRAD"); g_winograd = (e && e[0] == '0') ? 0 : 1; }
-  return g_winograd != 0;
-}
-void winograd_set_mode(int mode) { g_winograd = mode; }
-int winograd_mode() { (void)winograd_enabled(); return g_winograd; }
-int device_cu_count() {
-  static int cus[64] = {0};
-  int dev = 0; (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64) return 256;
-  if (!cus[dev] && (hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus[dev] <= 0)) cus[dev] = 256;
-  return cus[dev];
-}
-
-// mirrors the auto routing below: true when launch_conv(a, st) ends on a kernel whose epilogue can carry the fused
-// BatchNorm-backward sums (ConvArgs::bnb_*): conv_wino_kernel<NI>, conv_wino_x3_kernel, conv_patch16_kernel, conv_head_dgrad_kernel,
-// conv_up2_dgrad_kernel, conv_igemm_kernel, conv_c16_f16_kernel
-// (with a.bnb_y set: only the epilogues that read yhat from a separate tensor count — conv_wino_kernel<NI> and conv_igemm_kernel)
-bool conv_epilogue_carries_bnb(const ConvArgs& a) {
-  if (a.ig16 && a.prec != 2 && (conv_c16_f16_applicable(a) || conv_c32_f16_applicable(a))) return true;      // conv_c16_f16_kernel / conv_c32_f16_kernel (dgrad epilogue)
-  if (a.prec == 2) return !a.out_up && (a.wu_layout == 1 ? conv_f16x3v2_applicable(a) : conv_f16x3_applicable(a));
-  if (a.bnb_y) {
-    if (a.out_up || a.prec == 1) return false;
-    static const bool no_y = dbg_flag("UWM_NO_BNB_Y");
-    if (no_y || conv_up2_applicable(a) || conv_head_applicable(a) || conv_head_dgrad_applicable(a) || conv_patch16_applicable(a)) return false;
-    if (wino_mode_of(a.wino) != 0 && conv_wino_applicable(a)) return true;      // (launch_conv_wino skips the 8-wave variant when bnb_mean is set)
-    return !conv_patch_applicable(a);
-  }
-  static const bool no_up2 = dbg_flag("UWM_NO_UP2");
-  if (a.out_up) return (!no_up2 && conv_up2_dgrad_applicable(a)) || (a.prec == 1 ? conv_wino_x3_applicable(a) : conv_wino_applicable(a));
-  static const bool no_head = dbg_flag("UWM_NO_CONV_HEAD");
-  if (!no_up2 && conv_up2_applicable(a)) return false;
-  if (!no_head && conv_head_applicable(a)) return false;
-  if (!no_head && conv_head_dgrad_applicable(a)) return true;
-  if (wino_mode_of(a.wino) != 0 && conv_wino_applicable(a) && !conv_patch16_applicable(a))
-    return a.prec == 1 || !conv_wino8_applicable(a);      // (the 8-wave variant has no fused BatchNorm-backward sums)
-  if (conv_patch16_applicable(a)) return true;
-  if (conv_patch_applicable(a)) return false;             // (direct 3x3 kernels of Winograd mode 0: no bnb epilogue)
-  static const bool no_igemm_bnb = dbg_flag("UWM_NO_IGEMM_BNB");
-  return !no_igemm_bnb;                                   // flattened implicit GEMM / stride-2 parity classes (conv_igemm.hip)
+hipError_t launch_conv_s2_dgrad(const ConvArgs& a, hipStream_t st, int cfg) {
+  if (cfg == 4) return launch_s2_dgrad<64, 64, 2, 2>(a, st, 4);
+  return cfg == 1 ? launch_s2_dgrad<128, 64, 2, 2>(a, st, 1) : launch_s2_dgrad<128, 128, 2, 2>(a, st, 0);
 }
 
 // tile configurations: {BM, BN}: 0:{128,128} 1:{128,64} 2:{128,32} 3:{128,16} 4:{64,64} 5:{64,128}
-hipError_t launch_conv(const ConvArgs& a, hipStream_t st, int force_cfg) {
-  if (a.M <= 0 || a.Cout <= 0 || (a.Cout & 3) || (a.Kpad & 31) || (a.Ctot & 3) || (a.C0 & 3)) return hipErrorInvalidValue;
-  int cfg = force_cfg;
-  static const bool trace = dbg_flag("UWM_TRACE_CONV");
-  if (trace)
-    fprintf(stderr, "conv %s N=%d Ctot=%d(C0=%d up=%d) Cout=%d Ho=%d Wo=%d Hl=%d Wl=%d taps=%d smul=%d sdiv=%d wino=%d gflop=%.2f\n",
-            a.rmul < 0 ? "dgrad" : "fwd", a.N, a.Ctot, a.C0, a.s0.up, a.Cout, a.Ho, a.Wo, a.Hl, a.Wl, a.ntaps, a.smul, a.sdiv,
-            (int)(cfg < 0 && wino_mode_of(a.wino) != 0 && conv_wino_applicable(a)), a.flops * 1e-9);
-  if (cfg == 700) return launch_conv_up2(a, st);
-  if (cfg == 710 || (cfg < 0 && a.ig16 && a.prec != 2 && conv_c16_f16_applicable(a))) return launch_conv_c16_f16(a, st);
-  if (cfg == 711 || (cfg < 0 && a.ig16 && a.prec != 2 && conv_c32_f16_applicable(a))) return launch_conv_c32_f16(a, st);      // 32 -> 32, fp16x3      // 16 -> 16 at full resolution, fp16x3
-  if (cfg >= 800 && cfg < 1000) return launch_conv_gemm(a, st, cfg - 800);
-  if (cfg == 500) return launch_conv_head(a, st);
-  if ((cfg >= 600 && cfg <= 607) || (cfg < 0 && a.prec == 2)) return launch_conv_f16x3(a, st, cfg >= 600 ? cfg - 600 : 0);      // fp16x3 direct form: the bank behind a.wu is a conv_f16x3.hip one
-  if (cfg == 400) return launch_conv_wino_x3(a, st);
-  if (cfg >= 300) return launch_conv_wino(a, st, cfg - 300);
-  if (a.out_up) {                                                  // fused concat split: Winograd epilogues (and the sub-pixel dgrad of conv_up2.hip)
-    static const bool no_up2d = dbg_flag("UWM_NO_UP2");
-    if (cfg < 0 && !no_up2d && conv_up2_dgrad_applicable(a)) return launch_conv_up2_dgrad(a, st);
-    if (a.prec == 1) return launch_conv_wino_x3(a, st);
-    return conv_wino_applicable(a) ? launch_conv_wino(a, st) : hipErrorInvalidValue;
-  }
-  if (cfg == 200) return launch_conv_patch16(a, st);
-  static const bool no_up2 = dbg_flag("UWM_NO_UP2");
-  if (cfg < 0 && !no_up2 && conv_up2_applicable(a)) return launch_conv_up2(a, st);      // sub-pixel decomposition: Winograd's 2.25x without transforms
-  static const bool no_head = dbg_flag("UWM_NO_CONV_HEAD");
-  if (cfg < 0 && !no_head && conv_head_applicable(a)) return launch_conv_head(a, st);
-  if (cfg < 0 && !no_head && conv_head_dgrad_applicable(a)) return launch_conv_head_dgrad(a, st);      // few channels -> <= 4 classes: HBM streaming kernel
-  // 16-channel inputs at full resolution are HBM-bound: the one-barrier direct kernel beats the Winograd pipeline there
-  if (cfg < 0 && wino_mode_of(a.wino) != 0 && conv_wino_applicable(a) && !conv_patch16_applicable(a))
-    return a.prec == 1 ? launch_conv_wino_x3(a, st) : launch_conv_wino(a, st);      // prec 1: the bank behind a.wu is a bf16x3 one
-  if (cfg >= 100) return launch_conv_patch(a, st, cfg - 100);
-  if (cfg < 0 && conv_patch16_applicable(a)) return launch_conv_patch16(a, st);
-  if (cfg < 0 && conv_patch_applicable(a)) {
-    // patch-tiled 3x3: pick the channel tile so the launch has >= 512 workgroups when it can
-    const long sp = (long)route_N(a) * ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16);
-    int bn = a.Cout >= 128 ? 128 : (a.Cout > 32 ? 64 : (a.Cout > 16 ? 32 : 16));
-    if (bn == 128 && sp * ((a.Cout + 127) / 128) < 512) bn = 64;
-    return launch_conv_patch(a, st, bn);
-  }
-  if (cfg < 0 && conv_s2_dgrad_applicable(a))
-  {
-    // the four classes carry 1 / 2 / 2 / 4 of a 3x3's taps, so the launch is as long as its four-tap class: when that class alone
-    // has fewer 128-wide tiles than CUs (layer3 / layer4 at batch 16: 128 / 64 workgroups, 169 / 233 us), 64 x 64 tiles
-    const long t128 = (long)((route_N(a) * (a.Ho >> 1) * (a.Wo >> 1) + 127) / 128) * ((a.Cout + 127) / 128);
-    if (a.Cout > 64 && t128 < device_cu_count()) return launch_s2_dgrad<64, 64, 2, 2>(a, st, 4);
-    return a.Cout <= 64 ? launch_s2_dgrad<128, 64, 2, 2>(a, st, 1) : launch_s2_dgrad<128, 128, 2, 2>(a, st, 0);
-  }
-  if (cfg < 0 && conv_gemm_preferred(a)) return launch_conv_gemm(a, st, 0);      // 1x1 / stride 1, Cin % 32 == 0: persistent LDS-DMA GEMM
-  if (cfg < 0) {
-    const long tiles128 = (long)((route_M(a) + 127) / 128);
-    if (a.Cout <= 16) cfg = 3;
-    else if (a.Cout <= 32) cfg = 2;
-    else if (a.Cout <= 64) cfg = (tiles128 >= 512) ? 1 : 4;
-    else {
-      const long b0 = tiles128 * ((a.Cout + 127) / 128);
-      // 1x1 layers with channel counts like 144 or 192 (MBConv expand / project dgrad): the 128-wide tile pads them to 256;
-      // the 64-wide tile wastes far fewer MFMAs and LDS reads
-      static const bool narrow = !dbg_flag("UWM_NO_NARROW_1X1");
-      const int pad128 = ((a.Cout + 127) / 128) * 128, pad64 = ((a.Cout + 63) / 64) * 64;
-      if (narrow && a.ntaps == 1 && pad128 * 100 > pad64 * 115 && tiles128 * (pad64 / 64) >= 512) cfg = 1;
-      else if (b0 >= 512) cfg = 0;
-      else if (tiles128 * ((a.Cout + 63) / 64) >= 512) cfg = 1;
-      else cfg = 4;
-    }
-  }
+hipError_t launch_conv_igemm(const ConvArgs& a, hipStream_t st, int cfg) {
   switch (cfg) {
     case 0: return launch_cfg<128, 128, 2, 2>(a, st, 0);
     case 1: return launch_cfg<128, 64, 2, 2>(a, st, 1);

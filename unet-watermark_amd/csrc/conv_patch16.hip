@@ -250,7 +250,6 @@ bool conv_patch16_applicable(const ConvArgs& a) {
 
 hipError_t launch_conv_patch16(const ConvArgs& a, hipStream_t st) {
   if (!conv_patch16_applicable(a) || (a.Cout & 3)) return hipErrorInvalidValue;
-  if (a.bnb_mean && (!a.ssum || !a.ssq || !a.bnb_rstd || !a.mask)) return hipErrorInvalidValue;
   return a.Cout > 16 ? launch_p16<32>(a, st, 18) : launch_p16<16>(a, st, 17);
 }
 

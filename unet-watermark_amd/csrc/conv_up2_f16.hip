@@ -397,7 +397,6 @@ __global__ __launch_bounds__(256, 2) void conv_up2_dgrad_f16_kernel(const ConvAr
 
 hipError_t launch_conv_up2_dgrad_f16(const ConvArgs& a, hipStream_t st) {
   if (!conv_up2_dgrad_applicable(a)) return hipErrorInvalidValue;
-  if (a.bnb_mean && (!a.ssum || !a.ssq || !a.bnb_rstd || !a.up_mask || a.up_accum)) return hipErrorInvalidValue;
   const size_t lds = (size_t)kBankBytes + 2 * kDEnt * 128;
   const int ntiles = a.N * ((a.Ho >> 1) / kDH) * ((a.Wo >> 1) / kDW);
   const int nwg = ntiles < 2 * device_cu_count() ? ntiles : 2 * device_cu_count();

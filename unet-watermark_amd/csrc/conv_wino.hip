@@ -448,15 +448,9 @@ bool conv_wino_applicable(const ConvArgs& a) {
          (size_t)a.N * a.s0.H * a.s0.W * a.s0.C < 0x7fffffffull && (size_t)a.N * a.s1.H * a.s1.W * a.s1.C < 0x7fffffffull;   // 32-bit patch offsets
 }
 
-// bn: 0 auto | 64 | 32 | 16 output channels per workgroup
+// bn: 0 auto | 64 | 32 | 16 output channels per workgroup (conv_route decides between this kernel and the 8-wave variant)
 hipError_t launch_conv_wino(const ConvArgs& a, hipStream_t st, int bn) {
   if (!conv_wino_applicable(a)) return hipErrorInvalidValue;
-  if (a.out_up && ((a.Ho | a.Wo) & 1 || (a.up_c0 & 3) || a.up_c0 > a.Cout || a.addend || a.mask || a.bias || (a.ssum && !a.bnb_mean) ||
-                   (a.up_c0 < a.Cout && !a.out) || bn == 8))
-    return hipErrorInvalidValue;
-  if (a.bnb_mean && (!a.ssum || !a.ssq || !a.bnb_rstd || !(a.out_up ? a.up_mask : (a.bnb_y ? a.bnb_y : a.mask)) || a.up_accum || bn == 8 || (a.out_up && a.bnb_y))) return hipErrorInvalidValue;
-  if (bn == 8) return launch_conv_wino8(a, st);
-  if (bn <= 0 && !a.bnb_mean && conv_wino8_applicable(a)) return launch_conv_wino8(a, st);
   if (bn <= 0) {
     bn = a.Cout > 32 ? 64 : (a.Cout > 16 ? 32 : 16);
     // deep, spatially small layers: 64-channel tiles leave half the workgroup slots empty -> 32-channel tiles

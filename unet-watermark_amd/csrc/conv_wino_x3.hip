@@ -381,10 +381,6 @@ bool conv_wino_x3_applicable(const ConvArgs& a) {
 
 hipError_t launch_conv_wino_x3(const ConvArgs& a, hipStream_t st) {
   if (!conv_wino_x3_applicable(a)) return hipErrorInvalidValue;
-  if (a.out_up && ((a.Ho | a.Wo) & 1 || (a.up_c0 & 3) || a.up_c0 > a.Cout || a.addend || a.mask || a.bias || (a.ssum && !a.bnb_mean) ||
-                   (a.up_c0 < a.Cout && !a.out)))
-    return hipErrorInvalidValue;
-  if (a.bnb_mean && (!a.ssum || !a.ssq || !a.bnb_rstd || !(a.out_up ? a.up_mask : a.mask) || a.up_accum)) return hipErrorInvalidValue;
   const int tilesN = (a.Cout + kBN - 1) / kBN;
   const int tilesW = (a.Wo + kTW - 1) / kTW, tilesH = (a.Ho + kTH - 1) / kTH;
   const size_t main_lds = (size_t)(2 * kUs + 4 * kPlane) * sizeof(float);

@@ -534,8 +534,8 @@ static int op_f16x3_prepare(ConvArgs& a, hipStream_t st, int variant = 0, bool r
   }
   WinoJobs jobs; jobs.n = 1;
   WinoJob& j = jobs.j[0];
-  // bank layout: 601-603 force a conv_f16x3.hip kernel (layout 0), 604 / 605 a conv_f16x3v2.hip one (layout 1), 600 = what the model would take
-  const int layout = variant >= 4 ? 1 : (variant == 0 && f16x3v2_shape(a.Ho, a.Wo, a.wrows, a.Ctot, 0) && a.wrows == a.Cout ? 1 : 0);
+  // bank layout: 601-603 force a conv_f16x3.hip kernel (layout 0), 605 / 607 a conv_f16x3v2.hip one (layout 1), 600 = what the model would take
+  const int layout = variant >= 4 ? 1 : (variant == 0 && f16x3v2_shape(a.Ho, a.Wo, a.wrows, a.Ctot) && a.wrows == a.Cout ? 1 : 0);
   j.w = a.w; j.ut = buf; j.rows = a.wrows; j.chans = a.Ctot; j.Kpad = a.Kpad; j.mode = 0; j.src_rows = a.wrows; j.pad_ = layout;
   if (!(reuse && last_w == a.w && last_rows == a.wrows && last_chans == a.Ctot && last_layout == layout)) LCHK(launch_f16x3_weights_multi(jobs, st));
   last_w = a.w; last_rows = a.wrows; last_chans = a.Ctot; last_layout = layout;
@@ -672,7 +672,8 @@ int uwm_op_conv(const uwm_src* s0, const uwm_src* s1, const float* w, int wrows,
   }
   const bool reuse_bank = cfg >= 1600 && cfg <= 1607;      // 16xx = 6xx without re-packing the filter bank (kernel-only timing: the previous call must have been the same layer and layout)
   if (reuse_bank) cfg -= 1000;
-  if (cfg >= 600 && cfg <= 607) {                     // 606 / 607: conv_f16x3v2 8-wave kernel; 600 auto | 601 four-wave kernel | 602 eight-wave kernel | 603 four-wave, 32-channel tiles | 604 / 605 conv_f16x3v2 64- / 32-channel tiles
+  if (cfg == 604 || cfg == 606) return fail("uwm_op_conv: cfg %d names a removed conv_f16x3v2 form (607 is its kernel)", reuse_bank ? cfg + 1000 : cfg);
+  if (cfg >= 600 && cfg <= 607) {                     // the codes: include/uwm.h
     if (!op_wino_shape(a, kh, kw, stride, pad)) return fail("uwm_op_conv: cfg 600 (fp16x3) needs 3x3 s1 p1, Ho >= 8, Wo >= 16");
     if (op_f16x3_prepare(a, (hipStream_t)stream, cfg - 600, reuse_bank)) return 1;
   } else if (((cfg >= 300 && cfg < 500) || (cfg < 0 && winograd_mode() != 0)) && op_wino_shape(a, kh, kw, stride, pad)) {

@@ -42,7 +42,7 @@ struct DevOnce {
     return e;
   }
 };
-// ---- debug switches: ONE gate.  Every routing / ablation switch of the library (UWM_NO_*, UWM_TRACE_CONV, UWM_WGRAD_V1, UWM_WW_TA:
+// ---- debug switches: ONE gate.  Every routing / ablation switch of the library (UWM_NO_*, UWM_TRACE_CONV, UWM_WW_TA:
 // INTEGRATION.md 2b) is read through dbg_flag() / dbg_int(), which answer "unset" unless UWM_DEBUG=1 is in the environment — a
 // production process cannot be re-routed by a stray variable.  (UWM_WINOGRAD and UWM_SIDE_STREAM are documented process
 // defaults of public setters, not debug switches.)
@@ -185,11 +185,25 @@ int  prof_collect(double* out /* [kProfClasses][4] = launches, ms, flops, bytes 
 const char* prof_class_name(int cls);
 
 // ---- launchers (all asynchronous on `st`, no host sync, no allocation) ----
+// Routing (uwm_route.hip): ONE decision per launch.  conv_route / wgrad_route are pure host functions (nothing of HIP but
+// device_cu_count()); launch_conv / launch_wgrad are argument sanity, the route, one switch.  v = the variant / tile code the routed
+// kernel's launcher takes (0 where it takes none).
+enum ConvKernel { kConvInvalid = 0, kConvUp2, kConvUp2F16, kConvUp2Dgrad, kConvUp2DgradF16, kConvC16F16, kConvC32F16, kConvGemm, kConvHead,
+                  kConvHeadDgrad, kConvF16x3, kConvF16x3v2, kConvWinoX3, kConvWino, kConvWino8, kConvPatch16, kConvPatch, kConvS2Dgrad, kConvIgemm };
+struct ConvRoute { ConvKernel k; int v; };
+ConvRoute conv_route(const ConvArgs& a, int force_cfg);      // force_cfg: uwm_op_conv's cfg (include/uwm.h lists every code); -1 = auto
 hipError_t launch_conv(const ConvArgs& a, hipStream_t st, int force_cfg = -1);
-bool conv_epilogue_carries_bnb(const ConvArgs& a);      // launch_conv (auto routing) ends on a kernel whose epilogue carries the fused BatchNorm-backward sums (bnb_*); every launcher that cannot REJECTS a.bnb_mean, so a disagreement with the router is an error, not a wrong dgamma
+bool conv_epilogue_carries_bnb(const ConvArgs& a);      // conv_route(a, -1) ends on a kernel whose epilogue carries the fused BatchNorm-backward sums (bnb_*) for these arguments; launch_conv REJECTS a.bnb_mean on every other kernel, so a disagreement with the router is an error, not a wrong dgamma
+enum WgradKernel { kWgradInvalid = 0, kWgradGemm, kWgradUp2, kWgradF16x3, kWgradStem, kWgradC16, kWgradWino, kWgradPatch, kWgradIgemm };
+struct WgradRoute { WgradKernel k; int v; };                 // v (kWgradIgemm): 1 = the fp16x3 form where the tile has one
+WgradRoute wgrad_route(const WgradArgs& a);                  // WgradArgs::force_igemm: uwm_op_wgrad's (include/uwm.h)
 hipError_t launch_wgrad(const WgradArgs& a, hipStream_t st);
+// flattened implicit GEMM (conv_igemm.hip / wgrad_igemm.hip); tile configurations {BM, BN}: 0:{128,128} 1:{128,64} 2:{128,32} 3:{128,16} 4:{64,64} 5:{64,128}
+hipError_t launch_conv_igemm(const ConvArgs& a, hipStream_t st, int cfg);
+bool conv_s2_dgrad_applicable(const ConvArgs& a);            // stride-2 dgrad as four parity-class launches
+hipError_t launch_conv_s2_dgrad(const ConvArgs& a, hipStream_t st, int cfg);      // cfg 0 | 1 | 4
+hipError_t launch_wgrad_igemm(const WgradArgs& a, hipStream_t st, bool f16);       // tile and split from the shape
 // 3x3 s1 p1 patch-tiled conv (conv_patch.hip); launch_conv routes to it when applicable.
-// force_cfg for launch_conv: -1 auto, 0..5 conv_igemm tile config, 100+BN (116,132,164,228) conv_patch, 200 conv_patch16
 bool wgrad_patch_applicable(const WgradArgs& a);
 hipError_t launch_wgrad_patch(const WgradArgs& a, hipStream_t st);
 bool wgrad_wino_applicable(const WgradArgs& a);            // Winograd-domain wgrad (wgrad_wino.hip)
@@ -216,7 +230,7 @@ bool conv_up2_applicable(const ConvArgs& a);              // 3x3 over a nearest-
 hipError_t launch_conv_up2(const ConvArgs& a, hipStream_t st);
 bool conv_up2_dgrad_applicable(const ConvArgs& a);        // its dgrad wrt the low-resolution input, concat-split epilogue contract (ConvArgs::out_up)
 hipError_t launch_conv_up2_dgrad(const ConvArgs& a, hipStream_t st);
-// conv_up2_f16.hip: the same two launches on v_mfma_f32_16x16x32_f16 with fp16x3 split products (taken when ConvArgs::ig16 is set)
+// conv_up2_f16.hip: the same two launches on v_mfma_f32_16x16x32_f16 with fp16x3 split products (conv_route takes them when ConvArgs::ig16 is set)
 hipError_t launch_conv_up2_f16(const ConvArgs& a, hipStream_t st);
 hipError_t launch_conv_up2_dgrad_f16(const ConvArgs& a, hipStream_t st);
 // conv_c16_f16.hip: 3x3 from 16 to 16 channels at full resolution (decoder block 4 conv2), forward and dgrad, fp16x3 (taken when ConvArgs::ig16 is set); force_cfg 710
@@ -233,7 +247,7 @@ hipError_t launch_conv_patch16(const ConvArgs& a, hipStream_t st);
 hipError_t launch_conv_patch(const ConvArgs& a, hipStream_t st, int bn);
 // Winograd F(2x2,3x3) (conv_wino.hip): needs a.wu = launch_wino_weights(a.w ...) output; force_cfg 300 (auto tile) / 300+BN
 bool conv_wino_applicable(const ConvArgs& a);
-hipError_t launch_conv_wino(const ConvArgs& a, hipStream_t st, int bn = 0);   // bn 8 = conv_wino8
+hipError_t launch_conv_wino(const ConvArgs& a, hipStream_t st, int bn = 0);   // bn: 0 auto | 64 | 32 | 16 (the 8-wave variant: launch_conv_wino8)
 // segmentation head (3x3, 8|16|32 channels -> <= 4 classes, bias): HBM streaming kernel (conv_head.hip); force_cfg 500
 bool conv_head_applicable(const ConvArgs& a);
 hipError_t launch_conv_head(const ConvArgs& a, hipStream_t st);
@@ -257,11 +271,11 @@ hipError_t launch_f16x3_weights_multi(const WinoJobs& jobs, hipStream_t st);    
 bool conv_f16x3_applicable(const ConvArgs& a);
 static inline __host__ __device__ size_t f16x3_rinv_off_floats(int rows, int chans) { return (size_t)(chans / 16) * 5 * (size_t)(((rows + 63) / 64) * 4) * 512; }
 // conv_f16x3v2.hip: the same arithmetic on v_mfma_f32_32x32x16_f16, 8 x 32-pixel tiles (bank layout 1)
-bool f16x3v2_shape(int Ho, int Wo, int rows, int chans, int dgrad);      // layers it takes (whole tiles, 32-row fragments; which of them: measured, see the function): decides the bank layout
+bool f16x3v2_shape(int Ho, int Wo, int rows, int chans);      // layers it takes (whole tiles, 32-row fragments; which of them: measured, see the function): decides the bank layout
 int f16x3v2_nf(int rows);
 hipError_t launch_f16x3v2_weights_multi(const WinoJobs& jobs, hipStream_t st);      // the layout-1 jobs of a job table (row scales already made)
 bool conv_f16x3v2_applicable(const ConvArgs& a);
-hipError_t launch_conv_f16x3v2(const ConvArgs& a, hipStream_t st, int variant = 0);      // variant: 0 auto | 4 64-channel tiles | 5 32-channel tiles
+hipError_t launch_conv_f16x3v2(const ConvArgs& a, hipStream_t st, bool four_wave = false);      // the 8-wave kernel; four_wave: tests / timing (force_cfg 605)
 // conv_stem_f16x3.hip: the 7x7 / stride-2 ResNet stem on the fp16x3 arithmetic (one MFMA k-step per kernel row); a.wu = its bank
 size_t stem_f16x3_bank_floats();
 hipError_t launch_stem_f16x3_weights(const float* w, int Kpad, int cin_p, float* bank, hipStream_t st);

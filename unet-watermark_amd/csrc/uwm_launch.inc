@@ -31,12 +31,11 @@ static hipError_t fail_launch(const char* fmt, ...) {
 // The max|dY| contract of the fp16x3 backward.  Every fp16x3 dgrad / wgrad of conv ci stages dY times the power of two that
 // puts max|dY| into [2^13, 2^14); it reads that maximum from the 32 slots of the conv's BatchNorm (BNL::xmax_off), which the
 // BatchNorm backward that writes dY fills (run_bn_bwd, run_bn_bwd_act).  An unwritten slot reads 0 and the kernels fall back to
-// scale 1 without a word (dY below ~6e-5 loses mantissa, below ~6e-8 flushes to zero).  This one predicate decides both
-// sides: the producers write the slots of every conv it holds for, and the consumers read them only through dy_max_slot.
+// scale 1 without a word (dY below ~6e-5 loses mantissa, below ~6e-8 flushes to zero).  The producers write the slots of every
+// conv this predicate holds for; it is the OR of the very functions run_dgrad (f3_dgrad_on, conv_ig16) and run_wgrad (wgrad_f16_on)
+// switch their launch to fp16x3 by, and those read the slots only through dy_max_slot: no consumer without a producer.
 static bool dy_max_needed(const uwm_model* m, size_t ci) {
-  return m->convs[ci].bn >= 0 &&
-         (f3_dgrad_on(m, ci) || f3_wgrad_on(m, ci) || ig16_on(m, ci, true) || up2_f16_on(m, ci, true) || stem_wg16_on(m, ci) ||
-          c16_wg16_on(m, ci) || c16_f16_on(m, ci, true));
+  return m->convs[ci].bn >= 0 && (f3_dgrad_on(m, ci) || conv_ig16(m, ci, true) || wgrad_f16_on(m, ci));
 }
 // *slot = the max|dY| slots an fp16x3 dgrad / wgrad of conv ci reads; an error when no producer of this backward wrote them (a
 // new fp16x3 route without a producer fails here instead of silently running on unscaled fp16)
@@ -90,7 +89,7 @@ static hipError_t run_conv_fwd(const Ctx& c, int ci, const Src& s0, const Src* s
     }
   }
   a.wino = c.m->plan.wino_mode + 1; a.route_n = c.m->route_n;
-  if (ig16_on(c.m, (size_t)ci, false) || up2_f16_on(c.m, (size_t)ci, false) || c16_f16_on(c.m, (size_t)ci, false)) a.ig16 = 1;
+  if (conv_ig16(c.m, (size_t)ci, false)) a.ig16 = 1;
   return route_rec(c, "fwd", ci, launch_conv(a, c.st, cfg));
 }
 
@@ -119,16 +118,14 @@ static hipError_t run_dgrad(const Ctx& c, int ci, const float* dy, int Ho, int W
     a.wu = c.F(cv.wud_off); a.wu_ncb = wino_ncb(cv.CinP);
     const int pm = c.m->plan.prec;
     if ((pm == UWM_PREC_BF16X3 || pm == UWM_PREC_BF16X3_ALL) && cv.x3_d()) a.prec = 1;
-    if (f3_dgrad_on(c.m, (size_t)ci) && (!us || (us->C0 & 63) == 0)) {        // fp16x3 direct form: dY scaled by the power of two bn_bwd_apply's max|dy| calls for
+    if (f3_dgrad_on(c.m, (size_t)ci)) {        // fp16x3 direct form (a concat boundary sits on a 64-channel tile: f3d_plain)
       a.prec = 2; a.wu_layout = f3_layout(c.m, (size_t)ci, true); a.nprod = f3_nprod(c.m, true);
       a.wu_ncb = a.wu_layout == 1 ? f16x3v2_nf(cv.CinP) : f16x3_nj(cv.CinP); a.wu_rinv_off = (int)f16x3_rinv_off(cv.CinP, cv.CoutP);
-      const hipError_t e = dy_max_slot(c, ci, "dgrad", &a.xmax);
-      if (e != hipSuccess) return e;
     }
   }
   a.wino = c.m->plan.wino_mode + 1;
-  if (ig16_on(c.m, (size_t)ci, true) || up2_f16_on(c.m, (size_t)ci, true) || c16_f16_on(c.m, (size_t)ci, true)) {
-    a.ig16 = 1;
+  if (conv_ig16(c.m, (size_t)ci, true)) a.ig16 = 1;
+  if (a.prec == 2 || a.ig16) {                 // dY scaled by the power of two bn_bwd_apply's max|dy| calls for
     const hipError_t e = dy_max_slot(c, ci, "dgrad", &a.xmax);
     if (e != hipSuccess) return e;
   }
@@ -163,10 +160,9 @@ static hipError_t run_wgrad(const Ctx& c, int ci, const Src& s0, const Src* s1, 
   a.bytes = 4.0 * ((double)a.M * cv.CoutP + (double)c.N * s0.H * s0.W * s0.C + (s1 ? (double)c.N * s1->H * s1->W * s1->C : 0.0) +
                    (double)cv.Cout * cv.Kpad);
   a.wino = c.m->plan.wino_mode + 1; a.route_n = c.m->route_n;
-  if (stem_wg16_on(c.m, (size_t)ci) || c16_wg16_on(c.m, (size_t)ci) || up2_f16_on(c.m, (size_t)ci, true)) a.prec = 2;
-  if (ig16_on(c.m, (size_t)ci, true)) a.prec = 2;      // stride-2 and 1x1 layers: wgrad_igemm's fp16x3 form
-  if (f3_wgrad_on(c.m, (size_t)ci)) { a.prec = 2; a.nprod = f3_nprod(c.m, true); a.cu_share = (c.wst && c.wst != c.st) ? 3 : 0; }
-  if (a.prec == 2) {
+  if (f3_wgrad_on(c.m, (size_t)ci)) { a.nprod = f3_nprod(c.m, true); a.cu_share = (c.wst && c.wst != c.st) ? 3 : 0; }
+  if (wgrad_f16_on(c.m, (size_t)ci)) {
+    a.prec = 2;
     const hipError_t e = dy_max_slot(c, ci, "wgrad", &a.xmax);
     if (e != hipSuccess) return e;
   }

@@ -135,6 +135,18 @@ static void make_plan(uwm_model* m, int N, int H, int W, int training) {
   m->plan = p;
 }
 
+// The fill rule of the fp16x3 kernels: the launch gives at least every second CU a workgroup (uwm_set_precision_fill: another bar; uwm_set_routing_batch: another batch)
+static bool fills_chip(const uwm_model* m, long wgs_per_image, int per_cu = 1) {
+  const long wgs = (long)(m->route_n > 0 ? m->route_n : m->plan.N) * wgs_per_image;
+  return wgs >= (long)(m->f3_min_wgs > 0 ? m->f3_min_wgs : device_cu_count() / 2) * per_cu;
+}
+// conv ci as the conv1 of decoder block `block` (m->dec / m->nodes; -1: it is none): its input = concat(upsampled tensor: C0 channels, skips: C1)
+struct Conv1 { int block, C0, C1; };
+static Conv1 conv1_of(const uwm_model* m, size_t ci) {
+  for (size_t i = 0; i < m->dec.size(); ++i) if (m->dec[i].c1 == (int)ci) return {(int)i, m->dec[i].C0, m->dec[i].C1};
+  for (size_t i = 0; i < m->nodes.size(); ++i) if (m->nodes[i].c1 == (int)ci) return {(int)i, m->nodes[i].C0, m->nodes[i].C1};
+  return {-1, 0, 0};
+}
 // decoder block 4 conv2 (3x3, 16 -> 16 at full resolution) and block 3 conv2 (32 -> 32) on conv_c16_f16.hip, forward (fp16x3 modes) and dgrad (f16x3_all modes):
 // whole 8 x 32 tiles, the same fill rule as the other fp16x3 kernels
 static bool c16_f16_on(const uwm_model* m, size_t ci, bool dgrad) {
@@ -146,8 +158,7 @@ static bool c16_f16_on(const uwm_model* m, size_t ci, bool dgrad) {
   if (off || cv.bn < 0 || cv.dw || cv.k != 3 || cv.stride != 1 || cv.pad != 1 || !(c16 || c32)) return false;
   if (p.prec < (dgrad ? UWM_PREC_F16X3_ALL : UWM_PREC_F16X3) || (dgrad && !cv.dgrad) || p.wino_mode == 0) return false;
   if ((p.oh[ci] % 8) || (p.ow[ci] % 32)) return false;
-  const long wgs = (long)(m->route_n > 0 ? m->route_n : p.N) * (p.oh[ci] / 8) * (p.ow[ci] / 32);
-  return wgs >= (m->f3_min_wgs > 0 ? m->f3_min_wgs : device_cu_count() / 2) * (c32 ? 2 : 1);      // (32 channels: ONE workgroup per CU walks the tiles)
+  return fills_chip(m, (long)(p.oh[ci] / 8) * (p.ow[ci] / 32), c32 ? 2 : 1);      // (32 channels: ONE workgroup per CU walks the tiles)
 }
 // a conv takes the fp16x3 direct kernel (forward) when its shape is eligible AND the launch fills the chip: 16x16-pixel x 64-channel
 // workgroups, at least one per two CUs (measured: 973 vs 952 img/s with layer4's 128-workgroup launches on it; smaller launches
@@ -155,24 +166,18 @@ static bool c16_f16_on(const uwm_model* m, size_t ci, bool dgrad) {
 static bool f3_fwd_on(const uwm_model* m, size_t ci) {
   const ConvL& cv = m->convs[ci]; const Plan& p = m->plan;
   if (p.prec < UWM_PREC_F16X3 || !cv.f3() || !p.wino_ok(ci) || c16_f16_on(m, ci, false)) return false;
-  const long wgs = (long)(m->route_n > 0 ? m->route_n : p.N) * ((p.oh[ci] + 15) / 16) * ((p.ow[ci] + 15) / 16) * ((cv.Cout + 63) / 64);
-  return wgs >= (m->f3_min_wgs > 0 ? m->f3_min_wgs : device_cu_count() / 2);
+  return fills_chip(m, (long)((p.oh[ci] + 15) / 16) * ((p.ow[ci] + 15) / 16) * ((cv.Cout + 63) / 64));
 }
-// a decoder conv1's dgrad splits the concat gradient in its epilogue (ConvArgs::out_up): the fp16x3 kernel takes it when the
-// boundary sits on a 64-channel tile
 // the stem on conv_stem_f16x3: fp16x3 forward modes, the same fill rule over its 16x16-pixel workgroups
 static bool stem_f3_on(const uwm_model* m) {
   if (m->stem < 0) return false;
   const ConvL& cv = m->convs[m->stem]; const Plan& p = m->plan;
   if (p.prec < UWM_PREC_F16X3 || !cv.stem7() || !cv.wu_off || p.wino_mode == 0 || dbg_flag("UWM_NO_STEM_F16X3")) return false;
-  const long wgs = (long)(m->route_n > 0 ? m->route_n : p.N) * ((p.oh[m->stem] + 15) / 16) * ((p.ow[m->stem] + 15) / 16);
-  return wgs >= (m->f3_min_wgs > 0 ? m->f3_min_wgs : device_cu_count() / 2);
+  return fills_chip(m, (long)((p.oh[m->stem] + 15) / 16) * ((p.ow[m->stem] + 15) / 16));
 }
-static bool f3d_plain(const uwm_model* m, int ci) {
-  for (auto& d : m->dec) if (d.c1 == ci) return (d.C0 & 63) == 0;
-  for (auto& nd : m->nodes) if (nd.c1 == ci) return (nd.C0 & 63) == 0;
-  return true;
-}
+// a decoder conv1's dgrad splits the concat gradient in its epilogue (ConvArgs::out_up): the fp16x3 kernel takes it when the
+// boundary sits on a 64-channel tile
+static bool f3d_plain(const uwm_model* m, size_t ci) { return (conv1_of(m, ci).C0 & 63) == 0; }      // (no conv1: C0 = 0)
 // fp16x3 weight gradient: the map tiled by whole 4 x 32- or 8 x 16-pixel stages, 32-channel tiles on either side of the concat
 static bool f3_wgrad_on(const uwm_model* m, size_t ci) {
   const ConvL& cv = m->convs[ci]; const Plan& p = m->plan;
@@ -181,9 +186,8 @@ static bool f3_wgrad_on(const uwm_model* m, size_t ci) {
 }
 static bool f3_dgrad_on(const uwm_model* m, size_t ci) {
   const ConvL& cv = m->convs[ci]; const Plan& p = m->plan;
-  if (p.prec < UWM_PREC_F16X3_ALL || !cv.f3_d() || cv.bn < 0 || !p.wino_ok(ci) || !f3d_plain(m, (int)ci) || c16_f16_on(m, ci, true)) return false;
-  const long wgs = (long)(m->route_n > 0 ? m->route_n : p.N) * ((p.oh[ci] + 15) / 16) * ((p.ow[ci] + 15) / 16) * ((cv.CinP + 63) / 64);      // (stride 1: the input has the output's size)
-  return wgs >= (m->f3_min_wgs > 0 ? m->f3_min_wgs : device_cu_count() / 2);
+  if (p.prec < UWM_PREC_F16X3_ALL || !cv.f3_d() || cv.bn < 0 || !p.wino_ok(ci) || !f3d_plain(m, ci) || c16_f16_on(m, ci, true)) return false;
+  return fills_chip(m, (long)((p.oh[ci] + 15) / 16) * ((p.ow[ci] + 15) / 16) * ((cv.CinP + 63) / 64));      // (stride 1: the input has the output's size)
 }
 // stride-2 layers of the ResNet encoders (3x3 / stride 2 and the 1x1 / stride 2 downsample) and the 1x1 / stride-1 layers of the
 // Bottleneck encoders on the implicit GEMM / the 1x1 GEMM with fp16x3
@@ -203,10 +207,8 @@ static bool up2_f16_on(const uwm_model* m, size_t ci, bool dgrad) {
   const ConvL& cv = m->convs[ci]; const int pm = m->plan.prec;
   static const bool off = dbg_flag("UWM_NO_UP2_F16");
   if (off || cv.bn < 0 || cv.k != 3 || cv.stride != 1 || cv.CinP != 32 || cv.CoutP != 16) return false;
-  bool is = false;
-  for (auto& d : m->dec) if (d.c1 == (int)ci && d.C1 == 0) is = true;
-  for (auto& nd : m->nodes) if (nd.c1 == (int)ci && nd.C1 == 0) is = true;
-  if (!is) return false;
+  const Conv1 c1 = conv1_of(m, ci);
+  if (c1.block < 0 || c1.C1 != 0) return false;
   return dgrad ? pm >= UWM_PREC_F16X3_ALL : pm >= UWM_PREC_F16X3;
 }
 // the ResNet stem's weight gradient on wgrad_stem.hip's fp16x3 kernel (the last kernel of the step): from UWM_PREC_F16X3_ALL on
@@ -220,6 +222,14 @@ static bool c16_wg16_on(const uwm_model* m, size_t ci) {
   const ConvL& cv = m->convs[ci];
   return !off && m->plan.prec >= UWM_PREC_F16X3_ALL && cv.bn >= 0 && cv.k == 3 && cv.stride == 1 && cv.CinP == 16 && cv.CoutP == 16 && cv.Cout == 16 && !cv.dw;
 }
+// ConvArgs::ig16 of conv ci's forward / dgrad launch: the fp16x3 forms that are not the direct 3x3 kernel
+static bool conv_ig16(const uwm_model* m, size_t ci, bool dgrad) {
+  return ig16_on(m, ci, dgrad) || up2_f16_on(m, ci, dgrad) || c16_f16_on(m, ci, dgrad);
+}
+// conv ci's weight gradient runs in fp16x3 (WgradArgs::prec = 2): the direct 3x3 kernel, or a dedicated kernel's fp16x3 form
+static bool wgrad_f16_on(const uwm_model* m, size_t ci) {
+  return f3_wgrad_on(m, ci) || ig16_on(m, ci, true) || up2_f16_on(m, ci, true) || stem_wg16_on(m, ci) || c16_wg16_on(m, ci);
+}
 // split products per tile (ConvArgs::nprod / WgradArgs::nprod) under the handle's precision mode: f16x1 = hi*hi' everywhere;
 // f16x3_bwd2 = the backward's dY operand as ONE fp16 (two products), forward unchanged; the fp32-class modes: three
 static int f3_nprod(const uwm_model* m, bool backward) {
@@ -229,16 +239,13 @@ static int f3_nprod(const uwm_model* m, bool backward) {
   return 3;
 }
 // layout of a layer's fp16x3 bank (ConvArgs::wu_layout): 1 = conv_f16x3v2.hip (32x32x16 MFMA, 8 x 32-pixel tiles) where the map is
-// tiled by whole tiles and the output rows by 32-row fragments (a decoder conv1 dgrad with the fused concat split: 64-row tiles)
+// tiled by whole tiles and the output rows by 32-row fragments (never a decoder conv1 dgrad: that kernel has no fused concat split)
 static int f3_layout(const uwm_model* m, size_t ci, bool dgrad) {
   const ConvL& cv = m->convs[ci]; const Plan& p = m->plan;
   const int rows = dgrad ? cv.CinP : cv.Cout, chans = dgrad ? cv.CoutP : cv.CinP;
   if (rows != (dgrad ? cv.CinP : cv.CoutP)) return 0;
-  if (dgrad && !f3d_plain(m, (int)ci)) return 0;
-  bool split = false;
-  if (dgrad) { for (auto& d : m->dec) if (d.c1 == (int)ci) split = true; for (auto& nd : m->nodes) if (nd.c1 == (int)ci) split = true; }
-  if (split && (rows & 63)) return 0;
-  return f16x3v2_shape(p.oh[ci], p.ow[ci], rows, chans, dgrad ? 1 : 0) ? 1 : 0;
+  if (dgrad && conv1_of(m, ci).block >= 0) return 0;
+  return f16x3v2_shape(p.oh[ci], p.ow[ci], rows, chans) ? 1 : 0;
 }
 // everything the choice of a dgrad filter bank's FORM depends on (Winograd mode, precision mode, fp16x3 fill rule, routing batch):
 // a change between a forward and its backward re-packs the banks at the start of the backward

@@ -299,28 +299,9 @@ static hipError_t launch_w(const WgradArgs& a, hipStream_t st, int cls) {
   return hipGetLastError();
 }
 
-// tile (output channels x k-columns) chosen from the layer's Cout: 16x256, 32x256, 64x128, 128x128
-hipError_t launch_wgrad(const WgradArgs& a0, hipStream_t st) {
-  static const bool trace = dbg_flag("UWM_TRACE_CONV");
-  if (trace)
-    fprintf(stderr, "wgrad N=%d Ctot=%d(C0=%d) Cout=%d wrows=%d Ho=%d Wo=%d Hl=%d Wl=%d taps=%d stride=%d wino=%d patch=%d gflop=%.2f\n", a0.N, a0.Ctot,
-            a0.C0, a0.Cout, a0.wrows, a0.Ho, a0.Wo, a0.Hl, a0.Wl, a0.ntaps, a0.stride, (int)(wino_mode_of(a0.wino) != 0 && wgrad_wino_applicable(a0)),
-            (int)wgrad_patch_applicable(a0), a0.flops * 1e-9);
-  // force_igemm: 0 auto (Winograd-domain -> patch -> flattened), 1 flattened implicit GEMM only, 2 no Winograd, 4 = wgrad_gemm.hip wherever applicable
-  if ((a0.force_igemm & 0xff) == 4) return launch_wgrad_gemm(a0, st);
-  static const bool no_up2 = dbg_flag("UWM_NO_UP2") || dbg_flag("UWM_NO_UP2_WGRAD");
-  if (((a0.force_igemm & 0xff) == 0 || (a0.force_igemm & 0xff) == 6) && a0.prec == 2 && a0.xmax && !no_up2 && wgrad_up2_applicable(a0) && wgrad_up2_f16_shape(a0))
-    return launch_wgrad_up2(a0, st);      // sub-pixel form of conv-after-upsample on its fp16x3 kernel (2.25x fewer products than the direct form below)
-  if (((a0.force_igemm & 0xff) == 0 || (a0.force_igemm & 0xff) == 6) && a0.prec == 2 && wgrad_f16x3_applicable(a0)) return launch_wgrad_f16x3(a0, st);      // fp16x3 direct form
-  if ((a0.force_igemm & 0xff) == 6 && a0.prec == 2 && wgrad_stem_applicable(a0)) return launch_wgrad_stem(a0, st);      // (its fp16x3 kernel)
-  if ((a0.force_igemm & 0xff) == 6 && a0.prec == 2 && a0.Cout == 16 && wgrad_c16_applicable(a0)) return launch_wgrad_c16(a0, st);      // (likewise)
-  if ((a0.force_igemm & 0xff) == 6) return hipErrorInvalidValue;
-  if ((a0.force_igemm & 0xff) == 0 && !no_up2 && wgrad_up2_applicable(a0)) return launch_wgrad_up2(a0, st);      // sub-pixel form of conv-after-upsample
-  if ((a0.force_igemm & 0xff) == 0 && wgrad_stem_applicable(a0)) return launch_wgrad_stem(a0, st);         // the ResNet stem: compact K = 147
-  if ((a0.force_igemm & 0xff) == 0 && wgrad_gemm_preferred(a0)) return launch_wgrad_gemm(a0, st);        // 1x1 / stride 1: persistent LDS-DMA GEMM, deterministic
-  if ((a0.force_igemm & 0xff) == 0 && wgrad_c16_applicable(a0)) return launch_wgrad_c16(a0, st);      // 16-channel full-resolution layers, head
-  if ((a0.force_igemm & 0xff) == 0 && wino_mode_of(a0.wino) != 0 && wgrad_wino_applicable(a0)) return launch_wgrad_wino(a0, st);
-  if ((a0.force_igemm & 0xff) != 1 && (a0.force_igemm & 0xff) != 7 && wgrad_patch_applicable(a0)) return launch_wgrad_patch(a0, st);      // (7 = tests: the flattened implicit GEMM in its fp16x3 form)
+// tile (output channels x k-columns) chosen from the layer's Cout: 16x256, 32x256, 64x128, 128x128; f16: the fp16x3 form where the
+// tile has one (128- and 64-row tiles)
+hipError_t launch_wgrad_igemm(const WgradArgs& a0, hipStream_t st, bool f16) {
   WgradArgs a = a0;
   if (a.M <= 0 || (a.Cout & 3) || (a.Kpad & 31) || (a.Ctot & 3) || (a.C0 & 3)) return hipErrorInvalidValue;
   int TA, TB;
@@ -358,9 +339,6 @@ hipError_t launch_wgrad(const WgradArgs& a0, hipStream_t st) {
   msplit = (msplit + 31) & ~31;
   nsplit = (a.M + msplit - 1) / msplit;
   a.nsplit = nsplit; a.msplit = msplit;
-  // fp16x3 form (the stride-2 layers in the f16x3_all modes; channel counts in whole 32s): 128- and 64-row tiles
-  static const bool no_f16 = dbg_flag("UWM_NO_WGRAD_IG16");
-  const bool f16 = !no_f16 && a.prec == 2 && a.xmax && ((a.force_igemm & 0xff) == 0 || (a.force_igemm & 0xff) == 7) && (a.Ctot & 31) == 0 && (a.Cout & 31) == 0;
   if (f16 && TA == 128 && TB == 128) return launch_w<128, 128, 2, 2, true>(a, st, 60);
   if (f16 && TA == 128 && TB == 64) return launch_w<128, 64, 2, 2, true>(a, st, 61);
   if (f16 && TA == 64 && TB == 128) return launch_w<64, 128, 2, 2, true>(a, st, 62);

@@ -619,14 +619,13 @@ float* wgrad_op_scratch() {                   // single-operator entry points (n
 template <int TA>
 static hipError_t launch_ww(const WgradArgs& a, hipStream_t st, int cls, int nblocks) {
   size_t lds = (size_t)(2 * 64 * TA + 2 * kPP * kCW) * sizeof(float);
-  static const bool v1 = dbg_flag("UWM_WGRAD_V1");        // experiments: the round-1 row-per-wave kernel for every TA
-  if (TA == 16 || v1) {
+  if constexpr (TA == 16) {                   // the row-per-wave kernel (16-channel tiles only)
     const size_t rl = (size_t)9 * TA * kCW * sizeof(float);
     if (lds < rl) lds = rl;
     static DevOnce lds_attr;                  // hipFuncSetAttribute is per device
     { hipError_t e = lds_attr.set_max_lds((const void*)wgrad_wino_kernel<TA>, lds); if (e != hipSuccess) return e; }
     UWM_LAUNCH(cls, a.flops, a.bytes, (wgrad_wino_kernel<TA>), dim3((unsigned)nblocks), dim3(256), lds, st, a);
-  } else if constexpr (TA != 16) {
+  } else {
     static DevOnce lds_attr;
     { hipError_t e = lds_attr.set_max_lds((const void*)wgrad_wino2_kernel<TA>, lds); if (e != hipSuccess) return e; }
     UWM_LAUNCH(cls, a.flops, a.bytes, (wgrad_wino2_kernel<TA>), dim3((unsigned)nblocks), dim3(256), lds, st, a);
@@ -642,8 +641,7 @@ static hipError_t launch_ww(const WgradArgs& a, hipStream_t st, int cls, int nbl
 bool wgrad_wino_applicable(const WgradArgs& a) {
   const int TA = a.Cout >= 64 ? 64 : a.Cout;
   // channel tail (wgrad_wino2 only, TA >= 32): Ctot % 8 == 0 with the concat boundary on a 32-channel chunk
-  static const bool v1 = dbg_flag("UWM_WGRAD_V1");
-  const bool tail_ok = TA >= 32 && !v1 && (a.Ctot & 7) == 0 && (a.Ctot - a.C0 == 0 || (a.Ctot - a.C0) >= 4);
+  const bool tail_ok = TA >= 32 && (a.Ctot & 7) == 0 && (a.Ctot - a.C0 == 0 || (a.Ctot - a.C0) >= 4);
   return a.ntaps == 9 && a.kw == 3 && a.stride == 1 && a.pad == 1 && ((a.Ctot & 31) == 0 || tail_ok) && ((a.C0 & 31) == 0 || (tail_ok && a.C0 == a.Ctot)) &&
          (TA == 64 || TA == 32 || TA == 16) && a.Cout % TA == 0 && a.wrows <= a.Cout && a.Kpad >= 9 * a.Ctot && a.Kpad < 9 * a.Ctot + 32 &&
          a.Hl == a.Ho && a.Wl == a.Wo && (a.Ho % kSH) == 0 && (a.Wo % kSW) == 0;
