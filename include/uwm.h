@@ -398,6 +398,9 @@ typedef struct {
  * (16-byte aligned), padding channels zero; any pixel count */
 int  uwm_op_preprocess_u8_nhwc4(const uint8_t* images, long long npix, int C, const float* mean, const float* std, float* out,
                                 uwm_stream stream);
+/* on = 1: ... with the weight operand pre-split into a bank by one job of the fp16x3 bank launch, built on the fly (the model builds
+ * its banks once per step); on = 2: the same arithmetic with the weights split while staging (bit-identical products; the form
+ * behind UWM_DEBUG=1 UWM_NO_IG_BANK=1 in the model); 0: exact fp32 */
 int  uwm_op_set_igemm_f16x3(int on);   /* tests / kernel timing: uwm_op_conv / uwm_op_dgrad launches that end on the implicit GEMM (stride 2, 1x1) use its fp16x3 split-product form (what the model does for the stride-2 layers in the fp16x3 precision modes) */
 int  uwm_op_conv(const uwm_src* s0, const uwm_src* s1, const float* w, int wrows, int Kpad, int kh, int kw, int stride,
                  int pad, int N, int Cout, const float* bias, float* y, double* stats, int cfg, uwm_stream stream);

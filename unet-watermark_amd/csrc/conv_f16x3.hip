@@ -70,11 +70,13 @@ __device__ __forceinline__ float f16x3_wval(const WinoJob& jb, int row, int slot
 // (The first version — one wave per row walking the whole row — took 70-94 us per launch, 0.19 ms per step.)
 __global__ __launch_bounds__(256) void f16x3_rowzero_kernel(const WinoJobs jobs) {
   const WinoJob jb = jobs.j[blockIdx.y];
+  if (jb.mode == 3) return;
   const int row = blockIdx.x * 256 + threadIdx.x;
   if (row < f16x3_nj_(jb.rows) * 16) (jb.ut + f16x3_rinv_off_floats(jb.rows, jb.chans))[row] = 0.f;
 }
 __global__ __launch_bounds__(256) void f16x3_rowmax_kernel(const WinoJobs jobs) {
   const WinoJob jb = jobs.j[blockIdx.y];
+  if (jb.mode == 3) return;
   const int nJ = f16x3_nj_(jb.rows);
   unsigned* rmax = (unsigned*)(jb.ut + f16x3_rinv_off_floats(jb.rows, jb.chans));
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -106,6 +108,7 @@ __global__ __launch_bounds__(256) void f16x3_rowmax_kernel(const WinoJobs jobs) 
 }
 __global__ __launch_bounds__(256) void f16x3_rowscale_kernel(const WinoJobs jobs) {
   const WinoJob jb = jobs.j[blockIdx.y];
+  if (jb.mode == 3) return;
   const int nJ = f16x3_nj_(jb.rows);
   const int row = blockIdx.x * 256 + threadIdx.x;
   if (row >= nJ * 16) return;
@@ -117,6 +120,11 @@ __global__ __launch_bounds__(256) void f16x3_rowscale_kernel(const WinoJobs jobs
 }
 __global__ __launch_bounds__(256) void f16x3_weights_multi_kernel(const WinoJobs jobs) {
   const WinoJob jb = jobs.j[blockIdx.y];
+  if (jb.mode == 3) {                                  // the implicit GEMM's pre-split weight operand (conv_igemm.hip, ConvArgs::wbank): no row scales
+    const size_t u = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (u < (size_t)jb.rows * jb.Kpad / 4) ig_bank_unit(jb.w, jb.ut, u, jb.Kpad);
+    return;
+  }
   if (jb.pad_ == 1) return;                            // layout 1: f16x3v2_weights_multi_kernel
   const int nJ = f16x3_nj_(jb.rows);
   const size_t total = (size_t)(jb.chans / 16) * kFKs * nJ * 64;
@@ -146,14 +154,21 @@ hipError_t launch_f16x3_weights_multi(const WinoJobs& jobs, hipStream_t st) {
   if (jobs.n <= 0) return hipSuccess;
   size_t mx = 0; int mr = 0;
   for (int i = 0; i < jobs.n; ++i) {
+    if (jobs.j[i].mode == 3) {
+      if ((jobs.j[i].Kpad & 31) || jobs.j[i].pad_) return hipErrorInvalidValue;
+      mx = std::max(mx, (size_t)jobs.j[i].rows * jobs.j[i].Kpad / 4);
+      continue;
+    }
     if (jobs.j[i].chans & 15) return hipErrorInvalidValue;
     const size_t t = (size_t)(jobs.j[i].chans / 16) * kFKs * f16x3_nj(jobs.j[i].rows) * 64;
     if (t > mx) mx = t;
     if (f16x3_nj(jobs.j[i].rows) * 16 > mr) mr = f16x3_nj(jobs.j[i].rows) * 16;
   }
+  if (mr > 0) {                                        // (0: implicit-GEMM banks only, no row scales)
   hipLaunchKernelGGL(f16x3_rowzero_kernel, dim3((unsigned)((mr + 255) / 256), (unsigned)jobs.n), dim3(256), 0, st, jobs);      // the row maxima meet in atomicMax: start from zero
   hipLaunchKernelGGL(f16x3_rowmax_kernel, dim3((unsigned)((mr + 3) / 4), (unsigned)jobs.n, 8), dim3(256), 0, st, jobs);
   hipLaunchKernelGGL(f16x3_rowscale_kernel, dim3((unsigned)((mr + 255) / 256), (unsigned)jobs.n), dim3(256), 0, st, jobs);
+  }
   hipLaunchKernelGGL(f16x3_weights_multi_kernel, dim3((unsigned)((mx + 255) / 256), (unsigned)jobs.n), dim3(256), 0, st, jobs);
   { hipError_t e = hipGetLastError(); if (e != hipSuccess) return e; }
   return launch_f16x3v2_weights_multi(jobs, st);

@@ -38,15 +38,16 @@ __device__ __forceinline__ unsigned fdiv(unsigned n, FastDiv f) {
 // the fp32 form issues 8 of 32.  Range: weights times 2^12 (kaiming-scale weights land near 2^8; |w| < 16 cannot overflow, smaller
 // ones keep their low half normal), a dgrad's dY times the power of two that puts max|dY| into [2^13, 2^14) (ConvArgs::xmax),
 // activations as they are, clamped to +-65504; undone on the accumulator (exact powers of two).
-constexpr float kIgWScale = 4096.f;
 typedef _Float16 ig_h8 __attribute__((ext_vector_type(8)));
-template <int BM, int BN, int WM, int WN, bool PC = false, bool F16 = false>
+// WB (F16 only) = the weight operand comes pre-split from a bank (ConvArgs::wbank, ig_bank_unit): its staging is a 16-byte copy.
+template <int BM, int BN, int WM, int WN, bool PC = false, bool F16 = false, bool WB = false>
 __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvArgs a) {
   constexpr int MI = BM / WM / 16;      // 16-pixel MFMA tiles per wave
   constexpr int NI = BN / WN / 16;      // 16-channel MFMA tiles per wave
   constexpr int XR = BM / 32;           // X rows staged per thread
   constexpr int WR = (BN + 31) / 32;    // W rows staged per thread
   static_assert(WM * WN == 4, "4 waves");
+  static_assert(!WB || F16, "weight banks hold fp16 halves");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* const Xs = smem;                       // [2][BM][32]
   float* const Ws = smem + 2 * BM * 32;         // [2][BN][32]
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvArgs a) {
     for (int i = 0; i < WR; ++i) {
       int row = n0 + r0 + 32 * i;
       bool v = (row < a.wrows) && (BN >= 32 || r0 < BN);
-      wr[i] = v ? *(const f4*)(a.w + (size_t)row * a.Kpad + kc * 32 + unit * 4) : (f4){0.f, 0.f, 0.f, 0.f};
+      wr[i] = v ? *(const f4*)((WB ? a.wbank : a.w) + (size_t)row * a.Kpad + kc * 32 + unit * 4) : (f4){0.f, 0.f, 0.f, 0.f};
     }
   };
 
@@ -168,7 +169,9 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvArgs a) {
 #pragma unroll
     for (int i = 0; i < WR; ++i) {
       const int row = r0 + 32 * i;
-      if (F16) {
+      if (WB) {                                          // (the bank holds the row image: slot `unit` as it is)
+        if (BN >= 32 || r0 < BN) *(f4*)(ws + row * 32 + unit * 4) = wr[i];
+      } else if (F16) {
         if (BN >= 32 || r0 < BN) {
           uwm_u2 hi, lo;
           const f4 w4 = wr[i] * kIgWScale;
@@ -340,19 +343,20 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvArgs a) {
   }
 }
 
-template <int BM, int BN, int WM, int WN, bool F16>
+template <int BM, int BN, int WM, int WN, bool F16, bool WB>
 static hipError_t launch_cfg_(const ConvArgs& a, hipStream_t st, int cls) {
   const int tilesM = (a.M + BM - 1) / BM, tilesN = (a.Cout + BN - 1) / BN;
   const size_t lds = (size_t)2 * (BM + BN) * 32 * sizeof(float);
   static DevOnce lds_attr;                  // hipFuncSetAttribute is per device
-  { hipError_t e = lds_attr.set_max_lds((const void*)conv_igemm_kernel<BM, BN, WM, WN, false, F16>, lds); if (e != hipSuccess) return e; }
-  UWM_LAUNCH(F16 ? 53 + cls : cls, a.flops, a.bytes, (conv_igemm_kernel<BM, BN, WM, WN, false, F16>), dim3((unsigned)(tilesM * tilesN)), dim3(256), lds, st, a);
-  if (F16) route_note("(conv_igemm_kernel<BM, BN, WM, WN, false, true>)");        // (the routing record names the fp16x3 form)
+  { hipError_t e = lds_attr.set_max_lds((const void*)conv_igemm_kernel<BM, BN, WM, WN, false, F16, WB>, lds); if (e != hipSuccess) return e; }
+  UWM_LAUNCH(F16 ? 53 + cls : cls, a.flops, a.bytes, (conv_igemm_kernel<BM, BN, WM, WN, false, F16, WB>), dim3((unsigned)(tilesM * tilesN)), dim3(256), lds, st, a);
+  route_note(F16 ? "(conv_igemm_kernel<BM, BN, WM, WN, false, true>)" : "(conv_igemm_kernel<BM, BN, WM, WN, false, false>)");        // (the routing record names the arithmetic, not the WB flag)
   return hipGetLastError();
 }
 template <int BM, int BN, int WM, int WN>
 static hipError_t launch_cfg(const ConvArgs& a, hipStream_t st, int cls) {
-  return a.ig16 ? launch_cfg_<BM, BN, WM, WN, true>(a, st, cls) : launch_cfg_<BM, BN, WM, WN, false>(a, st, cls);
+  if (!a.ig16) return a.wbank ? hipErrorInvalidValue : launch_cfg_<BM, BN, WM, WN, false, false>(a, st, cls);
+  return a.wbank ? launch_cfg_<BM, BN, WM, WN, true, true>(a, st, cls) : launch_cfg_<BM, BN, WM, WN, true, false>(a, st, cls);
 }
 
 // stride-2 dgrad as four parity-class launches (see the PC template flag)
@@ -360,19 +364,20 @@ bool conv_s2_dgrad_applicable(const ConvArgs& a) {
   return a.rmul == -1 && a.sdiv == 2 && a.smul == 1 && (a.ntaps == 9 || a.ntaps == 1) && (a.Ctot & 31) == 0 && a.C0 == a.Ctot &&
          (a.Ho & 1) == 0 && (a.Wo & 1) == 0 && a.s0.up == 0;
 }
-template <int BM, int BN, int WM, int WN, bool F16>
+template <int BM, int BN, int WM, int WN, bool F16, bool WB>
 static hipError_t launch_s2_dgrad_(const ConvArgs& a0, hipStream_t st, int cls);
 template <int BM, int BN, int WM, int WN>
 static hipError_t launch_s2_dgrad(const ConvArgs& a0, hipStream_t st, int cls) {
-  return a0.ig16 ? launch_s2_dgrad_<BM, BN, WM, WN, true>(a0, st, cls) : launch_s2_dgrad_<BM, BN, WM, WN, false>(a0, st, cls);
+  if (!a0.ig16) return a0.wbank ? hipErrorInvalidValue : launch_s2_dgrad_<BM, BN, WM, WN, false, false>(a0, st, cls);
+  return a0.wbank ? launch_s2_dgrad_<BM, BN, WM, WN, true, true>(a0, st, cls) : launch_s2_dgrad_<BM, BN, WM, WN, true, false>(a0, st, cls);
 }
-template <int BM, int BN, int WM, int WN, bool F16>
+template <int BM, int BN, int WM, int WN, bool F16, bool WB>
 static hipError_t launch_s2_dgrad_(const ConvArgs& a0, hipStream_t st, int cls) {
   const int Mg = a0.N * (a0.Ho >> 1) * (a0.Wo >> 1);
   const int tilesM = (Mg + BM - 1) / BM, tilesN = (a0.Cout + BN - 1) / BN;
   const size_t lds = (size_t)2 * (BM + BN) * 32 * sizeof(float);
   static DevOnce lds_attr;                  // hipFuncSetAttribute is per device
-  { hipError_t e = lds_attr.set_max_lds((const void*)conv_igemm_kernel<BM, BN, WM, WN, true, F16>, lds); if (e != hipSuccess) return e; }
+  { hipError_t e = lds_attr.set_max_lds((const void*)conv_igemm_kernel<BM, BN, WM, WN, true, F16, WB>, lds); if (e != hipSuccess) return e; }
   ConvArgs a = a0;
   for (int pc = 0; pc < 4; ++pc) {
     a.pc_taps[pc] = 0; a.pc_ntaps[pc] = 0;
@@ -380,8 +385,8 @@ static hipError_t launch_s2_dgrad_(const ConvArgs& a0, hipStream_t st, int cls) 
       for (int s = 0; s < a.kw; ++s)         // tap (r, s) reaches an input pixel iff (ho - r + off) and (wo - s + off) are even
         if (((((pc >> 1) - r + a.off) | ((pc & 1) - s + a.off)) & 1) == 0) { a.pc_taps[pc] |= (unsigned)(r * a.kw + s) << (4 * a.pc_ntaps[pc]); ++a.pc_ntaps[pc]; }
   }
-  UWM_LAUNCH(F16 ? 53 + cls : cls, a.flops, a.bytes, (conv_igemm_kernel<BM, BN, WM, WN, true, F16>), dim3((unsigned)(tilesM * tilesN), 4), dim3(256), lds, st, a);
-  if (F16) route_note("(conv_igemm_kernel<BM, BN, WM, WN, true, true>)");        // (the routing record names the fp16x3 form)
+  UWM_LAUNCH(F16 ? 53 + cls : cls, a.flops, a.bytes, (conv_igemm_kernel<BM, BN, WM, WN, true, F16, WB>), dim3((unsigned)(tilesM * tilesN), 4), dim3(256), lds, st, a);
+  route_note(F16 ? "(conv_igemm_kernel<BM, BN, WM, WN, true, true>)" : "(conv_igemm_kernel<BM, BN, WM, WN, true, false>)");        // (the routing record names the arithmetic, not the WB flag)
   return hipGetLastError();
 }
 

@@ -644,8 +644,24 @@ int uwm_allreduce_grads(uwm_handle h, void* comm, int sb, int se, uwm_stream str
 float* uwm_grad_arena(uwm_handle h) { return h ? h->grads : nullptr; }
 static Src to_src(const uwm_src* s) { return mk_src(s->ptr, s->C, s->H, s->W, s->scale, s->shift, s->relu, s->up); }
 
-static int g_op_ig16 = 0;
-int uwm_op_set_igemm_f16x3(int on) { g_op_ig16 = on != 0; return 0; }      // tests / kernel timing: the single-operator conv / dgrad entry points take the implicit GEMM's fp16x3 form (ConvArgs::ig16)
+static int g_op_ig16 = 0;                          // 0 exact fp32 | 1 fp16x3, weight operand pre-split into a bank (what the model runs) | 2 fp16x3, split while staging
+// the bank of a single-operator launch, built on the fly (the model builds its banks once per step): one job of the fp16x3 bank launch
+static int op_ig_bank(const float* w, int rows, int Kpad, int slot, hipStream_t st, const float** bank) {
+  static float* buf[2] = {nullptr, nullptr}; static size_t cap[2] = {0, 0};
+  const size_t n = (size_t)rows * Kpad;
+  if (n > cap[slot]) {
+    if (buf[slot]) HIPCHK(hipFree(buf[slot]));     // (waits for the launches that still read it)
+    buf[slot] = nullptr; cap[slot] = 0;
+    HIPCHK(hipMalloc((void**)&buf[slot], n * sizeof(float)));
+    cap[slot] = n;
+  }
+  WinoJobs jobs; memset(&jobs, 0, sizeof(jobs)); jobs.n = 1;
+  jobs.j[0].w = w; jobs.j[0].ut = buf[slot]; jobs.j[0].rows = rows; jobs.j[0].Kpad = Kpad; jobs.j[0].mode = 3; jobs.j[0].src_rows = rows;
+  LCHK(launch_f16x3_weights_multi(jobs, st));
+  *bank = buf[slot];
+  return 0;
+}
+int uwm_op_set_igemm_f16x3(int on) { g_op_ig16 = on == 2 ? 2 : (on != 0); return 0; }      // tests / kernel timing: the single-operator conv / dgrad entry points take the implicit GEMM's fp16x3 form (ConvArgs::ig16)
 int uwm_op_conv(const uwm_src* s0, const uwm_src* s1, const float* w, int wrows, int Kpad, int kh, int kw, int stride,
                 int pad, int N, int Cout, const float* bias, float* y, double* stats, int cfg, uwm_stream stream) {
   if (!s0 || !w || !y) return fail("uwm_op_conv: null argument");
@@ -660,7 +676,8 @@ int uwm_op_conv(const uwm_src* s0, const uwm_src* s1, const float* w, int wrows,
   a.out = y; a.bias = bias;
   if (stats) { a.ssum = stats; a.ssq = stats + Cout; }
   a.dv_ctot = make_fastdiv(a.Ctot); a.dv_kw = make_fastdiv(a.kw);
-  a.ig16 = g_op_ig16;
+  a.ig16 = g_op_ig16 != 0;
+  if (g_op_ig16 == 1 && !(Kpad & 31) && cfg < 6 && conv_route(a, cfg).k == kConvIgemm && op_ig_bank(w, wrows, Kpad, 0, (hipStream_t)stream, &a.wbank)) return 1;
   if (cfg == 610) {                                     // the ResNet stem on conv_stem_f16x3.hip
     static float* sbuf = nullptr;
     if (!sbuf) HIPCHK(hipMalloc((void**)&sbuf, stem_f16x3_bank_floats() * sizeof(float)));
@@ -700,6 +717,10 @@ int uwm_op_dgrad(const float* dy, int N, int Ho, int Wo, int Cout, const float* 
     a.ig16 = 1; a.xmax = xm;
   }
   if (winograd_mode() != 0 && op_wino_shape(a, kh, kw, stride, pad) && op_wino_prepare(a, 1, (hipStream_t)stream)) return 1;
+  if (g_op_ig16 == 1 && !(KpadD & 31)) {
+    const ConvKernel k = conv_route(a, -1).k;
+    if ((k == kConvIgemm || k == kConvS2Dgrad) && op_ig_bank(wd, Cin, KpadD, 0, (hipStream_t)stream, &a.wbank)) return 1;
+  }
   LCHK(launch_conv(a, (hipStream_t)stream));
   return 0;
 }

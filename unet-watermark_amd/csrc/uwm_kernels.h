@@ -94,6 +94,9 @@ struct ConvArgs {            // implicit-GEMM conv: forward conv AND dgrad (tran
   int route_n;               // > 0: choose the kernel VARIANT as if the batch were route_n images (uwm_set_routing_batch: a small parity sample on the kernels the full batch takes); 0: N
   int ig16;                  // implicit-GEMM launches (conv_igemm.hip: stride-2 3x3, 1x1 stride 2, their dgrads) and the sub-pixel decoder conv (conv_up2_f16.hip): 1 = fp16x3 split products on v_mfma_f32_16x16x32_f16 (operands split while staging, weights times 2^12, a dgrad's dY by xmax); 0 = exact fp32
   int nprod;                 // prec 2: split products per tile — 0 / 3: hi*hi' + hi*lo' + lo*hi' (fp32-class); 2: the pixel operand (a dgrad's dY) as ONE fp16 (hi*hi' + lo_w*hi'); 1: hi*hi' only (plain fp16 products, the reference's autocast arithmetic)
+  // ig16 launches of conv_igemm.hip: w pre-split once per step (ig_bank_unit below, built inside the multi-job bank
+  // launches) — same [wrows][Kpad] indexing, every 32-float chunk replaced by its 128-byte LDS row image; nullptr = split while staging
+  const float* wbank;
   int wu_layout;             // prec 2: layout of the fp16x3 bank behind wu — 0: conv_f16x3.hip (tap pairs, 16-row fragments), 1: conv_f16x3v2.hip (taps, 32-row fragments); set by whoever packed the bank (f16x3v2_shape)
 };
 
@@ -119,6 +122,24 @@ __device__ __forceinline__ void uwm_split4(float x0, float x1, float x2, float x
       "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
       : "=&v"(l1) : "v"(hi.y), "v"(x2), "v"(x3));
   lo.x = l0; lo.y = l1;
+}
+// The weight operand of conv_igemm.hip's fp16x3 form, pre-split: unit i = floats [4i, 4i + 4) of a [rows][Kpad] matrix (Kpad % 32 == 0)
+// goes times 2^12, clamped, as hi / lo fp16 halves to its place in the 128-byte LDS row image of its 32-float chunk (32 hi halfs |
+// 32 lo halfs, 16-byte slots XOR-swizzled by (row >> 1) & 7) — the very arithmetic and layout of conv_igemm_kernel's staging code,
+// so a banked launch copies 16 bytes per thread and every product is bit-identical to the on-the-fly split's.
+constexpr float kIgWScale = 4096.f;
+__device__ __forceinline__ void ig_bank_unit(const float* __restrict__ src, float* __restrict__ dst, size_t i, int Kpad) {
+  typedef float f4_ __attribute__((ext_vector_type(4)));
+  const size_t g = i >> 3;                             // 32-float chunk
+  const int unit = (int)(i & 7), row = (int)((g * 32) / (size_t)Kpad);
+  const f4_ w4 = *(const f4_*)(src + i * 4) * kIgWScale;
+  uwm_u2 hi, lo;
+  uwm_split4(__builtin_amdgcn_fmed3f(w4.x, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(w4.y, -65504.f, 65504.f),
+             __builtin_amdgcn_fmed3f(w4.z, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(w4.w, -65504.f, 65504.f), hi, lo);
+  char* rb = (char*)(dst + g * 32);
+  const int sw = (row >> 1) & 7;
+  *(uwm_u2*)(rb + (((unit >> 1) ^ sw) << 4) + (unit & 1) * 8) = hi;
+  *(uwm_u2*)(rb + ((((unit >> 1) + 4) ^ sw) << 4) + (unit & 1) * 8) = lo;
 }
 #endif
 
@@ -258,8 +279,8 @@ hipError_t launch_conv_wino8(const ConvArgs& a, hipStream_t st);
 size_t wino_weights_floats(int wrows, int Ctot);
 int wino_ncb(int wrows);
 hipError_t launch_wino_weights(const float* w, int wrows, int Kpad, int Ctot, int mirror, float* ut, hipStream_t st);
-struct WinoJob { const float* w; float* ut; int rows, chans, Kpad, mode, src_rows, pad_; };
-struct WinoJobs { WinoJob j[40]; int n; };
+struct WinoJob { const float* w; float* ut; int rows, chans, Kpad, mode, src_rows, pad_; };      // mode 3 (launch_f16x3_weights_multi only): ut = ig_bank_unit image of the [rows][Kpad] matrix w
+struct WinoJobs { static constexpr int kMax = 56; WinoJob j[kMax]; int n; };      // (resnet34: 38 fp16x3 forward banks + 6 implicit-GEMM ones in ONE launch)
 hipError_t launch_wino_weights_multi(const WinoJobs& jobs, hipStream_t st);   // every layer's transform in one launch
 // bf16x3 precision mode (conv_wino_x3.hip): split-bf16 filter banks (same size as the fp32 ones) and the conv kernel; force_cfg 400
 hipError_t launch_wino_weights_x3_multi(const WinoJobs& jobs, hipStream_t st);

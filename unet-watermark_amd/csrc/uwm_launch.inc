@@ -77,7 +77,7 @@ static hipError_t run_conv_fwd(const Ctx& c, int ci, const Src& s0, const Src* s
     if (conv_stem_f16x3_applicable(a)) return route_rec(c, "fwd", ci, launch_conv_stem_f16x3(a, c.st));
     a.wu = nullptr;
   }
-  if (cv.wu_off && !cv.stem7() && a.Ctot == cv.CinP && c.m->plan.wino_ok((size_t)ci)) {
+  if (cv.wu_off && !cv.stem7() && !cv.igb() && a.Ctot == cv.CinP && c.m->plan.wino_ok((size_t)ci)) {
     a.wu = c.wu(cv); a.wu_ncb = wino_ncb(cv.Cout);
     if (c.m->plan.prec == UWM_PREC_BF16X3_ALL && cv.x3()) {
       if (a.C0 != cv.c0 && a.C0 != a.Ctot) return hipErrorInvalidValue;       // the bank was split for this concat boundary
@@ -90,6 +90,7 @@ static hipError_t run_conv_fwd(const Ctx& c, int ci, const Src& s0, const Src* s
   }
   a.wino = c.m->plan.wino_mode + 1; a.route_n = c.m->route_n;
   if (conv_ig16(c.m, (size_t)ci, false)) a.ig16 = 1;
+  if (ig_bank_on(c.m, (size_t)ci, false) && a.Ctot == cv.CinP && cfg < 0) a.wbank = c.wu(cv);
   return route_rec(c, "fwd", ci, launch_conv(a, c.st, cfg));
 }
 
@@ -125,6 +126,7 @@ static hipError_t run_dgrad(const Ctx& c, int ci, const float* dy, int Ho, int W
   }
   a.wino = c.m->plan.wino_mode + 1;
   if (conv_ig16(c.m, (size_t)ci, true)) a.ig16 = 1;
+  if (ig_bank_on(c.m, (size_t)ci, true)) a.wbank = c.F(cv.wdb_off);
   if (a.prec == 2 || a.ig16) {                 // dY scaled by the power of two bn_bwd_apply's max|dy| calls for
     const hipError_t e = dy_max_slot(c, ci, "dgrad", &a.xmax);
     if (e != hipSuccess) return e;
@@ -248,21 +250,31 @@ static hipError_t run_bn_bwd_act(const Ctx& c, int ci, const float* g, float* dy
        return fail("launch failed: %s at %s:%d (%s)", hipGetErrorString(e_), __FILE__, __LINE__, #expr); } } while (0)
 
 // Winograd filter transforms of every eligible layer (forward banks, or dgrad banks straight from the forward
-// weights), at most 40 layers per launch
+// weights), at most WinoJobs::kMax layers per launch
 // (forward banks go where Ctx::wu points: the workspace, or the frozen arena when uwm_freeze fills it)
+// (+ the pre-split weight operands of the implicit GEMM's fp16x3 form, ig_bank_on: jobs of the fp16x3 bank launch — the forward
+// ones from the parameters, the dgrad ones from the [Cin][tap][Cout] repacks enqueued on this stream before this call)
 static hipError_t wino_jobs(const Ctx& c, bool dgrad, hipStream_t st) {
-  if (c.m->plan.wino_mode == 0) return hipSuccess;
   uwm_model* m = c.m;
+  const bool wino_on = m->plan.wino_mode != 0;
   // three passes: fp32 banks, then (bf16x3 modes) the split-bf16 banks of the layers that run on conv_wino_x3, then (fp16x3
   // modes) the split-fp16 banks of the layers that run on conv_f16x3
   const int prec = m->plan.prec;
   const bool bf = prec == UWM_PREC_BF16X3 || prec == UWM_PREC_BF16X3_ALL;
-  for (int x3 = 0; x3 <= 2; ++x3) {
+  for (int x3 = wino_on ? 0 : 2; x3 <= 2; ++x3) {
     WinoJobs jobs; jobs.n = 0;
     auto flush = [&]() { if (jobs.n > 0 && !dgrad) ++m->prep_launches; hipError_t e = x3 == 2 ? launch_f16x3_weights_multi(jobs, st) : (x3 ? launch_wino_weights_x3_multi(jobs, st) : launch_wino_weights_multi(jobs, st)); jobs.n = 0; return e; };
     for (size_t ci = 0; ci < m->convs.size(); ++ci) {
       const ConvL& cv = m->convs[ci];
-      if (!m->plan.wino_ok(ci) || !(dgrad ? cv.wud_off : cv.wu_off) || cv.stem7()) continue;      // (the stem's slot holds conv_stem_f16x3's bank, built by its own kernel)
+      if (x3 == 2 && ig_bank_on(m, ci, dgrad)) {
+        WinoJob& j = jobs.j[jobs.n++];
+        j.chans = 0; j.mode = 3; j.pad_ = 0;
+        if (dgrad) { j.w = c.F(cv.wd_off); j.ut = c.F(cv.wdb_off); j.rows = cv.CinP; j.Kpad = cv.KpadD; j.src_rows = cv.CinP; }
+        else { j.w = m->params + cv.w_off; j.ut = c.wu(cv); j.rows = cv.Cout; j.Kpad = cv.Kpad; j.src_rows = cv.Cout; }
+        if (jobs.n == WinoJobs::kMax) { hipError_t e = flush(); if (e != hipSuccess) return e; }
+        continue;
+      }
+      if (!wino_on || cv.igb() || !m->plan.wino_ok(ci) || !(dgrad ? cv.wud_off : cv.wu_off) || cv.stem7()) continue;      // (the stem's slot holds conv_stem_f16x3's bank, built by its own kernel)
       int kind = 0;
       if (dgrad) { if (bf && cv.x3_d()) kind = 1; if (f3_dgrad_on(m, ci)) kind = 2; }
       else { if (prec == UWM_PREC_BF16X3_ALL && cv.x3()) kind = 1; if (f3_fwd_on(m, ci)) kind = 2; }
@@ -271,7 +283,7 @@ static hipError_t wino_jobs(const Ctx& c, bool dgrad, hipStream_t st) {
       j.w = m->params + cv.w_off; j.Kpad = cv.Kpad; j.pad_ = kind == 2 ? f3_layout(m, ci, dgrad) : 0;
       if (dgrad) { j.ut = c.F(cv.wud_off); j.rows = cv.CinP; j.chans = cv.CoutP; j.mode = 2; j.src_rows = cv.Cout; }
       else { j.ut = c.wu(cv); j.rows = cv.Cout; j.chans = cv.CinP; j.mode = 0; j.src_rows = cv.Cout; }
-      if (jobs.n == 40) { hipError_t e = flush(); if (e != hipSuccess) return e; }
+      if (jobs.n == WinoJobs::kMax) { hipError_t e = flush(); if (e != hipSuccess) return e; }
     }
     hipError_t e = flush();
     if (e != hipSuccess) return e;

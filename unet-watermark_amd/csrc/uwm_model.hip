@@ -52,6 +52,10 @@ struct ConvL {
   size_t wd_off;                   // workspace floats: [CinP][KpadD] dgrad repack
   size_t wu_off, wud_off;          // workspace floats: Winograd-transformed weights (forward / dgrad); 0 = none
   size_t wu_floats = 0, fz_wu = 0; // size of the forward slot; its place in the frozen arena (uwm_freeze), in floats
+  size_t wdb_off = 0;              // workspace floats: igb() layers, the pre-split image of the dgrad repack (ConvArgs::wbank); 0 = none
+  // stride-2 layers of the ResNet encoders that run on conv_igemm.hip's fp16x3 form (ig16_on): their weight operand is pre-split once
+  // per step into a bank of the matrix's own size — the forward one in the wu slot (frozen with the other forward banks), the dgrad one at wdb_off
+  bool igb() const { return !dw && bn >= 0 && stride == 2 && (k == 3 || k == 1) && !(CinP & 31) && !(CoutP & 31); }
   bool wino() const { return k == 3 && stride == 1 && pad == 1 && (CinP & 7) == 0; }
   bool wino_d() const { return dgrad && k == 3 && stride == 1 && pad == 1 && (CoutP & 7) == 0; }
   int c0 = 0;                      // channels of the FIRST source of this conv's input (decoder conv1: the up-sampled tensor; else CinP)
@@ -358,6 +362,8 @@ static int build_model(uwm_model* m) {
     // (one slot per direction holds whichever bank the precision mode asks for: fp32 Winograd, bf16x3 Winograd or fp16x3 direct)
     if (c.wino()) { c.wu_off = f; c.wu_floats = std::max(wino_weights_floats(c.Cout, c.CinP), c.f3() ? f16x3_bank_floats(c.Cout, c.CinP) : 0); f += c.wu_floats; f = (size_t)rup((long long)f, 64); }
     if (c.stem7()) { c.wu_off = f; c.wu_floats = stem_f16x3_bank_floats(); f += c.wu_floats; f = (size_t)rup((long long)f, 64); }
+    if (c.igb() && !c.wu_off) { c.wu_off = f; c.wu_floats = (size_t)c.Cout * c.Kpad; f += c.wu_floats; f = (size_t)rup((long long)f, 64); }
+    if (c.igb() && c.dgrad) { c.wdb_off = f; f += (size_t)c.CinP * c.KpadD; f = (size_t)rup((long long)f, 64); }
     if (c.wino_d()) { c.wud_off = f; f += std::max(wino_weights_floats(c.CinP, c.CoutP), c.f3_d() ? f16x3_bank_floats(c.CinP, c.CoutP) : 0); f = (size_t)rup((long long)f, 64); }
   }
   m->fixed_floats = f;

@@ -201,6 +201,12 @@ static bool ig16_on(const uwm_model* m, size_t ci, bool dgrad) {
   if (off || cv.dw || cv.bn < 0 || !(s2 || p11) || (cv.CinP & 31) || (cv.CoutP & 31)) return false;
   return dgrad ? (pm >= UWM_PREC_F16X3_ALL && cv.dgrad) : pm >= UWM_PREC_F16X3;
 }
+// ... with the weight operand pre-split into a bank (ConvL::igb, wino_jobs; UWM_NO_IG_BANK: split while staging, as before)
+static bool ig_bank_on(const uwm_model* m, size_t ci, bool dgrad) {
+  static const bool off = dbg_flag("UWM_NO_IG_BANK");
+  const ConvL& cv = m->convs[ci];
+  return !off && cv.igb() && (dgrad ? cv.wdb_off : cv.wu_off) != 0 && ig16_on(m, ci, dgrad);
+}
 // the sub-pixel decoder conv (3x3 over the x2-upsampled 32-channel map, 16 outputs, no skip: conv_up2.hip) on conv_up2_f16.hip's
 // fp16x3 kernels: forward from UWM_PREC_F16X3 on, its dgrad from UWM_PREC_F16X3_ALL on
 static bool up2_f16_on(const uwm_model* m, size_t ci, bool dgrad) {
@@ -254,12 +260,13 @@ static int pack_key(const uwm_model* m) {
 }
 // The FORM of the bank conv ci's forward slot holds under the current plan and modes; 0 = the slot is not used.  It mirrors what
 // wino_jobs(dgrad = false) and the stem bank builder of do_forward make: 1 fp32 Winograd, 2 bf16x3 Winograd, 3 / 4 fp16x3 in conv_f16x3 /
-// conv_f16x3v2 layout, 5 the stem's fp16x3 bank.  uwm_freeze records it per layer; an eval forward reads the frozen arena only when
+// conv_f16x3v2 layout, 5 the stem's fp16x3 bank, 6 the implicit GEMM's pre-split weight operand.  uwm_freeze records it per layer; an eval forward reads the frozen arena only when
 // every layer's form is the recorded one.
 static int fwd_bank_form(const uwm_model* m, size_t ci) {
   const ConvL& cv = m->convs[ci];
   if (!cv.wu_off) return 0;
   if (cv.stem7()) return stem_f3_on(m) ? 5 : 0;
+  if (cv.igb() && !cv.wino()) return ig_bank_on(m, ci, false) ? 6 : 0;
   if (!m->plan.wino_ok(ci)) return 0;
   if (f3_fwd_on(m, ci)) return 3 + f3_layout(m, ci, false);
   return m->plan.prec == UWM_PREC_BF16X3_ALL && cv.x3() ? 2 : 1;
