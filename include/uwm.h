@@ -308,6 +308,44 @@ int  uwm_set_drop_connect(uwm_handle h, const float* rowscale);
 int  uwm_op_depthwise(int mode, const float* a, const float* b, int k, int stride, int pad_begin, int N, int H, int W, int C,
                       int Ho, int Wo, const float* addend, float* out, float* scratch, uwm_stream stream);
 long long uwm_op_depthwise_scratch_floats(int k, int N, int C, int Ho, int Wo);
+/* Single-operator entry points of the rest of the MBConv block (tests and kernel timing).  Activations are NHWC
+ * [N][hw][C] floats with C a multiple of 4 (>= 4), per-channel vectors [C], per-sample vectors [N][C]; N, hw, npix >= 1.
+ * Every entry returns non-zero without launching on a NULL required pointer or a size outside these limits.
+ * out[npix][C] = swish(y*scale + shift),  swish(z) = z * sigmoid(z) */
+int  uwm_op_swish(const float* y, const float* scale, const float* shift, long long npix, int C, float* out, uwm_stream stream);
+/* act_out = swish(y*scale + shift) and pool[N][C] = mean over hw of act_out, one pass; part: uwm_op_se_scratch_floats(N, C)
+ * floats.  A sample's pool row does not depend on N, bit for bit. */
+int  uwm_op_swish_pool(const float* y, const float* scale, const float* shift, int N, long long hw, int C, float* act_out,
+                       float* pool, float* part, uwm_stream stream);
+/* out[N][C] = mult * sum over hw of a (b == NULL) or of a*b; part as above; deterministic and independent of N */
+int  uwm_op_se_reduce(const float* a, const float* b, int N, long long hw, int C, float mult, float* out, float* part,
+                      uwm_stream stream);
+long long uwm_op_se_scratch_floats(int N, int C);
+/* Squeeze-and-excitation FC pair: hpre[N][nsq] = W1 pool + b1, hid = swish(hpre), s[N][C] = sigmoid(W2 hid + b2).
+ * w1 [nsq][K1pad] (K1pad >= C), w2 [C][K2pad] (K2pad >= nsq rounded up to 4, a multiple of 4, w2 16-byte aligned): the
+ * parameter arena's layout of the two 1x1 layers; pad columns are never read for their value. */
+int  uwm_op_se_fc(const float* pool, const float* w1, const float* b1, int K1pad, const float* w2, const float* b2, int K2pad,
+                  int N, int C, int nsq, float* hpre, float* hid, float* s, uwm_stream stream);
+/* Backward of the pair: gs[N][C] (gradient wrt s) is overwritten with the gradient wrt W2 hid + b2; gpool[N][C], gw1
+ * [nsq][K1pad], gb1 [nsq], gw2 [C][K2pad], gb2 [C] are plain stores that leave the pad columns alone; acc1: scratch
+ * [N][nsq], zeroed here. */
+int  uwm_op_se_fc_backward(float* gs, const float* s, const float* hpre, const float* pool, const float* w1, int K1pad,
+                           const float* w2, int K2pad, int N, int C, int nsq, float* gpool, float* acc1, float* gw1, float* gb1,
+                           float* gw2, float* gb2, uwm_stream stream);
+/* out[n][hw][c] = a[n][hw][c] * s[n][c] */
+int  uwm_op_se_scale(const float* a, const float* s, int N, long long hw, int C, float* out, uwm_stream stream);
+/* block output: out = (y*scale + shift) * rowscale[n] + id; rowscale [N] (drop connect) and id may each be NULL */
+int  uwm_op_mb_out(const float* y, const float* scale, const float* shift, const float* rowscale, const float* id, int N,
+                   long long hw, int C, float* out, uwm_stream stream);
+/* out[n][hw][c] = g[n][hw][c] * rowscale[n] */
+int  uwm_op_rowscale(const float* g, const float* rowscale, int N, long long hw, int C, float* out, uwm_stream stream);
+/* Training-mode BatchNorm statistics of y[npix][C] as a depthwise layer takes them: per-channel sum and sum of squares
+ * into sums2c (2*C doubles, zeroed here), then mean, rstd = 1/sqrt(var + eps) (biased variance), scale = gamma*rstd,
+ * shift = beta - mean*scale; with update_running != 0 also run = (1 - momentum)*run + momentum*{mean, unbiased variance}
+ * (run_mean / run_var may be NULL otherwise and are left untouched). */
+int  uwm_op_bn_stats(const float* y, long long npix, int C, const float* gamma, const float* beta, float eps, float momentum,
+                     int update_running, float* run_mean, float* run_var, double* sums2c, float* mean, float* rstd,
+                     float* scale, float* shift, uwm_stream stream);
 int  uwm_num_mbconv_blocks(uwm_handle h);
 float uwm_mbconv_drop_rate(uwm_handle h, int block);
 /* predict.py:620-625 on the device: bilinear resize (cv2.INTER_LINEAR convention) of each image's logit plane

@@ -31,6 +31,53 @@ def test_abi_exports_every_declared_symbol(U):
     assert lib.uwm_version() >= 1
 
 
+def test_mbconv_op_entries_reject_bad_arguments(U):
+    """The MBConv single-operator entry points check their arguments on the host and fail before any launch: a null pointer,
+    C < 4, C % 4 != 0, N < 1, hw < 1, nsq < 1, pads smaller than the logical width.  (The pointers below are host memory that
+    is never dereferenced: every call here must be refused.)"""
+    import ctypes as C
+    from unet_watermark_amd import _lib as L
+    lib = L.lib()
+    buf = (C.c_float * 64)()
+    p, z = C.c_void_p(C.addressof(buf)), None
+    bad = []
+
+    def refused(name, *args):
+        if getattr(lib, name)(*args) == 0 or name.encode() not in lib.uwm_last_error():
+            bad.append((name, args))
+
+    for c, n, hw in [(0, 1, 1), (2, 1, 1), (6, 1, 1), (8, 0, 1), (8, 1, 0), (8, -1, 4)]:
+        if n == 1:
+            refused("uwm_op_swish", p, p, p, hw, c, p, z)
+            refused("uwm_op_bn_stats", p, hw, c, p, p, 1e-3, 0.01, 1, p, p, p, p, p, p, p, z)
+        refused("uwm_op_swish_pool", p, p, p, n, hw, c, p, p, p, z)
+        refused("uwm_op_se_reduce", p, z, n, hw, c, 1.0, p, p, z)
+        refused("uwm_op_se_scale", p, p, n, hw, c, p, z)
+        refused("uwm_op_mb_out", p, p, p, z, z, n, hw, c, p, z)
+        refused("uwm_op_rowscale", p, p, n, hw, c, p, z)
+        if hw == 1:
+            refused("uwm_op_se_fc", p, p, p, 32, p, p, 32, n, c, 4, p, p, p, z)
+            refused("uwm_op_se_fc_backward", p, p, p, p, p, 32, p, 32, n, c, 4, p, p, p, p, p, p, z)
+    for k1, k2, nsq in [(4, 32, 4), (32, 4, 6), (32, 32, 0), (32, 6, 6)]:         # K1pad < C; K2pad < rup(nsq, 4); nsq < 1; K2pad % 4
+        refused("uwm_op_se_fc", p, p, p, k1, p, p, k2, 1, 8, nsq, p, p, p, z)
+        refused("uwm_op_se_fc_backward", p, p, p, p, p, k1, p, k2, 1, 8, nsq, p, p, p, p, p, p, z)
+    # one null pointer at a time (optional ones excepted: se_reduce's b, mb_out's rowscale / id)
+    good = {"uwm_op_swish": ([p, p, p, 4, 8, p, z], [0, 1, 2, 5]),
+            "uwm_op_swish_pool": ([p, p, p, 1, 4, 8, p, p, p, z], [0, 1, 2, 6, 7, 8]),
+            "uwm_op_se_reduce": ([p, p, 1, 4, 8, 1.0, p, p, z], [0, 6, 7]),
+            "uwm_op_se_fc": ([p, p, p, 32, p, p, 32, 1, 8, 4, p, p, p, z], [0, 1, 2, 4, 5, 10, 11, 12]),
+            "uwm_op_se_fc_backward": ([p, p, p, p, p, 32, p, 32, 1, 8, 4, p, p, p, p, p, p, z], [0, 1, 2, 3, 4, 6, 11, 12, 13, 14, 15, 16]),
+            "uwm_op_se_scale": ([p, p, 1, 4, 8, p, z], [0, 1, 5]),
+            "uwm_op_mb_out": ([p, p, p, z, z, 1, 4, 8, p, z], [0, 1, 2, 8]),
+            "uwm_op_rowscale": ([p, p, 1, 4, 8, p, z], [0, 1, 5]),
+            "uwm_op_bn_stats": ([p, 4, 8, p, p, 1e-3, 0.01, 1, p, p, p, p, p, p, p, z], [0, 3, 4, 8, 9, 10, 11, 12, 13, 14])}
+    for name, (args, ptrs) in good.items():
+        for i in ptrs:
+            refused(name, *[z if j == i else a for j, a in enumerate(args)])
+    assert not bad, bad
+    assert lib.uwm_op_se_scratch_floats(0, 8) == 0 and lib.uwm_op_se_scratch_floats(2, 48) >= 2 * 48
+
+
 def test_state_dict_contract_matches_oracle(U):
     from oracle import unet_oracle as O
     for enc, count in (("resnet18", 14_328_209), ("resnet34", 24_436_369)):

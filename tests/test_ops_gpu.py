@@ -750,13 +750,20 @@ def test_bn_backward_matches_autograd(cuda, c, n, h, w):
 
 
 @pytest.mark.parametrize("se", [False, True], ids=["swish", "swish-se"])
-@pytest.mark.parametrize("c,n,h,w", [(32, 2, 24, 40), (192, 3, 8, 12), (2688, 2, 6, 10)])
+@pytest.mark.parametrize("c,n,h,w", [(32, 2, 24, 40), (192, 3, 8, 12), (2688, 2, 6, 10), (960, 2, 84, 100)])
 def test_bn_backward_act_matches_autograd(cuda, c, n, h, w, se):
     """bn_bwd_reduce_act + bn_bwd_apply_act (mbconv.hip: the EfficientNet MBConv BatchNorm backward behind swish [and the
     squeeze-and-excitation product]) == autograd of batch_norm -> swish [-> x SE scale, + the pooled branch] in fp64.  Upstream
     gradient with a non-zero mean; C = 2688 > 1024 splits the channels over grid.y (pick_cw).  The optional max|dy| output
-    must equal max|dy| of the written dy bit for bit: the fp16x3 dgrad / wgrad that reads dy scales by it."""
+    must equal max|dy| of the written dy bit for bit: the fp16x3 dgrad / wgrad that reads dy scales by it.
+    (960, 2, 84, 100) is past both grid clamps of 2048 workgroups: 16 800 pixels at one pixel row per workgroup pass for the
+    reduce, 4.03 M quads for the apply, whose grid is then rounded up to a multiple of 15 workgroups."""
     L = lib()
+    if (c, n, h, w) == (960, 2, 84, 100):
+        tr = 256 // (960 // 4)                                          # pick_cw(960) = 960: one pixel row per pass
+        assert tr == 1 and -(-n * h * w // (tr * 8)) > 2048            # bn_bwd_reduce_act_kernel clamped
+        assert -(-(n * h * w * c // 4) // 1024) > 2048                 # bn_bwd_apply_act_kernel clamped ...
+        assert 2048 % 15 != 0 and (15 * 256) % (c // 4) == 0           # ... and its grid rounded up to unit = 15
     g = torch.Generator().manual_seed(c + 7 * se)
     y = (torch.randn(n, c, h, w, generator=g) * 2 + 0.7).double().requires_grad_()
     gamma = (torch.rand(c, generator=g) + 0.5).double().requires_grad_()
@@ -785,6 +792,10 @@ def test_bn_backward_act_matches_autograd(cuda, c, n, h, w, se):
                                            P(scr), P(dy), P(dgam), P(dbet), P(xmax), stream()))
     torch.cuda.synchronize()
     ref = y.grad.float()
+    print(f"\nbn_backward_act C {c} N {n} {h}x{w} se {se}: dy max err {float((nchw(dy.cpu()) - ref).abs().max()):.3e} "
+          f"(bar {3e-5 * float(ref.abs().max()) + 1e-6:.3e}), dgamma {float((dgam.cpu() - gamma.grad.float()).abs().max()):.3e} "
+          f"of max {float(gamma.grad.abs().max()):.3e}, dbeta {float((dbet.cpu() - beta.grad.float()).abs().max()):.3e} "
+          f"of max {float(beta.grad.abs().max()):.3e}")
     assert (nchw(dy.cpu()) - ref).abs().max() < 3e-5 * float(ref.abs().max()) + 1e-6
     assert torch.allclose(dgam.cpu(), gamma.grad.float(), rtol=1e-4, atol=1e-4 * float(gamma.grad.abs().max()))
     assert torch.allclose(dbet.cpu(), beta.grad.float(), rtol=1e-4, atol=1e-4 * float(beta.grad.abs().max()))

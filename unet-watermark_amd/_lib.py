@@ -107,6 +107,16 @@ SIGNATURES = {
     "uwm_set_drop_connect": (I, [P, P]),
     "uwm_op_depthwise": (I, [I, P, P, I, I, I, I, I, I, I, I, I, P, P, P, P]),
     "uwm_op_depthwise_scratch_floats": (L, [I, I, I, I, I]),
+    "uwm_op_swish": (I, [P, P, P, L, I, P, P]),
+    "uwm_op_swish_pool": (I, [P, P, P, I, L, I, P, P, P, P]),
+    "uwm_op_se_reduce": (I, [P, P, I, L, I, F, P, P, P]),
+    "uwm_op_se_scratch_floats": (L, [I, I]),
+    "uwm_op_se_fc": (I, [P, P, P, I, P, P, I, I, I, I, P, P, P, P]),
+    "uwm_op_se_fc_backward": (I, [P, P, P, P, P, I, P, I, I, I, I, P, P, P, P, P, P, P]),
+    "uwm_op_se_scale": (I, [P, P, I, L, I, P, P]),
+    "uwm_op_mb_out": (I, [P, P, P, P, P, I, L, I, P, P]),
+    "uwm_op_rowscale": (I, [P, P, I, L, I, P, P]),
+    "uwm_op_bn_stats": (I, [P, L, I, P, P, F, F, I, P, P, P, P, P, P, P, P]),
     "uwm_num_mbconv_blocks": (I, [P]),
     "uwm_mbconv_drop_rate": (F, [P, I]),
     "uwm_preprocess_u8": (I, [P, I, I, I, I, C.POINTER(C.c_float), C.POINTER(C.c_float), P, P, P]),

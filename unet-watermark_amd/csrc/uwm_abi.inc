@@ -571,6 +571,78 @@ int uwm_op_depthwise(int mode, const float* a, const float* b, int k, int stride
   return 0;
 }
 long long uwm_op_depthwise_scratch_floats(int k, int N, int C, int Ho, int Wo) { return (long long)dw_wgrad_scratch_floats(k, N, C, Ho, Wo); }
+// Single-operator entry points of the MBConv plumbing (mbconv.hip) and the depthwise BatchNorm statistics: tests and kernel
+// timing.  Each checks its arguments on the host, zeroes what the model zeroes for the launcher, and calls the launcher the
+// forward / backward calls.  (A C with no channel slice, pick_cw(C) == 0, is refused by the reducing launchers themselves
+// before they launch; with C % 4 == 0 and C >= 4 there always is one.)
+static bool op_nc_bad(int N, long long hw, int C) { return N < 1 || hw < 1 || C < 4 || (C & 3); }
+int uwm_op_swish(const float* y, const float* scale, const float* shift, long long npix, int C, float* out, uwm_stream stream) {
+  if (!y || !scale || !shift || !out || op_nc_bad(1, npix, C)) return fail("uwm_op_swish: bad argument");
+  LCHK(launch_swish_fwd(y, scale, shift, C, out, (size_t)npix, (hipStream_t)stream));
+  return 0;
+}
+long long uwm_op_se_scratch_floats(int N, int C) { return (N < 1 || C < 4 || (C & 3)) ? 0 : (long long)se_reduce_scratch_floats(N, C); }
+int uwm_op_swish_pool(const float* y, const float* scale, const float* shift, int N, long long hw, int C, float* act_out,
+                      float* pool, float* part, uwm_stream stream) {
+  if (!y || !scale || !shift || !act_out || !pool || !part || op_nc_bad(N, hw, C) || N > 65535) return fail("uwm_op_swish_pool: bad argument");
+  LCHK(launch_swish_pool(y, scale, shift, act_out, N, (size_t)hw, C, pool, part, (hipStream_t)stream));
+  return 0;
+}
+int uwm_op_se_reduce(const float* a, const float* b, int N, long long hw, int C, float mult, float* out, float* part,
+                     uwm_stream stream) {
+  if (!a || !out || !part || op_nc_bad(N, hw, C) || N > 65535) return fail("uwm_op_se_reduce: bad argument");
+  LCHK(launch_se_reduce_hw(a, b, N, (size_t)hw, C, mult, out, part, (hipStream_t)stream));
+  return 0;
+}
+static bool op_fc_bad(int K1pad, int K2pad, int N, int C, int nsq) {
+  return op_nc_bad(N, 1, C) || N > 65535 || nsq < 1 || nsq > 8192 || K1pad < C || K2pad < (int)rup(nsq, 4) || (K2pad & 3);
+}
+int uwm_op_se_fc(const float* pool, const float* w1, const float* b1, int K1pad, const float* w2, const float* b2, int K2pad,
+                 int N, int C, int nsq, float* hpre, float* hid, float* s, uwm_stream stream) {
+  if (!pool || !w1 || !b1 || !w2 || !b2 || !hpre || !hid || !s || op_fc_bad(K1pad, K2pad, N, C, nsq)) return fail("uwm_op_se_fc: bad argument");
+  if ((uintptr_t)w2 & 15) return fail("uwm_op_se_fc: w2 must be 16-byte aligned");
+  LCHK(launch_se_fc_fwd(pool, w1, b1, K1pad, w2, b2, K2pad, N, C, nsq, hpre, hid, s, (hipStream_t)stream));
+  return 0;
+}
+int uwm_op_se_fc_backward(float* gs, const float* s, const float* hpre, const float* pool, const float* w1, int K1pad,
+                          const float* w2, int K2pad, int N, int C, int nsq, float* gpool, float* acc1, float* gw1, float* gb1,
+                          float* gw2, float* gb2, uwm_stream stream) {
+  if (!gs || !s || !hpre || !pool || !w1 || !w2 || !gpool || !acc1 || !gw1 || !gb1 || !gw2 || !gb2 || op_fc_bad(K1pad, K2pad, N, C, nsq))
+    return fail("uwm_op_se_fc_backward: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipMemsetAsync(acc1, 0, (size_t)N * nsq * sizeof(float), st));
+  LCHK(launch_se_fc_bwd(gs, s, hpre, pool, w1, K1pad, w2, K2pad, N, C, nsq, gpool, acc1, gw1, gb1, gw2, gb2, st));
+  return 0;
+}
+int uwm_op_se_scale(const float* a, const float* s, int N, long long hw, int C, float* out, uwm_stream stream) {
+  if (!a || !s || !out || op_nc_bad(N, hw, C)) return fail("uwm_op_se_scale: bad argument");
+  LCHK(launch_se_scale(a, s, N, (size_t)hw, C, out, (hipStream_t)stream));
+  return 0;
+}
+int uwm_op_mb_out(const float* y, const float* scale, const float* shift, const float* rowscale, const float* id, int N,
+                  long long hw, int C, float* out, uwm_stream stream) {
+  if (!y || !scale || !shift || !out || op_nc_bad(N, hw, C)) return fail("uwm_op_mb_out: bad argument");
+  LCHK(launch_mb_out(y, scale, shift, rowscale, id, N, (size_t)hw, C, out, (hipStream_t)stream));
+  return 0;
+}
+int uwm_op_rowscale(const float* g, const float* rowscale, int N, long long hw, int C, float* out, uwm_stream stream) {
+  if (!g || !rowscale || !out || op_nc_bad(N, hw, C)) return fail("uwm_op_rowscale: bad argument");
+  LCHK(launch_rowscale(g, rowscale, N, (size_t)hw, C, out, (hipStream_t)stream));
+  return 0;
+}
+int uwm_op_bn_stats(const float* y, long long npix, int C, const float* gamma, const float* beta, float eps, float momentum,
+                    int update_running, float* run_mean, float* run_var, double* sums2c, float* mean, float* rstd, float* scale,
+                    float* shift, uwm_stream stream) {
+  if (!y || !gamma || !beta || !sums2c || !mean || !rstd || !scale || !shift || op_nc_bad(1, npix, C) ||
+      (update_running && (!run_mean || !run_var)))
+    return fail("uwm_op_bn_stats: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipMemsetAsync(sums2c, 0, 2 * (size_t)C * sizeof(double), st));
+  LCHK(launch_colstats(y, (size_t)npix, C, sums2c, sums2c + C, st));
+  LCHK(launch_bn_finalize(sums2c, sums2c + C, gamma, beta, run_mean, run_var, mean, rstd, scale, shift, C, (double)npix, eps,
+                          momentum, update_running != 0, st, 1, 2 * C));
+  return 0;
+}
 int uwm_set_winograd(int on) { winograd_set_mode(on < 0 ? 0 : (on > 2 ? 1 : on)); return 0; }
 int uwm_set_winograd_mode(uwm_handle h, int mode) {
   if (!h) return fail("uwm_set_winograd_mode: null handle");
