@@ -158,6 +158,45 @@ int  uwm_predict_u8(uwm_handle h, const uint8_t* images, const float* mean, cons
                     int apply_sigmoid, int out_h, int out_w, uint8_t* mask, float* logits, void* workspace,
                     size_t workspace_bytes, int N, int H, int W, uwm_stream stream);
 
+/* Images of ANY size, device-resident from their bytes to masks at each image's own size: the reference's predict path
+ * (A.Resize(IMG_SIZE, IMG_SIZE) = cv2.resize INTER_LINEAR on the uint8 image, src/utils/dataset.py:391-393; cv2.resize of the
+ * prediction back to the original size + threshold, src/predict.py:327-335,620-625).
+ *   A ragged batch is ONE buffer `src` of src_bytes bytes (4-byte aligned) plus one uwm_image_desc per image in DEVICE memory
+ * (8-byte aligned): image i is h*w*C tightly packed interleaved bytes at src + offset (offset in bytes, 4-byte aligned).  Every
+ * launch is sized from N, H, W or from a fixed block count per image, never from the descriptors, so ONE captured hipGraph serves
+ * every batch of N images whatever their sizes: overwrite the bytes and the descriptors, replay.  No read leaves
+ * [src, src + src_bytes) and no write leaves [mask, mask + mask_bytes): an image whose descriptor does not fit gives zeros / is skipped.
+ *   The resize rule (exact integer work after the taps; a restatement of OpenCV 4.x's 8-bit HResizeLinear / VResizeLinear
+ * fixed-point path with 11 coefficient bits, and of resizeNN — written from the source, NOT run against cv2).  One axis, dst
+ * samples from src:
+ *     scale = 1.0 / ((double)dst / (double)src)                                   doubles, in this order
+ *     LINEAR   f = (float)((d + 0.5) * scale - 0.5); s = floor(f); f -= s; s < 0: f = 0, s = 0; s >= src - 1: f = 0, s = src - 1
+ *              taps (s, min(s + 1, src - 1)), weights a0 = rint((1.f - f) * 2048), a1 = rint(f * 2048)      (round half to even)
+ *     NEAREST  s = min((int)floor(d * scale), src - 1)
+ *   and a pixel, per channel, with column taps (sx, sx1, a0, a1) and row taps (sy, sy1, b0, b1):
+ *     S(row) = src[row][sx]*a0 + src[row][sx1]*a1;  dst = (((b0 * (S(sy) >> 4)) >> 16) + ((b1 * (S(sy1) >> 4)) >> 16) + 2) >> 2
+ *   (within 0.78 grey levels of float bilinear with align_corners = false on the shapes of tests/test_resize.py; the identity at
+ *   equal size.)
+ * uwm_resize_u8: -> uint8 [N][H][W][C], C in 1..4.  uwm_op_resize_norm_u8_nhwc4: the LINEAR resize, then Normalize, as fp32
+ * [N][H][W][4] (16-byte aligned, padding channels zero) = uwm_resize_u8 -> uwm_op_preprocess_u8_nhwc4 bit for bit.
+ * uwm_resize_threshold_ragged: the logit plane [N][h][w] (element stride ld) of image i resized to out_descs[i]'s (h, w) and
+ * thresholded into mask + out_descs[i].offset (any alignment) = uwm_resize_threshold on that image bit for bit.
+ * uwm_predict_images_u8 = uwm_op_resize_norm_u8_nhwc4 into the forward's input -> eval forward (frozen or not) ->
+ * uwm_resize_threshold_ragged; C = the model's in_channels; logits / workspace / N, H, W as uwm_predict_u8 (the same
+ * uwm_predict_workspace_bytes).  Capturable, no host synchronisation.  Every argument is checked before any launch. */
+typedef struct { long long offset; int h, w; } uwm_image_desc;
+enum { UWM_INTER_NEAREST = 0, UWM_INTER_LINEAR = 1 };            /* cv2's values */
+int  uwm_resize_u8(const uint8_t* src, size_t src_bytes, const uwm_image_desc* descs, int N, int C, int H, int W, int interp,
+                   uint8_t* out, uwm_stream stream);
+int  uwm_op_resize_norm_u8_nhwc4(const uint8_t* src, size_t src_bytes, const uwm_image_desc* descs, int N, int C, int H, int W,
+                                 const float* mean, const float* std, float* out, uwm_stream stream);
+int  uwm_resize_threshold_ragged(const float* logits, int ld, int N, int h, int w, const uwm_image_desc* out_descs, float threshold,
+                                 int apply_sigmoid, uint8_t* mask, size_t mask_bytes, uwm_stream stream);
+int  uwm_predict_images_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, const uwm_image_desc* in_descs, const float* mean,
+                           const float* std, float threshold, int apply_sigmoid, const uwm_image_desc* out_descs, uint8_t* mask,
+                           size_t mask_bytes, float* logits, void* workspace, size_t workspace_bytes, int N, int H, int W,
+                           uwm_stream stream);
+
 /* Backward of the last training forward held in `workspace`; writes (overwrites) the gradient arena
  * ranges of stages [stage_begin, stage_end).  Call with (0, uwm_num_stages) for everything, or stage
  * by stage to overlap gradient all-reduce with the rest of the backward. */

@@ -13,5 +13,5 @@ from .metrics import (get_metrics, get_stats, micro_scores, logits_metrics, thre
 __version__ = "0.1.0"
 
 from .postprocess import optimize_mask, morphology, connected_components, structuring_element  # noqa: F401,E402
-from .data import device_preprocess, aug_flags, random_aug_flags  # noqa: F401,E402
+from .data import device_preprocess, aug_flags, random_aug_flags, pack_images, device_resize  # noqa: F401,E402
 from .train import FusedAdam, FusedAdamW  # noqa: F401,E402

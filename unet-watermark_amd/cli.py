@@ -265,6 +265,12 @@ def predict_command(args):
     for i in range(0, len(files), bs):
         chunk = files[i:i + bs]
         ims = [Image.open(os.path.join(args.input, f)).convert("RGB") for f in chunk]
+        if args.resize == "device":                            # cv2-convention resize on the device, both ways, in one call
+            masks = pred.predict_images([np.asarray(im, dtype=np.uint8) for im in ims], args.sigmoid, args.mask_type,
+                                        use_graph=len(chunk) == bs)
+            for f, m in zip(chunk, masks):
+                Image.fromarray(m.cpu().numpy()).save(os.path.join(args.output, os.path.splitext(f)[0] + "_mask.png"))
+            continue
         arr = np.stack([np.asarray(im.resize((s, s), Image.BILINEAR), dtype=np.uint8) for im in ims])
         logits = pred.logits(pred.preprocess(torch.from_numpy(arr)), use_graph=len(chunk) == bs)
         from .metrics import resize_threshold
@@ -278,7 +284,7 @@ def predict_command(args):
     print(f"wrote {len(files)} masks to {args.output}")
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description="MI355X-native U-Net watermark segmentation (train | predict)")
     sub = ap.add_subparsers(dest="command")
     tp = sub.add_parser("train")
@@ -309,6 +315,15 @@ def main(argv=None):
     pp.add_argument("--batch-size", type=int); pp.add_argument("--sigmoid", action="store_true")
     pp.add_argument("--mask-type", choices=["watermark", "text", "mixed"], default=None,
                     help="post-process every mask as the reference's _optimize_mask does for this watermark type (absent: raw thresholded masks)")
+    pp.add_argument("--resize", choices=["host", "device"], default="host",
+                    help="where images are resized to IMG_SIZE: 'device' = the reference's rule (cv2.resize INTER_LINEAR as A.Resize "
+                         "does, restated in HIP; images of any size in one captured graph); 'host' (default) = PIL BILINEAR, which "
+                         "widens its support on a downscale and so does NOT give the reference's pixels")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
     if args.command == "train":
         return train_command(args)

@@ -497,16 +497,7 @@ hipError_t launch_upsplit(const float* dcat, int N, int H, int W, int C0, int C1
 // VerticalFlip, RandomRotate90) are index arithmetic in the same pass.  flags[n]: bit0 hflip, bit1 vflip,
 // bits 2-3 = k of rot90 (counter-clockwise, numpy/torch convention; needs H == W), applied in albumentations'
 // pipeline order: flips first, then the rotation.
-struct PreArgs { float mul[4], add[4]; };
-// Normalize of one byte: ONE function (explicit fused multiply-add) for preprocess_u8_kernel and preprocess_u8_nhwc4_kernel, so that
-// the stem sees the same bits on either path
-__device__ __forceinline__ float pre_norm(uint32_t b, float mul, float add) { return fmaf((float)b, mul, add); }
-static PreArgs make_pre_args(int C, const float* mean, const float* std) {
-  PreArgs pa;
-  for (int c = 0; c < 4; ++c) { pa.mul[c] = 0.f; pa.add[c] = 0.f; }
-  for (int c = 0; c < C; ++c) { pa.mul[c] = 1.f / (255.f * std[c]); pa.add[c] = -mean[c] / std[c]; }
-  return pa;
-}
+// (PreArgs, pre_norm and make_pre_args live in uwm_kernels.h: resize_u8.hip normalises with the same function)
 __device__ __forceinline__ void aug_src(int flags, int H, int W, int y, int x, int& sy, int& sx) {
   // output (y, x) of rot90^k(flip(img)) -> coordinates in the flipped image, then undo the flips
   const int k = (flags >> 2) & 3;

@@ -238,6 +238,70 @@ int uwm_predict_u8(uwm_handle h, const uint8_t* images, const float* mean, const
   LCHK(launch_resize_threshold(lg, h->CP, N, H, W, out_h, out_w, threshold, apply_sigmoid, mask, nullptr, st));
   return 0;
 }
+// ---- cv2-convention resize of ragged uint8 batches (resize_u8.hip): every argument is checked here, before any launch (the
+// descriptors are device memory: the kernels clamp them)
+static_assert(sizeof(uwm_image_desc) == sizeof(ImageDesc) && sizeof(uwm_image_desc) == 16, "uwm_image_desc layout");
+static int resize_args_check(const char* fn, const void* src, size_t src_bytes, const void* descs, int N, int C, int H, int W, const void* out) {
+  if (!src || !descs || !out) return fail("%s: null argument", fn);
+  if (C < 1 || C > 4) return fail("%s: C must be 1..4 (got %d)", fn, C);
+  if (N < 1 || H < 1 || W < 1 || src_bytes < 1) return fail("%s: N, H, W and src_bytes must be >= 1 (got %d, %d, %d, %zu)", fn, N, H, W, src_bytes);
+  if ((long long)N * ((H + kResizeRowsPerBlock - 1) / kResizeRowsPerBlock) > 2147483647ll) return fail("%s: N * H too large for one launch (%d x %d)", fn, N, H);
+  if ((uintptr_t)src & 3) return fail("%s: src must be 4-byte aligned", fn);
+  if ((uintptr_t)descs & 7) return fail("%s: descriptors must be 8-byte aligned", fn);
+  return 0;
+}
+int uwm_resize_u8(const uint8_t* src, size_t src_bytes, const uwm_image_desc* descs, int N, int C, int H, int W, int interp,
+                  uint8_t* out, uwm_stream stream) {
+  if (resize_args_check("uwm_resize_u8", src, src_bytes, descs, N, C, H, W, out)) return 1;
+  if (interp != UWM_INTER_NEAREST && interp != UWM_INTER_LINEAR)
+    return fail("uwm_resize_u8: unknown interp %d (UWM_INTER_NEAREST = 0 | UWM_INTER_LINEAR = 1)", interp);
+  LCHK(launch_resize_u8(src, src_bytes, (const ImageDesc*)descs, N, C, H, W, interp, out, (hipStream_t)stream));
+  return 0;
+}
+int uwm_op_resize_norm_u8_nhwc4(const uint8_t* src, size_t src_bytes, const uwm_image_desc* descs, int N, int C, int H, int W,
+                                const float* mean, const float* std, float* out, uwm_stream stream) {
+  if (resize_args_check("uwm_op_resize_norm_u8_nhwc4", src, src_bytes, descs, N, C, H, W, out)) return 1;
+  if (!mean || !std) return fail("uwm_op_resize_norm_u8_nhwc4: null argument");
+  if ((uintptr_t)out & 15) return fail("uwm_op_resize_norm_u8_nhwc4: out must be 16-byte aligned");
+  for (int c = 0; c < C; ++c) if (!(std[c] > 0.f)) return fail("uwm_op_resize_norm_u8_nhwc4: std[%d] must be positive", c);
+  LCHK(launch_resize_norm_u8_nhwc4(src, src_bytes, (const ImageDesc*)descs, N, C, H, W, mean, std, out, (hipStream_t)stream));
+  return 0;
+}
+int uwm_resize_threshold_ragged(const float* logits, int ld, int N, int h, int w, const uwm_image_desc* out_descs, float threshold,
+                                int apply_sigmoid, uint8_t* mask, size_t mask_bytes, uwm_stream stream) {
+  if (!logits || !out_descs || !mask) return fail("uwm_resize_threshold_ragged: null argument");
+  if (N < 1 || h < 1 || w < 1 || ld < 1 || mask_bytes < 1)
+    return fail("uwm_resize_threshold_ragged: N, h, w, ld and mask_bytes must be >= 1 (got %d, %d, %d, %d, %zu)", N, h, w, ld, mask_bytes);
+  if (N > (1 << 24)) return fail("uwm_resize_threshold_ragged: N too large for one launch (%d)", N);
+  if ((uintptr_t)out_descs & 7) return fail("uwm_resize_threshold_ragged: descriptors must be 8-byte aligned");
+  LCHK(launch_resize_threshold_ragged(logits, ld, N, h, w, (const ImageDesc*)out_descs, threshold, apply_sigmoid, mask, mask_bytes,
+                                      (hipStream_t)stream));
+  return 0;
+}
+int uwm_predict_images_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, const uwm_image_desc* in_descs, const float* mean,
+                          const float* std, float threshold, int apply_sigmoid, const uwm_image_desc* out_descs, uint8_t* mask,
+                          size_t mask_bytes, float* logits, void* ws, size_t ws_bytes, int N, int H, int W, uwm_stream stream) {
+  if (!h || !src || !in_descs || !mean || !std || !out_descs || !mask || !ws) return fail("uwm_predict_images_u8: null argument");
+  if (check_shape(N, H, W)) return 1;
+  if (!h->params || !h->buffers) return fail("uwm_predict_images_u8: call uwm_bind first");
+  if (src_bytes < 1 || mask_bytes < 1) return fail("uwm_predict_images_u8: src_bytes and mask_bytes must be >= 1");
+  const int C = h->desc.in_channels;
+  if (C < 1 || C > 4) return fail("uwm_predict_images_u8: the model takes %d channels; images have 1..4", C);
+  for (int c = 0; c < C; ++c) if (!(std[c] > 0.f)) return fail("uwm_predict_images_u8: std[%d] must be positive", c);
+  if ((uintptr_t)src & 3) return fail("uwm_predict_images_u8: src must be 4-byte aligned");
+  if (((uintptr_t)in_descs | (uintptr_t)out_descs) & 7) return fail("uwm_predict_images_u8: descriptors must be 8-byte aligned");
+  if (((uintptr_t)logits | (uintptr_t)ws) & 15) return fail("uwm_predict_images_u8: logits and workspace must be 16-byte aligned");
+  const size_t need = uwm_predict_workspace_bytes(h, N, H, W, logits ? 0 : 1);
+  if (ws_bytes < need) return fail("uwm_predict_images_u8: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+  float* lg = logits ? logits : (float*)ws + h->plan.bytes / sizeof(float);      // (no caller buffer: behind the plan)
+  h->have_fwd = false;
+  DeviceGuard guard(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  LCHK(launch_resize_norm_u8_nhwc4(src, src_bytes, (const ImageDesc*)in_descs, N, C, H, W, mean, std, (float*)ws + h->plan.x4, st));
+  if (do_forward(h, nullptr, lg, (float*)ws, N, H, W, 0, st)) return 1;
+  LCHK(launch_resize_threshold_ragged(lg, h->CP, N, H, W, (const ImageDesc*)out_descs, threshold, apply_sigmoid, mask, mask_bytes, st));
+  return 0;
+}
 int uwm_op_preprocess_u8_nhwc4(const uint8_t* images, long long npix, int C, const float* mean, const float* std, float* out,
                                uwm_stream stream) {
   if (!images || !mean || !std || !out || npix < 1 || C < 1 || C > 4) return fail("uwm_op_preprocess_u8_nhwc4: bad argument");

@@ -371,6 +371,45 @@ hipError_t launch_preprocess_u8(const uint8_t* img, int N, int H, int W, int C, 
 hipError_t launch_preprocess_u8_nhwc4(const uint8_t* img, size_t npix, int C, const float* mean, const float* std, float* out,
                                       hipStream_t st);
 hipError_t launch_preprocess_mask(const uint8_t* m, int N, int H, int W, int thr, const int* flags, uint8_t* out, hipStream_t st);
+struct PreArgs { float mul[4], add[4]; };
+// Normalize of one byte: ONE function (explicit fused multiply-add) for preprocess_u8_kernel, preprocess_u8_nhwc4_kernel and
+// resize_norm_u8_nhwc4_kernel, so that the stem sees the same bits on every path
+__device__ __forceinline__ float pre_norm(uint32_t b, float mul, float add) { return fmaf((float)b, mul, add); }
+static inline PreArgs make_pre_args(int C, const float* mean, const float* std) {
+  PreArgs pa;
+  for (int c = 0; c < 4; ++c) { pa.mul[c] = 0.f; pa.add[c] = 0.f; }
+  for (int c = 0; c < C; ++c) { pa.mul[c] = 1.f / (255.f * std[c]); pa.add[c] = -mean[c] / std[c]; }
+  return pa;
+}
+// One output pixel (Y, X) of the bilinear resize of a logit plane b[h][w] (element stride ld) by sy = h / H, sx = w / W: ONE function
+// for resize_threshold_kernel (loss.hip) and resize_threshold_ragged_kernel (resize_u8.hip), so that a ragged batch's masks are the
+// uniform call's bit for bit
+__device__ __forceinline__ float resize_logit(const float* __restrict__ b, int ld, int h, int w, float sy, float sx, int Y, int X,
+                                              int apply_sigmoid) {
+  float fy = ((float)Y + 0.5f) * sy - 0.5f, fx = ((float)X + 0.5f) * sx - 0.5f;
+  fy = fmaxf(fy, 0.f); fx = fmaxf(fx, 0.f);
+  int y0 = (int)fy, x0 = (int)fx;
+  y0 = min(y0, h - 1); x0 = min(x0, w - 1);
+  const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
+  const float wy = fy - (float)y0, wx = fx - (float)x0;
+  const float v00 = b[((size_t)y0 * w + x0) * ld], v01 = b[((size_t)y0 * w + x1) * ld];
+  const float v10 = b[((size_t)y1 * w + x0) * ld], v11 = b[((size_t)y1 * w + x1) * ld];
+  float v = (1.f - wy) * ((1.f - wx) * v00 + wx * v01) + wy * ((1.f - wx) * v10 + wx * v11);
+  if (apply_sigmoid) v = 1.f / (1.f + expf(-v));
+  return v;
+}
+// ---- cv2-convention resize of a ragged batch of uint8 images (resize_u8.hip; the rule: include/uwm.h)
+constexpr int kResizeRowsPerBlock = 4;               // output rows of one resize workgroup: grid = N * ceil(H / this) (also the ABI's launch-size check)
+struct ImageDesc { long long offset; int h, w; };      // = uwm_image_desc: one per image, in DEVICE memory
+// [N] images (h_i, w_i, C) at src + offset_i -> uint8 [N][H][W][C]; interp 0 nearest | 1 linear.  No read leaves [src, src + src_bytes)
+hipError_t launch_resize_u8(const uint8_t* src, size_t src_bytes, const ImageDesc* descs, int N, int C, int H, int W, int interp,
+                            uint8_t* out, hipStream_t st);
+// the linear resize, then Normalize (pre_norm) as fp32 [N][H][W][4], padding channels zero: launch_resize_u8 -> launch_preprocess_u8_nhwc4
+hipError_t launch_resize_norm_u8_nhwc4(const uint8_t* src, size_t src_bytes, const ImageDesc* descs, int N, int C, int H, int W,
+                                       const float* mean, const float* std, float* out, hipStream_t st);
+// logit plane [N][h][w] (stride ld) -> image i's own (h_i, w_i) at mask + offset_i, thresholded; nothing is written outside [mask, mask + mask_bytes)
+hipError_t launch_resize_threshold_ragged(const float* logits, int ld, int N, int h, int w, const ImageDesc* out_descs, float thr,
+                                          int apply_sigmoid, uint8_t* mask, size_t mask_bytes, hipStream_t st);
 
 // EfficientNet MBConv pieces (mbconv.hip): swish, depthwise k x k conv (weights tap-major [k*k][C]) with static "same"
 // padding (pb = pad at the begin of H and W; the end pad is implied by Ho/Wo), squeeze-and-excitation, block output with drop-connect

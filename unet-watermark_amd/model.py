@@ -436,6 +436,45 @@ class Unet(nn.Module):
                     SegmentationModelError)
         return (mask, self._logits_view(logits)) if return_logits else mask
 
+    @torch.no_grad()
+    def predict_images_u8(self, packed: torch.Tensor, in_descs: torch.Tensor, out_descs: torch.Tensor, mask: torch.Tensor, n: int,
+                          size, mean, std, threshold: float = 0.5, apply_sigmoid: bool = False, return_logits: bool = False):
+        """A packed ragged batch of n uint8 images of any sizes (data.pack_images; `packed` flat uint8, `in_descs` / `out_descs` the
+        bytes of the uwm_image_desc arrays, all on the HIP device) -> every image's uint8 {0,255} mask at its own size, written into
+        the flat uint8 buffer `mask` at out_descs' offsets, in ONE library call (uwm_predict_images_u8): cv2-convention resize to
+        `size` = (H, W) + Normalize into the forward's input, eval forward (frozen or not), resize back + threshold.  Nothing in the
+        call depends on the image sizes, so a graph captured around it serves every batch of n images.  Returns `mask`
+        [, logits (n,classes,H,W)]."""
+        if self.training:
+            raise RuntimeError("predict_images_u8 is an eval-mode path: call .eval() first")
+        for t in (packed, in_descs, out_descs, mask):
+            self._require_gpu(t)
+            if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+                raise RuntimeError("predict_images_u8 takes flat contiguous uint8 tensors (data.pack_images / data.descs_tensor)")
+        n = int(n)
+        if n < 1 or in_descs.numel() < 16 * n or out_descs.numel() < 16 * n:
+            raise RuntimeError(f"predict_images_u8: {n} images need {16 * n} descriptor bytes each way")
+        h, w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+        self.check_input_shape(torch.empty((0, self.in_channels, h, w)))
+        self._ensure_bound()
+        if self._frozen and not L.lib().uwm_is_frozen(self._h):
+            self._freeze_now(n, h, w)
+        ws = self._workspace(n, h, w, False, logits_inside=not return_logits)
+        logits = torch.empty((n, h, w, self._cp), dtype=torch.float32, device=packed.device) if return_logits else None
+        self._fwd_gen += 1
+        if self._n_mb:
+            self._set_drop_connect(n, False, packed.device)
+        c = self.in_channels
+        mean_c = (C.c_float * c)(*[float(v) for v in mean[:c]]); std_c = (C.c_float * c)(*[float(v) for v in std[:c]])
+        with L.on_device(packed):
+            L.check(L.lib().uwm_predict_images_u8(self._h, C.c_void_p(packed.data_ptr()), packed.numel(), C.c_void_p(in_descs.data_ptr()),
+                                                  mean_c, std_c, float(threshold), int(apply_sigmoid), C.c_void_p(out_descs.data_ptr()),
+                                                  C.c_void_p(mask.data_ptr()), mask.numel(),
+                                                  C.c_void_p(logits.data_ptr() if logits is not None else 0),
+                                                  C.c_void_p(ws.data_ptr()), ws.numel(), n, h, w, C.c_void_p(L.stream_ptr(packed.device))),
+                    SegmentationModelError)
+        return (mask, self._logits_view(logits)) if return_logits else mask
+
     def _set_drop_connect(self, n: int, training: bool, device):
         """Draw this step's per-block, per-sample keep masks (efficientnet_pytorch utils.drop_connect: floor(keep_prob +
         U[0,1)) / keep_prob) on the device and hand them to the library; the tensor lives until the next forward."""

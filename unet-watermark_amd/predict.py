@@ -8,6 +8,7 @@ from __future__ import annotations
 
 from typing import Optional
 
+import numpy as np
 import torch
 
 from .checkpoint import load_checkpoint
@@ -50,6 +51,10 @@ class WatermarkPredictor:
         self._pgraph = None                   # predict_mask(mask_type=...): the forward + threshold + post-processing graph
         self._pkey = None
         self._pin = self._pout = self._pws = None
+        self._igraph = None                   # predict_images: ONE graph per (N, H, W, apply_sigmoid, threshold), whatever the image sizes
+        self._ikey = None
+        self._ibuf = self._idesc = self._mdesc = self._mbuf = self._iws = None      # its static staging buffers
+        self._hbuf = self._hevt = None        # pinned host staging of the packed bytes + the event of its last upload
         self.freeze = bool(freeze)
         if self.freeze:
             self.model.freeze()               # the first forward fixes the bank forms
@@ -109,7 +114,7 @@ class WatermarkPredictor:
         captured on the old arena contents go."""
         if self.freeze and not self.model.frozen_serves(n, h, w):
             self.model.freeze(batch_shape=(n, h, w))
-            self._graph = self._gkey = self._ugraph = self._ukey = self._pgraph = self._pkey = None
+            self._graph = self._gkey = self._ugraph = self._ukey = self._pgraph = self._pkey = self._igraph = self._ikey = None
 
     @torch.no_grad()
     def predict_mask_u8(self, images_u8_nhwc: torch.Tensor, out_size=None, apply_sigmoid: bool = False,
@@ -150,3 +155,68 @@ class WatermarkPredictor:
         self._uin.copy_(x)
         self._ugraph.replay()
         return pick(self._uout)
+
+    def _staging(self, name: str, need: int):
+        """the static device buffer `name` holds at least `need` bytes; grown geometrically.  A graph captured on the old buffer
+        goes with it."""
+        buf = getattr(self, name)
+        if buf is not None and buf.numel() >= need:
+            return
+        cap = max(need, 256 if buf is None else 2 * buf.numel())
+        setattr(self, name, torch.zeros(cap, dtype=torch.uint8, device=self.device))
+        self._igraph = self._ikey = None
+
+    @torch.no_grad()
+    def predict_images(self, images, apply_sigmoid: bool = False, mask_type: Optional[str] = None, use_graph: bool = True):
+        """uint8 (h_i, w_i, C) images of ANY sizes (arrays or tensors) -> a list of uint8 {0,255} device masks, one per image at its
+        own size: the reference's predict path (src/predict.py:327-335,614-625) device-resident from the image bytes on — cv2's
+        INTER_LINEAR resize to IMG_SIZE (A.Resize) + Normalize, eval forward, bilinear resize of the logits back to (h_i, w_i) +
+        threshold, in ONE library call (uwm_predict_images_u8).  The per-image geometry lives in device memory, so one captured
+        graph per (N, IMG_SIZE, apply_sigmoid) serves every batch of N images; it is re-captured only when a staging buffer had
+        to grow or the frozen arena was re-made.  mask_type 'watermark' | 'text' | 'mixed': each mask then goes through
+        optimize_mask at its own size, outside the graph."""
+        from .data import descs_tensor, pack_images
+        if mask_type is not None:
+            mask_type_code(mask_type)
+        # pack into ONE persistent pinned buffer (pinned allocation is expensive), grown geometrically; the previous batch's upload
+        # from it must have finished before it is overwritten
+        need = sum((int(np.prod(im.shape)) + 3) // 4 * 4 for im in images)
+        if self._hbuf is None or self._hbuf.numel() < need:
+            self._hbuf = torch.empty(max(need, 2 * (0 if self._hbuf is None else self._hbuf.numel())), dtype=torch.uint8, pin_memory=True)
+        elif self._hevt is not None:
+            self._hevt.synchronize()
+        packed, descs, mdescs = pack_images(images, out=self._hbuf)
+        channels = int(images[0].shape[2])
+        if channels != self.model.in_channels:
+            raise RuntimeError(f"the model takes {self.model.in_channels}-channel images, got {channels}")
+        n, s = len(descs), int(self.cfg.DATA.IMG_SIZE)
+        areas = descs["h"].astype("int64") * descs["w"]
+        mask_bytes = int(mdescs["offset"][-1] + areas[-1])
+        for name, need in (("_ibuf", packed.numel()), ("_idesc", 16 * n), ("_mdesc", 16 * n), ("_mbuf", mask_bytes)):
+            self._staging(name, need)
+        self._ibuf[:packed.numel()].copy_(packed, non_blocking=True)
+        if self._hevt is None:
+            self._hevt = torch.cuda.Event()
+        self._hevt.record()
+        self._idesc[:16 * n].copy_(descs_tensor(descs))
+        self._mdesc[:16 * n].copy_(descs_tensor(mdescs))
+        run = lambda: self.model.predict_images_u8(self._ibuf, self._idesc, self._mdesc, self._mbuf, n, (s, s), IMAGENET_MEAN,
+                                                   IMAGENET_STD, self.threshold, apply_sigmoid)
+        if not use_graph:
+            run()
+        else:
+            key = (n, s, s, bool(apply_sigmoid), float(self.threshold))      # (the threshold is a captured kernel argument)
+            if self._ikey != key or self._igraph is None:
+                self._refreeze_for(n, s, s)
+                run()                                 # eager warm-up: plans the workspace, sets kernel attributes
+                torch.cuda.synchronize(self.device)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    run()
+                self._igraph, self._ikey, self._iws = g, key, self.model._ws
+            self._igraph.replay()
+        out = self._mbuf[:mask_bytes].clone()         # (the staging buffer is overwritten by the next call)
+        masks = [out[int(o): int(o) + int(a)].view(int(h), int(w)) for o, a, h, w in zip(mdescs["offset"], areas, descs["h"], descs["w"])]
+        if mask_type is not None:
+            masks = [optimize_mask(m, mask_type) for m in masks]
+        return masks
