@@ -281,6 +281,45 @@ int  uwm_preprocess_u8(const uint8_t* images, int N, int H, int W, int C, const 
                        const int* flags, float* out_nchw, uwm_stream stream);
 int  uwm_preprocess_mask_u8(const uint8_t* masks, int N, int H, int W, int threshold, const int* flags, uint8_t* out,
                             uwm_stream stream);
+/* Train-time augmentation on the device: the reference's basic recipe (get_train_transform, src/utils/dataset.py:375-387) behind
+ * the resize, in one launch for the images and one for the masks, on the caller's stream, without host synchronisation;
+ * capturable like uwm_preprocess_u8.  images uint8 [N][H][W][C], C in 1..4; masks uint8 [N][H][W] (NULL together with out_masks:
+ * no masks); descs: one uwm_aug_desc per image in DEVICE memory (8-byte aligned).  out_nchw: fp32 [N][C][H][W] normalised;
+ * out_masks: uint8 {0,1}; out_u8 (may be NULL): the augmented uint8 image [N][H][W][C] before Normalize, for tests and for
+ * looking at what the augmenter makes.  mean / std are host pointers (C values).
+ *   Stage order per output pixel: flips -> rot90 -> affine warp -> table -> HSV -> Normalize.  The warp is an inverse-map gather,
+ * so output (x, y) goes to fixed-point coordinates in the flipped and rotated image, four taps are taken there, each
+ * border-reflected, and each goes through the flags' index map of uwm_preprocess_u8 into the input.
+ *   The rule, in integers so that it can be checked bit for bit (a restatement of OpenCV 4.x's 8-bit warpAffine with
+ * WARP_INVERSE_MAP semantics, AB_BITS = 10, INTER_BITS = 5, BORDER_REFLECT_101 — written from knowledge of the source, NOT run
+ * against cv2).  rne = round half to even to int; float64 arithmetic with every product and sum rounded on its own (no fused
+ * multiply-add):
+ *     adelta[x] = rne(minv0*x*1024)               bdelta[x] = rne(minv3*x*1024)
+ *     X0[y] = rne((minv1*y + minv2)*1024) + r      Y0[y] = rne((minv4*y + minv5)*1024) + r
+ *   image (linear), r = 16:  X = (X0[y] + adelta[x]) >> 5, Y likewise; sx = X >> 5, fx = X & 31, sy = Y >> 5, fy = Y & 31;
+ *     out = ((32-fx)(32-fy)*p00 + fx(32-fy)*p01 + (32-fx)fy*p10 + fx*fy*p11 + 512) >> 10    p_ij = tap (sy + i, sx + j)
+ *   mask (nearest), r = 512: sx = (X0[y] + adelta[x]) >> 10, sy likewise; then (m > mask_threshold) -> {0,1}.
+ *   border: reflect-101 of ANY coordinate (period 2(n-1), as many reflections as it takes; n = 1 -> 0).
+ *   table: v = lut[v] on every channel (brightness / contrast; computed by the host, so no device float rule is involved).
+ *   HSV, only when C == 3 and some shift != 0.  Forward = OpenCV's 8-bit RGB -> HSV with H in 0..179:
+ *     v = max, d = max - min, s = (d*sdiv[v] + 2048) >> 12, h0 = (v == r) ? g-b : (v == g) ? b-r+2d : r-g+4d,
+ *     h = (h0*hdiv[d] + 2048) >> 12 (+180 if negative); sdiv[i] = rne((255<<12)/i), hdiv[i] = rne((180<<12)/(6i)), both 0 at i = 0
+ *     shifts: h = (h + hue) mod 180 (non-negative), s = clip(s + sat, 0, 255), v = clip(v + val, 0, 255)
+ *   The way back is THIS PROJECT'S OWN integer rule (OpenCV's goes through float32 and is not bit-stable across its own builds):
+ *     sec = h/30, f = h%30, p = (v(255-s) + 127)/255, q = (v(7650 - s*f) + 3825)/7650, t = (v(7650 - s(30-f)) + 3825)/7650,
+ *     (r,g,b) = (v,t,p) (q,v,p) (p,v,t) (p,q,v) (t,p,v) (v,p,q) for sec = 0..5
+ *   Normalize: the expression of uwm_preprocess_u8, so out_nchw = uwm_preprocess_u8(out_u8, flags = NULL) bit for bit.
+ *   The kernels only clamp: coordinates are clamped to +-(2^30 - 2048) fixed-point units, rot90 flags are ignored where H != W and
+ *   HSV shifts where C != 3.  A host wrapper should refuse such descriptors, and matrices with non-finite entries, before the call. */
+typedef struct {
+  int flags;              /* as uwm_preprocess_u8: bit0 hflip, bit1 vflip, bits 2-3 rot90 k (needs H == W) */
+  int hue, sat, val;      /* HueSaturationValue shifts; all three 0 = stage skipped */
+  double minv[6];         /* INVERSE affine map, dst (x,y) -> src: sx = minv0*x + minv1*y + minv2, sy = minv3*x + minv4*y + minv5 */
+  unsigned char lut[256]; /* per-value table applied to every channel after the warp */
+} uwm_aug_desc;           /* 320 bytes */
+int  uwm_augment_u8(const uint8_t* images, const uint8_t* masks, const uwm_aug_desc* descs, int N, int H, int W, int C,
+                    const float* mean, const float* std, int mask_threshold, float* out_nchw, uint8_t* out_masks, uint8_t* out_u8,
+                    uwm_stream stream);
 /* 3x3/stride-1 convolutions (forward, dgrad and weight gradient) run as Winograd F(2x2,3x3) on the fp32 MFMA path by
  * default (2.25x fewer multiplies, results within a few fp32 ulps of the direct form); mode 0 selects the direct
  * kernels everywhere; 2 (tests) prefers the 512-thread Winograd variant wherever its shape rules allow, whatever the

@@ -14,4 +14,6 @@ __version__ = "0.1.0"
 
 from .postprocess import optimize_mask, morphology, connected_components, structuring_element  # noqa: F401,E402
 from .data import device_preprocess, aug_flags, random_aug_flags, pack_images, device_resize  # noqa: F401,E402
+from .data import (device_augment, sample_aug_params, identity_aug_params, affine_inverse, brightness_contrast_lut,  # noqa: F401,E402
+                   AUG_DESC_DTYPE)
 from .train import FusedAdam, FusedAdamW  # noqa: F401,E402

@@ -18,7 +18,8 @@ from torch.utils.data.distributed import DistributedSampler
 
 from .checkpoint import load_checkpoint, save_checkpoint
 from .config import get_cfg_defaults, update_config
-from .data import FolderDataset, SyntheticWatermarkDataset
+from .data import (AUG_RECIPES, DeviceInputPipeline, DeviceU8Dataset, FolderDataset, RawFolderDataset, SyntheticWatermarkDataset,
+                   list_collate)
 from .losses import get_loss_function
 from .metrics import logits_metrics
 from .model import create_model_from_config
@@ -37,9 +38,14 @@ def _loss_weights(cfg):
     raise ValueError(f"unsupported LOSS.NAME {name!r} (DiceLoss | BCEWithLogitsLoss | CombinedLoss)")
 
 
-def _datasets(cfg, synthetic):
+def _datasets(cfg, synthetic, device_input=None):
+    """device_input: a torch.device = the raw datasets of the device input path (--augment basic) instead of host-prepared tensors"""
     if synthetic or not os.path.isdir(os.path.join(cfg.DATA.ROOT_DIR, "watermarked")):
         full = SyntheticWatermarkDataset(int(synthetic or 256), cfg.DATA.IMG_SIZE, cfg.DATA.SEED)
+        if device_input is not None:
+            full = DeviceU8Dataset(full, device_input)
+    elif device_input is not None:
+        full = RawFolderDataset(cfg.DATA.ROOT_DIR)
     else:
         full = FolderDataset(cfg.DATA.ROOT_DIR, cfg.DATA.IMG_SIZE)
     n = len(full)
@@ -50,11 +56,16 @@ def _datasets(cfg, synthetic):
 
 
 @torch.no_grad()
-def _validate(model, loader, criterion, device):
+def _validate(model, loader, criterion, device, pipe=None):
     model.eval()
     tot, nb, agg = 0.0, 0, {}
-    for x, t in loader:
-        x, t = x.to(device, non_blocking=True), t.to(device, non_blocking=True)
+    for batch in loader:
+        if pipe is not None:                               # device input path: resize + Normalize, no augmentation
+            x, t = pipe.val_batch(batch)
+            t = t.long()
+        else:
+            x, t = batch
+            x, t = x.to(device, non_blocking=True), t.to(device, non_blocking=True)
         out = model(x)
         tot += float(criterion(out, t.unsqueeze(1)))
         for k, v in logits_metrics(out, t).items():
@@ -186,12 +197,25 @@ def train_command(args):
             broadcast_model(model, 0)
     stopper = (EarlyStopping(patience=int(cfg.TRAIN.EARLY_STOPPING_PATIENCE), restore_best_weights=True)
                if cfg.TRAIN.USE_EARLY_STOPPING else None)       # /root/reference/src/train.py:362-368
-    tr_set, va_set = _datasets(cfg, args.synthetic)
+    augment = getattr(args, "augment", None) or "none"
+    if augment not in ("none",) + AUG_RECIPES:
+        raise ValueError(f"--augment {augment!r}: this build serves 'none' and {AUG_RECIPES}")
+    pipe = None
+    tr_set, va_set = _datasets(cfg, args.synthetic, device if augment != "none" else None)
+    if augment != "none":
+        pipe = DeviceInputPipeline(cfg.DATA.IMG_SIZE, device, source=tr_set.dataset, recipe=augment)
+        if rank == 0:
+            asked = cfg.DATA.get("AUGMENTATION_TYPE", None)
+            note = "" if asked == augment else f" (DATA.AUGMENTATION_TYPE={asked!r} is not served; its extra stages are NOT applied)"
+            print(f"augmentation: serving the {augment!r} recipe on the device{note}", flush=True)
     bs = int(cfg.TRAIN.BATCH_SIZE)
     sampler = DistributedSampler(tr_set, world, rank, shuffle=True, seed=int(cfg.DATA.SEED)) if world > 1 else None
-    tr = DataLoader(tr_set, bs, shuffle=sampler is None, sampler=sampler, num_workers=int(args.workers), drop_last=True,
-                    pin_memory=True)
-    va = DataLoader(va_set, bs * 2, shuffle=False, num_workers=int(args.workers), pin_memory=True)
+    # the device input path gets raw items from the workers (uint8 arrays of any size, or indices): nothing to stack or pin
+    extra = dict(pin_memory=True) if pipe is None else dict(collate_fn=list_collate)
+    if isinstance(tr_set.dataset, DeviceU8Dataset):
+        extra["num_workers"] = 0                           # items are indices into device tensors
+    tr = DataLoader(tr_set, bs, shuffle=sampler is None, sampler=sampler, drop_last=True, **{"num_workers": int(args.workers), **extra})
+    va = DataLoader(va_set, bs * 2, shuffle=False, **{"num_workers": int(args.workers), **extra})
     hist = []
     for epoch in range(start_epoch, int(cfg.TRAIN.EPOCHS)):
         if sampler is not None:
@@ -199,13 +223,19 @@ def train_command(args):
         model.train()
         t0, seen = time.time(), 0
         acc = torch.zeros(3, device=device)
-        for x, t in tr:
-            acc += trainer.step(x.to(device, non_blocking=True), t.to(device, non_blocking=True))
+        if pipe is not None:                              # ranks draw different parameters; a rerun reproduces them
+            aug_gen = torch.Generator().manual_seed((int(cfg.DATA.SEED) * 1000003 + epoch) * 1009 + rank)
+        for batch in tr:
+            if pipe is not None:
+                x, t = pipe.train_batch(batch, aug_gen)
+            else:
+                x, t = batch[0].to(device, non_blocking=True), batch[1].to(device, non_blocking=True)
+            acc += trainer.step(x, t)
             seen += x.shape[0]
         torch.cuda.synchronize(device)
         dt = time.time() - t0
         tl = _rank_mean(float(acc[0]) / max(1, len(tr)), device, world)
-        vl_local, vm = _validate(model, va, criterion, device)
+        vl_local, vm = _validate(model, va, criterion, device, pipe)
         # ONE validation loss for every rank: LR schedule, best-model bookkeeping and early stopping all read it, so
         # the replicas take the same decisions and nobody leaves the collective early
         vl = _rank_mean(vl_local, device, world)
@@ -300,6 +330,10 @@ def build_parser():
     tp.add_argument("--encoder", type=str); tp.add_argument("--img-size", type=int)
     tp.add_argument("--synthetic", type=int, default=0, help="train on N synthetic images instead of DATA.ROOT_DIR")
     tp.add_argument("--workers", type=int, default=2)
+    tp.add_argument("--augment", choices=["none", "basic"], default="none",
+                    help="'basic' = the device input path: workers only decode, the device resizes (cv2's rule), augments with the "
+                         "reference's basic recipe (flips, rot90, ShiftScaleRotate, RandomBrightnessContrast, HueSaturationValue) and "
+                         "normalises; validation is resized and normalised only.  'none' (default) = host-prepared tensors, no augmentation")
     tp.add_argument("--model", choices=["Unet", "UnetPlusPlus"], default=None, help="MODEL.NAME (reference default: UnetPlusPlus)")
     tp.add_argument("--grad-clip", action="store_true", help="honour TRAIN.GRADIENT_CLIP (the reference defines but never applies it)")
     tp.add_argument("--optimizer", choices=["Adam", "AdamW", "SGD"], default=None, help="OPTIMIZER.NAME")

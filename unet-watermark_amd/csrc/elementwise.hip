@@ -497,18 +497,7 @@ hipError_t launch_upsplit(const float* dcat, int N, int H, int W, int C0, int C1
 // VerticalFlip, RandomRotate90) are index arithmetic in the same pass.  flags[n]: bit0 hflip, bit1 vflip,
 // bits 2-3 = k of rot90 (counter-clockwise, numpy/torch convention; needs H == W), applied in albumentations'
 // pipeline order: flips first, then the rotation.
-// (PreArgs, pre_norm and make_pre_args live in uwm_kernels.h: resize_u8.hip normalises with the same function)
-__device__ __forceinline__ void aug_src(int flags, int H, int W, int y, int x, int& sy, int& sx) {
-  // output (y, x) of rot90^k(flip(img)) -> coordinates in the flipped image, then undo the flips
-  const int k = (flags >> 2) & 3;
-  int fy = y, fx = x;
-  if (k == 1) { fy = x; fx = W - 1 - y; }            // torch.rot90(a, 1)[y][x] = a[x][W-1-y]
-  else if (k == 2) { fy = H - 1 - y; fx = W - 1 - x; }
-  else if (k == 3) { fy = H - 1 - x; fx = y; }
-  if (flags & 1) fx = W - 1 - fx;
-  if (flags & 2) fy = H - 1 - fy;
-  sy = fy; sx = fx;
-}
+// (PreArgs, pre_norm, make_pre_args and the index map aug_src live in uwm_kernels.h: resize_u8.hip and augment_u8.hip use the same functions)
 __global__ void preprocess_u8_kernel(const uint8_t* __restrict__ img, int H, int W, int C, PreArgs pa,
                                      const int* __restrict__ flags, float* __restrict__ out, size_t total) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {

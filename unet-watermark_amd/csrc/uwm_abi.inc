@@ -477,6 +477,23 @@ int uwm_preprocess_mask_u8(const uint8_t* masks, int N, int H, int W, int thresh
   LCHK(launch_preprocess_mask(masks, N, H, W, threshold, flags, out, (hipStream_t)stream));
   return 0;
 }
+// ---- train-time augmentation (augment_u8.hip).  The descriptors are device memory: what can be checked without reading them is
+// checked here, before any launch; the kernels clamp the rest (they ignore rot90 where H != W and HSV shifts where C != 3)
+static_assert(sizeof(uwm_aug_desc) == sizeof(AugDesc) && sizeof(uwm_aug_desc) == 320 && offsetof(uwm_aug_desc, minv) == 16 &&
+              offsetof(uwm_aug_desc, lut) == 64 && offsetof(AugDesc, minv) == 16 && offsetof(AugDesc, lut) == 64, "uwm_aug_desc layout");
+int uwm_augment_u8(const uint8_t* images, const uint8_t* masks, const uwm_aug_desc* descs, int N, int H, int W, int C, const float* mean,
+                   const float* std, int mask_threshold, float* out_nchw, uint8_t* out_masks, uint8_t* out_u8, uwm_stream stream) {
+  if (!images || !descs || !mean || !std || !out_nchw) return fail("uwm_augment_u8: null argument");
+  if ((masks == nullptr) != (out_masks == nullptr)) return fail("uwm_augment_u8: masks and out_masks go together (both or neither)");
+  if (C < 1 || C > 4) return fail("uwm_augment_u8: C must be 1..4 (got %d)", C);
+  if (N < 1 || H < 1 || W < 1) return fail("uwm_augment_u8: N, H and W must be >= 1 (got %d, %d, %d)", N, H, W);
+  if ((long long)N * ((H + 3) / 4) > 2147483647ll) return fail("uwm_augment_u8: N * H too large for one launch (%d x %d)", N, H);
+  if ((uintptr_t)descs & 7) return fail("uwm_augment_u8: descriptors must be 8-byte aligned");
+  for (int c = 0; c < C; ++c) if (!(std[c] > 0.f)) return fail("uwm_augment_u8: std[%d] must be positive", c);
+  LCHK(launch_augment_u8(images, (const AugDesc*)descs, N, H, W, C, mean, std, out_nchw, out_u8, (hipStream_t)stream));
+  if (masks) LCHK(launch_augment_mask(masks, (const AugDesc*)descs, N, H, W, mask_threshold, out_masks, (hipStream_t)stream));
+  return 0;
+}
 int uwm_scale(float* p, long long n, float s, uwm_stream stream) {
   if (!p || n < 1) return fail("uwm_scale: bad argument");
   LCHK(launch_scale(p, (size_t)n, s, (hipStream_t)stream));

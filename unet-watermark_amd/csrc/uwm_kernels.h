@@ -381,6 +381,25 @@ static inline PreArgs make_pre_args(int C, const float* mean, const float* std) 
   for (int c = 0; c < C; ++c) { pa.mul[c] = 1.f / (255.f * std[c]); pa.add[c] = -mean[c] / std[c]; }
   return pa;
 }
+// flags -> source index of uwm_preprocess_u8 / uwm_preprocess_mask_u8 / uwm_augment_u8: ONE function, so that the three agree
+__device__ __forceinline__ void aug_src(int flags, int H, int W, int y, int x, int& sy, int& sx) {
+  // output (y, x) of rot90^k(flip(img)) -> coordinates in the flipped image, then undo the flips
+  const int k = (flags >> 2) & 3;
+  int fy = y, fx = x;
+  if (k == 1) { fy = x; fx = W - 1 - y; }            // torch.rot90(a, 1)[y][x] = a[x][W-1-y]
+  else if (k == 2) { fy = H - 1 - y; fx = W - 1 - x; }
+  else if (k == 3) { fy = H - 1 - x; fx = y; }
+  if (flags & 1) fx = W - 1 - fx;
+  if (flags & 2) fy = H - 1 - fy;
+  sy = fy; sx = fx;
+}
+// ---- train-time augmentation (augment_u8.hip; the rule: include/uwm.h)
+struct AugDesc { int flags, hue, sat, val; double minv[6]; unsigned char lut[256]; };      // = uwm_aug_desc: one per image, in DEVICE memory
+// images [N][H][W][C] -> out_f fp32 NCHW (Normalize = pre_norm) and, where out_u8 != nullptr, the augmented bytes [N][H][W][C]
+hipError_t launch_augment_u8(const uint8_t* img, const AugDesc* descs, int N, int H, int W, int C, const float* mean, const float* std,
+                             float* out_f, uint8_t* out_u8, hipStream_t st);
+// masks [N][H][W] -> nearest warp of the same descriptors, then (m > thr) as {0,1}
+hipError_t launch_augment_mask(const uint8_t* m, const AugDesc* descs, int N, int H, int W, int thr, uint8_t* out, hipStream_t st);
 // One output pixel (Y, X) of the bilinear resize of a logit plane b[h][w] (element stride ld) by sy = h / H, sx = w / W: ONE function
 // for resize_threshold_kernel (loss.hip) and resize_threshold_ragged_kernel (resize_u8.hip), so that a ragged batch's masks are the
 // uniform call's bit for bit

@@ -1,7 +1,8 @@
 """Minimal data side of the boundary: tensors with the contract of the reference's dataset
 (/root/reference/src/utils/dataset.py:113-122,332-333,389-395) — image fp32 NCHW normalised with the
-ImageNet mean/std, mask int64 {0,1} (H,W).  The reference's OpenCV/albumentations pipeline is out of scope
-(SURVEY.md §2 row 8); a synthetic generator and a plain PIL folder reader are provided."""
+ImageNet mean/std, mask int64 {0,1} (H,W).  A synthetic generator and a plain PIL folder reader are provided; the reference's
+basic albumentations recipe runs on the device (device_augment, DeviceInputPipeline: `main.py train --augment basic`), its other
+recipes' noise / blur / JPEG / CLAHE stages are out of scope."""
 from __future__ import annotations
 
 import os
@@ -185,3 +186,230 @@ def device_resize(packed: torch.Tensor, descs, size, channels: int, interp: str 
         L.check(L.lib().uwm_resize_u8(C.c_void_p(src.data_ptr()), src.numel(), C.c_void_p(dd.data_ptr()), n, int(channels), H, W,
                                       INTERP[interp], C.c_void_p(out.data_ptr()), C.c_void_p(L.stream_ptr(src.device))), ValueError)
     return out
+
+
+# ---------------------------------------------------------------------------- train-time augmentation (uwm_augment_u8, csrc/augment_u8.hip)
+AUG_DESC_DTYPE = np.dtype({"names": ["flags", "hue", "sat", "val", "minv", "lut"],
+                           "formats": ["<i4", "<i4", "<i4", "<i4", ("<f8", (6,)), ("u1", (256,))],
+                           "offsets": [0, 4, 8, 12, 16, 64], "itemsize": 320})      # = uwm_aug_desc (include/uwm.h)
+IDENTITY_MINV = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+AUG_RECIPES = ("basic",)                  # the reference's get_train_transform (dataset.py:375-387)
+_AUG_COORD_LIMIT = float(1 << 29)         # fixed-point units (1/1024 pixel): half of what the kernel clamps to
+
+
+def affine_inverse(h, w, angle, scale, dx, dy, shear=0.0):
+    """The inverse map (6 float64, dst -> src) of ShiftScaleRotate on an h x w image: the forward matrix is
+    cv2.getRotationMatrix2D((w/2 - 0.5, h/2 - 0.5), angle, scale) (degrees, counter-clockwise) with dx*w, dy*h added to its
+    translations, inverted in float64 in the order of cv2.invertAffineTransform.  shear (degrees) multiplies the linear part by an
+    x-shear [[1, tan(shear)], [0, 1]] about the same centre (0 leaves getRotationMatrix2D's entries as they are)."""
+    cx, cy = w / 2.0 - 0.5, h / 2.0 - 0.5
+    a = np.float64(angle) * (np.pi / 180.0)
+    alpha, beta = np.cos(a) * np.float64(scale), np.sin(a) * np.float64(scale)
+    m00, m01, m10, m11 = alpha, beta, -beta, alpha
+    if shear:
+        t = np.tan(np.float64(shear) * (np.pi / 180.0))
+        m01, m11 = m00 * t + m01, m10 * t + m11
+        m02, m12 = cx - m00 * cx - m01 * cy, cy - m10 * cx - m11 * cy
+    else:
+        m02, m12 = (1.0 - alpha) * cx - beta * cy, beta * cx + (1.0 - alpha) * cy
+    m02, m12 = m02 + np.float64(dx) * w, m12 + np.float64(dy) * h
+    det = m00 * m11 - m01 * m10
+    det = 1.0 / det if det != 0.0 else 0.0
+    a11, a22, a12, a21 = m11 * det, m00 * det, -m01 * det, -m10 * det
+    b1, b2 = -a11 * m02 - a12 * m12, -a21 * m02 - a22 * m12
+    return np.array([a11, a12, b1, a21, a22, b2], dtype=np.float64)
+
+
+def brightness_contrast_lut(alpha, beta):
+    """RandomBrightnessContrast's table for uint8 with brightness_by_max (the reference's transform leaves that default):
+    clip(float32(v) * float32(alpha) + float32(beta * 255), 0, 255), truncated."""
+    v = np.arange(256, dtype=np.float32) * np.float32(alpha) + np.float32(float(beta) * 255.0)
+    return np.clip(v, 0, 255).astype(np.uint8)
+
+
+def identity_aug_params(n: int) -> np.ndarray:
+    """n descriptors that change nothing: no flags, identity map, identity table, zero shifts"""
+    p = np.zeros(int(n), AUG_DESC_DTYPE)
+    p["minv"] = IDENTITY_MINV
+    p["lut"] = np.arange(256, dtype=np.uint8)
+    return p
+
+
+def sample_aug_params(n, h, w, generator=None, recipe="basic") -> np.ndarray:
+    """One uwm_aug_desc per image, drawn independently with the numbers of the reference's get_train_transform
+    (dataset.py:379-384): flips / rot90 as random_aug_flags; ShiftScaleRotate p = 0.3 (shift +-0.1, scale 1 +- 0.1, angle +-15
+    degrees); RandomBrightnessContrast p = 0.3 (limits 0.2); HueSaturationValue p = 0.3 (integer limits 10 / 20 / 10).  A stage
+    that is not drawn leaves the identity map / identity table / zero shifts.  Deterministic for a seeded torch.Generator."""
+    if recipe not in AUG_RECIPES:
+        raise ValueError(f"unknown augmentation recipe {recipe!r} (served: {', '.join(AUG_RECIPES)})")
+    n = int(n)
+    p = identity_aug_params(n)
+    flags = random_aug_flags(n, generator)
+    if h != w:
+        flags = flags & 3                                       # RandomRotate90 needs a square image
+    p["flags"] = flags.numpy()
+    u = torch.rand(n, 9, generator=generator, dtype=torch.float64).numpy()
+    hsv = torch.stack([torch.randint(-lim, lim + 1, (n,), generator=generator) for lim in (10, 20, 10)], 1).numpy()
+    span = lambda col, lim: (2.0 * u[:, col] - 1.0) * lim      # noqa: E731   uniform in [-lim, lim)
+    angle, scale, dx, dy = span(1, 15.0), 1.0 + span(2, 0.1), span(3, 0.1), span(4, 0.1)
+    alpha, beta = 1.0 + span(6, 0.2), span(7, 0.2)
+    for i in range(n):
+        if u[i, 0] < 0.3:
+            p["minv"][i] = affine_inverse(h, w, angle[i], scale[i], dx[i], dy[i])
+        if u[i, 5] < 0.3:
+            p["lut"][i] = brightness_contrast_lut(alpha[i], beta[i])
+        if u[i, 8] < 0.3:
+            p["hue"][i], p["sat"][i], p["val"][i] = hsv[i]
+    return p
+
+
+def _check_aug_params(params, n, h, w, c):
+    p = np.ascontiguousarray(params)
+    if p.dtype != AUG_DESC_DTYPE or p.ndim != 1:
+        raise TypeError("params must be a 1-D array of data.AUG_DESC_DTYPE")
+    if p.shape[0] != n:
+        raise ValueError(f"params must have one descriptor per image ({p.shape[0]} for {n} images)")
+    if h != w and bool(((p["flags"] >> 2) & 3).any()):
+        raise ValueError("rot90 needs square images")
+    if c != 3 and bool((p["hue"] != 0).any() or (p["sat"] != 0).any() or (p["val"] != 0).any()):
+        raise ValueError("HueSaturationValue shifts need 3-channel images")
+    m = p["minv"]
+    if not np.isfinite(m).all():
+        raise ValueError("affine matrix with a non-finite entry")
+    # every fixed-point term the kernel forms is largest at a corner of the image
+    reach = np.stack([np.abs(m[:, 0]) * (w - 1), np.abs(m[:, 3]) * (w - 1), np.abs(m[:, 2]), np.abs(m[:, 5]),
+                      np.abs(m[:, 1] * (h - 1) + m[:, 2]), np.abs(m[:, 4] * (h - 1) + m[:, 5])])
+    if not (reach * 1024.0 < _AUG_COORD_LIMIT).all():
+        raise ValueError("affine matrix maps the image outside the int32 fixed-point coordinate range")
+    return p
+
+
+def device_augment(images_u8: torch.Tensor, masks_u8, params, mean=IMAGENET_MEAN, std=IMAGENET_STD, return_u8=False,
+                   mask_threshold: int = 127):
+    """uint8 (N,H,W,C) images [+ uint8 (N,H,W) masks] on the HIP device, one AUG_DESC_DTYPE record per image (sample_aug_params) ->
+    (N,C,H,W) fp32 normalised images [, uint8 {0,1} masks] [, the augmented uint8 (N,H,W,C) images when return_u8]: flips / rot90 ->
+    affine warp (reflect-101 border) -> brightness / contrast table -> HueSaturationValue -> Normalize in one kernel, the mask's
+    nearest warp in a second (uwm_augment_u8; the rule is in include/uwm.h).  The descriptors are validated here, on the host: the
+    kernels only clamp.  No CPU fallback."""
+    import ctypes as C
+    from . import _lib as L
+    if images_u8.device.type != "cuda" or images_u8.dtype != torch.uint8 or images_u8.dim() != 4:
+        raise RuntimeError("device_augment needs a uint8 (N,H,W,C) tensor on a HIP device (no CPU fallback)")
+    x = images_u8.contiguous()
+    n, h, w, c = x.shape
+    if not 1 <= c <= 4:
+        raise ValueError(f"device_augment: C must be 1..4 (got {c})")
+    p = _check_aug_params(params, n, h, w, c)
+    m = None
+    if masks_u8 is not None:
+        m = masks_u8.contiguous()
+        if m.dtype != torch.uint8 or m.shape != (n, h, w) or m.device != x.device:
+            raise ValueError("masks must be uint8 (N,H,W) on the same device")
+    host = torch.from_numpy(p.view(np.uint8).reshape(-1).copy())
+    dd = (host.pin_memory() if torch.cuda.is_available() else host).to(x.device, non_blocking=True)
+    out = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
+    mo = torch.empty((n, h, w), dtype=torch.uint8, device=x.device) if m is not None else None
+    u8 = torch.empty((n, h, w, c), dtype=torch.uint8, device=x.device) if return_u8 else None
+    mean_c = (C.c_float * c)(*[float(v) for v in mean[:c]]); std_c = (C.c_float * c)(*[float(v) for v in std[:c]])
+    ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)      # noqa: E731
+    with L.on_device(x):
+        L.check(L.lib().uwm_augment_u8(ptr(x), ptr(m), ptr(dd), n, h, w, c, mean_c, std_c, int(mask_threshold), ptr(out), ptr(mo),
+                                       ptr(u8), C.c_void_p(L.stream_ptr(x.device))), ValueError)
+    res = (out,) + ((mo,) if m is not None else ()) + ((u8,) if return_u8 else ())
+    return res[0] if len(res) == 1 else res
+
+
+# ---------------------------------------------------------------------------- the device input path of `main.py train --augment basic`
+class RawFolderDataset(Dataset):
+    """FolderDataset's files, decoded and nothing else: (image uint8 (h, w, 3) RGB, mask uint8 (h, w)) numpy arrays at the file's
+    own size.  Resize, augmentation and Normalize happen on the device (DeviceInputPipeline)."""
+
+    def __init__(self, root):
+        from PIL import Image  # noqa: F401
+        self.root = root
+        wd = os.path.join(root, "watermarked")
+        self.files = sorted(f for f in os.listdir(wd) if f.lower().endswith((".png", ".jpg", ".jpeg")))
+
+    def __len__(self):
+        return len(self.files)
+
+    def __getitem__(self, i):
+        from PIL import Image
+        f = self.files[i]
+        img = np.asarray(Image.open(os.path.join(self.root, "watermarked", f)).convert("RGB"), dtype=np.uint8)
+        m = np.asarray(Image.open(os.path.join(self.root, "masks", os.path.splitext(f)[0] + ".png")).convert("L"), dtype=np.uint8)
+        return img, m
+
+
+class DeviceU8Dataset(Dataset):
+    """A dataset of (normalised fp32 image, {0,1} mask) pairs (SyntheticWatermarkDataset) converted ONCE to uint8 tensors on the
+    device: images (n, S, S, C), masks (n, S, S) in {0, 255}.  Items are indices; DeviceInputPipeline gathers them on the device."""
+
+    def __init__(self, base, device, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+        xs, ms = zip(*(base[i] for i in range(len(base))))
+        x = torch.stack(xs).to(device)
+        c = x.shape[1]
+        mean_t = torch.tensor(mean[:c], device=device).view(1, c, 1, 1); std_t = torch.tensor(std[:c], device=device).view(1, c, 1, 1)
+        self.images = ((x * std_t + mean_t) * 255.0).round_().clamp_(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+        self.masks = (torch.stack(ms).to(device) > 0).to(torch.uint8) * 255
+
+    def __len__(self):
+        return self.images.shape[0]
+
+    def __getitem__(self, i):
+        return int(i)
+
+
+def list_collate(batch):
+    """keeps the items as they are: raw images differ in size, so there is nothing to stack"""
+    return list(batch)
+
+
+class DeviceInputPipeline:
+    """Batches of a raw dataset -> what Trainer.step takes, on the device.  Raw folder items (uint8 arrays of any size) are packed
+    into persistent pinned buffers (pack_images), uploaded and resized to size x size by uwm_resize_u8 — linear for the image,
+    nearest for the mask (the reference's A.Resize); DeviceU8Dataset items are gathered.  Training batches then go through
+    device_augment with parameters drawn from `generator`, validation batches through device_preprocess (get_val_transform)."""
+
+    def __init__(self, size, device, source=None, recipe="basic", mean=IMAGENET_MEAN, std=IMAGENET_STD):
+        self.size, self.device, self.source, self.recipe = int(size), torch.device(device), source, recipe
+        self.mean, self.std = mean, std
+        self._pin, self._sent = [None, None], [None, None]
+
+    def _upload(self, arrays, slot):
+        need = sum((a.size + 3) // 4 * 4 for a in arrays)
+        buf = self._pin[slot]
+        if buf is None or buf.numel() < need:
+            buf = self._pin[slot] = torch.empty(max(need, 1 << 20), dtype=torch.uint8, pin_memory=True)
+            self._sent[slot] = torch.cuda.Event()
+        else:
+            self._sent[slot].synchronize()                   # the previous batch's upload has left the buffer
+        packed, descs, _ = pack_images(arrays, out=buf)
+        dev = packed.to(self.device, non_blocking=True)
+        self._sent[slot].record(torch.cuda.current_stream(self.device))
+        return dev, descs
+
+    def to_u8(self, items):
+        """-> (images uint8 (N, S, S, C), masks uint8 (N, S, S)) on the device"""
+        if isinstance(self.source, DeviceU8Dataset):
+            idx = torch.as_tensor([int(i) for i in items], device=self.device)
+            return self.source.images[idx], self.source.masks[idx]
+        imgs = [np.ascontiguousarray(i) for i, _ in items]; masks = [np.ascontiguousarray(m)[..., None] for _, m in items]
+        for i, (a, m) in enumerate(zip(imgs, masks)):
+            if a.shape[:2] != m.shape[:2]:
+                raise ValueError(f"image {i} is {a.shape[:2]}, its mask {m.shape[:2]}")
+        with torch.cuda.device(self.device):
+            pi, di = self._upload(imgs, 0)
+            pm, dm = self._upload(masks, 1)
+            x = device_resize(pi, di, self.size, imgs[0].shape[2], "linear")
+            m = device_resize(pm, dm, self.size, 1, "nearest")
+        return x, m.view(len(items), self.size, self.size)
+
+    def train_batch(self, items, generator=None):
+        x, m = self.to_u8(items)
+        params = sample_aug_params(x.shape[0], x.shape[1], x.shape[2], generator, self.recipe)
+        return device_augment(x, m, params, self.mean, self.std)
+
+    def val_batch(self, items):
+        x, m = self.to_u8(items)
+        return device_preprocess(x, m, None, self.mean, self.std)
