@@ -320,6 +320,65 @@ typedef struct {
 int  uwm_augment_u8(const uint8_t* images, const uint8_t* masks, const uwm_aug_desc* descs, int N, int H, int W, int C,
                     const float* mean, const float* std, int mask_threshold, float* out_nchw, uint8_t* out_masks, uint8_t* out_u8,
                     uwm_stream stream);
+/* The stages that the reference's enhanced recipe (get_enhanced_train_transform, src/utils/dataset.py:336-373) adds behind the basic
+ * ones: per image, on the uint8 image that uwm_augment_u8 forms (flips -> rot90 -> warp -> table -> HSV),
+ *     tone -> noise -> blur -> Normalize
+ * from a SECOND descriptor array, one uwm_aug_ext_desc per image in DEVICE memory (8-byte aligned).  ext == NULL is uwm_augment_u8
+ * bit for bit (workspace is then not used).  The mask does not see these stages: out_masks is uwm_augment_u8's.  Arguments and
+ * checks as uwm_augment_u8, plus workspace: device memory, 16-byte aligned, at least uwm_augment_ext_workspace_bytes(N, H, W, C)
+ * bytes (a uint8 stage image [N][H][W][C] and the CLAHE tile tables [N][64][256]).  No host synchronisation and every launch is
+ * sized from N, H, W alone, so a captured graph serves every batch of a shape — except that the FIRST call on a device copies the
+ * library's tables there synchronously and is refused inside a stream capture: call once before capturing.
+ *   After the host's parameter and table setup everything is integer work, or float32 with every product, sum and difference rounded
+ * on its own (no fused multiply-add), so the result can be checked bit for bit (tests/augment_ext_ref.py is the numpy form).
+ * rne = round half to even; reflect-101 as above.
+ *   tone = 2 (RandomGamma): v = lut2[v] on every channel; the host builds the table, trunc(((i/255.0)**gamma)*255).
+ *   tone = 1 (CLAHE, 8 x 8 tiles; OpenCV 4.x's algorithm, written from knowledge of the source, NOT run against cv2).  C = 1: on the
+ * plane; C = 3: on the lightness plane L8 below; skipped where C is 2 or 4 or H < 8 or W < 8.  The plane is extended at the bottom
+ * and the right by reflect-101 to multiples of 8; tileH = Hp/8, tileW = Wp/8, area = tileH*tileW.  Per tile: 256-bin histogram over
+ * the padded tile; with clip = max(clahe_clip, 1): excess = sum max(h - clip, 0), h = min(h, clip) + excess/256, and the residual
+ * excess%256 goes one to a bin at bins 0, step, 2 step, ... (step = max(256/residual, 1)) until spent;
+ * lut[i] = saturate(rne(float(cumsum[i]) * (255.0f/area))).  Per pixel: tyf = float(y) * (1.0f/tileH) - 0.5f, ty1 = floor(tyf),
+ * ya = tyf - ty1, ty1 and ty1 + 1 clamped to 0..7, x likewise;
+ * res = (lut11[v]*(1-xa) + lut12[v]*xa)*(1-ya) + (lut21[v]*(1-xa) + lut22[v]*xa)*ya, then saturate(rne(res)).  The host passes
+ * clahe_clip = max(1, int(clipLimit * area / 256)) (data.clahe_clip_limit).
+ *   Lightness (C = 3) is THIS PROJECT'S OWN integer rule (OpenCV's 8-bit Lab code is not restated).  With the tables of
+ * uwm_aug_lab_tables — LIN[256] = rne(16384 * srgb_to_linear(v/255)); F[i] = rne(32768 * f(i/16384)), f(t) = cbrt(t) above
+ * 0.008856, else 7.787 t + 16/116; FINV[j] = rne(16384 * f^-1(j/8192)) (f^3 above 0.206893, else (f - 16/116)/7.787, not below 0);
+ * GAM[i] = rne(255 * linear_to_srgb(i/16384)) — and OpenCV's D65 matrix over the white point in 12 fraction bits:
+ *     X = (1777 r + 1541 g + 778 b + 2048) >> 12, Y = (871 r + 2929 g + 296 b + 2048) >> 12, Z = (73 r + 448 g + 3575 b + 2048) >> 12
+ *     (r, g, b = LIN of the bytes; every row sums to 4096, so a grey has X = Y = Z), fx = F[X], fy = F[Y], fz = F[Z],
+ *     L8 = clip((2 * (116 fy - 524288) * 255 + 3276800) / 6553600)                          = round(L * 255 / 100)
+ *   back, with the new L8: fy' = (65536 * (100 L8 + 4080) + 29580) / 59160, fx' = fy' + (fx - fy), fz' = fy' - (fy - fz),
+ *     t = FINV[(clip(f', 0, 65535) + 2) >> 2], linear = clip((row . t + 2048) >> 12, 0, 16384) with the rows
+ *     (12615, -6296, -2223), (-3773, 7684, 185), (217, -836, 4715), byte = GAM[linear].
+ *   noise (GaussNoise; numpy's generator is not reproduced, only the distribution): noise_sigma = sigma * 256 (0 = off, clamped to
+ * 16383), per byte counter = (y*W + x)*4 + c, z = seed + (counter + 1) * 0x9E3779B97F4A7C15, then splitmix64's finaliser
+ * (z ^= z >> 30, *= 0xBF58476D1CE4E5B9, z ^= z >> 27, *= 0x94D049BB133111EB, z ^= z >> 31); r = z >> 40, k = r >> 14, fr = r & 16383,
+ * normal = (QN[k] * (16384 - fr) + QN[k+1] * fr) >> 12 with QN[i] = rne(4096 * Phi^-1(i/1024)) and the two ends at
+ * Phi^-1(1/4096) = -+3.4871, where the tails stop (the table's distribution has variance 0.99908);
+ * out = clip(v + ((normal * noise_sigma) >> 22), 0, 255) = clip(floor(v + g)).
+ *   blur, 3 x 3 correlation over the pre-blur values (tone and noise of the neighbours, reflect-101): blur = 2 (Gaussian, sigma 0):
+ * weights [1 2 1] x [1 2 1], out = (sum + 8) >> 4; blur = 1 (motion): weights blur_w[3*i + j] != 0 for the tap (y + i - 1, x + j - 1),
+ * out = sum / count rounded half to even; no tap set = no blur.  The host rasterises a line between two distinct points of the 3 x 3
+ * grid: both end points and, between end points two apart, the middle, a half rounded up (the project's rasterisation).
+ *   The kernels only clamp: unknown tone / blur values are "none", clahe_clip < 1 is 1, noise_sigma is clamped. */
+typedef struct {
+  int tone;                  /* 0 none, 1 CLAHE, 2 table lut2 */
+  int clahe_clip;            /* CLAHE's integer clip limit per bin, >= 1 */
+  int noise_sigma;           /* GaussNoise sigma * 256; 0 = off */
+  int blur;                  /* 0 none, 1 motion (blur_w), 2 Gaussian */
+  unsigned char blur_w[9];   /* the motion kernel's 0/1 taps, row by row */
+  unsigned long long seed;   /* of the noise (offset 32) */
+  unsigned char lut2[256];   /* tone = 2: per-value table (offset 40) */
+} uwm_aug_ext_desc;          /* 296 bytes */
+size_t uwm_augment_ext_workspace_bytes(int N, int H, int W, int C);      /* 0 (and an error message) for a bad shape */
+int  uwm_augment_ext_u8(const uint8_t* images, const uint8_t* masks, const uwm_aug_desc* descs, const uwm_aug_ext_desc* ext, int N,
+                        int H, int W, int C, const float* mean, const float* std, int mask_threshold, void* workspace,
+                        size_t workspace_bytes, float* out_nchw, uint8_t* out_masks, uint8_t* out_u8, uwm_stream stream);
+/* The host's tables of the rule above, built at first use: which = 0 LIN (int), 1 F (unsigned short), 2 FINV (int), 3 GAM
+ * (unsigned char), 4 QN (int). */
+int  uwm_aug_lab_tables(int which, const void** data, int* count, int* elem_bytes);
 /* 3x3/stride-1 convolutions (forward, dgrad and weight gradient) run as Winograd F(2x2,3x3) on the fp32 MFMA path by
  * default (2.25x fewer multiplies, results within a few fp32 ulps of the direct form); mode 0 selects the direct
  * kernels everywhere; 2 (tests) prefers the 512-thread Winograd variant wherever its shape rules allow, whatever the

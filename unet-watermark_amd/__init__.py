@@ -16,4 +16,6 @@ from .postprocess import optimize_mask, morphology, connected_components, struct
 from .data import device_preprocess, aug_flags, random_aug_flags, pack_images, device_resize  # noqa: F401,E402
 from .data import (device_augment, sample_aug_params, identity_aug_params, affine_inverse, brightness_contrast_lut,  # noqa: F401,E402
                    AUG_DESC_DTYPE)
+from .data import (sample_aug_recipe, identity_aug_ext_params, gamma_lut, motion_kernel, clahe_clip_limit,  # noqa: F401,E402
+                   AUG_EXT_DTYPE)
 from .train import FusedAdam, FusedAdamW  # noqa: F401,E402

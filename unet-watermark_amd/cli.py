@@ -18,7 +18,7 @@ from torch.utils.data.distributed import DistributedSampler
 
 from .checkpoint import load_checkpoint, save_checkpoint
 from .config import get_cfg_defaults, update_config
-from .data import (AUG_RECIPES, DeviceInputPipeline, DeviceU8Dataset, FolderDataset, RawFolderDataset, SyntheticWatermarkDataset,
+from .data import (AUG_RECIPES, AUG_RECIPES_EXT, DeviceInputPipeline, DeviceU8Dataset, FolderDataset, RawFolderDataset, SyntheticWatermarkDataset,
                    list_collate)
 from .losses import get_loss_function
 from .metrics import logits_metrics
@@ -36,6 +36,27 @@ def _loss_weights(cfg):
     if name == "CombinedLoss":
         return float(cfg.LOSS.DICE_WEIGHT), float(cfg.LOSS.BCE_WEIGHT)
     raise ValueError(f"unsupported LOSS.NAME {name!r} (DiceLoss | BCEWithLogitsLoss | CombinedLoss)")
+
+
+def _served_recipe(augment, cfg):
+    """--augment and DATA.AUGMENTATION_TYPE -> (the recipe the device serves, or 'none'; a note for the 'serving' line).  'basic'
+    serves the basic recipe whatever the config asks for, and says so; 'config' serves the recipe that DATA.AUGMENTATION_TYPE names
+    as the reference chooses it (src/utils/dataset.py:417-427: 'transparent_watermark', 'enhanced', anything else is basic) and
+    refuses 'transparent_watermark', whose ImageCompression stage (a JPEG round trip) is not built."""
+    asked = cfg.DATA.get("AUGMENTATION_TYPE", None)
+    if augment == "none":
+        return "none", ""
+    if augment == "config":
+        if asked == "transparent_watermark":
+            raise ValueError("--augment config: DATA.AUGMENTATION_TYPE='transparent_watermark' is not served: its ImageCompression stage "
+                             "(a JPEG round trip) is not built; --augmentation-type enhanced or basic is")
+        if asked in AUG_RECIPES_EXT:
+            return asked, f" (DATA.AUGMENTATION_TYPE={asked!r})"
+        return "basic", f" (DATA.AUGMENTATION_TYPE={asked!r} selects the basic recipe, as in the reference)"
+    if augment not in AUG_RECIPES:
+        raise ValueError(f"--augment {augment!r}: this build serves 'none', 'config' and {AUG_RECIPES}")
+    note = "" if asked == augment else f" (DATA.AUGMENTATION_TYPE={asked!r} is not served; its extra stages are NOT applied)"
+    return augment, note
 
 
 def _datasets(cfg, synthetic, device_input=None):
@@ -147,6 +168,9 @@ def train_command(args):
         cfg.OPTIMIZER.NAME = args.optimizer
     if getattr(args, "lr_scheduler", None):
         cfg.OPTIMIZER.LR_SCHEDULER = args.lr_scheduler
+    if getattr(args, "augmentation_type", None):
+        cfg.DATA.AUGMENTATION_TYPE = args.augmentation_type
+    augment, aug_note = _served_recipe(getattr(args, "augment", None) or "none", cfg)      # refusals come before any device work
     if getattr(args, "checkpoint_dir", None):
         cfg.TRAIN.CHECKPOINT_DIR = args.checkpoint_dir
     if cfg.MODEL.NAME not in ("Unet", "UnetPlusPlus"):
@@ -197,17 +221,12 @@ def train_command(args):
             broadcast_model(model, 0)
     stopper = (EarlyStopping(patience=int(cfg.TRAIN.EARLY_STOPPING_PATIENCE), restore_best_weights=True)
                if cfg.TRAIN.USE_EARLY_STOPPING else None)       # /root/reference/src/train.py:362-368
-    augment = getattr(args, "augment", None) or "none"
-    if augment not in ("none",) + AUG_RECIPES:
-        raise ValueError(f"--augment {augment!r}: this build serves 'none' and {AUG_RECIPES}")
     pipe = None
     tr_set, va_set = _datasets(cfg, args.synthetic, device if augment != "none" else None)
     if augment != "none":
         pipe = DeviceInputPipeline(cfg.DATA.IMG_SIZE, device, source=tr_set.dataset, recipe=augment)
         if rank == 0:
-            asked = cfg.DATA.get("AUGMENTATION_TYPE", None)
-            note = "" if asked == augment else f" (DATA.AUGMENTATION_TYPE={asked!r} is not served; its extra stages are NOT applied)"
-            print(f"augmentation: serving the {augment!r} recipe on the device{note}", flush=True)
+            print(f"augmentation: serving the {augment!r} recipe on the device{aug_note}", flush=True)
     bs = int(cfg.TRAIN.BATCH_SIZE)
     sampler = DistributedSampler(tr_set, world, rank, shuffle=True, seed=int(cfg.DATA.SEED)) if world > 1 else None
     # the device input path gets raw items from the workers (uint8 arrays of any size, or indices): nothing to stack or pin
@@ -330,10 +349,15 @@ def build_parser():
     tp.add_argument("--encoder", type=str); tp.add_argument("--img-size", type=int)
     tp.add_argument("--synthetic", type=int, default=0, help="train on N synthetic images instead of DATA.ROOT_DIR")
     tp.add_argument("--workers", type=int, default=2)
-    tp.add_argument("--augment", choices=["none", "basic"], default="none",
+    tp.add_argument("--augment", choices=["none", "basic", "config"], default="none",
                     help="'basic' = the device input path: workers only decode, the device resizes (cv2's rule), augments with the "
                          "reference's basic recipe (flips, rot90, ShiftScaleRotate, RandomBrightnessContrast, HueSaturationValue) and "
-                         "normalises; validation is resized and normalised only.  'none' (default) = host-prepared tensors, no augmentation")
+                         "normalises; validation is resized and normalised only.  'config' = the same path with the recipe that "
+                         "DATA.AUGMENTATION_TYPE names: 'enhanced' adds CLAHE / gamma, Gaussian noise and motion / Gaussian blur; "
+                         "'transparent_watermark' is refused (its JPEG stage, ImageCompression, is not built).  'none' (default) = "
+                         "host-prepared tensors, no augmentation")
+    tp.add_argument("--augmentation-type", choices=["basic", "enhanced", "transparent_watermark"], default=None,
+                    help="DATA.AUGMENTATION_TYPE (read by --augment config)")
     tp.add_argument("--model", choices=["Unet", "UnetPlusPlus"], default=None, help="MODEL.NAME (reference default: UnetPlusPlus)")
     tp.add_argument("--grad-clip", action="store_true", help="honour TRAIN.GRADIENT_CLIP (the reference defines but never applies it)")
     tp.add_argument("--optimizer", choices=["Adam", "AdamW", "SGD"], default=None, help="OPTIMIZER.NAME")

@@ -494,6 +494,43 @@ int uwm_augment_u8(const uint8_t* images, const uint8_t* masks, const uwm_aug_de
   if (masks) LCHK(launch_augment_mask(masks, (const AugDesc*)descs, N, H, W, mask_threshold, out_masks, (hipStream_t)stream));
   return 0;
 }
+// ---- the enhanced recipe's stages behind uwm_augment_u8 (augment_ext_u8.hip): the same checks, plus the workspace
+static_assert(sizeof(uwm_aug_ext_desc) == sizeof(AugExtDesc) && sizeof(uwm_aug_ext_desc) == 296 && offsetof(uwm_aug_ext_desc, blur_w) == 16 &&
+              offsetof(uwm_aug_ext_desc, seed) == 32 && offsetof(uwm_aug_ext_desc, lut2) == 40 && offsetof(AugExtDesc, blur_w) == 16 &&
+              offsetof(AugExtDesc, seed) == 32 && offsetof(AugExtDesc, lut2) == 40, "uwm_aug_ext_desc layout");
+size_t uwm_augment_ext_workspace_bytes(int N, int H, int W, int C) {
+  if (N < 1 || H < 1 || W < 1 || C < 1 || C > 4) { fail("uwm_augment_ext_workspace_bytes: bad shape %d x %d x %d x %d", N, H, W, C); return 0; }
+  return aug_ext_workspace_bytes(N, H, W, C);
+}
+int uwm_augment_ext_u8(const uint8_t* images, const uint8_t* masks, const uwm_aug_desc* descs, const uwm_aug_ext_desc* ext, int N, int H, int W,
+                       int C, const float* mean, const float* std, int mask_threshold, void* workspace, size_t workspace_bytes,
+                       float* out_nchw, uint8_t* out_masks, uint8_t* out_u8, uwm_stream stream) {
+  if (!images || !descs || !mean || !std || !out_nchw) return fail("uwm_augment_ext_u8: null argument");
+  if ((masks == nullptr) != (out_masks == nullptr)) return fail("uwm_augment_ext_u8: masks and out_masks go together (both or neither)");
+  if (C < 1 || C > 4) return fail("uwm_augment_ext_u8: C must be 1..4 (got %d)", C);
+  if (N < 1 || H < 1 || W < 1) return fail("uwm_augment_ext_u8: N, H and W must be >= 1 (got %d, %d, %d)", N, H, W);
+  if ((long long)N * ((H + 3) / 4) > 2147483647ll || (long long)N * 64 > 2147483647ll)
+    return fail("uwm_augment_ext_u8: N * H too large for one launch (%d x %d)", N, H);
+  if (((uintptr_t)descs & 7) || ((uintptr_t)ext & 7)) return fail("uwm_augment_ext_u8: descriptors must be 8-byte aligned");
+  for (int c = 0; c < C; ++c) if (!(std[c] > 0.f)) return fail("uwm_augment_ext_u8: std[%d] must be positive", c);
+  if (ext) {
+    if (!workspace) return fail("uwm_augment_ext_u8: null workspace");
+    if ((uintptr_t)workspace & 15) return fail("uwm_augment_ext_u8: workspace must be 16-byte aligned");
+    const size_t need = aug_ext_workspace_bytes(N, H, W, C);
+    if (workspace_bytes < need) return fail("uwm_augment_ext_u8: workspace too small (%zu bytes, need %zu)", workspace_bytes, need);
+  }
+  const hipError_t e = launch_augment_ext(images, masks, (const AugDesc*)descs, (const AugExtDesc*)ext, N, H, W, C, mean, std, mask_threshold,
+                                          workspace, workspace_bytes, out_nchw, out_masks, out_u8, (hipStream_t)stream);
+  if (e == hipErrorStreamCaptureUnsupported)
+    return fail("uwm_augment_ext_u8: the first call on a device uploads the tables and cannot be captured; call it once before capturing");
+  LCHK(e);
+  return 0;
+}
+int uwm_aug_lab_tables(int which, const void** data, int* count, int* elem_bytes) {
+  if (!data || !count || !elem_bytes) return fail("uwm_aug_lab_tables: null argument");
+  if (!aug_ext_host_table(which, data, count, elem_bytes)) return fail("uwm_aug_lab_tables: which must be 0..4 (got %d)", which);
+  return 0;
+}
 int uwm_scale(float* p, long long n, float s, uwm_stream stream) {
   if (!p || n < 1) return fail("uwm_scale: bad argument");
   LCHK(launch_scale(p, (size_t)n, s, (hipStream_t)stream));

@@ -400,6 +400,14 @@ hipError_t launch_augment_u8(const uint8_t* img, const AugDesc* descs, int N, in
                              float* out_f, uint8_t* out_u8, hipStream_t st);
 // masks [N][H][W] -> nearest warp of the same descriptors, then (m > thr) as {0,1}
 hipError_t launch_augment_mask(const uint8_t* m, const AugDesc* descs, int N, int H, int W, int thr, uint8_t* out, hipStream_t st);
+// ---- the enhanced recipe's stages behind the basic ones (augment_ext_u8.hip; the rule: include/uwm.h)
+struct AugExtDesc { int tone, clahe_clip, noise_sigma, blur; unsigned char blur_w[9]; unsigned long long seed; unsigned char lut2[256]; };   // = uwm_aug_ext_desc
+size_t aug_ext_workspace_bytes(int N, int H, int W, int C);      // 0 for a bad shape
+// ext == nullptr: launch_augment_u8 + launch_augment_mask as they are.  Otherwise the stage pass, the CLAHE tile tables and the apply pass.
+hipError_t launch_augment_ext(const uint8_t* img, const uint8_t* masks, const AugDesc* descs, const AugExtDesc* ext, int N, int H, int W, int C,
+                              const float* mean, const float* std, int thr, void* workspace, size_t workspace_bytes, float* out_f,
+                              uint8_t* out_masks, uint8_t* out_u8, hipStream_t st);
+bool aug_ext_host_table(int which, const void** data, int* count, int* elem_bytes);      // the host's tables (uwm_aug_lab_tables)
 // One output pixel (Y, X) of the bilinear resize of a logit plane b[h][w] (element stride ld) by sy = h / H, sx = w / W: ONE function
 // for resize_threshold_kernel (loss.hip) and resize_threshold_ragged_kernel (resize_u8.hip), so that a ragged batch's masks are the
 // uniform call's bit for bit

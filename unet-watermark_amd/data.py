@@ -1,8 +1,8 @@
 """Minimal data side of the boundary: tensors with the contract of the reference's dataset
 (/root/reference/src/utils/dataset.py:113-122,332-333,389-395) — image fp32 NCHW normalised with the
 ImageNet mean/std, mask int64 {0,1} (H,W).  A synthetic generator and a plain PIL folder reader are provided; the reference's
-basic albumentations recipe runs on the device (device_augment, DeviceInputPipeline: `main.py train --augment basic`), its other
-recipes' noise / blur / JPEG / CLAHE stages are out of scope."""
+basic and enhanced albumentations recipes run on the device (device_augment, DeviceInputPipeline: `main.py train --augment basic` /
+`--augment config`); the transparent_watermark recipe's JPEG round trip (ImageCompression) is not built."""
 from __future__ import annotations
 
 import os
@@ -285,12 +285,14 @@ def _check_aug_params(params, n, h, w, c):
 
 
 def device_augment(images_u8: torch.Tensor, masks_u8, params, mean=IMAGENET_MEAN, std=IMAGENET_STD, return_u8=False,
-                   mask_threshold: int = 127):
+                   mask_threshold: int = 127, ext=None):
     """uint8 (N,H,W,C) images [+ uint8 (N,H,W) masks] on the HIP device, one AUG_DESC_DTYPE record per image (sample_aug_params) ->
     (N,C,H,W) fp32 normalised images [, uint8 {0,1} masks] [, the augmented uint8 (N,H,W,C) images when return_u8]: flips / rot90 ->
     affine warp (reflect-101 border) -> brightness / contrast table -> HueSaturationValue -> Normalize in one kernel, the mask's
-    nearest warp in a second (uwm_augment_u8; the rule is in include/uwm.h).  The descriptors are validated here, on the host: the
-    kernels only clamp.  No CPU fallback."""
+    nearest warp in a second (uwm_augment_u8; the rule is in include/uwm.h).  ext: one AUG_EXT_DTYPE record per image
+    (sample_aug_recipe) adds tone (CLAHE / gamma) -> noise -> blur in front of Normalize (uwm_augment_ext_u8; its workspace is
+    allocated once per device and reused); None (default) is the call as it was.  The descriptors are validated here, on the host:
+    the kernels only clamp.  No CPU fallback."""
     import ctypes as C
     from . import _lib as L
     if images_u8.device.type != "cuda" or images_u8.dtype != torch.uint8 or images_u8.dim() != 4:
@@ -300,6 +302,7 @@ def device_augment(images_u8: torch.Tensor, masks_u8, params, mean=IMAGENET_MEAN
     if not 1 <= c <= 4:
         raise ValueError(f"device_augment: C must be 1..4 (got {c})")
     p = _check_aug_params(params, n, h, w, c)
+    ex = _check_aug_ext_params(ext, n, h, w, c) if ext is not None else None
     m = None
     if masks_u8 is not None:
         m = masks_u8.contiguous()
@@ -313,10 +316,151 @@ def device_augment(images_u8: torch.Tensor, masks_u8, params, mean=IMAGENET_MEAN
     mean_c = (C.c_float * c)(*[float(v) for v in mean[:c]]); std_c = (C.c_float * c)(*[float(v) for v in std[:c]])
     ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)      # noqa: E731
     with L.on_device(x):
-        L.check(L.lib().uwm_augment_u8(ptr(x), ptr(m), ptr(dd), n, h, w, c, mean_c, std_c, int(mask_threshold), ptr(out), ptr(mo),
-                                       ptr(u8), C.c_void_p(L.stream_ptr(x.device))), ValueError)
+        if ex is None:
+            L.check(L.lib().uwm_augment_u8(ptr(x), ptr(m), ptr(dd), n, h, w, c, mean_c, std_c, int(mask_threshold), ptr(out), ptr(mo),
+                                           ptr(u8), C.c_void_p(L.stream_ptr(x.device))), ValueError)
+        else:
+            ehost = torch.from_numpy(ex.view(np.uint8).reshape(-1).copy())
+            ed = (ehost.pin_memory() if torch.cuda.is_available() else ehost).to(x.device, non_blocking=True)
+            need = int(L.lib().uwm_augment_ext_workspace_bytes(n, h, w, c))
+            ws = _ext_workspace(x.device, need)
+            L.check(L.lib().uwm_augment_ext_u8(ptr(x), ptr(m), ptr(dd), ptr(ed), n, h, w, c, mean_c, std_c, int(mask_threshold), ptr(ws),
+                                               ws.numel(), ptr(out), ptr(mo), ptr(u8), C.c_void_p(L.stream_ptr(x.device))), ValueError)
     res = (out,) + ((mo,) if m is not None else ()) + ((u8,) if return_u8 else ())
     return res[0] if len(res) == 1 else res
+
+
+# ---------------------------------------------------------------------------- the enhanced recipe's stages (uwm_augment_ext_u8, csrc/augment_ext_u8.hip)
+AUG_EXT_DTYPE = np.dtype({"names": ["tone", "clahe_clip", "noise_sigma", "blur", "blur_w", "seed", "lut2"],
+                          "formats": ["<i4", "<i4", "<i4", "<i4", ("u1", (9,)), "<u8", ("u1", (256,))],
+                          "offsets": [0, 4, 8, 12, 16, 32, 40], "itemsize": 296})      # = uwm_aug_ext_desc (include/uwm.h)
+TONE_NONE, TONE_CLAHE, TONE_TABLE = 0, 1, 2
+BLUR_NONE, BLUR_MOTION, BLUR_GAUSS = 0, 1, 2
+NOISE_SIGMA_MAX = 16383                   # noise_sigma is sigma * 256; the kernel clamps to this
+AUG_RECIPES_EXT = ("basic", "enhanced")   # what sample_aug_recipe serves (get_train_transform, get_enhanced_train_transform)
+
+
+def identity_aug_ext_params(n: int) -> np.ndarray:
+    """n ext descriptors that change nothing: no tone stage, no noise, no blur (clahe_clip 1 and an identity lut2, both unused)"""
+    e = np.zeros(int(n), AUG_EXT_DTYPE)
+    e["clahe_clip"] = 1
+    e["lut2"] = np.arange(256, dtype=np.uint8)
+    return e
+
+
+def gamma_lut(gamma):
+    """RandomGamma's table for uint8: trunc(((i / 255) ** gamma) * 255) in float64 (gamma = gamma_limit / 100)"""
+    return ((np.arange(256, dtype=np.float64) / 255.0) ** np.float64(gamma) * 255.0).astype(np.uint8)
+
+
+def motion_kernel(p0, p1) -> np.ndarray:
+    """MotionBlur(blur_limit=3): the 0/1 taps (9 bytes, row by row) of the line between two DISTINCT points (x, y) of the 3 x 3
+    grid: both end points and, between end points two apart, the middle point, a half rounded up (2 or 3 taps)."""
+    (x0, y0), (x1, y1) = (int(p0[0]), int(p0[1])), (int(p1[0]), int(p1[1]))
+    if (x0, y0) == (x1, y1) or not all(0 <= v <= 2 for v in (x0, y0, x1, y1)):
+        raise ValueError("motion_kernel needs two distinct points of the 3 x 3 grid")
+    k = np.zeros(9, dtype=np.uint8)
+    k[3 * y0 + x0] = k[3 * y1 + x1] = 1
+    if max(abs(x1 - x0), abs(y1 - y0)) == 2:
+        k[3 * ((y0 + y1 + 1) // 2) + (x0 + x1 + 1) // 2] = 1
+    return k
+
+
+def clahe_clip_limit(clip, h, w) -> int:
+    """OpenCV's integer clip limit per histogram bin for an h x w plane on 8 x 8 tiles: max(1, int(clip * tileArea / 256)), the
+    tiles those of the plane padded to multiples of 8"""
+    area = ((int(h) + 7) // 8) * ((int(w) + 7) // 8)
+    return max(1, int(float(clip) * area / 256.0))
+
+
+def sample_aug_recipe(n, h, w, generator=None, recipe="basic"):
+    """-> (params, ext): one uwm_aug_desc and (for 'enhanced') one uwm_aug_ext_desc per image.  'basic' is sample_aug_params, byte for
+    byte, with ext = None.  'enhanced' carries the numbers of the reference's get_enhanced_train_transform (dataset.py:336-373):
+    flips / rot90 as random_aug_flags; ShiftScaleRotate p = 0.3 (shift +-0.1, scale 1 +- 0.1, angle +-15 degrees), as basic;
+    RandomBrightnessContrast p = 0.6 (limits 0.25); HueSaturationValue p = 0.4 (12 / 25 / 15); OneOf(CLAHE clip 1..2, RandomGamma
+    0.8..1.2) p = 0.3; GaussNoise var 5..30 p = 0.2; OneOf(MotionBlur 3, GaussianBlur 3) p = 0.15.  A OneOf picks one member with
+    probability 1/2 each and always applies it.  A stage that is not drawn is an exact identity.  Deterministic for a seeded
+    torch.Generator."""
+    if recipe == "basic":
+        return sample_aug_params(n, h, w, generator, "basic"), None
+    if recipe != "enhanced":
+        raise ValueError(f"unknown augmentation recipe {recipe!r} (served: {', '.join(AUG_RECIPES_EXT)})")
+    n = int(n)
+    p, e = identity_aug_params(n), identity_aug_ext_params(n)
+    flags = random_aug_flags(n, generator)
+    if h != w:
+        flags = flags & 3
+    p["flags"] = flags.numpy()
+    u = torch.rand(n, 17, generator=generator, dtype=torch.float64).numpy()
+    hsv = torch.stack([torch.randint(-lim, lim + 1, (n,), generator=generator) for lim in (12, 25, 15)], 1).numpy()
+    seeds = torch.randint(0, 1 << 62, (n,), generator=generator).numpy().astype(np.uint64)
+    ends = torch.stack([torch.randint(0, 9, (n,), generator=generator), torch.randint(1, 9, (n,), generator=generator)], 1).numpy()
+    span = lambda col, lim: (2.0 * u[:, col] - 1.0) * lim      # noqa: E731   uniform in [-lim, lim)
+    angle, scale, dx, dy = span(1, 15.0), 1.0 + span(2, 0.1), span(3, 0.1), span(4, 0.1)
+    alpha, beta = 1.0 + span(6, 0.25), span(7, 0.25)
+    for i in range(n):
+        if u[i, 0] < 0.3:
+            p["minv"][i] = affine_inverse(h, w, angle[i], scale[i], dx[i], dy[i])
+        if u[i, 5] < 0.6:
+            p["lut"][i] = brightness_contrast_lut(alpha[i], beta[i])
+        if u[i, 8] < 0.4:
+            p["hue"][i], p["sat"][i], p["val"][i] = hsv[i]
+        if u[i, 9] < 0.3:
+            if u[i, 10] < 0.5:
+                e["tone"][i] = TONE_CLAHE
+                e["clahe_clip"][i] = clahe_clip_limit(1.0 + u[i, 11], h, w)
+            else:
+                e["tone"][i] = TONE_TABLE
+                e["lut2"][i] = gamma_lut(0.8 + 0.4 * u[i, 12])
+        if u[i, 13] < 0.2:
+            e["noise_sigma"][i] = int(round(np.sqrt(5.0 + 25.0 * u[i, 14]) * 256.0))
+            e["seed"][i] = seeds[i]
+        if u[i, 15] < 0.15:
+            if u[i, 16] < 0.5:
+                a, b = int(ends[i, 0]), int((ends[i, 0] + ends[i, 1]) % 9)      # two distinct cells of the grid
+                e["blur"][i] = BLUR_MOTION
+                e["blur_w"][i] = motion_kernel((a % 3, a // 3), (b % 3, b // 3))
+            else:
+                e["blur"][i] = BLUR_GAUSS
+    return p, e
+
+
+def _check_aug_ext_params(ext, n, h, w, c):
+    """the host's refusals for an ext descriptor array: what the kernels would only clamp or skip"""
+    e = np.ascontiguousarray(ext)
+    if e.dtype != AUG_EXT_DTYPE or e.ndim != 1:
+        raise TypeError("ext must be a 1-D array of data.AUG_EXT_DTYPE")
+    if e.shape[0] != n:
+        raise ValueError(f"ext must have one descriptor per image ({e.shape[0]} for {n} images)")
+    if not np.isin(e["tone"], (TONE_NONE, TONE_CLAHE, TONE_TABLE)).all():
+        raise ValueError("unknown tone stage (0 none, 1 CLAHE, 2 table)")
+    if not np.isin(e["blur"], (BLUR_NONE, BLUR_MOTION, BLUR_GAUSS)).all():
+        raise ValueError("unknown blur stage (0 none, 1 motion, 2 gaussian)")
+    clahe = e["tone"] == TONE_CLAHE
+    if clahe.any():
+        if c not in (1, 3):
+            raise ValueError("CLAHE needs 1-channel or 3-channel images")
+        if h < 8 or w < 8:
+            raise ValueError("CLAHE needs H and W >= 8 (8 x 8 tiles)")
+        if (e["clahe_clip"][clahe] < 1).any():
+            raise ValueError("CLAHE clip limit must be >= 1")
+    if ((e["noise_sigma"] < 0) | (e["noise_sigma"] > NOISE_SIGMA_MAX)).any():
+        raise ValueError(f"noise_sigma (sigma * 256) must be 0..{NOISE_SIGMA_MAX}")
+    motion = e["blur"] == BLUR_MOTION
+    if motion.any() and (e["blur_w"][motion] != 0).sum(1).min() == 0:
+        raise ValueError("empty motion kernel (no tap set)")
+    return e
+
+
+_EXT_WORKSPACE = {}
+
+
+def _ext_workspace(device, nbytes):
+    """one workspace per device, grown when a larger one is needed (calls on one stream are ordered, so it is reused)"""
+    ws = _EXT_WORKSPACE.get(device)
+    if ws is None or ws.numel() < nbytes:
+        ws = _EXT_WORKSPACE[device] = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+    return ws
 
 
 # ---------------------------------------------------------------------------- the device input path of `main.py train --augment basic`
@@ -407,8 +551,8 @@ class DeviceInputPipeline:
 
     def train_batch(self, items, generator=None):
         x, m = self.to_u8(items)
-        params = sample_aug_params(x.shape[0], x.shape[1], x.shape[2], generator, self.recipe)
-        return device_augment(x, m, params, self.mean, self.std)
+        params, ext = sample_aug_recipe(x.shape[0], x.shape[1], x.shape[2], generator, self.recipe)
+        return device_augment(x, m, params, self.mean, self.std, ext=ext)
 
     def val_batch(self, items):
         x, m = self.to_u8(items)
