@@ -379,6 +379,44 @@ int  uwm_augment_ext_u8(const uint8_t* images, const uint8_t* masks, const uwm_a
 /* The host's tables of the rule above, built at first use: which = 0 LIN (int), 1 F (unsigned short), 2 FINV (int), 3 GAM
  * (unsigned char), 4 QN (int). */
 int  uwm_aug_lab_tables(int which, const void** data, int* count, int* elem_bytes);
+/* A.ImageCompression of the reference's transparent_watermark recipe (get_transparent_watermark_transform, src/utils/dataset.py:298-334)
+ * in front of Normalize: what a baseline JPEG encode + decode at quality q does to the pixels.  Huffman coding is lossless, so this is
+ * libjpeg's default path without it (what cv2.imencode / imdecode and Pillow run, through libjpeg-turbo): 4:2:0 sampling, the "islow"
+ * integer DCT, "fancy" up-sampling.  images uint8 [N][H][W][3] RGB, H % 16 == 0 and W % 16 == 0; quality: DEVICE int[N] (4-byte aligned),
+ * 0 = the image passes through unchanged (and is still normalised), else 1..100 (the kernels clamp to 0..100; a host wrapper should
+ * refuse other values).  out_nchw (fp32 [N][3][H][W], 16-byte aligned) and out_u8 ([N][H][W][3], 4-byte aligned like images): either
+ * may be NULL, not both;
+ * out_nchw = uwm_preprocess_u8(out_u8, flags = NULL) bit for bit.  workspace: device memory, 16-byte aligned, at least
+ * uwm_jpeg_workspace_bytes(N, H, W) bytes (the reconstructed Y plane [N][H][W] and Cb, Cr planes [N][H/2][W/2]).  mean / std are host
+ * pointers (3 values).  Two launches on the caller's stream, sized from N, H, W alone, no host synchronisation: capturable.
+ *   The rule (tests/jpeg_ref.py is the numpy form, held to Pillow bit for bit).  All arithmetic is signed 32-bit integer, >> is an
+ * arithmetic shift, D(x, n) = (x + (1 << (n-1))) >> n.
+ *   tables: T = Annex K luminance (for Y) and chrominance (for Cb, Cr), natural order; s = 5000 / q for q < 50, else 200 - 2q;
+ *     Q[i] = clamp((T[i]*s + 50) / 100, 1, 255).
+ *   RGB -> YCbCr: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + (128<<16) + 32767) >> 16,
+ *     Cr = (32768 R - 27439 G - 5329 B + (128<<16) + 32767) >> 16.
+ *   chroma down-sampling 2 x 2: (sum of the four + bias) >> 2, bias 1 in even output columns and 2 in odd ones.
+ *   forward DCT of every 8 x 8 block of (sample - 128), libjpeg's jfdctint (CONST_BITS 13, PASS1_BITS 2), rows first, then columns.
+ *     1-D pass on d0..d7: t0 = d0+d7, t7 = d0-d7, t1 = d1+d6, t6 = d1-d6, t2 = d2+d5, t5 = d2-d5, t3 = d3+d4, t4 = d3-d4;
+ *     t10 = t0+t3, t13 = t0-t3, t11 = t1+t2, t12 = t1-t2; rows: out0, out4 = (t10 +- t11) << 2; columns: D(t10 +- t11, 2);
+ *     z1 = (t12+t13)*4433, out2 = D(z1 + t13*6270, n), out6 = D(z1 - t12*15137, n)          n = 11 for rows, 15 for columns
+ *     z1 = t4+t7, z2 = t5+t6, z3 = t4+t6, z4 = t5+t7, z5 = (z3+z4)*9633; t4 *= 2446, t5 *= 16819, t6 *= 25172, t7 *= 12299;
+ *     z1 *= -7373, z2 *= -20995, z3 = z3*-16069 + z5, z4 = z4*-3196 + z5;
+ *     out7 = D(t4+z1+z3, n), out5 = D(t5+z2+z4, n), out3 = D(t6+z2+z3, n), out1 = D(t7+z1+z4, n).       (8 times the DCT)
+ *   quantise: qv = Q[i] << 3, a = (|c| + (qv >> 1)) / qv, coefficient = a with the sign of c; dequantised value = coefficient * Q[i].
+ *   inverse DCT, libjpeg's jidctint, columns first with n = 11, then rows with n = 18.  1-D pass: z1 = (d2+d6)*4433,
+ *     t2 = z1 - d6*15137, t3 = z1 + d2*6270, t0 = (d0+d4) << 13, t1 = (d0-d4) << 13, t10 = t0+t3, t13 = t0-t3, t11 = t1+t2, t12 = t1-t2;
+ *     (t0, t1, t2, t3) = (d7, d5, d3, d1); z1 = t0+t3, z2 = t1+t2, z3 = t0+t2, z4 = t1+t3, z5 = (z3+z4)*9633; t0 *= 2446, t1 *= 16819,
+ *     t2 *= 25172, t3 *= 12299; z1 *= -7373, z2 *= -20995, z3 = z3*-16069 + z5, z4 = z4*-3196 + z5; t0 += z1+z3, t1 += z2+z4,
+ *     t2 += z2+z3, t3 += z1+z4; out0, out7 = D(t10 +- t3, n), out1, out6 = D(t11 +- t2, n), out2, out5 = D(t12 +- t1, n),
+ *     out3, out4 = D(t13 +- t0, n).  Then + 128 and clamp to 0..255.
+ *   chroma up-sampling, h2v2 "fancy": for output row 2r + v, s[x] = 3*c[r][x] + c[r'][x], r' = r-1 (v = 0) or r+1 (v = 1);
+ *     out[2x] = (3 s[x] + s[x-1] + 8) >> 4, out[2x+1] = (3 s[x] + s[x+1] + 7) >> 4; r', x-1 and x+1 clamped to the plane.
+ *   YCbCr -> RGB with cb, cr minus 128: R = Y + ((91881 cr + 32768) >> 16), B = Y + ((116130 cb + 32768) >> 16),
+ *     G = Y + ((-22554 cb - 46802 cr + 32768) >> 16); clamp to 0..255. */
+size_t uwm_jpeg_workspace_bytes(int N, int H, int W);      /* 0 (and an error message) for a bad shape */
+int  uwm_jpeg_u8(const uint8_t* images, const int* quality, int N, int H, int W, const float* mean, const float* std, void* workspace,
+                 size_t workspace_bytes, float* out_nchw, uint8_t* out_u8, uwm_stream stream);
 /* 3x3/stride-1 convolutions (forward, dgrad and weight gradient) run as Winograd F(2x2,3x3) on the fp32 MFMA path by
  * default (2.25x fewer multiplies, results within a few fp32 ulps of the direct form); mode 0 selects the direct
  * kernels everywhere; 2 (tests) prefers the 512-thread Winograd variant wherever its shape rules allow, whatever the

@@ -38,18 +38,25 @@ def _loss_weights(cfg):
     raise ValueError(f"unsupported LOSS.NAME {name!r} (DiceLoss | BCEWithLogitsLoss | CombinedLoss)")
 
 
-def _served_recipe(augment, cfg):
-    """--augment and DATA.AUGMENTATION_TYPE -> (the recipe the device serves, or 'none'; a note for the 'serving' line).  'basic'
-    serves the basic recipe whatever the config asks for, and says so; 'config' serves the recipe that DATA.AUGMENTATION_TYPE names
-    as the reference chooses it (src/utils/dataset.py:417-427: 'transparent_watermark', 'enhanced', anything else is basic) and
-    refuses 'transparent_watermark', whose ImageCompression stage (a JPEG round trip) is not built."""
+def _served_recipe(augment, cfg, jpeg="refuse"):
+    """--augment, DATA.AUGMENTATION_TYPE and --jpeg -> (the recipe the device serves, or 'none'; a note for the 'serving' line).
+    'basic' serves the basic recipe whatever the config asks for, and says so; 'config' serves the recipe that DATA.AUGMENTATION_TYPE
+    names as the reference chooses it (src/utils/dataset.py:417-427: 'transparent_watermark', 'enhanced', anything else is basic).
+    'transparent_watermark' is served only with --jpeg device (its ImageCompression stage is then the baseline libjpeg round trip
+    of uwm_jpeg_u8) and refused otherwise."""
     asked = cfg.DATA.get("AUGMENTATION_TYPE", None)
+    if jpeg not in ("refuse", "device"):
+        raise ValueError(f"--jpeg {jpeg!r}: 'refuse' or 'device'")
     if augment == "none":
         return "none", ""
     if augment == "config":
         if asked == "transparent_watermark":
-            raise ValueError("--augment config: DATA.AUGMENTATION_TYPE='transparent_watermark' is not served: its ImageCompression stage "
-                             "(a JPEG round trip) is not built; --augmentation-type enhanced or basic is")
+            if jpeg != "device":
+                raise ValueError("--augment config: DATA.AUGMENTATION_TYPE='transparent_watermark' is served only with --jpeg device "
+                                 "(its ImageCompression stage then runs as a baseline JPEG round trip on the device); without the flag "
+                                 "--augmentation-type enhanced or basic is served")
+            return asked, (f" (DATA.AUGMENTATION_TYPE={asked!r}; ImageCompression is the baseline libjpeg round trip (4:2:0, integer "
+                           "DCT) on the device, and Affine uses the warp's reflect-101 border and one scale instead of a zero fill)")
         if asked in AUG_RECIPES_EXT:
             return asked, f" (DATA.AUGMENTATION_TYPE={asked!r})"
         return "basic", f" (DATA.AUGMENTATION_TYPE={asked!r} selects the basic recipe, as in the reference)"
@@ -170,7 +177,7 @@ def train_command(args):
         cfg.OPTIMIZER.LR_SCHEDULER = args.lr_scheduler
     if getattr(args, "augmentation_type", None):
         cfg.DATA.AUGMENTATION_TYPE = args.augmentation_type
-    augment, aug_note = _served_recipe(getattr(args, "augment", None) or "none", cfg)      # refusals come before any device work
+    augment, aug_note = _served_recipe(getattr(args, "augment", None) or "none", cfg, getattr(args, "jpeg", None) or "refuse")      # refusals come before any device work
     if getattr(args, "checkpoint_dir", None):
         cfg.TRAIN.CHECKPOINT_DIR = args.checkpoint_dir
     if cfg.MODEL.NAME not in ("Unet", "UnetPlusPlus"):
@@ -354,8 +361,12 @@ def build_parser():
                          "reference's basic recipe (flips, rot90, ShiftScaleRotate, RandomBrightnessContrast, HueSaturationValue) and "
                          "normalises; validation is resized and normalised only.  'config' = the same path with the recipe that "
                          "DATA.AUGMENTATION_TYPE names: 'enhanced' adds CLAHE / gamma, Gaussian noise and motion / Gaussian blur; "
-                         "'transparent_watermark' is refused (its JPEG stage, ImageCompression, is not built).  'none' (default) = "
-                         "host-prepared tensors, no augmentation")
+                         "'transparent_watermark' (the config's default) adds a sheared Affine, noise, blur and ImageCompression and is "
+                         "served only with --jpeg device.  'none' (default) = host-prepared tensors, no augmentation")
+    tp.add_argument("--jpeg", choices=["refuse", "device"], default="refuse",
+                    help="ImageCompression of the 'transparent_watermark' recipe (read by --augment config): 'device' = a baseline "
+                         "libjpeg round trip (4:2:0, integer DCT, no entropy coding) on the device, bit-equal to Pillow / OpenCV; "
+                         "'refuse' (default) = that recipe is refused")
     tp.add_argument("--augmentation-type", choices=["basic", "enhanced", "transparent_watermark"], default=None,
                     help="DATA.AUGMENTATION_TYPE (read by --augment config)")
     tp.add_argument("--model", choices=["Unet", "UnetPlusPlus"], default=None, help="MODEL.NAME (reference default: UnetPlusPlus)")

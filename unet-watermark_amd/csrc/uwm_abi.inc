@@ -531,6 +531,30 @@ int uwm_aug_lab_tables(int which, const void** data, int* count, int* elem_bytes
   if (!aug_ext_host_table(which, data, count, elem_bytes)) return fail("uwm_aug_lab_tables: which must be 0..4 (got %d)", which);
   return 0;
 }
+// ---- ImageCompression of the transparent_watermark recipe (jpeg_u8.hip): every refusal comes before any launch
+size_t uwm_jpeg_workspace_bytes(int N, int H, int W) {
+  const size_t need = jpeg_workspace_bytes(N, H, W);
+  if (!need) fail("uwm_jpeg_workspace_bytes: bad shape %d x %d x %d (N, H, W >= 1; H and W multiples of 16)", N, H, W);
+  return need;
+}
+int uwm_jpeg_u8(const uint8_t* images, const int* quality, int N, int H, int W, const float* mean, const float* std, void* workspace,
+                size_t workspace_bytes, float* out_nchw, uint8_t* out_u8, uwm_stream stream) {
+  if (!images || !quality || !mean || !std) return fail("uwm_jpeg_u8: null argument");
+  if (!out_nchw && !out_u8) return fail("uwm_jpeg_u8: out_nchw and out_u8 are both null");
+  if (N < 1 || H < 1 || W < 1) return fail("uwm_jpeg_u8: N, H and W must be >= 1 (got %d, %d, %d)", N, H, W);
+  if ((H & 15) || (W & 15)) return fail("uwm_jpeg_u8: H and W must be multiples of 16 (got %d, %d)", H, W);
+  if ((long long)N * H * (W / 4) / 256 >= 2147483647ll) return fail("uwm_jpeg_u8: N * H * W too large for one launch (%d x %d x %d)", N, H, W);
+  if ((uintptr_t)quality & 3) return fail("uwm_jpeg_u8: quality must be 4-byte aligned");
+  if (((uintptr_t)images & 3) || ((uintptr_t)out_u8 & 3)) return fail("uwm_jpeg_u8: images and out_u8 must be 4-byte aligned");
+  if ((uintptr_t)out_nchw & 15) return fail("uwm_jpeg_u8: out_nchw must be 16-byte aligned");
+  for (int c = 0; c < 3; ++c) if (!(std[c] > 0.f)) return fail("uwm_jpeg_u8: std[%d] must be positive", c);
+  if (!workspace) return fail("uwm_jpeg_u8: null workspace");
+  if ((uintptr_t)workspace & 15) return fail("uwm_jpeg_u8: workspace must be 16-byte aligned");
+  const size_t need = jpeg_workspace_bytes(N, H, W);
+  if (workspace_bytes < need) return fail("uwm_jpeg_u8: workspace too small (%zu bytes, need %zu)", workspace_bytes, need);
+  LCHK(launch_jpeg_u8(images, quality, N, H, W, mean, std, workspace, workspace_bytes, out_nchw, out_u8, (hipStream_t)stream));
+  return 0;
+}
 int uwm_scale(float* p, long long n, float s, uwm_stream stream) {
   if (!p || n < 1) return fail("uwm_scale: bad argument");
   LCHK(launch_scale(p, (size_t)n, s, (hipStream_t)stream));

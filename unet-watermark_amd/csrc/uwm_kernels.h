@@ -408,6 +408,11 @@ hipError_t launch_augment_ext(const uint8_t* img, const uint8_t* masks, const Au
                               const float* mean, const float* std, int thr, void* workspace, size_t workspace_bytes, float* out_f,
                               uint8_t* out_masks, uint8_t* out_u8, hipStream_t st);
 bool aug_ext_host_table(int which, const void** data, int* count, int* elem_bytes);      // the host's tables (uwm_aug_lab_tables)
+// ---- the transparent_watermark recipe's ImageCompression: a baseline 4:2:0 JPEG round trip (jpeg_u8.hip; the rule: include/uwm.h)
+size_t jpeg_workspace_bytes(int N, int H, int W);      // 0 for a bad shape (H, W multiples of 16)
+// images [N][H][W][3], quality DEVICE int[N] (0 = unchanged, else 1..100) -> out_f fp32 NCHW (Normalize = pre_norm) and / or the bytes out_u8
+hipError_t launch_jpeg_u8(const uint8_t* img, const int* quality, int N, int H, int W, const float* mean, const float* std, void* workspace,
+                          size_t workspace_bytes, float* out_f, uint8_t* out_u8, hipStream_t st);
 // One output pixel (Y, X) of the bilinear resize of a logit plane b[h][w] (element stride ld) by sy = h / H, sx = w / W: ONE function
 // for resize_threshold_kernel (loss.hip) and resize_threshold_ragged_kernel (resize_u8.hip), so that a ragged batch's masks are the
 // uniform call's bit for bit

@@ -2,7 +2,8 @@
 (/root/reference/src/utils/dataset.py:113-122,332-333,389-395) — image fp32 NCHW normalised with the
 ImageNet mean/std, mask int64 {0,1} (H,W).  A synthetic generator and a plain PIL folder reader are provided; the reference's
 basic and enhanced albumentations recipes run on the device (device_augment, DeviceInputPipeline: `main.py train --augment basic` /
-`--augment config`); the transparent_watermark recipe's JPEG round trip (ImageCompression) is not built."""
+`--augment config`), and so does the transparent_watermark recipe, whose ImageCompression is a baseline JPEG round trip on the device
+(device_jpeg, sample_transparent_recipe; `--augment config --jpeg device`)."""
 from __future__ import annotations
 
 import os
@@ -383,6 +384,8 @@ def sample_aug_recipe(n, h, w, generator=None, recipe="basic"):
     torch.Generator."""
     if recipe == "basic":
         return sample_aug_params(n, h, w, generator, "basic"), None
+    if recipe == "transparent_watermark":
+        raise ValueError("the 'transparent_watermark' recipe has a third part, the JPEG qualities: draw it with sample_transparent_recipe")
     if recipe != "enhanced":
         raise ValueError(f"unknown augmentation recipe {recipe!r} (served: {', '.join(AUG_RECIPES_EXT)})")
     n = int(n)
@@ -463,6 +466,111 @@ def _ext_workspace(device, nbytes):
     return ws
 
 
+# ---------------------------------------------------------------------------- ImageCompression (uwm_jpeg_u8, csrc/jpeg_u8.hip)
+JPEG_QUALITY_RANGE = (60, 100)            # A.ImageCompression(quality_range=(60, 100)) of the transparent_watermark recipe
+_JPEG_WORKSPACE = {}
+
+
+def _jpeg_workspace(device, nbytes):
+    """as _ext_workspace: one per device, grown when a larger one is needed"""
+    ws = _JPEG_WORKSPACE.get(device)
+    if ws is None or ws.numel() < nbytes:
+        ws = _JPEG_WORKSPACE[device] = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+    return ws
+
+
+def device_jpeg(images_u8: torch.Tensor, quality, mean=IMAGENET_MEAN, std=IMAGENET_STD, return_u8=False):
+    """A.ImageCompression on the HIP device: uint8 (N,H,W,3) RGB images, H and W multiples of 16, and one integer quality per image
+    (0 = the image passes through unchanged, else 1..100; a host array, or an int32 tensor already on the device, which is then not
+    checked) -> (N,3,H,W) fp32 normalised images [, the uint8 (N,H,W,3) images when return_u8]: what a baseline 4:2:0 JPEG encode +
+    decode at that quality does to the pixels, bit-equal to libjpeg's default path (Pillow, cv2.imencode / imdecode), then Normalize
+    (uwm_jpeg_u8; the rule is in include/uwm.h).  The workspace is allocated once per device and reused.  No CPU fallback."""
+    import ctypes as C
+    from . import _lib as L
+    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4:
+        raise RuntimeError("device_jpeg needs a uint8 (N,H,W,3) tensor on a HIP device (no CPU fallback)")
+    n, h, w, c = images_u8.shape
+    if c != 3:
+        raise ValueError(f"device_jpeg: C must be 3 (got {c})")
+    if n < 1 or h < 16 or w < 16 or h % 16 or w % 16:
+        raise ValueError(f"device_jpeg: H and W must be multiples of 16 (got {h} x {w})")
+    on_device = isinstance(quality, torch.Tensor) and quality.device.type == "cuda"
+    if on_device:
+        if quality.dtype != torch.int32 or quality.numel() != n or quality.device != images_u8.device:
+            raise ValueError("a device quality tensor must be int32, on the images' device, with one entry per image")
+    else:
+        q = np.asarray(quality)
+        if q.ndim != 1 or q.shape[0] != n or not np.issubdtype(q.dtype, np.integer):
+            raise ValueError(f"quality must be {n} integers, one per image")
+        if ((q < 0) | (q > 100)).any():
+            raise ValueError("quality must be 0 (pass through) or 1..100")
+    if images_u8.device.type != "cuda":
+        raise RuntimeError("device_jpeg needs a uint8 (N,H,W,3) tensor on a HIP device (no CPU fallback)")
+    x = images_u8.contiguous()
+    if on_device:
+        qd = quality.contiguous()
+    else:
+        host = torch.from_numpy(q.astype(np.int32))
+        qd = host.pin_memory().to(x.device, non_blocking=True)
+    out = torch.empty((n, 3, h, w), dtype=torch.float32, device=x.device)
+    u8 = torch.empty((n, h, w, 3), dtype=torch.uint8, device=x.device) if return_u8 else None
+    mean_c = (C.c_float * 3)(*[float(v) for v in mean[:3]]); std_c = (C.c_float * 3)(*[float(v) for v in std[:3]])
+    with L.on_device(x):
+        ws = _jpeg_workspace(x.device, int(L.lib().uwm_jpeg_workspace_bytes(n, h, w)))
+        L.check(L.lib().uwm_jpeg_u8(C.c_void_p(x.data_ptr()), C.c_void_p(qd.data_ptr()), n, h, w, mean_c, std_c, C.c_void_p(ws.data_ptr()),
+                                    ws.numel(), C.c_void_p(out.data_ptr()), C.c_void_p(u8.data_ptr() if u8 is not None else 0),
+                                    C.c_void_p(L.stream_ptr(x.device))), ValueError)
+    return (out, u8) if return_u8 else out
+
+
+def sample_transparent_recipe(n, h, w, generator=None):
+    """-> (params, ext, quality): one uwm_aug_desc, one uwm_aug_ext_desc and one JPEG quality (int32) per image, with the numbers of
+    the reference's get_transparent_watermark_transform (dataset.py:298-334): flips / rot90 as random_aug_flags; Affine p = 0.3
+    (scale 0.9..1.1, rotate +-15 degrees, shear +-5 degrees, no translation); RandomBrightnessContrast p = 0.7 (limits 0.3);
+    HueSaturationValue p = 0.5 (15 / 30 / 20); GaussNoise p = 0.3 (albumentations 1.3's default variance 10..50);
+    OneOf(MotionBlur 3, GaussianBlur 3) p = 0.2; ImageCompression p = 0.3, quality an integer uniform in 60..100 inclusive, else 0
+    (= not drawn: device_jpeg passes the image through).  A stage that is not drawn is an exact identity.  Deterministic for a seeded
+    torch.Generator.
+      Two deviations: albumentations' Affine fills the border with zeros and draws the x and y scale (and shear) separately; here the
+    stage runs through the warp of uwm_augment_u8 and affine_inverse(..., shear=...), so the border is reflect-101, as for
+    ShiftScaleRotate, there is one scale, and the shear is an x-shear.  Image and mask stay consistent either way."""
+    n = int(n)
+    p, e = identity_aug_params(n), identity_aug_ext_params(n)
+    flags = random_aug_flags(n, generator)
+    if h != w:
+        flags = flags & 3
+    p["flags"] = flags.numpy()
+    u = torch.rand(n, 13, generator=generator, dtype=torch.float64).numpy()
+    hsv = torch.stack([torch.randint(-lim, lim + 1, (n,), generator=generator) for lim in (15, 30, 20)], 1).numpy()
+    seeds = torch.randint(0, 1 << 62, (n,), generator=generator).numpy().astype(np.uint64)
+    ends = torch.stack([torch.randint(0, 9, (n,), generator=generator), torch.randint(1, 9, (n,), generator=generator)], 1).numpy()
+    qual = torch.randint(JPEG_QUALITY_RANGE[0], JPEG_QUALITY_RANGE[1] + 1, (n,), generator=generator).numpy()
+    span = lambda col, lim: (2.0 * u[:, col] - 1.0) * lim      # noqa: E731   uniform in [-lim, lim)
+    angle, scale, shear = span(1, 15.0), 1.0 + span(2, 0.1), span(3, 5.0)
+    alpha, beta = 1.0 + span(5, 0.3), span(6, 0.3)
+    quality = np.zeros(n, dtype=np.int32)
+    for i in range(n):
+        if u[i, 0] < 0.3:
+            p["minv"][i] = affine_inverse(h, w, angle[i], scale[i], 0.0, 0.0, shear=shear[i])
+        if u[i, 4] < 0.7:
+            p["lut"][i] = brightness_contrast_lut(alpha[i], beta[i])
+        if u[i, 7] < 0.5:
+            p["hue"][i], p["sat"][i], p["val"][i] = hsv[i]
+        if u[i, 8] < 0.3:
+            e["noise_sigma"][i] = int(round(np.sqrt(10.0 + 40.0 * u[i, 9]) * 256.0))
+            e["seed"][i] = seeds[i]
+        if u[i, 10] < 0.2:
+            if u[i, 11] < 0.5:
+                a, b = int(ends[i, 0]), int((ends[i, 0] + ends[i, 1]) % 9)      # two distinct cells of the grid
+                e["blur"][i] = BLUR_MOTION
+                e["blur_w"][i] = motion_kernel((a % 3, a // 3), (b % 3, b // 3))
+            else:
+                e["blur"][i] = BLUR_GAUSS
+        if u[i, 12] < 0.3:
+            quality[i] = qual[i]
+    return p, e, quality
+
+
 # ---------------------------------------------------------------------------- the device input path of `main.py train --augment basic`
 class RawFolderDataset(Dataset):
     """FolderDataset's files, decoded and nothing else: (image uint8 (h, w, 3) RGB, mask uint8 (h, w)) numpy arrays at the file's
@@ -513,7 +621,8 @@ class DeviceInputPipeline:
     """Batches of a raw dataset -> what Trainer.step takes, on the device.  Raw folder items (uint8 arrays of any size) are packed
     into persistent pinned buffers (pack_images), uploaded and resized to size x size by uwm_resize_u8 — linear for the image,
     nearest for the mask (the reference's A.Resize); DeviceU8Dataset items are gathered.  Training batches then go through
-    device_augment with parameters drawn from `generator`, validation batches through device_preprocess (get_val_transform)."""
+    device_augment with parameters drawn from `generator`, validation batches through device_preprocess (get_val_transform).
+    recipe 'transparent_watermark' (sample_transparent_recipe) sends the augmented uint8 images through device_jpeg, which normalises."""
 
     def __init__(self, size, device, source=None, recipe="basic", mean=IMAGENET_MEAN, std=IMAGENET_STD):
         self.size, self.device, self.source, self.recipe = int(size), torch.device(device), source, recipe
@@ -551,6 +660,10 @@ class DeviceInputPipeline:
 
     def train_batch(self, items, generator=None):
         x, m = self.to_u8(items)
+        if self.recipe == "transparent_watermark":
+            params, ext, quality = sample_transparent_recipe(x.shape[0], x.shape[1], x.shape[2], generator)
+            _, mo, u8 = device_augment(x, m, params, self.mean, self.std, return_u8=True, ext=ext)
+            return device_jpeg(u8, quality, self.mean, self.std), mo
         params, ext = sample_aug_recipe(x.shape[0], x.shape[1], x.shape[2], generator, self.recipe)
         return device_augment(x, m, params, self.mean, self.std, ext=ext)
 
