@@ -197,6 +197,30 @@ int  uwm_predict_images_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, c
                            size_t mask_bytes, float* logits, void* workspace, size_t workspace_bytes, int N, int H, int W,
                            uwm_stream stream);
 
+/* Masks from watermarked / clean pairs: the reference's WatermarkDataset._generate_mask with use_blurred_mask = False
+ * (src/utils/dataset.py:197-211,277-278), which serves every image that has a clean counterpart and no mask file.  wm, clean and mask
+ * are ragged batches as above (uint8 RGB interleaved, C = 3; masks one byte per pixel at any alignment); image i, at its OWN size:
+ *     d = |wm - clean| per channel                                                 cv2.absdiff
+ *     g = (d.R*9798 + d.G*19235 + d.B*3735 + 16384) >> 15                          cvtColor RGB2GRAY, OpenCV 4.x's 8-bit rule (15 bits;
+ *                                                                                  3.x used 14: 4899, 9617, 1868) — restated, NOT run
+ *     m = g > threshold ? 255 : 0                                                  cv2.threshold THRESH_BINARY
+ *     m = open(m, ELLIPSE(3,3) = the cross, 1 iteration)                           the morphology of uwm_optimize_mask below: the erosion
+ *                                                                                  ignores pixels outside the image, the dilation reads
+ *                                                                                  the eroded plane as 0 there
+ *   and the reference's closing GaussianBlur((3,3), 0.5) + threshold 127 is the identity on {0,255} images (see uwm_optimize_mask).
+ * A clean image of another size is first brought to the watermarked size by uwm_resize_u8(UWM_INTER_LINEAR): the caller's step.
+ * image i: mask_i = open3(gray(|wm_i - clean_i|) > threshold) at the image's own size, into mask + mask_descs[i].offset.
+ * clean_descs[i].h == 0: image skipped, its mask bytes untouched (a mask read from a file stays).  Any other misfit
+ * (sizes differ, a descriptor leaves its buffer, a side above 2^30): the mask region, if it fits, is zeroed.  open != 0: with the
+ * opening; 0: without it.  One launch of N * 64 workgroups on the caller's stream, no workspace, no host synchronisation: capturable,
+ * and one captured launch serves every batch of N pairs.  Every argument is checked before any launch (C must be 3, threshold 0..255,
+ * wm / clean 4-byte and descriptors 8-byte aligned).  No read leaves [wm, wm+wm_bytes) or [clean, clean+clean_bytes), no write leaves
+ * [mask, mask+mask_bytes). */
+int  uwm_pair_mask_u8(const uint8_t* wm, size_t wm_bytes, const uwm_image_desc* wm_descs,
+                      const uint8_t* clean, size_t clean_bytes, const uwm_image_desc* clean_descs,
+                      int N, int C /* 3 */, int threshold /* 0..255 */, int open,
+                      uint8_t* mask, size_t mask_bytes, const uwm_image_desc* mask_descs, uwm_stream stream);
+
 /* Backward of the last training forward held in `workspace`; writes (overwrites) the gradient arena
  * ranges of stages [stage_begin, stage_end).  Call with (0, uwm_num_stages) for everything, or stage
  * by stage to overlap gradient all-reduce with the rest of the backward. */

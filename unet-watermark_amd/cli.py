@@ -1,4 +1,4 @@
-"""`python main.py train|predict ...` — counterpart of the reference's CLI for the model path
+"""`python main.py train|predict|masks ...` — counterpart of the reference's CLI for the model path
 (/root/reference/src/cli.py:368-395 flag names; train loop order /root/reference/src/train.py:207-499:
 epochs of train_epoch + validate (val batch = 2x train batch, :254), Adam | SGD (:265-279), ReduceLROnPlateau on the
 val loss | CosineAnnealingLR (:280-296,408-412), best / periodic checkpoints (:428-460), early stopping (:37-66,362-368)).
@@ -18,8 +18,8 @@ from torch.utils.data.distributed import DistributedSampler
 
 from .checkpoint import load_checkpoint, save_checkpoint
 from .config import get_cfg_defaults, update_config
-from .data import (AUG_RECIPES, AUG_RECIPES_EXT, DeviceInputPipeline, DeviceU8Dataset, FolderDataset, RawFolderDataset, SyntheticWatermarkDataset,
-                   list_collate)
+from .data import (AUG_RECIPES, AUG_RECIPES_EXT, DeviceInputPipeline, DeviceU8Dataset, FolderDataset, RawFolderDataset, RawPairDataset,
+                   SyntheticWatermarkDataset, list_collate)
 from .losses import get_loss_function
 from .metrics import logits_metrics
 from .model import create_model_from_config
@@ -66,6 +66,19 @@ def _served_recipe(augment, cfg, jpeg="refuse"):
     return augment, note
 
 
+def _pair_roots(cfg):
+    """DATA.ROOT_DIR + DATA.ADDITIONAL_ROOT_DIRS: the roots of the reference's create_datasets (src/utils/dataset.py:406-414)"""
+    return [cfg.DATA.ROOT_DIR] + list(cfg.DATA.get("ADDITIONAL_ROOT_DIRS", None) or [])
+
+
+def _pair_dataset(cfg):
+    """The RawPairDataset of the configured roots when the data needs it — more than one root, or an image without a mask file, whose
+    mask is then derived from its clean counterpart — else None: RawFolderDataset serves a single root with every mask as a file."""
+    roots = _pair_roots(cfg)
+    pair = RawPairDataset(roots, int(cfg.DATA.GENERATE_MASK_THRESHOLD))
+    return pair if len(roots) > 1 or pair.missing_masks() else None
+
+
 def _datasets(cfg, synthetic, device_input=None):
     """device_input: a torch.device = the raw datasets of the device input path (--augment basic) instead of host-prepared tensors"""
     if synthetic or not os.path.isdir(os.path.join(cfg.DATA.ROOT_DIR, "watermarked")):
@@ -73,7 +86,7 @@ def _datasets(cfg, synthetic, device_input=None):
         if device_input is not None:
             full = DeviceU8Dataset(full, device_input)
     elif device_input is not None:
-        full = RawFolderDataset(cfg.DATA.ROOT_DIR)
+        full = _pair_dataset(cfg) or RawFolderDataset(cfg.DATA.ROOT_DIR)
     else:
         full = FolderDataset(cfg.DATA.ROOT_DIR, cfg.DATA.IMG_SIZE)
     n = len(full)
@@ -180,6 +193,11 @@ def train_command(args):
     augment, aug_note = _served_recipe(getattr(args, "augment", None) or "none", cfg, getattr(args, "jpeg", None) or "refuse")      # refusals come before any device work
     if getattr(args, "checkpoint_dir", None):
         cfg.TRAIN.CHECKPOINT_DIR = args.checkpoint_dir
+    if (getattr(args, "use_blurred_mask", False) and not args.synthetic and os.path.isdir(os.path.join(cfg.DATA.ROOT_DIR, "watermarked"))
+            and RawPairDataset(_pair_roots(cfg), int(cfg.DATA.GENERATE_MASK_THRESHOLD)).missing_masks()):
+        raise ValueError("--use-blurred-mask: this dataset has images without a mask file, whose masks are derived from their clean "
+                         "counterparts, and the reference's blurred variant of that rule (contours, convex hulls, approxPolyDP) is not "
+                         "served; drop the flag (exact masks, the reference's default) or provide every mask as a file")
     if cfg.MODEL.NAME not in ("Unet", "UnetPlusPlus"):
         raise ValueError(f"MODEL.NAME={cfg.MODEL.NAME!r}: this build serves 'Unet' and 'UnetPlusPlus'")
     if cfg.OPTIMIZER.NAME not in ("Adam", "AdamW", "SGD"):
@@ -234,6 +252,10 @@ def train_command(args):
         pipe = DeviceInputPipeline(cfg.DATA.IMG_SIZE, device, source=tr_set.dataset, recipe=augment)
         if rank == 0:
             print(f"augmentation: serving the {augment!r} recipe on the device{aug_note}", flush=True)
+            if isinstance(tr_set.dataset, RawPairDataset):
+                print(f"masks: {len(tr_set.dataset.missing_masks())} of {len(tr_set.dataset)} images have no mask file; theirs are derived on "
+                      f"the device from the clean counterpart (DATA.GENERATE_MASK_THRESHOLD={tr_set.dataset.mask_threshold}), zero without "
+                      "one; nothing is written (`main.py masks` persists them)", flush=True)
     bs = int(cfg.TRAIN.BATCH_SIZE)
     sampler = DistributedSampler(tr_set, world, rank, shuffle=True, seed=int(cfg.DATA.SEED)) if world > 1 else None
     # the device input path gets raw items from the workers (uint8 arrays of any size, or indices): nothing to stack or pin
@@ -340,6 +362,49 @@ def predict_command(args):
     print(f"wrote {len(files)} masks to {args.output}")
 
 
+def masks_command(args):
+    """Write masks/<stem>.png, at the image's own size, for every image that has a clean counterpart and no mask file: the masks
+    `train --augment basic|config` derives on the fly, persisted where the reference persists them (its first mask directory,
+    src/utils/dataset.py:179-190)."""
+    import numpy as np
+    from PIL import Image
+    from .data import device_pair_mask, mask_descs_for, pack_images, stage_clean
+    cfg = get_cfg_defaults()
+    if args.config and os.path.exists(args.config):
+        update_config(cfg, args.config)
+    if args.data_dir:
+        cfg.DATA.ROOT_DIR = args.data_dir
+    thr = int(args.threshold if args.threshold is not None else cfg.DATA.GENERATE_MASK_THRESHOLD)
+    ds = RawPairDataset(_pair_roots(cfg), thr)                        # (refuses a threshold outside 0..255)
+    if not torch.cuda.is_available():
+        raise SystemExit("masks needs a HIP device (this path has no CPU fallback)")
+    device = torch.device("cuda", torch.cuda.current_device())
+    missing = ds.missing_masks()
+    out_dir = ds.mask_dirs[0]
+    os.makedirs(out_dir, exist_ok=True)
+    bs = max(1, int(args.batch_size or 16))
+    written = no_clean = 0
+    for b in range(0, len(missing), bs):
+        pairs = [(i, ds[i]) for i in missing[b:b + bs]]
+        no_clean += sum(1 for _, it in pairs if it[2] is None)
+        pairs = [(i, it) for i, it in pairs if it[2] is not None]
+        if not pairs:
+            continue
+        packed, descs, _ = pack_images([it[0] for _, it in pairs])
+        wm = packed.to(device, non_blocking=True)
+        clean, cdescs = stage_clean([it[2] for _, it in pairs], descs, device)
+        out = device_pair_mask(wm, descs, clean, cdescs, thr).cpu().numpy()
+        for (i, _), d in zip(pairs, mask_descs_for(descs)):
+            o, h, w = int(d["offset"]), int(d["h"]), int(d["w"])
+            stem = os.path.splitext(os.path.basename(ds.files[i]))[0]
+            Image.fromarray(out[o:o + h * w].reshape(h, w)).save(os.path.join(out_dir, stem + ".png"))
+            written += 1
+    res = dict(written=written, skipped=len(ds) - len(missing), no_clean=no_clean, threshold=thr, output=out_dir)
+    print(f"wrote {written} masks to {out_dir} (threshold {thr}); skipped {res['skipped']} with a mask file; "
+          f"{no_clean} left without a clean image")
+    return res
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description="MI355X-native U-Net watermark segmentation (train | predict)")
     sub = ap.add_subparsers(dest="command")
@@ -352,7 +417,9 @@ def build_parser():
     tp.add_argument("--no-early-stopping", action="store_true")
     tp.add_argument("--early-stopping-patience", type=int)
     tp.add_argument("--resume", type=str)
-    tp.add_argument("--use-blurred-mask", action="store_true", help="accepted for compatibility (dataset-side option)")
+    tp.add_argument("--use-blurred-mask", action="store_true",
+                    help="accepted for compatibility where every mask is a file (it only concerns generated masks); refused on a dataset "
+                         "that needs masks derived from watermarked / clean pairs: only the reference's exact rule is served")
     tp.add_argument("--encoder", type=str); tp.add_argument("--img-size", type=int)
     tp.add_argument("--synthetic", type=int, default=0, help="train on N synthetic images instead of DATA.ROOT_DIR")
     tp.add_argument("--workers", type=int, default=2)
@@ -377,6 +444,11 @@ def build_parser():
     tp.add_argument("--lr-scheduler", choices=["ReduceLROnPlateau", "CosineAnnealingLR", "CosineAnnealingWarmRestarts", "none"],
                     default=None, help="OPTIMIZER.LR_SCHEDULER")
     tp.add_argument("--checkpoint-dir", type=str, default=None, help="TRAIN.CHECKPOINT_DIR")
+    mp = sub.add_parser("masks", help="derive masks/<stem>.png from watermarked / clean pairs on the device, for every pair without one")
+    mp.add_argument("--data-dir", type=str, default=None, help="DATA.ROOT_DIR: the directory with watermarked/, clean/ and masks/")
+    mp.add_argument("--config", type=str, default=None)
+    mp.add_argument("--threshold", type=int, default=None, help="DATA.GENERATE_MASK_THRESHOLD (0..255)")
+    mp.add_argument("--batch-size", type=int, default=None, help="pairs per launch (default 16)")
     pp = sub.add_parser("predict")
     pp.add_argument("--input", type=str, required=True); pp.add_argument("--output", type=str, required=True)
     pp.add_argument("--model", type=str, required=True); pp.add_argument("--config", type=str, default=None)
@@ -398,4 +470,6 @@ def main(argv=None):
         return train_command(args)
     if args.command == "predict":
         return predict_command(args)
+    if args.command == "masks":
+        return masks_command(args)
     ap.print_help()

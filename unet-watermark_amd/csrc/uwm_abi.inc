@@ -278,6 +278,22 @@ int uwm_resize_threshold_ragged(const float* logits, int ld, int N, int h, int w
                                       (hipStream_t)stream));
   return 0;
 }
+// ---- masks from watermarked / clean pairs (pair_mask_u8.hip): every argument is checked here, before any launch
+int uwm_pair_mask_u8(const uint8_t* wm, size_t wm_bytes, const uwm_image_desc* wm_descs, const uint8_t* clean, size_t clean_bytes,
+                     const uwm_image_desc* clean_descs, int N, int C, int threshold, int open, uint8_t* mask, size_t mask_bytes,
+                     const uwm_image_desc* mask_descs, uwm_stream stream) {
+  if (!wm || !wm_descs || !clean || !clean_descs || !mask || !mask_descs) return fail("uwm_pair_mask_u8: null argument");
+  if (C != 3) return fail("uwm_pair_mask_u8: C must be 3 (RGB pairs; got %d)", C);
+  if (threshold < 0 || threshold > 255) return fail("uwm_pair_mask_u8: threshold must be 0..255 (got %d)", threshold);
+  if (N < 1 || wm_bytes < 1 || clean_bytes < 1 || mask_bytes < 1)
+    return fail("uwm_pair_mask_u8: N, wm_bytes, clean_bytes and mask_bytes must be >= 1 (got %d, %zu, %zu, %zu)", N, wm_bytes, clean_bytes, mask_bytes);
+  if (N > 2147483647 / kPairMaskBlocks) return fail("uwm_pair_mask_u8: N too large for one launch (%d)", N);
+  if (((uintptr_t)wm | (uintptr_t)clean) & 3) return fail("uwm_pair_mask_u8: wm and clean must be 4-byte aligned");
+  if (((uintptr_t)wm_descs | (uintptr_t)clean_descs | (uintptr_t)mask_descs) & 7) return fail("uwm_pair_mask_u8: descriptors must be 8-byte aligned");
+  LCHK(launch_pair_mask_u8(wm, wm_bytes, (const ImageDesc*)wm_descs, clean, clean_bytes, (const ImageDesc*)clean_descs, N, threshold, open != 0,
+                           mask, mask_bytes, (const ImageDesc*)mask_descs, (hipStream_t)stream));
+  return 0;
+}
 int uwm_predict_images_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, const uwm_image_desc* in_descs, const float* mean,
                           const float* std, float threshold, int apply_sigmoid, const uwm_image_desc* out_descs, uint8_t* mask,
                           size_t mask_bytes, float* logits, void* ws, size_t ws_bytes, int N, int H, int W, uwm_stream stream) {

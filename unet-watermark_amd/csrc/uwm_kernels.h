@@ -442,6 +442,14 @@ hipError_t launch_resize_norm_u8_nhwc4(const uint8_t* src, size_t src_bytes, con
 // logit plane [N][h][w] (stride ld) -> image i's own (h_i, w_i) at mask + offset_i, thresholded; nothing is written outside [mask, mask + mask_bytes)
 hipError_t launch_resize_threshold_ragged(const float* logits, int ld, int N, int h, int w, const ImageDesc* out_descs, float thr,
                                           int apply_sigmoid, uint8_t* mask, size_t mask_bytes, hipStream_t st);
+// ---- masks from watermarked / clean pairs (pair_mask_u8.hip; the rule: include/uwm.h)
+constexpr int kPairMaskBlocks = 64;                  // workgroups per image, each walking that image's tiles: grid = N * this
+constexpr int kPairMaskTileW = 120, kPairMaskTileH = 32;      // mask pixels of one tile
+// image i: mask + mask_descs[i].offset <- open3(gray(|wm_i - clean_i|) > threshold) (open == 0: without the opening); clean_descs[i].h == 0
+// skips the image, any other misfit zeroes its mask.  No read leaves the two source buffers, no write leaves [mask, mask + mask_bytes)
+hipError_t launch_pair_mask_u8(const uint8_t* wm, size_t wm_bytes, const ImageDesc* wm_descs, const uint8_t* clean, size_t clean_bytes,
+                               const ImageDesc* clean_descs, int N, int threshold, int open, uint8_t* mask, size_t mask_bytes,
+                               const ImageDesc* mask_descs, hipStream_t st);
 
 // EfficientNet MBConv pieces (mbconv.hip): swish, depthwise k x k conv (weights tap-major [k*k][C]) with static "same"
 // padding (pb = pad at the begin of H and W; the end pad is implied by Ho/Wo), squeeze-and-excitation, block output with drop-connect

@@ -3,7 +3,8 @@
 ImageNet mean/std, mask int64 {0,1} (H,W).  A synthetic generator and a plain PIL folder reader are provided; the reference's
 basic and enhanced albumentations recipes run on the device (device_augment, DeviceInputPipeline: `main.py train --augment basic` /
 `--augment config`), and so does the transparent_watermark recipe, whose ImageCompression is a baseline JPEG round trip on the device
-(device_jpeg, sample_transparent_recipe; `--augment config --jpeg device`)."""
+(device_jpeg, sample_transparent_recipe; `--augment config --jpeg device`).  An image without a mask file gets the
+mask the reference derives from its clean counterpart, also on the device (RawPairDataset, device_pair_mask)."""
 from __future__ import annotations
 
 import os
@@ -593,6 +594,164 @@ class RawFolderDataset(Dataset):
         return img, m
 
 
+# ---------------------------------------------------------------------------- masks from watermarked / clean pairs (uwm_pair_mask_u8, csrc/pair_mask_u8.hip)
+def mask_descs_for(descs) -> np.ndarray:
+    """uwm_image_desc array of images -> the same sizes with offsets that pack one h*w-byte mask per image back to back
+    (pack_images' third result)"""
+    m = np.zeros(len(descs), DESC_DTYPE)
+    m["h"], m["w"] = descs["h"], descs["w"]
+    sizes = descs["h"].astype(np.int64) * descs["w"].astype(np.int64)
+    m["offset"] = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    return m
+
+
+def device_pair_mask(packed_wm, wm_descs, packed_clean, clean_descs, threshold, open=True, mask=None, mask_descs=None) -> torch.Tensor:
+    """The reference's WatermarkDataset._generate_mask (use_blurred_mask = False) for every pair of a ragged batch on the HIP device:
+    mask_i = open3(gray(|wm_i - clean_i|) > threshold) at the image's own size, {0, 255} (uwm_pair_mask_u8; the rule is in
+    include/uwm.h).  packed_wm / packed_clean: flat uint8 tensors of RGB images (pack_images) with their uwm_image_desc arrays; a
+    clean descriptor with h == 0 skips that image (its mask bytes stay), a pair whose sizes differ gets a zero mask — bring such a
+    clean image to the watermarked size with uwm_resize_u8 first.  mask / mask_descs: a packed mask buffer on the device to write
+    into (e.g. one that already holds the masks read from files); absent, one is made, zero-filled, with the layout of
+    mask_descs_for(wm_descs).  -> the packed mask (flat uint8, on the device).  No CPU fallback."""
+    import ctypes as C
+    from . import _lib as L
+    t = int(threshold)
+    if not 0 <= t <= 255:
+        raise ValueError(f"device_pair_mask: threshold must be 0..255 (got {threshold})")
+    wd, cd = np.ascontiguousarray(wm_descs), np.ascontiguousarray(clean_descs)
+    if wd.dtype != DESC_DTYPE or cd.dtype != DESC_DTYPE or wd.ndim != 1 or wd.shape != cd.shape or len(wd) == 0:
+        raise ValueError("device_pair_mask: wm_descs and clean_descs must be 1-D data.DESC_DTYPE arrays of one length")
+    if (mask is None) != (mask_descs is None):
+        raise ValueError("device_pair_mask: mask and mask_descs come together")
+    md = mask_descs_for(wd) if mask_descs is None else np.ascontiguousarray(mask_descs)
+    if md.dtype != DESC_DTYPE or md.shape != wd.shape:
+        raise ValueError("device_pair_mask: mask_descs must be a data.DESC_DTYPE array with one entry per image")
+    wm = packed_wm if packed_wm.device.type == "cuda" else (packed_wm.cuda(non_blocking=True) if torch.cuda.is_available() else packed_wm)
+    if wm.device.type != "cuda" or wm.dtype != torch.uint8 or wm.dim() != 1:
+        raise RuntimeError("device_pair_mask needs flat uint8 tensors and a HIP device (no CPU fallback)")
+    cl = packed_clean.to(wm.device, non_blocking=True)
+    if cl.dtype != torch.uint8 or cl.dim() != 1:
+        raise RuntimeError("device_pair_mask needs flat uint8 tensors and a HIP device (no CPU fallback)")
+    if mask is None:
+        mask = torch.zeros(max(1, int((md["h"].astype(np.int64) * md["w"]).sum())), dtype=torch.uint8, device=wm.device)
+    elif mask.device != wm.device or mask.dtype != torch.uint8 or mask.dim() != 1 or not mask.is_contiguous():
+        raise ValueError("device_pair_mask: mask must be a flat contiguous uint8 tensor on the images' device")
+    wm, cl = wm.contiguous(), cl.contiguous()
+    dd = descs_tensor(np.concatenate([wd, cd, md]), wm.device)                 # one upload; 16-byte records keep every part 8-byte aligned
+    n, step = len(wd), len(wd) * DESC_DTYPE.itemsize
+    with L.on_device(wm):
+        L.check(L.lib().uwm_pair_mask_u8(C.c_void_p(wm.data_ptr()), wm.numel(), C.c_void_p(dd.data_ptr()), C.c_void_p(cl.data_ptr()), cl.numel(),
+                                         C.c_void_p(dd.data_ptr() + step), n, 3, t, int(bool(open)), C.c_void_p(mask.data_ptr()), mask.numel(),
+                                         C.c_void_p(dd.data_ptr() + 2 * step), C.c_void_p(L.stream_ptr(wm.device))), ValueError)
+    return mask
+
+
+def stage_clean(cleans, wm_descs, device, upload=None):
+    """The clean images of a batch on the device, each at its watermarked image's size: cleans holds a uint8 (h, w, 3) array or None
+    per image, wm_descs the watermarked images' descriptors.  The arrays are packed and uploaded (upload(arrays, extra_bytes) ->
+    (flat device tensor with extra_bytes spare bytes behind the packed images, descs); default: pack_images + a fresh tensor); a clean
+    image of another size is then resized by uwm_resize_u8 (LINEAR: cv2.resize's default, as the reference calls it) into the spare
+    bytes, one launch per such image.  -> (flat device tensor, clean_descs) for device_pair_mask: h == 0 where cleans[i] is None;
+    (None, None) when every entry is None."""
+    import ctypes as C
+    from . import _lib as L
+    have = [i for i, c in enumerate(cleans) if c is not None]
+    if not have:
+        return None, None
+    arrays = [np.ascontiguousarray(cleans[i]) for i in have]
+    for i, a in zip(have, arrays):
+        if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
+            raise ValueError(f"clean image {i} has shape {a.shape}, dtype {a.dtype}: expected uint8 (h, w, 3)")
+    odd = [(k, i) for k, i in enumerate(have) if arrays[k].shape[:2] != (int(wm_descs[i]["h"]), int(wm_descs[i]["w"]))]
+    spare = [(int(wm_descs[i]["h"]) * int(wm_descs[i]["w"]) * 3 + 3) // 4 * 4 for _, i in odd]
+    if upload is None:
+        def upload(arrs, extra):
+            packed, d, _ = pack_images(arrs)
+            dev = torch.empty(packed.numel() + extra, dtype=torch.uint8, device=device)
+            dev[:packed.numel()].copy_(packed, non_blocking=True)
+            return dev, d
+    dev, d = upload(arrays, sum(spare))
+    used = dev.numel() - sum(spare)
+    cd = np.zeros(len(cleans), DESC_DTYPE)
+    for k, i in enumerate(have):
+        cd[i] = d[k]
+    if odd:
+        dd = descs_tensor(d, dev.device)
+        off = used
+        with L.on_device(dev):
+            for (k, i), nbytes in zip(odd, spare):
+                h, w = int(wm_descs[i]["h"]), int(wm_descs[i]["w"])
+                L.check(L.lib().uwm_resize_u8(C.c_void_p(dev.data_ptr()), used, C.c_void_p(dd.data_ptr() + k * DESC_DTYPE.itemsize), 1, 3, h, w,
+                                              INTERP["linear"], C.c_void_p(dev.data_ptr() + off), C.c_void_p(L.stream_ptr(dev.device))),
+                        ValueError)
+                cd[i] = (off, h, w)
+                off += nbytes
+    return dev, cd
+
+
+PAIR_IMAGE_EXTENSIONS = (".jpg", ".jpeg", ".png", ".bmp", ".tiff", ".tif")      # the reference's _collect_image_files
+
+
+class RawPairDataset(Dataset):
+    """The reference's dataset contract, decoded and nothing else: roots = [DATA.ROOT_DIR] + DATA.ADDITIONAL_ROOT_DIRS, each with
+    watermarked/, clean/ and masks/.  The file list is every image file of every watermarked/ directory, sorted by path
+    (dataset.py:57-69).  An image's mask is <stem>.png in the FIRST masks/ directory (in root order) that has a readable one; failing
+    that, its clean counterpart is the file of the SAME NAME in the first clean/ directory that has a readable one
+    (dataset.py:158-195).  Items are (image uint8 (h, w, 3) RGB, mask uint8 (h, w) or None, clean uint8 (h', w', 3) or None); the
+    clean image is only read when there is no mask.  DeviceInputPipeline derives the missing masks on the device with
+    `mask_threshold` (DATA.GENERATE_MASK_THRESHOLD); an image with neither gets a zero mask."""
+
+    def __init__(self, roots, mask_threshold):
+        from PIL import Image  # noqa: F401
+        self.roots = [roots] if isinstance(roots, (str, os.PathLike)) else list(roots)
+        if not self.roots:
+            raise ValueError("RawPairDataset: no root directory")
+        self.mask_threshold = int(mask_threshold)
+        if not 0 <= self.mask_threshold <= 255:
+            raise ValueError(f"RawPairDataset: mask_threshold must be 0..255 (got {mask_threshold})")
+        files = []
+        for root in self.roots:
+            wd = os.path.join(root, "watermarked")
+            if os.path.isdir(wd):
+                files += [os.path.join(wd, f) for f in os.listdir(wd) if f.lower().endswith(PAIR_IMAGE_EXTENSIONS)]
+        self.files = sorted(files)
+        self.mask_dirs = [os.path.join(r, "masks") for r in self.roots]
+        self.clean_dirs = [os.path.join(r, "clean") for r in self.roots]
+
+    def __len__(self):
+        return len(self.files)
+
+    def mask_paths(self, i):
+        """the existing mask files of image i, in lookup order"""
+        name = os.path.splitext(os.path.basename(self.files[i]))[0] + ".png"
+        return [p for p in (os.path.join(d, name) for d in self.mask_dirs) if os.path.exists(p)]
+
+    def clean_paths(self, i):
+        name = os.path.basename(self.files[i])
+        return [p for p in (os.path.join(d, name) for d in self.clean_dirs) if os.path.exists(p)]
+
+    def missing_masks(self):
+        """indices of the images without a mask file"""
+        return [i for i in range(len(self.files)) if not self.mask_paths(i)]
+
+    @staticmethod
+    def _read(paths, mode):
+        from PIL import Image
+        for p in paths:
+            try:
+                return np.asarray(Image.open(p).convert(mode), dtype=np.uint8)
+            except (OSError, ValueError):          # unreadable: the reference goes on to the next directory
+                continue
+        return None
+
+    def __getitem__(self, i):
+        from PIL import Image
+        img = np.asarray(Image.open(self.files[i]).convert("RGB"), dtype=np.uint8)
+        m = self._read(self.mask_paths(i), "L")
+        clean = self._read(self.clean_paths(i), "RGB") if m is None else None
+        return img, m, clean
+
+
 class DeviceU8Dataset(Dataset):
     """A dataset of (normalised fp32 image, {0,1} mask) pairs (SyntheticWatermarkDataset) converted ONCE to uint8 tensors on the
     device: images (n, S, S, C), masks (n, S, S) in {0, 255}.  Items are indices; DeviceInputPipeline gathers them on the device."""
@@ -620,16 +779,19 @@ def list_collate(batch):
 class DeviceInputPipeline:
     """Batches of a raw dataset -> what Trainer.step takes, on the device.  Raw folder items (uint8 arrays of any size) are packed
     into persistent pinned buffers (pack_images), uploaded and resized to size x size by uwm_resize_u8 — linear for the image,
-    nearest for the mask (the reference's A.Resize); DeviceU8Dataset items are gathered.  Training batches then go through
+    nearest for the mask (the reference's A.Resize); RawPairDataset items (image, mask or None, clean or None) get their missing masks
+    from uwm_pair_mask_u8 at the image's own size first; DeviceU8Dataset items are gathered.  Training batches then go through
     device_augment with parameters drawn from `generator`, validation batches through device_preprocess (get_val_transform).
     recipe 'transparent_watermark' (sample_transparent_recipe) sends the augmented uint8 images through device_jpeg, which normalises."""
 
-    def __init__(self, size, device, source=None, recipe="basic", mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    def __init__(self, size, device, source=None, recipe="basic", mean=IMAGENET_MEAN, std=IMAGENET_STD, mask_threshold=None):
         self.size, self.device, self.source, self.recipe = int(size), torch.device(device), source, recipe
         self.mean, self.std = mean, std
-        self._pin, self._sent = [None, None], [None, None]
+        self.mask_threshold = mask_threshold if mask_threshold is not None else getattr(source, "mask_threshold", None)
+        self._pin, self._sent = [None, None, None], [None, None, None]
 
-    def _upload(self, arrays, slot):
+    def _upload(self, arrays, slot, extra=0):
+        """extra: spare bytes behind the packed images in the device tensor"""
         need = sum((a.size + 3) // 4 * 4 for a in arrays)
         buf = self._pin[slot]
         if buf is None or buf.numel() < need:
@@ -638,7 +800,11 @@ class DeviceInputPipeline:
         else:
             self._sent[slot].synchronize()                   # the previous batch's upload has left the buffer
         packed, descs, _ = pack_images(arrays, out=buf)
-        dev = packed.to(self.device, non_blocking=True)
+        if extra:
+            dev = torch.empty(packed.numel() + extra, dtype=torch.uint8, device=self.device)
+            dev[:packed.numel()].copy_(packed, non_blocking=True)
+        else:
+            dev = packed.to(self.device, non_blocking=True)
         self._sent[slot].record(torch.cuda.current_stream(self.device))
         return dev, descs
 
@@ -647,13 +813,23 @@ class DeviceInputPipeline:
         if isinstance(self.source, DeviceU8Dataset):
             idx = torch.as_tensor([int(i) for i in items], device=self.device)
             return self.source.images[idx], self.source.masks[idx]
-        imgs = [np.ascontiguousarray(i) for i, _ in items]; masks = [np.ascontiguousarray(m)[..., None] for _, m in items]
+        imgs = [np.ascontiguousarray(it[0]) for it in items]
+        cleans = [(it[2] if it[1] is None else None) if len(it) > 2 else None for it in items]      # (a file mask wins over a clean image)
+        # an image without a mask file uploads zeros: they stay where there is no clean image either
+        masks = [np.ascontiguousarray(it[1])[..., None] if it[1] is not None else np.zeros(a.shape[:2] + (1,), np.uint8)
+                 for it, a in zip(items, imgs)]
         for i, (a, m) in enumerate(zip(imgs, masks)):
             if a.shape[:2] != m.shape[:2]:
                 raise ValueError(f"image {i} is {a.shape[:2]}, its mask {m.shape[:2]}")
+        generate = any(c is not None for c in cleans)
+        if generate and self.mask_threshold is None:
+            raise ValueError("items with a clean image and no mask need mask_threshold (DATA.GENERATE_MASK_THRESHOLD)")
         with torch.cuda.device(self.device):
             pi, di = self._upload(imgs, 0)
             pm, dm = self._upload(masks, 1)
+            if generate:
+                pc, dc = stage_clean(cleans, di, self.device, lambda arrs, extra: self._upload(arrs, 2, extra))
+                device_pair_mask(pi, di, pc, dc, self.mask_threshold, True, pm, dm)
             x = device_resize(pi, di, self.size, imgs[0].shape[2], "linear")
             m = device_resize(pm, dm, self.size, 1, "nearest")
         return x, m.view(len(items), self.size, self.size)
