@@ -221,6 +221,41 @@ int  uwm_pair_mask_u8(const uint8_t* wm, size_t wm_bytes, const uwm_image_desc* 
                       int N, int C /* 3 */, int threshold /* 0..255 */, int open,
                       uint8_t* mask, size_t mask_bytes, const uwm_image_desc* mask_descs, uwm_stream stream);
 
+/* The dataset filter: the reference's src/scripts/watermark_filter.py (predict_mask, _post_process_mask, has_watermark), which sorts a
+ * folder by the share of each image that the model calls watermark.  Only one integer per image is wanted, so the mask need not leave
+ * the kernel.  Image i of a ragged batch, at its OWN size (h_i, w_i) = out_descs[i], from the logit plane [N][h][w] (element stride ld):
+ *     p = 1.f / (1.f + expf(-logit))                       at each of the four taps: sigmoid FIRST          (watermark_filter.py:136)
+ *     v = bilinear(p)                                      uwm_resize_threshold's interpolation, unchanged: same coordinates, clamps
+ *                                                          and order of operations, horizontal inside vertical   (:147, cv2.resize)
+ *     m = v > threshold ? 255 : 0                                                                                (:150)
+ *     post_process != 0:  m = close(open(m, E), E), E = ELLIPSE(3,3) = the cross, one iteration each            (:164-171)
+ *                         with the morphology of uwm_op_morph: an erosion ignores pixels outside the image, a dilation reads its
+ *                         input plane as 0 there
+ *     counts[i] = {number of pixels with m != 0, h_i * w_i};  mask != NULL: m is also stored at mask + out_descs[i].offset
+ *   This is NOT uwm_resize_threshold(apply_sigmoid = 1), which interpolates the logits and applies the sigmoid afterwards; the two
+ *   agree without a resize only.  Logits -1 and +5 with weight 0.25 on the second: sigmoid(0.5) = 0.62 > 0.5 logit first,
+ *   0.75 * 0.269 + 0.25 * 0.993 = 0.45 < 0.5 probability first.  uwm_resize_threshold* keep their order.
+ * A misfit image (a side outside 1 .. 2^30 or, with a mask, a region that leaves [0, mask_bytes)) gets counts[i] = {0, 0} and costs
+ * that image only; its mask region is zeroed if that region fits.  mask == NULL: mask_bytes and the offsets are not read.
+ * uwm_filter_workspace_bytes(N): the bytes of per-workgroup partial counts (N * 64 * 8; 0 and a message for N < 1 or too large); the
+ * counts are integer sums in a fixed order, the same on every run.  uwm_prob_mask_count_ragged: two launches (N * 64 workgroups, then
+ * the sum) on the caller's stream, no host synchronisation: capturable, and one captured call serves every batch of N images.
+ * uwm_filter_images_u8 = uwm_op_resize_norm_u8_nhwc4 into the forward's input -> eval forward (frozen or not) ->
+ * uwm_prob_mask_count_ragged; logits / workspace / N, H, W as uwm_predict_images_u8 (the same uwm_predict_workspace_bytes).
+ * Both check every argument before any launch: nulls, N >= 1, ld >= 1, a finite threshold, logits 4-byte, descriptors / counts /
+ * filter workspace 8-byte aligned, the workspace sizes.  No read leaves the inputs, no write leaves [mask, mask + mask_bytes),
+ * counts[0 .. 2N) or the workspaces. */
+size_t uwm_filter_workspace_bytes(int N);
+int  uwm_prob_mask_count_ragged(const float* logits, int ld, int N, int h, int w, const uwm_image_desc* out_descs, float threshold,
+                                int post_process, uint8_t* mask /* may be NULL */, size_t mask_bytes,
+                                long long* counts /* device, [N][2] = {foreground pixels, h_i*w_i} */,
+                                void* workspace, size_t workspace_bytes, uwm_stream stream);
+int  uwm_filter_images_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, const uwm_image_desc* in_descs, const float* mean,
+                          const float* std, float threshold, int post_process, const uwm_image_desc* out_descs,
+                          uint8_t* mask /* may be NULL */, size_t mask_bytes, long long* counts, float* logits, void* workspace,
+                          size_t workspace_bytes, void* filter_workspace, size_t filter_workspace_bytes, int N, int H, int W,
+                          uwm_stream stream);
+
 /* Backward of the last training forward held in `workspace`; writes (overwrites) the gradient arena
  * ranges of stages [stage_begin, stage_end).  Call with (0, uwm_num_stages) for everything, or stage
  * by stage to overlap gradient all-reduce with the rest of the backward. */

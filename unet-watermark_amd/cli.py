@@ -405,8 +405,36 @@ def masks_command(args):
     return res
 
 
+def filter_command(args):
+    """The reference's src/scripts/watermark_filter.py on the device: one line per kept or moved file, then the stats."""
+    from .filter import WatermarkFilter
+    if not os.path.isdir(args.input):
+        raise SystemExit(f"filter: input directory not found: {args.input}")
+    if not os.path.exists(args.model):
+        raise SystemExit(f"filter: model file not found: {args.model}")
+    if args.config and not os.path.exists(args.config):
+        raise SystemExit(f"filter: config file not found: {args.config}")
+    if not torch.cuda.is_available():
+        raise SystemExit("filter needs a HIP device (this path has no CPU fallback)")
+    cfg = get_cfg_defaults()
+    if args.config:
+        update_config(cfg, args.config)
+    if args.encoder:
+        cfg.MODEL.ENCODER_NAME = args.encoder
+    flt = WatermarkFilter(args.model, None, "cuda", args.threshold, args.batch_size, config=cfg)
+    stats = flt.filter_images(args.input, args.no_watermark_dir, args.dry_run, args.delete)
+    print("=" * 50)
+    print(f"total: {stats['total']}  with watermark: {stats['with_watermark']}  without: {stats['without_watermark']}  "
+          f"moved/deleted: {stats['moved']}  errors: {stats['errors']}")
+    if args.dry_run:
+        print("dry run: no file was touched")
+    elif not args.no_watermark_dir and not args.delete:
+        print("report only: give --no-watermark-dir DIR to move the images without a watermark, or --delete to delete them")
+    return stats
+
+
 def build_parser():
-    ap = argparse.ArgumentParser(description="MI355X-native U-Net watermark segmentation (train | predict)")
+    ap = argparse.ArgumentParser(description="MI355X-native U-Net watermark segmentation (train | masks | filter | predict)")
     sub = ap.add_subparsers(dest="command")
     tp = sub.add_parser("train")
     tp.add_argument("--config", type=str, default=None)
@@ -449,6 +477,22 @@ def build_parser():
     mp.add_argument("--config", type=str, default=None)
     mp.add_argument("--threshold", type=int, default=None, help="DATA.GENERATE_MASK_THRESHOLD (0..255)")
     mp.add_argument("--batch-size", type=int, default=None, help="pairs per launch (default 16)")
+    fp = sub.add_parser("filter", help="sort a folder by predicted watermark area (the reference's scripts/watermark_filter.py)",
+                        description="Predict every image's watermark mask on the device and move away (or delete) the images whose mask "
+                                    "covers less than --threshold of the image.  Two deliberate departures from the reference's script: "
+                                    "an image that cannot be read counts under 'errors' and stays where it is (the reference treats it "
+                                    "as 'no watermark' and moves or deletes it), and files are deleted only with --delete (the reference "
+                                    "deletes whenever no target directory is given); with neither --no-watermark-dir nor --delete the "
+                                    "run only reports.")
+    fp.add_argument("--input", type=str, required=True, help="the folder of images (jpg, jpeg, png, bmp, tiff, tif; either letter case)")
+    fp.add_argument("--model", type=str, required=True); fp.add_argument("--config", type=str, default=None)
+    fp.add_argument("--encoder", type=str)
+    fp.add_argument("--threshold", type=float, default=0.0001, help="least share of watermark pixels that keeps an image (the script's default)")
+    act = fp.add_mutually_exclusive_group()
+    act.add_argument("--no-watermark-dir", type=str, default=None, help="move the images without a watermark here")
+    act.add_argument("--delete", action="store_true", help="delete the images without a watermark (never done without this flag)")
+    fp.add_argument("--dry-run", action="store_true", help="report what would be moved or deleted; touch nothing")
+    fp.add_argument("--batch-size", type=int, default=None, help="images per captured call (default PREDICT.BATCH_SIZE)")
     pp = sub.add_parser("predict")
     pp.add_argument("--input", type=str, required=True); pp.add_argument("--output", type=str, required=True)
     pp.add_argument("--model", type=str, required=True); pp.add_argument("--config", type=str, default=None)
@@ -472,4 +516,6 @@ def main(argv=None):
         return predict_command(args)
     if args.command == "masks":
         return masks_command(args)
+    if args.command == "filter":
+        return filter_command(args)
     ap.print_help()

@@ -13,7 +13,7 @@ namespace uwm {
 namespace {
 
 constexpr int kPW = 128;                   // plane columns of a tile: image columns x0 - 4 .. x0 + 123, four to a dword
-constexpr int kGroups = kPW / 4;           // dwords per plane row
+constexpr int kGroups = kPlaneGroups;      // dwords per plane row (column_mask, cross, store_px4: uwm_kernels.h)
 constexpr int kTW = kPairMaskTileW;        // mask columns of a tile = plane columns 4 .. 123 (the halo of 2 is rounded up to a dword)
 constexpr int kTH = kPairMaskTileH;        // mask rows of a tile
 constexpr int kTRows = kTH + 4;            // thresholded plane: rows y0 - 2 .. y0 + kTH + 1
@@ -25,15 +25,6 @@ static_assert(kTW == kPW - 8 && kGroups == 32 && kRawDwords == 97, "tile geometr
 __device__ __forceinline__ bool pair_desc_ok(const ImageDesc& d, int C, size_t bytes) {
   if (d.h < 1 || d.w < 1 || d.h > (1 << 30) || d.w > (1 << 30) || d.offset < 0 || (unsigned long long)d.offset > bytes) return false;
   return (unsigned long long)d.h * (unsigned long long)d.w <= (bytes - (unsigned long long)d.offset) / (unsigned)C;
-}
-
-// bytes k = 0..3 of the result are 0xFF where 0 <= x + k < w
-__device__ __forceinline__ uint32_t column_mask(int x, int w) {
-  if (x >= 0 && x + 3 < w) return 0xFFFFFFFFu;
-  uint32_t m = 0u;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) if (x + k >= 0 && x + k < w) m |= 0xFFu << (8 * k);
-  return m;
 }
 
 // one image row's bytes [g0, g0 + nbytes) -> LDS as aligned-down dwords, one per lane of ONE wave (coalesced); byte k of the range is
@@ -75,24 +66,6 @@ __device__ __forceinline__ uint32_t diff_gray_threshold(const Px4& a, const Px4&
     if (g > thr) m |= 0xFFu << (8 * k);
   }
   return m;
-}
-
-// the cross (cv2's 3 x 3 ELLIPSE) on a plane of byte pixels, four to a dword: centre, up, down, left, right of dword (r, g)
-template <bool AND>
-__device__ __forceinline__ uint32_t cross(const uint32_t (*p)[kGroups], int r, int g) {
-  const uint32_t c = p[r][g], up = p[r - 1][g], dn = p[r + 1][g];
-  const uint32_t prev = g > 0 ? p[r][g - 1] : 0u, next = g < kGroups - 1 ? p[r][g + 1] : 0u;      // (columns 0 and 127 feed no mask pixel)
-  const uint32_t lf = (c << 8) | (prev >> 24), rt = (c >> 8) | (next << 24);
-  return AND ? (c & up & dn & lf & rt) : (c | up | dn | lf | rt);
-}
-
-// four mask pixels (x .. x + 3 of row y) of an h x w mask at out: one dword where it is aligned and whole, else bytes
-__device__ __forceinline__ void store_px4(uint8_t* __restrict__ out, int y, int x, int w, uint32_t v) {
-  if (x >= w) return;
-  uint8_t* p = out + (size_t)y * w + x;
-  if (x + 3 < w && ((uintptr_t)p & 3) == 0) { *(uint32_t*)p = v; return; }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) if (x + k < w) p[k] = (uint8_t)(v >> (8 * k));
 }
 
 __global__ __launch_bounds__(256) void pair_mask_u8_kernel(const uint8_t* __restrict__ wm, size_t wm_bytes, const ImageDesc* __restrict__ wm_descs,

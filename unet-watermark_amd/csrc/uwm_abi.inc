@@ -318,6 +318,62 @@ int uwm_predict_images_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, co
   LCHK(launch_resize_threshold_ragged(lg, h->CP, N, H, W, (const ImageDesc*)out_descs, threshold, apply_sigmoid, mask, mask_bytes, st));
   return 0;
 }
+// ---- the dataset filter (filter_u8.hip): every argument is checked here, before any launch
+size_t uwm_filter_workspace_bytes(int N) {
+  const size_t need = filter_workspace_bytes(N);
+  if (!need) fail("uwm_filter_workspace_bytes: N must be 1..%d (got %d)", 2147483647 / kFilterBlocks, N);
+  return need;
+}
+static int filter_args_check(const char* fn, int N, const void* out_descs, float threshold, const void* mask, size_t mask_bytes,
+                             const void* counts, const void* fws, size_t fws_bytes) {
+  if (!out_descs || !counts || !fws) return fail("%s: null argument", fn);
+  if (N < 1) return fail("%s: N must be >= 1 (got %d)", fn, N);
+  if (N > 2147483647 / kFilterBlocks) return fail("%s: N too large for one launch (%d)", fn, N);
+  if (!std::isfinite(threshold)) return fail("%s: threshold must be finite", fn);
+  if (mask && mask_bytes < 1) return fail("%s: mask_bytes must be >= 1 with a mask", fn);
+  if (((uintptr_t)out_descs | (uintptr_t)counts | (uintptr_t)fws) & 7) return fail("%s: descriptors, counts and the filter workspace must be 8-byte aligned", fn);
+  const size_t need = filter_workspace_bytes(N);
+  if (fws_bytes < need) return fail("%s: filter workspace too small (%zu < %zu bytes)", fn, fws_bytes, need);
+  return 0;
+}
+int uwm_prob_mask_count_ragged(const float* logits, int ld, int N, int h, int w, const uwm_image_desc* out_descs, float threshold,
+                               int post_process, uint8_t* mask, size_t mask_bytes, long long* counts, void* workspace,
+                               size_t workspace_bytes, uwm_stream stream) {
+  if (!logits) return fail("uwm_prob_mask_count_ragged: null argument");
+  if (filter_args_check("uwm_prob_mask_count_ragged", N, out_descs, threshold, mask, mask_bytes, counts, workspace, workspace_bytes)) return 1;
+  if (h < 1 || w < 1 || ld < 1) return fail("uwm_prob_mask_count_ragged: h, w and ld must be >= 1 (got %d, %d, %d)", h, w, ld);
+  if ((uintptr_t)logits & 3) return fail("uwm_prob_mask_count_ragged: logits must be 4-byte aligned");
+  LCHK(launch_prob_mask_count(logits, ld, N, h, w, (const ImageDesc*)out_descs, threshold, post_process != 0, mask, mask_bytes, counts,
+                              workspace, workspace_bytes, (hipStream_t)stream));
+  return 0;
+}
+int uwm_filter_images_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, const uwm_image_desc* in_descs, const float* mean,
+                         const float* std, float threshold, int post_process, const uwm_image_desc* out_descs, uint8_t* mask,
+                         size_t mask_bytes, long long* counts, float* logits, void* ws, size_t ws_bytes, void* fws, size_t fws_bytes,
+                         int N, int H, int W, uwm_stream stream) {
+  if (!h || !src || !in_descs || !mean || !std || !ws) return fail("uwm_filter_images_u8: null argument");
+  if (filter_args_check("uwm_filter_images_u8", N, out_descs, threshold, mask, mask_bytes, counts, fws, fws_bytes)) return 1;
+  if (check_shape(N, H, W)) return 1;
+  if (!h->params || !h->buffers) return fail("uwm_filter_images_u8: call uwm_bind first");
+  if (src_bytes < 1) return fail("uwm_filter_images_u8: src_bytes must be >= 1");
+  const int C = h->desc.in_channels;
+  if (C < 1 || C > 4) return fail("uwm_filter_images_u8: the model takes %d channels; images have 1..4", C);
+  for (int c = 0; c < C; ++c) if (!(std[c] > 0.f)) return fail("uwm_filter_images_u8: std[%d] must be positive", c);
+  if ((uintptr_t)src & 3) return fail("uwm_filter_images_u8: src must be 4-byte aligned");
+  if ((uintptr_t)in_descs & 7) return fail("uwm_filter_images_u8: descriptors must be 8-byte aligned");
+  if (((uintptr_t)logits | (uintptr_t)ws) & 15) return fail("uwm_filter_images_u8: logits and workspace must be 16-byte aligned");
+  const size_t need = uwm_predict_workspace_bytes(h, N, H, W, logits ? 0 : 1);
+  if (ws_bytes < need) return fail("uwm_filter_images_u8: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+  float* lg = logits ? logits : (float*)ws + h->plan.bytes / sizeof(float);      // (no caller buffer: behind the plan)
+  h->have_fwd = false;
+  DeviceGuard guard(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  LCHK(launch_resize_norm_u8_nhwc4(src, src_bytes, (const ImageDesc*)in_descs, N, C, H, W, mean, std, (float*)ws + h->plan.x4, st));
+  if (do_forward(h, nullptr, lg, (float*)ws, N, H, W, 0, st)) return 1;
+  LCHK(launch_prob_mask_count(lg, h->CP, N, H, W, (const ImageDesc*)out_descs, threshold, post_process != 0, mask, mask_bytes, counts, fws,
+                              fws_bytes, st));
+  return 0;
+}
 int uwm_op_preprocess_u8_nhwc4(const uint8_t* images, long long npix, int C, const float* mean, const float* std, float* out,
                                uwm_stream stream) {
   if (!images || !mean || !std || !out || npix < 1 || C < 1 || C > 4) return fail("uwm_op_preprocess_u8_nhwc4: bad argument");

@@ -450,6 +450,56 @@ constexpr int kPairMaskTileW = 120, kPairMaskTileH = 32;      // mask pixels of 
 hipError_t launch_pair_mask_u8(const uint8_t* wm, size_t wm_bytes, const ImageDesc* wm_descs, const uint8_t* clean, size_t clean_bytes,
                                const ImageDesc* clean_descs, int N, int threshold, int open, uint8_t* mask, size_t mask_bytes,
                                const ImageDesc* mask_descs, hipStream_t st);
+// planes of byte pixels (0 / 255) in LDS, four to a dword, kPlaneGroups dwords to a row: what pair_mask_u8.hip and filter_u8.hip share
+constexpr int kPlaneGroups = 32;
+// bytes k = 0..3 of the result are 0xFF where 0 <= x + k < w
+__device__ __forceinline__ uint32_t column_mask(int x, int w) {
+  if (x >= 0 && x + 3 < w) return 0xFFFFFFFFu;
+  uint32_t m = 0u;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) if (x + k >= 0 && x + k < w) m |= 0xFFu << (8 * k);
+  return m;
+}
+// the cross (cv2's 3 x 3 ELLIPSE): centre, up, down, left, right of dword (r, g); AND = erosion, else dilation.  The columns left of
+// group 0 and right of the last group read as 0, so each pass spoils one more plane column at either end: the halo covers them
+template <bool AND>
+__device__ __forceinline__ uint32_t cross(const uint32_t (*p)[kPlaneGroups], int r, int g) {
+  const uint32_t c = p[r][g], up = p[r - 1][g], dn = p[r + 1][g];
+  const uint32_t prev = g > 0 ? p[r][g - 1] : 0u, next = g < kPlaneGroups - 1 ? p[r][g + 1] : 0u;
+  const uint32_t lf = (c << 8) | (prev >> 24), rt = (c >> 8) | (next << 24);
+  return AND ? (c & up & dn & lf & rt) : (c | up | dn | lf | rt);
+}
+// four mask pixels (x .. x + 3 of row y) of an h x w mask at out: one dword where it is aligned and whole, else bytes
+__device__ __forceinline__ void store_px4(uint8_t* __restrict__ out, int y, int x, int w, uint32_t v) {
+  if (x >= w) return;
+  uint8_t* p = out + (size_t)y * w + x;
+  if (x + 3 < w && ((uintptr_t)p & 3) == 0) { *(uint32_t*)p = v; return; }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) if (x + k < w) p[k] = (uint8_t)(v >> (8 * k));
+}
+// ---- the dataset filter: watermark area of every image of a ragged batch (filter_u8.hip; the rule: include/uwm.h)
+constexpr int kFilterBlocks = 64;                    // workgroups per image, each walking that image's tiles: grid = N * this
+constexpr int kFilterTileW = 120, kFilterTileH = 32; // mask pixels of one tile
+// One output pixel (Y, X) in watermark_filter.py's order: the sigmoid (loss.hip's form) at the four taps FIRST, then resize_logit's
+// interpolation on the four probabilities, with its coordinates, clamps and order of operations
+__device__ __forceinline__ float resize_prob(const float* __restrict__ b, int ld, int h, int w, float sy, float sx, int Y, int X) {
+  float fy = ((float)Y + 0.5f) * sy - 0.5f, fx = ((float)X + 0.5f) * sx - 0.5f;
+  fy = fmaxf(fy, 0.f); fx = fmaxf(fx, 0.f);
+  int y0 = (int)fy, x0 = (int)fx;
+  y0 = min(y0, h - 1); x0 = min(x0, w - 1);
+  const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
+  const float wy = fy - (float)y0, wx = fx - (float)x0;
+  const float v00 = 1.f / (1.f + expf(-b[((size_t)y0 * w + x0) * ld])), v01 = 1.f / (1.f + expf(-b[((size_t)y0 * w + x1) * ld]));
+  const float v10 = 1.f / (1.f + expf(-b[((size_t)y1 * w + x0) * ld])), v11 = 1.f / (1.f + expf(-b[((size_t)y1 * w + x1) * ld]));
+  return (1.f - wy) * ((1.f - wx) * v00 + wx * v01) + wy * ((1.f - wx) * v10 + wx * v11);
+}
+size_t filter_workspace_bytes(int N);                // 0 for N < 1 or a launch too large
+// image i: counts[i] = {foreground pixels, h_i * w_i} of close3(open3(resize(sigmoid(logits_i)) > thr)) (post_process == 0: without
+// the morphology) and, where mask != nullptr, that mask at mask + out_descs[i].offset.  A misfit image counts {0, 0}.  No write
+// leaves [mask, mask + mask_bytes), counts[0 .. 2N) or the workspace
+hipError_t launch_prob_mask_count(const float* logits, int ld, int N, int h, int w, const ImageDesc* out_descs, float thr, int post_process,
+                                  uint8_t* mask, size_t mask_bytes, long long* counts, void* workspace, size_t workspace_bytes,
+                                  hipStream_t st);
 
 // EfficientNet MBConv pieces (mbconv.hip): swish, depthwise k x k conv (weights tap-major [k*k][C]) with static "same"
 // padding (pb = pad at the begin of H and W; the end pad is implied by Ho/Wo), squeeze-and-excitation, block output with drop-connect

@@ -475,6 +475,57 @@ class Unet(nn.Module):
                     SegmentationModelError)
         return (mask, self._logits_view(logits)) if return_logits else mask
 
+    @torch.no_grad()
+    def filter_images_u8(self, packed: torch.Tensor, in_descs: torch.Tensor, out_descs: torch.Tensor, counts: torch.Tensor, n: int,
+                         size, mean, std, threshold: float = 0.5, post_process: bool = True, mask: Optional[torch.Tensor] = None,
+                         return_logits: bool = False):
+        """The reference's watermark_filter.py for a packed ragged batch of n uint8 images (as predict_images_u8 takes it), in ONE
+        library call (uwm_filter_images_u8): resize to `size` + Normalize, eval forward (frozen or not), then per image at its own
+        size sigmoid -> bilinear resize of the PROBABILITIES -> threshold -> [open, close with the 3 x 3 cross] -> the foreground
+        count.  `counts`: an int64 (n, 2) device tensor that receives {foreground pixels, h_i * w_i}; `mask`: absent, no mask is
+        written at all; else the flat uint8 buffer that receives every mask at out_descs' offsets.  Capturable like
+        predict_images_u8.  Returns `counts` [, logits (n,classes,H,W)]."""
+        if self.training:
+            raise RuntimeError("filter_images_u8 is an eval-mode path: call .eval() first")
+        for t in (packed, in_descs, out_descs) + (() if mask is None else (mask,)):
+            self._require_gpu(t)
+            if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+                raise RuntimeError("filter_images_u8 takes flat contiguous uint8 tensors (data.pack_images / data.descs_tensor)")
+        n = int(n)
+        if n < 1 or in_descs.numel() < 16 * n or out_descs.numel() < 16 * n:
+            raise RuntimeError(f"filter_images_u8: {n} images need {16 * n} descriptor bytes each way")
+        self._require_gpu(counts)
+        if counts.dtype != torch.int64 or counts.numel() < 2 * n or not counts.is_contiguous():
+            raise RuntimeError(f"filter_images_u8: counts must be a contiguous int64 tensor of at least ({n}, 2)")
+        h, w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+        self.check_input_shape(torch.empty((0, self.in_channels, h, w)))
+        self._ensure_bound()
+        if self._frozen and not L.lib().uwm_is_frozen(self._h):
+            self._freeze_now(n, h, w)
+        ws = self._workspace(n, h, w, False, logits_inside=not return_logits)
+        need = L.lib().uwm_filter_workspace_bytes(n)
+        if need == 0:
+            raise SegmentationModelError(L.lib().uwm_last_error().decode(errors="replace"))
+        fws = getattr(self, "_filter_ws", None)
+        if fws is None or fws.numel() < need or fws.device != packed.device:
+            fws = self._filter_ws = torch.empty(need, dtype=torch.uint8, device=packed.device)      # (a captured graph's owner keeps its own reference)
+        logits = torch.empty((n, h, w, self._cp), dtype=torch.float32, device=packed.device) if return_logits else None
+        self._fwd_gen += 1
+        if self._n_mb:
+            self._set_drop_connect(n, False, packed.device)
+        c = self.in_channels
+        mean_c = (C.c_float * c)(*[float(v) for v in mean[:c]]); std_c = (C.c_float * c)(*[float(v) for v in std[:c]])
+        with L.on_device(packed):
+            L.check(L.lib().uwm_filter_images_u8(self._h, C.c_void_p(packed.data_ptr()), packed.numel(), C.c_void_p(in_descs.data_ptr()),
+                                                 mean_c, std_c, float(threshold), int(bool(post_process)), C.c_void_p(out_descs.data_ptr()),
+                                                 C.c_void_p(mask.data_ptr() if mask is not None else 0), mask.numel() if mask is not None else 0,
+                                                 C.c_void_p(counts.data_ptr()),
+                                                 C.c_void_p(logits.data_ptr() if logits is not None else 0),
+                                                 C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(fws.data_ptr()), fws.numel(), n, h, w,
+                                                 C.c_void_p(L.stream_ptr(packed.device))),
+                    SegmentationModelError)
+        return (counts, self._logits_view(logits)) if return_logits else counts
+
     def _set_drop_connect(self, n: int, training: bool, device):
         """Draw this step's per-block, per-sample keep masks (efficientnet_pytorch utils.drop_connect: floor(keep_prob +
         U[0,1)) / keep_prob) on the device and hand them to the library; the tensor lives until the next forward."""

@@ -54,6 +54,9 @@ class WatermarkPredictor:
         self._igraph = None                   # predict_images: ONE graph per (N, H, W, apply_sigmoid, threshold), whatever the image sizes
         self._ikey = None
         self._ibuf = self._idesc = self._mdesc = self._mbuf = self._iws = None      # its static staging buffers
+        self._cgraph = None                   # watermark_counts: ONE graph per (N, IMG_SIZE, threshold, post_process, with masks)
+        self._ckey = None
+        self._cbuf = self._cws = None         # its static counts buffer and workspaces
         self._hbuf = self._hevt = None        # pinned host staging of the packed bytes + the event of its last upload
         self.freeze = bool(freeze)
         if self.freeze:
@@ -114,7 +117,7 @@ class WatermarkPredictor:
         captured on the old arena contents go."""
         if self.freeze and not self.model.frozen_serves(n, h, w):
             self.model.freeze(batch_shape=(n, h, w))
-            self._graph = self._gkey = self._ugraph = self._ukey = self._pgraph = self._pkey = self._igraph = self._ikey = None
+            self._graph = self._gkey = self._ugraph = self._ukey = self._pgraph = self._pkey = self._igraph = self._ikey = self._cgraph = self._ckey = None
 
     @torch.no_grad()
     def predict_mask_u8(self, images_u8_nhwc: torch.Tensor, out_size=None, apply_sigmoid: bool = False,
@@ -164,20 +167,12 @@ class WatermarkPredictor:
             return
         cap = max(need, 256 if buf is None else 2 * buf.numel())
         setattr(self, name, torch.zeros(cap, dtype=torch.uint8, device=self.device))
-        self._igraph = self._ikey = None
+        self._igraph = self._ikey = self._cgraph = self._ckey = None
 
-    @torch.no_grad()
-    def predict_images(self, images, apply_sigmoid: bool = False, mask_type: Optional[str] = None, use_graph: bool = True):
-        """uint8 (h_i, w_i, C) images of ANY sizes (arrays or tensors) -> a list of uint8 {0,255} device masks, one per image at its
-        own size: the reference's predict path (src/predict.py:327-335,614-625) device-resident from the image bytes on — cv2's
-        INTER_LINEAR resize to IMG_SIZE (A.Resize) + Normalize, eval forward, bilinear resize of the logits back to (h_i, w_i) +
-        threshold, in ONE library call (uwm_predict_images_u8).  The per-image geometry lives in device memory, so one captured
-        graph per (N, IMG_SIZE, apply_sigmoid) serves every batch of N images; it is re-captured only when a staging buffer had
-        to grow or the frozen arena was re-made.  mask_type 'watermark' | 'text' | 'mixed': each mask then goes through
-        optimize_mask at its own size, outside the graph."""
+    def _stage_images(self, images):
+        """pack `images` into the static staging buffers (_ibuf, _idesc, _mdesc; _mbuf sized for their masks) -> (n, IMG_SIZE, descs,
+        mask descs, areas, mask bytes)"""
         from .data import descs_tensor, pack_images
-        if mask_type is not None:
-            mask_type_code(mask_type)
         # pack into ONE persistent pinned buffer (pinned allocation is expensive), grown geometrically; the previous batch's upload
         # from it must have finished before it is overwritten
         need = sum((int(np.prod(im.shape)) + 3) // 4 * 4 for im in images)
@@ -200,6 +195,20 @@ class WatermarkPredictor:
         self._hevt.record()
         self._idesc[:16 * n].copy_(descs_tensor(descs))
         self._mdesc[:16 * n].copy_(descs_tensor(mdescs))
+        return n, s, descs, mdescs, areas, mask_bytes
+
+    @torch.no_grad()
+    def predict_images(self, images, apply_sigmoid: bool = False, mask_type: Optional[str] = None, use_graph: bool = True):
+        """uint8 (h_i, w_i, C) images of ANY sizes (arrays or tensors) -> a list of uint8 {0,255} device masks, one per image at its
+        own size: the reference's predict path (src/predict.py:327-335,614-625) device-resident from the image bytes on — cv2's
+        INTER_LINEAR resize to IMG_SIZE (A.Resize) + Normalize, eval forward, bilinear resize of the logits back to (h_i, w_i) +
+        threshold, in ONE library call (uwm_predict_images_u8).  The per-image geometry lives in device memory, so one captured
+        graph per (N, IMG_SIZE, apply_sigmoid) serves every batch of N images; it is re-captured only when a staging buffer had
+        to grow or the frozen arena was re-made.  mask_type 'watermark' | 'text' | 'mixed': each mask then goes through
+        optimize_mask at its own size, outside the graph."""
+        if mask_type is not None:
+            mask_type_code(mask_type)
+        n, s, descs, mdescs, areas, mask_bytes = self._stage_images(images)
         run = lambda: self.model.predict_images_u8(self._ibuf, self._idesc, self._mdesc, self._mbuf, n, (s, s), IMAGENET_MEAN,
                                                    IMAGENET_STD, self.threshold, apply_sigmoid)
         if not use_graph:
@@ -220,3 +229,41 @@ class WatermarkPredictor:
         if mask_type is not None:
             masks = [optimize_mask(m, mask_type) for m in masks]
         return masks
+
+    @torch.no_grad()
+    def watermark_counts(self, images, post_process: Optional[bool] = None, return_masks: bool = False, use_graph: bool = True):
+        """uint8 (h_i, w_i, C) images of ANY sizes -> an int64 (N, 2) HOST array {watermark pixels, h_i * w_i} per image: the
+        reference's src/scripts/watermark_filter.py (predict_mask + has_watermark's count) in ONE library call
+        (uwm_filter_images_u8) — resize + Normalize, eval forward, then at each image's own size sigmoid -> bilinear resize of the
+        PROBABILITIES -> > PREDICT.THRESHOLD -> [open, close with the 3 x 3 cross] -> count.  post_process=None reads
+        cfg.PREDICT.POST_PROCESS.  The staging and the one-graph-per-(N, IMG_SIZE, threshold, post_process) scheme are
+        predict_images'; the result comes back in one device-to-host copy of 16 N bytes, and no mask is written unless
+        return_masks, which adds the list of uint8 {0,255} device masks."""
+        post = bool(self.cfg.PREDICT.POST_PROCESS if post_process is None else post_process)
+        n, s, descs, mdescs, areas, mask_bytes = self._stage_images(images)
+        counts = None
+
+        def run():
+            return self.model.filter_images_u8(self._ibuf, self._idesc, self._mdesc, counts, n, (s, s), IMAGENET_MEAN, IMAGENET_STD,
+                                               self.threshold, post, self._mbuf if return_masks else None)
+        if not use_graph:
+            counts = torch.zeros((n, 2), dtype=torch.int64, device=self.device)
+            run()
+        else:
+            key = (n, s, s, float(self.threshold), post, bool(return_masks))      # (threshold, post_process and the mask pointer are captured arguments)
+            if self._ckey != key or self._cgraph is None:
+                self._refreeze_for(n, s, s)
+                counts = self._cbuf = torch.zeros((n, 2), dtype=torch.int64, device=self.device)
+                run()                                 # eager warm-up: plans the workspace, sets kernel attributes
+                torch.cuda.synchronize(self.device)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    run()
+                self._cgraph, self._ckey, self._cws = g, key, (self.model._ws, self.model._filter_ws)
+            counts = self._cbuf
+            self._cgraph.replay()
+        host = counts.cpu().numpy()
+        if not return_masks:
+            return host
+        out = self._mbuf[:mask_bytes].clone()         # (the staging buffer is overwritten by the next call)
+        return host, [out[int(o): int(o) + int(a)].view(int(h), int(w)) for o, a, h, w in zip(mdescs["offset"], areas, descs["h"], descs["w"])]
