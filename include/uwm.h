@@ -221,6 +221,88 @@ int  uwm_pair_mask_u8(const uint8_t* wm, size_t wm_bytes, const uwm_image_desc* 
                       int N, int C /* 3 */, int threshold /* 0..255 */, int open,
                       uint8_t* mask, size_t mask_bytes, const uwm_image_desc* mask_descs, uwm_stream stream);
 
+/* Logo-watermarked training samples: the LOGO branch of the reference's src/scripts/gen_data.py (apply_watermark_effects,
+ * resize_watermark, generate_multiple_watermarks_image / generate_watermarked_image, calculate_overlap_area, and main()'s
+ * single/multi and transparent/normal choices).  Text and mixed watermarks, the JPEG quality=95 save and a device-resident logo bank
+ * are NOT served.  A JOB is one logo on one image.  The HOST draws every random number, computes every size and does the placement
+ * loop (data.sample_synth_jobs); the device only executes descriptors, so a batch is a pure function of its inputs.  Stages, in
+ * order, on an RGBA patch (uint8, R G B A interleaved); MULDIV255(x, y) = (t = x*y + 128, ((t >> 8) + t) >> 8):
+ *   1 RESIZE to (w1, h1) = Image.resize(LANCZOS) on RGBA.  Equal size: a copy.  Else premultiply c = MULDIV255(c, a); the horizontal
+ *     pass, then the vertical pass, each to uint8 and each skipped when its side does not change; unpremultiply: a == 0 or 255
+ *     copies, else min(255, (255*c) / a) (integer division).  Coefficients per axis (in -> out), all float64, Pillow's
+ *     precompute_coeffs: scale = in/out; fs = max(scale, 1.0); support = 3.0*fs; ksize = (int)ceil(support)*2 + 1; ss = 1.0/fs;
+ *     for output xx: center = (xx + 0.5)*scale; xmin = max((int)(center - support + 0.5), 0);
+ *     xmax = min((int)(center + support + 0.5), in) - xmin; w[x] = lanczos((x + xmin - center + 0.5)*ss);
+ *     lanczos(x) = sinc(x)*sinc(x/3) on -3 <= x < 3, else 0; sinc(0) = 1, sinc(x) = sin(pi*x)/(pi*x); ww = the sequential sum of w;
+ *     w /= ww when ww != 0; k = (int)(w*2^22 + 0.5), or - 0.5 for w < 0.  Pixel: clip8(((1 << 21) + sum k*p) >> 22).
+ *   2 ROTATE (rotate != 0) = Image.rotate(angle, expand=True), NEAREST, fill 0.  Host, as Image.rotate: a = -radians(angle % 360);
+ *     rot = [round(cos a, 15), round(sin a, 15), 0, round(-sin a, 15), round(cos a, 15), 0] about the centre (w/2, h/2); (w2, h2) from
+ *     ceil(max) - floor(min) of the four transformed corners; the final translation.  angle % 360 == 0 is the identity (rotate = 0).
+ *     Device, Pillow's affine_fixed, FIX(v) = floor(v*65536 + 0.5): a2 = FIX(m2 + m0/2 + m1/2), a5 = FIX(m5 + m3/2 + m4/2),
+ *     xin = (a2 + a1*y + a0*x) >> 16, yin = (a5 + a4*y + a3*x) >> 16; outside the source gives 0.
+ *   3 STRETCH (stretch != 0): stage 1 again, to (w3, h3).  Then, shear != 0: cv2.warpAffine(M = [[1, sx, 0], [sy, 1, 0]] as float32,
+ *     (w, h), INTER_LINEAR, BORDER_CONSTANT 0) on the four channels — restated from knowledge and NOT run against cv2: shear_minv =
+ *     OpenCV's float64 inverse (D = 1/(M0*M4 - M1*M3); A11 = M4*D, A22 = M0*D; M1 *= -D, M3 *= -D; b1 = -A11*M2 - M1*M5,
+ *     b2 = -M3*M2 - A22*M5) = [A11, M1, b1, M3, A22, b2]; X = (rint((m1*y + m2)*1024) + 16 + rint(m0*x*1024)) >> 5, Y likewise with
+ *     m4, m5, m3 (round half to even; 10 coordinate bits, 5 interpolation bits); taps (X >> 5, Y >> 5) and + 1 with weights from
+ *     X & 31, Y & 31, out = (acc + 512) >> 10; a tap outside the patch reads 0.
+ *   4 BLUR (blur != 0) = ImageFilter.GaussianBlur on all four channels, not premultiplied: three horizontal box passes, then three
+ *     vertical, out = (ww*sum_{i=-R..R} p[clamp(x + i)] + fw*(p[clamp(x - R - 1)] + p[clamp(x + R + 1)]) + 2^23) >> 24, edges
+ *     replicated.  Host, as Pillow's C (float32 unless said): sigma2 = r*r/3; L = (float)sqrt(12.0*sigma2 + 1.0) (the square root in
+ *     double); l = floor((L - 1)/2); a = (2l + 1)*(l*(l + 1) - 3*sigma2) / (6*(sigma2 - (l + 1)^2)); fr = l + a; blur_r = R = (int)fr;
+ *     blur_ww = (uint32)(2^24/(2*fr + 1)); blur_fw = (2^24 - (2R + 1)*ww)/2.  R is at most 32.
+ *   5 DEFECTS: ndefects (0..3) rectangles {x, y, w, h} get alpha 0.
+ *   6 ENHANCE (enhance != 0) = ImageEnhance.Brightness, Contrast, Color: each Image.blend(degenerate, image, f) over RGB, alpha
+ *     untouched; in float32 t = d + f*(p - d); 0 <= f <= 1: (uint8)t truncated; else 0 for t <= 0, 255 for t >= 255, else truncated.
+ *     Degenerates: Brightness 0; Contrast the constant (int)(mean(L) + 0.5) (float64) over ALL pixels of the patch, transparent ones
+ *     included; Color the pixel's own L; L = (19595*R + 38470*G + 7471*B + 0x8000) >> 16.
+ *   7 OPACITY: a = opacity[a], the host's table of (uint8)(a*alpha) in float64.
+ *   8 PASTE = watermarked.paste(patch, (x, y), patch) and combined_mask.paste(alpha, (x, y), alpha), clipped to the image:
+ *     c = MULDIV255-blend: t = src*a + dst*(255 - a) + 128, ((t >> 8) + t) >> 8; the mask likewise with src = a, from 0.  The jobs of
+ *     one image are applied in slot order.
+ * A PLAIN job (the reference's fallback resize_watermark for an oversized patch) is stage 1 with every other stage off and the
+ * identity opacity table.  Stages 1, 2, 4, 6, 7 and 8 are held to Pillow bit for bit by tests/test_synth.py; stage 3's shear is not
+ * run against cv2.
+ * images: a ragged batch as above (uint8 RGB interleaved), worked on IN PLACE; masks (may be NULL): one byte per pixel, every pixel
+ * of a mask whose descriptor equals its image's is written (0 where no logo landed).  logos: a ragged batch of RGBA images, each
+ * offset a multiple of 4.  jobs: [N][K] in device memory, K <= 8 slots per image.  The workspace holds, per job, two patch buffers
+ * of max_patch_pixels pixels, four coefficient tables of max_taps int32 (a table in -> out takes out*(ksize + 2)) and the partial
+ * sums of the Contrast mean.  A job with enabled == 0, or one that does not fit (a logo index or descriptor outside its buffer, a
+ * side outside 1..32767, an intermediate or final patch above max_patch_pixels, a table above max_taps, non-finite matrix
+ * entries, blur_r above 32, a defect outside 0..32767) is skipped by every stage and costs only itself.  16 launches of
+ * N * K * 32 workgroups on the caller's stream, sized from N and K alone, no host synchronisation: capturable, and one captured call
+ * serves every batch.  Integer sums have one result whatever their order and every float operation is spelt out, so runs are
+ * bit-identical.  The LANCZOS tables are built on the device in float64 (one thread per output index);
+ * uwm_op_lanczos_table exposes that builder: int32 [out][2 + ksize] = {xmin, xmax, coefficients}.  uwm_op_synth_patches runs stages
+ * 1-7 on J jobs and stores job j's finished patch at out + j*max_patch_pixels*4 (stage-level tests).  Every argument is checked
+ * before any launch.  No read leaves the inputs; no write leaves [images, +image_bytes), [masks, +mask_bytes) or the workspace. */
+typedef struct uwm_synth_job {
+  int enabled;                 /* 0: an empty slot */
+  int logo;                    /* index into logo_descs */
+  int w1, h1;                  /* stage 1 */
+  int rotate, w2, h2;          /* stage 2 and its expanded size */
+  int stretch, w3, h3, shear;  /* stage 3 */
+  int blur, blur_r;            /* stage 4 */
+  unsigned blur_ww, blur_fw;
+  int ndefects, defects[3][4]; /* stage 5: {x, y, w, h} */
+  int enhance;                 /* stage 6 */
+  float brightness, contrast, color;
+  int x, y;                    /* stage 8 */
+  double rot[6], shear_minv[6];
+  uint8_t opacity[256];        /* stage 7 */
+} uwm_synth_job;
+size_t uwm_synth_workspace_bytes(int N, int K, long long max_patch_pixels, long long max_taps);
+int  uwm_synth_u8(uint8_t* images, size_t image_bytes, const uwm_image_desc* image_descs,
+                  uint8_t* masks /* may be NULL */, size_t mask_bytes, const uwm_image_desc* mask_descs,
+                  const uint8_t* logos, size_t logo_bytes, const uwm_image_desc* logo_descs, int num_logos,
+                  const uwm_synth_job* jobs, int N, int K, long long max_patch_pixels, long long max_taps,
+                  void* workspace, size_t workspace_bytes, uwm_stream stream);
+int  uwm_op_synth_patches(const uint8_t* logos, size_t logo_bytes, const uwm_image_desc* logo_descs, int num_logos,
+                          const uwm_synth_job* jobs, int J, long long max_patch_pixels, long long max_taps,
+                          void* workspace, size_t workspace_bytes, uint8_t* out, size_t out_bytes, uwm_stream stream);
+int  uwm_lanczos_table_ints(int in, int out);         /* out*(ksize + 2); 0 for a side outside 1..32767 */
+int  uwm_op_lanczos_table(int in, int out, int* table /* device */, size_t table_ints, uwm_stream stream);
+
 /* The dataset filter: the reference's src/scripts/watermark_filter.py (predict_mask, _post_process_mask, has_watermark), which sorts a
  * folder by the share of each image that the model calls watermark.  Only one integer per image is wanted, so the mask need not leave
  * the kernel.  Image i of a ragged batch, at its OWN size (h_i, w_i) = out_descs[i], from the logit plane [N][h][w] (element stride ld):

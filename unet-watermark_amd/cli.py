@@ -1,8 +1,9 @@
-"""`python main.py train|predict|masks ...` — counterpart of the reference's CLI for the model path
+"""`python main.py train|predict|masks|filter|synth ...` — counterpart of the reference's CLI for the model path
 (/root/reference/src/cli.py:368-395 flag names; train loop order /root/reference/src/train.py:207-499:
 epochs of train_epoch + validate (val batch = 2x train batch, :254), Adam | SGD (:265-279), ReduceLROnPlateau on the
 val loss | CosineAnnealingLR (:280-296,408-412), best / periodic checkpoints (:428-460), early stopping (:37-66,362-368)).
-`repair` / `auto` (IOPaint, OCR, video, data synthesis) are out of scope (SURVEY.md §2 rows 6,9,10).
+`repair` / `auto` (IOPaint, OCR, video, text-watermark synthesis) are out of scope (SURVEY.md §2 rows 6,9,10); the logo branch of the
+data synthesis runs on the device (`train --synthesize`, `synth`).
 Multi-GPU: launch with torch.distributed.run; every rank trains its shard, gradients are all-reduced."""
 from __future__ import annotations
 
@@ -19,7 +20,7 @@ from torch.utils.data.distributed import DistributedSampler
 from .checkpoint import load_checkpoint, save_checkpoint
 from .config import get_cfg_defaults, update_config
 from .data import (AUG_RECIPES, AUG_RECIPES_EXT, DeviceInputPipeline, DeviceU8Dataset, FolderDataset, RawFolderDataset, RawPairDataset,
-                   SyntheticWatermarkDataset, list_collate)
+                   RawSynthDataset, SyntheticWatermarkDataset, list_collate)
 from .losses import get_loss_function
 from .metrics import logits_metrics
 from .model import create_model_from_config
@@ -94,6 +95,33 @@ def _datasets(cfg, synthetic, device_input=None):
     perm = torch.randperm(n, generator=g).tolist() if cfg.DATA.SHUFFLE else list(range(n))
     ntr = max(1, int(n * float(cfg.DATA.TRAIN_RATIO)))
     return Subset(full, perm[:ntr]), Subset(full, perm[ntr:] or perm[:1])
+
+
+def _check_synthesize(args, augment):
+    """the refusals of `train --synthesize`, before any device work"""
+    if not getattr(args, "synthesize", False):
+        return
+    if args.synthetic:
+        raise ValueError("--synthesize and --synthetic exclude each other: --synthetic N trains on a toy generator's images, --synthesize "
+                         "pastes real logos onto the images of --clean-dir")
+    if augment == "none":
+        raise ValueError("--synthesize runs on the device input path (the logos are pasted at each image's own size, in front of the "
+                         "device's resize, augmentation and Normalize): give --augment basic or --augment config")
+    if not args.clean_dir or not args.logos_dir:
+        raise ValueError("--synthesize needs --clean-dir (clean photographs) and --logos-dir (logo images)")
+
+
+def _synth_datasets(cfg, args):
+    """train / validation splits of the clean images, as _datasets splits a folder; the training split draws new samples every epoch
+    (set_epoch), the validation split is never told the epoch and so reproduces its samples"""
+    kw = dict(seed=int(args.synth_seed), transparent_ratio=float(args.transparent_ratio), multi_watermark_ratio=float(args.multi_watermark_ratio),
+              max_watermarks=int(args.synth_max_watermarks), mask_threshold=int(cfg.DATA.GENERATE_MASK_THRESHOLD), mask_source=args.synth_mask)
+    train, val = RawSynthDataset(args.clean_dir, args.logos_dir, **kw), RawSynthDataset(args.clean_dir, args.logos_dir, **kw)
+    n = len(train)
+    g = torch.Generator().manual_seed(int(cfg.DATA.SEED))
+    perm = torch.randperm(n, generator=g).tolist() if cfg.DATA.SHUFFLE else list(range(n))
+    ntr = max(1, int(n * float(cfg.DATA.TRAIN_RATIO)))
+    return Subset(train, perm[:ntr]), Subset(val, perm[ntr:] or perm[:1])
 
 
 @torch.no_grad()
@@ -191,9 +219,11 @@ def train_command(args):
     if getattr(args, "augmentation_type", None):
         cfg.DATA.AUGMENTATION_TYPE = args.augmentation_type
     augment, aug_note = _served_recipe(getattr(args, "augment", None) or "none", cfg, getattr(args, "jpeg", None) or "refuse")      # refusals come before any device work
+    _check_synthesize(args, augment)
+    synthesize = bool(getattr(args, "synthesize", False))
     if getattr(args, "checkpoint_dir", None):
         cfg.TRAIN.CHECKPOINT_DIR = args.checkpoint_dir
-    if (getattr(args, "use_blurred_mask", False) and not args.synthetic and os.path.isdir(os.path.join(cfg.DATA.ROOT_DIR, "watermarked"))
+    if (getattr(args, "use_blurred_mask", False) and not args.synthetic and not synthesize and os.path.isdir(os.path.join(cfg.DATA.ROOT_DIR, "watermarked"))
             and RawPairDataset(_pair_roots(cfg), int(cfg.DATA.GENERATE_MASK_THRESHOLD)).missing_masks()):
         raise ValueError("--use-blurred-mask: this dataset has images without a mask file, whose masks are derived from their clean "
                          "counterparts, and the reference's blurred variant of that rule (contours, convex hulls, approxPolyDP) is not "
@@ -247,7 +277,7 @@ def train_command(args):
     stopper = (EarlyStopping(patience=int(cfg.TRAIN.EARLY_STOPPING_PATIENCE), restore_best_weights=True)
                if cfg.TRAIN.USE_EARLY_STOPPING else None)       # /root/reference/src/train.py:362-368
     pipe = None
-    tr_set, va_set = _datasets(cfg, args.synthetic, device if augment != "none" else None)
+    tr_set, va_set = _synth_datasets(cfg, args) if synthesize else _datasets(cfg, args.synthetic, device if augment != "none" else None)
     if augment != "none":
         pipe = DeviceInputPipeline(cfg.DATA.IMG_SIZE, device, source=tr_set.dataset, recipe=augment)
         if rank == 0:
@@ -256,6 +286,10 @@ def train_command(args):
                 print(f"masks: {len(tr_set.dataset.missing_masks())} of {len(tr_set.dataset)} images have no mask file; theirs are derived on "
                       f"the device from the clean counterpart (DATA.GENERATE_MASK_THRESHOLD={tr_set.dataset.mask_threshold}), zero without "
                       "one; nothing is written (`main.py masks` persists them)", flush=True)
+            if synthesize:
+                print(f"synthesis: {len(tr_set.dataset)} clean images x {len(tr_set.dataset.logos)} logos, pasted on the device at each image's "
+                      f"own size (logo watermarks only; masks from {'the pasted alpha planes' if args.synth_mask == 'alpha' else 'synthesized / clean pairs'})",
+                      flush=True)
     bs = int(cfg.TRAIN.BATCH_SIZE)
     sampler = DistributedSampler(tr_set, world, rank, shuffle=True, seed=int(cfg.DATA.SEED)) if world > 1 else None
     # the device input path gets raw items from the workers (uint8 arrays of any size, or indices): nothing to stack or pin
@@ -268,6 +302,8 @@ def train_command(args):
     for epoch in range(start_epoch, int(cfg.TRAIN.EPOCHS)):
         if sampler is not None:
             sampler.set_epoch(epoch)
+        if synthesize:
+            tr_set.dataset.set_epoch(epoch)                   # (the workers of this epoch's loader start after this)
         model.train()
         t0, seen = time.time(), 0
         acc = torch.zeros(3, device=device)
@@ -405,6 +441,56 @@ def masks_command(args):
     return res
 
 
+def synth_command(args):
+    """The logo branch of the reference's src/scripts/gen_data.py on the device: --count samples into <output-dir>/watermarked (PNG, so
+    the pixels are the device's; the reference saves JPEG quality 95), a same-named copy of the clean image into <output-dir>/clean —
+    which is what lets RawPairDataset derive the masks — and, with --generate-mask, the pasted alpha planes into <output-dir>/masks."""
+    import random
+    import numpy as np
+    from PIL import Image
+    from .data import device_synth, mask_descs_for, pack_images
+    if int(args.count) < 1:
+        raise ValueError("synth: --count must be >= 1")
+    ds = RawSynthDataset(args.clean_dir, args.logos_dir, seed=int(args.seed), transparent_ratio=float(args.transparent_ratio),
+                         multi_watermark_ratio=float(args.multi_watermark_ratio), max_watermarks=int(args.max_watermarks))
+    if not torch.cuda.is_available():
+        raise SystemExit("synth needs a HIP device (this path has no CPU fallback)")
+    device = torch.device("cuda", torch.cuda.current_device())
+    dirs = {k: os.path.join(args.output_dir, k) for k in ("watermarked", "clean") + (("masks",) if args.generate_mask else ())}
+    for d in dirs.values():
+        os.makedirs(d, exist_ok=True)
+    pick = random.Random(f"uwm-synth-pick:{int(args.seed)}")
+    bs = max(1, int(args.batch_size or 16))
+    written = 0
+    for b in range(0, int(args.count), bs):
+        idx = list(range(b, min(b + bs, int(args.count))))
+        which = [pick.randrange(len(ds)) for _ in idx]       # the script picks a clean image at random for every sample
+        cleans, logos, jobs, names = [], [], [], []
+        for n, i in zip(idx, which):
+            ds.set_epoch(n)                                   # sample n's draws: a function of (seed, n, clean image)
+            clean, lg, j = ds[i]
+            transparent = bool(ds.draw(i, (clean.shape[1], clean.shape[0]))[0])
+            j = np.array(j, copy=True); j["logo"] += len(logos)
+            cleans.append(clean); logos += list(lg); jobs.append(j)
+            count = int((j["enabled"] != 0).sum())
+            names.append(f"{'multi_' if count > 1 else ''}{'trans' if transparent else 'norm'}_{n:06d}")
+        pc, dc, _ = pack_images(cleans)
+        pl, dl, _ = pack_images(logos)
+        out, mask = device_synth(pc.to(device), dc, pl.to(device), dl, np.stack(jobs), with_mask=bool(args.generate_mask), inplace=True)
+        out = out.cpu().numpy()
+        mask = mask.cpu().numpy() if mask is not None else None
+        for name, clean, d, m in zip(names, cleans, dc, mask_descs_for(dc)):
+            o, h, w = int(d["offset"]), int(d["h"]), int(d["w"])
+            Image.fromarray(out[o:o + h * w * 3].reshape(h, w, 3)).save(os.path.join(dirs["watermarked"], name + ".png"))
+            Image.fromarray(clean).save(os.path.join(dirs["clean"], name + ".png"))
+            if mask is not None:
+                mo = int(m["offset"])
+                Image.fromarray(mask[mo:mo + h * w].reshape(h, w)).save(os.path.join(dirs["masks"], name + ".png"))
+            written += 1
+    print(f"wrote {written} samples to {args.output_dir} (watermarked/, clean/{', masks/' if args.generate_mask else ''})")
+    return dict(written=written, output=args.output_dir)
+
+
 def filter_command(args):
     """The reference's src/scripts/watermark_filter.py on the device: one line per kept or moved file, then the stats."""
     from .filter import WatermarkFilter
@@ -472,6 +558,27 @@ def build_parser():
     tp.add_argument("--lr-scheduler", choices=["ReduceLROnPlateau", "CosineAnnealingLR", "CosineAnnealingWarmRestarts", "none"],
                     default=None, help="OPTIMIZER.LR_SCHEDULER")
     tp.add_argument("--checkpoint-dir", type=str, default=None, help="TRAIN.CHECKPOINT_DIR")
+    tp.add_argument("--synthesize", action="store_true",
+                    help="make the training pairs on the device: paste logos of --logos-dir onto the images of --clean-dir with the logo "
+                         "branch of the reference's gen_data.py (resize, rotate, stretch, shear, blur, defects, colour, opacity), new samples "
+                         "every epoch; needs --augment basic|config")
+    tp.add_argument("--clean-dir", type=str, default=None, help="--synthesize: directory of clean images")
+    tp.add_argument("--logos-dir", type=str, default=None,
+                    help="--synthesize: directory of logos, with combined/, independent/ and car_logo/ as in the reference, or flat")
+    tp.add_argument("--transparent-ratio", type=float, default=0.6, help="--synthesize: share of samples with low-opacity logos")
+    tp.add_argument("--multi-watermark-ratio", type=float, default=0.4, help="--synthesize: share of samples with several logos")
+    tp.add_argument("--synth-max-watermarks", type=int, default=3, help="--synthesize: most logos on one image (1..3)")
+    tp.add_argument("--synth-mask", choices=["pair", "alpha"], default="pair",
+                    help="--synthesize: 'pair' (default) derives the mask from (synthesized, clean) as the reference's dataset does; 'alpha' "
+                         "takes the pasted alpha planes, which the reference binarises at 127, so low-opacity samples get nearly empty masks")
+    tp.add_argument("--synth-seed", type=int, default=42, help="--synthesize: seed of the draws")
+    sp = sub.add_parser("synth", help="write logo-watermarked samples (the logo branch of the reference's scripts/gen_data.py) made on the device")
+    sp.add_argument("--clean-dir", type=str, required=True); sp.add_argument("--logos-dir", type=str, required=True)
+    sp.add_argument("--output-dir", type=str, required=True); sp.add_argument("--count", type=int, required=True)
+    sp.add_argument("--generate-mask", action="store_true", help="also write the pasted alpha planes to masks/")
+    sp.add_argument("--seed", type=int, default=42)
+    sp.add_argument("--transparent-ratio", type=float, default=0.6); sp.add_argument("--multi-watermark-ratio", type=float, default=0.4)
+    sp.add_argument("--max-watermarks", type=int, default=3); sp.add_argument("--batch-size", type=int, default=None)
     mp = sub.add_parser("masks", help="derive masks/<stem>.png from watermarked / clean pairs on the device, for every pair without one")
     mp.add_argument("--data-dir", type=str, default=None, help="DATA.ROOT_DIR: the directory with watermarked/, clean/ and masks/")
     mp.add_argument("--config", type=str, default=None)
@@ -518,4 +625,6 @@ def main(argv=None):
         return masks_command(args)
     if args.command == "filter":
         return filter_command(args)
+    if args.command == "synth":
+        return synth_command(args)
     ap.print_help()

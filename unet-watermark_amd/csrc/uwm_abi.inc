@@ -294,6 +294,68 @@ int uwm_pair_mask_u8(const uint8_t* wm, size_t wm_bytes, const uwm_image_desc* w
                            mask, mask_bytes, (const ImageDesc*)mask_descs, (hipStream_t)stream));
   return 0;
 }
+// ---- logo-watermarked training samples (synth_u8.hip): every argument is checked here, before any launch (descriptors and jobs are
+// device memory: the kernels check each job and skip the ones that do not fit)
+static_assert(sizeof(uwm_synth_job) == sizeof(SynthJob) && sizeof(uwm_synth_job) == 488 && offsetof(uwm_synth_job, rot) == 136 &&
+              offsetof(uwm_synth_job, opacity) == offsetof(SynthJob, opacity) && offsetof(uwm_synth_job, x) == offsetof(SynthJob, x), "uwm_synth_job layout");
+size_t uwm_synth_workspace_bytes(int N, int K, long long max_patch_pixels, long long max_taps) {
+  const size_t b = synth_workspace_bytes(N, K, max_patch_pixels, max_taps);
+  if (!b) (void)fail("uwm_synth_workspace_bytes: need N >= 1, K in 1..%d, max_patch_pixels in 1..%lld, max_taps in 1..%lld and N * K * %d within one "
+                     "launch (got %d, %d, %lld, %lld)", kSynthMaxSlots, kSynthMaxPatchPixels, kSynthMaxTaps, kSynthBlocks, N, K, max_patch_pixels, max_taps);
+  return b;
+}
+static int synth_args_check(const char* fn, const void* logos, size_t logo_bytes, const void* logo_descs, int num_logos, const void* jobs, int N, int K,
+                            long long P, long long T, const void* ws, size_t ws_bytes) {
+  if (!logos || !logo_descs || !jobs || !ws) return fail("%s: null argument", fn);
+  if (num_logos < 1 || logo_bytes < 1) return fail("%s: num_logos and logo_bytes must be >= 1 (got %d, %zu)", fn, num_logos, logo_bytes);
+  const size_t need = synth_workspace_bytes(N, K, P, T);
+  if (!need) return fail("%s: need N >= 1, K in 1..%d, max_patch_pixels in 1..%lld, max_taps in 1..%lld and N * K * %d within one launch (got %d, %d, %lld, "
+                         "%lld)", fn, kSynthMaxSlots, kSynthMaxPatchPixels, kSynthMaxTaps, kSynthBlocks, N, K, P, T);
+  if (ws_bytes < need) return fail("%s: workspace of %zu bytes, need %zu (uwm_synth_workspace_bytes)", fn, ws_bytes, need);
+  if ((uintptr_t)logos & 3) return fail("%s: logos must be 4-byte aligned", fn);
+  if (((uintptr_t)logo_descs | (uintptr_t)jobs | (uintptr_t)ws) & 7) return fail("%s: descriptors, jobs and workspace must be 8-byte aligned", fn);
+  return 0;
+}
+int uwm_synth_u8(uint8_t* images, size_t image_bytes, const uwm_image_desc* image_descs, uint8_t* masks, size_t mask_bytes,
+                 const uwm_image_desc* mask_descs, const uint8_t* logos, size_t logo_bytes, const uwm_image_desc* logo_descs, int num_logos,
+                 const uwm_synth_job* jobs, int N, int K, long long max_patch_pixels, long long max_taps, void* ws, size_t ws_bytes,
+                 uwm_stream stream) {
+  if (!images || !image_descs) return fail("uwm_synth_u8: null argument");
+  if (synth_args_check("uwm_synth_u8", logos, logo_bytes, logo_descs, num_logos, jobs, N, K, max_patch_pixels, max_taps, ws, ws_bytes)) return 1;
+  if (image_bytes < 1) return fail("uwm_synth_u8: image_bytes must be >= 1");
+  if ((uintptr_t)image_descs & 7) return fail("uwm_synth_u8: descriptors must be 8-byte aligned");
+  if (masks && (!mask_descs || mask_bytes < 1 || ((uintptr_t)mask_descs & 7)))
+    return fail("uwm_synth_u8: masks need mask_descs (8-byte aligned) and mask_bytes >= 1");
+  LCHK(launch_synth_u8(images, image_bytes, (const ImageDesc*)image_descs, masks, mask_bytes, (const ImageDesc*)mask_descs, logos, logo_bytes,
+                       (const ImageDesc*)logo_descs, num_logos, (const SynthJob*)jobs, N, K, max_patch_pixels, max_taps, ws, ws_bytes,
+                       (hipStream_t)stream));
+  return 0;
+}
+int uwm_op_synth_patches(const uint8_t* logos, size_t logo_bytes, const uwm_image_desc* logo_descs, int num_logos, const uwm_synth_job* jobs, int J,
+                         long long max_patch_pixels, long long max_taps, void* ws, size_t ws_bytes, uint8_t* out, size_t out_bytes,
+                         uwm_stream stream) {
+  if (!out) return fail("uwm_op_synth_patches: null argument");
+  if (synth_args_check("uwm_op_synth_patches", logos, logo_bytes, logo_descs, num_logos, jobs, J, 1, max_patch_pixels, max_taps, ws, ws_bytes)) return 1;
+  if ((uintptr_t)out & 3) return fail("uwm_op_synth_patches: out must be 4-byte aligned");
+  if (out_bytes / 4 / (size_t)max_patch_pixels < (size_t)J)
+    return fail("uwm_op_synth_patches: out of %zu bytes, need J * max_patch_pixels * 4 = %zu", out_bytes, (size_t)J * (size_t)max_patch_pixels * 4);
+  LCHK(launch_synth_patches(logos, logo_bytes, (const ImageDesc*)logo_descs, num_logos, (const SynthJob*)jobs, J, max_patch_pixels, max_taps, ws,
+                            ws_bytes, out, out_bytes, (hipStream_t)stream));
+  return 0;
+}
+int uwm_lanczos_table_ints(int in, int out) {
+  if (in < 1 || out < 1 || in > 32767 || out > 32767) return 0;
+  return out * (synth_lanczos_ksize(in, out) + 2);
+}
+int uwm_op_lanczos_table(int in, int out, int* table, size_t table_ints, uwm_stream stream) {
+  if (!table) return fail("uwm_op_lanczos_table: null argument");
+  if (in < 1 || out < 1 || in > 32767 || out > 32767) return fail("uwm_op_lanczos_table: in and out must be 1..32767 (got %d, %d)", in, out);
+  if ((uintptr_t)table & 3) return fail("uwm_op_lanczos_table: table must be 4-byte aligned");
+  if (table_ints < (size_t)uwm_lanczos_table_ints(in, out))
+    return fail("uwm_op_lanczos_table: table of %zu ints, need %d (uwm_lanczos_table_ints)", table_ints, uwm_lanczos_table_ints(in, out));
+  LCHK(launch_lanczos_table(in, out, table, (hipStream_t)stream));
+  return 0;
+}
 int uwm_predict_images_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, const uwm_image_desc* in_descs, const float* mean,
                           const float* std, float threshold, int apply_sigmoid, const uwm_image_desc* out_descs, uint8_t* mask,
                           size_t mask_bytes, float* logits, void* ws, size_t ws_bytes, int N, int H, int W, uwm_stream stream) {

@@ -500,6 +500,33 @@ size_t filter_workspace_bytes(int N);                // 0 for N < 1 or a launch 
 hipError_t launch_prob_mask_count(const float* logits, int ld, int N, int h, int w, const ImageDesc* out_descs, float thr, int post_process,
                                   uint8_t* mask, size_t mask_bytes, long long* counts, void* workspace, size_t workspace_bytes,
                                   hipStream_t st);
+// ---- logo-watermarked training samples (synth_u8.hip; the rule: include/uwm.h)
+constexpr int kSynthBlocks = 32;                     // workgroups per job in every stage launch: grid = N * K * this
+constexpr int kSynthMaxSlots = 8;                    // K, the logo slots of one image
+constexpr long long kSynthMaxPatchPixels = 1ll << 26, kSynthMaxTaps = 1ll << 24;
+struct SynthJob {                                    // = uwm_synth_job: one per (image, slot), in DEVICE memory
+  int enabled, logo, w1, h1, rotate, w2, h2, stretch, w3, h3, shear, blur, blur_r;
+  unsigned blur_ww, blur_fw;
+  int ndefects, defects[3][4], enhance;
+  float brightness, contrast, color;
+  int x, y;
+  double rot[6], shear_minv[6];
+  uint8_t opacity[256];
+};
+size_t synth_workspace_bytes(int N, int K, long long max_patch_pixels, long long max_taps);      // 0 for arguments out of range
+int synth_lanczos_ksize(int in, int out);            // taps per output of the table in -> out (host)
+// int32 [out][2 + ksize] = {xmin, xmax, coefficients} of Pillow's LANCZOS resample in -> out, built in fp64 on the device
+hipError_t launch_lanczos_table(int in, int out, int* table, hipStream_t st);
+// stages 1-8 of every job, in place on the ragged RGB batch; masks (may be nullptr) <- the pasted alpha planes.  No read leaves the
+// inputs, no write leaves [images, +image_bytes), [masks, +mask_bytes) or the workspace
+hipError_t launch_synth_u8(uint8_t* images, size_t image_bytes, const ImageDesc* image_descs, uint8_t* masks, size_t mask_bytes,
+                           const ImageDesc* mask_descs, const uint8_t* logos, size_t logo_bytes, const ImageDesc* logo_descs, int num_logos,
+                           const SynthJob* jobs, int N, int K, long long max_patch_pixels, long long max_taps, void* ws, size_t ws_bytes,
+                           hipStream_t st);
+// stages 1-7 only: job j's finished RGBA patch -> out + j * max_patch_pixels * 4 (a job that is off or does not fit writes nothing)
+hipError_t launch_synth_patches(const uint8_t* logos, size_t logo_bytes, const ImageDesc* logo_descs, int num_logos, const SynthJob* jobs, int J,
+                                long long max_patch_pixels, long long max_taps, void* ws, size_t ws_bytes, uint8_t* out, size_t out_bytes,
+                                hipStream_t st);
 
 // EfficientNet MBConv pieces (mbconv.hip): swish, depthwise k x k conv (weights tap-major [k*k][C]) with static "same"
 // padding (pb = pad at the begin of H and W; the end pad is implied by Ho/Wo), squeeze-and-excitation, block output with drop-connect
