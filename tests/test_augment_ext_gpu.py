@@ -252,3 +252,41 @@ def test_train_with_the_enhanced_recipe_on_a_folder_of_mixed_sizes(cuda, tmp_pat
     with pytest.raises(ValueError, match="ImageCompression"):
         _train(root, tmp_path, "d", "transparent_watermark")
     assert cli.build_parser().parse_args(["train", "--augment", "basic"]).augment == "basic"
+
+
+# ------------------------------------------------------------------------------------- the wrappers' shared per-device workspaces
+def test_workspaces_grow_and_are_reused_without_changing_a_result(cuda):
+    """CLAHE on 2 x 16x16x3, on 3 x 32x48x3 (its workspace has to grow), a JPEG round trip on 2 x 16x16x3 and the first call again, one
+    after the other through the public wrappers: the fourth result is the first, and every result is what the same call gives when
+    no workspace exists yet.  The smallest shapes the kernels take: CLAHE needs H, W >= 8, JPEG multiples of 16."""
+    D = _D()
+
+    def clear():
+        D._EXT_WORKSPACE.clear(); D._JPEG_WORKSPACE.clear()
+
+    def clahe(n, h, w):
+        img, mask = G._batch(n, h, w, 3, seed=n + h)
+        x, m = torch.from_numpy(img).to(cuda), torch.from_numpy(mask).to(cuda)
+        e = D.identity_aug_ext_params(n)
+        e["tone"], e["clahe_clip"] = D.TONE_CLAHE, 2
+        return lambda: D.device_augment(x, m, D.identity_aug_params(n), MEAN, STD, return_u8=True, ext=e)
+
+    def jpeg(n, h, w):
+        x = torch.from_numpy(G._batch(n, h, w, 3, seed=5)[0]).to(cuda)
+        return lambda: D.device_jpeg(x, np.array([35, 90][:n], dtype=np.int32), MEAN, STD, return_u8=True)
+
+    def run(call):
+        res = call()
+        torch.cuda.synchronize()
+        return [t.cpu().numpy().view(np.uint8) for t in res]      # bytes, so fp32 results compare bit for bit
+
+    first = clahe(2, 16, 16)
+    calls = [first, clahe(3, 32, 48), jpeg(2, 16, 16), first]
+    clear()
+    got = [run(c) for c in calls]
+    assert all(np.array_equal(a, b) for a, b in zip(got[3], got[0]))
+    assert not np.array_equal(got[0][2], G._batch(2, 16, 16, 3, seed=18)[0])      # (CLAHE did change the images)
+    for c, g in zip(calls, got):
+        clear()
+        fresh = run(c)
+        assert len(fresh) == len(g) and all(np.array_equal(a, b) for a, b in zip(fresh, g))

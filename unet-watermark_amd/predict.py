@@ -13,12 +13,11 @@ import torch
 
 from .checkpoint import load_checkpoint
 from .config import get_cfg_defaults, update_config
+from .constants import IMAGENET_MEAN, IMAGENET_STD  # noqa: F401   (predict.IMAGENET_MEAN is part of this module's surface)
+from .data import descs_tensor, device_preprocess, pack_images
 from .metrics import threshold_mask
 from .model import create_model_from_config
 from .postprocess import mask_type_code, optimize_mask, workspace as mask_workspace
-
-IMAGENET_MEAN = (0.485, 0.456, 0.406)
-IMAGENET_STD = (0.229, 0.224, 0.225)
 
 
 class WatermarkPredictor:
@@ -64,7 +63,6 @@ class WatermarkPredictor:
 
     # --- input contract of dataset.get_val_transform: Resize -> Normalize(ImageNet) -> NCHW fp32
     def preprocess(self, images_u8_nhwc: torch.Tensor) -> torch.Tensor:
-        from .data import device_preprocess
         return device_preprocess(images_u8_nhwc.to(self.device, non_blocking=True))      # one kernel: uint8 HWC -> normalised NCHW fp32
 
     @torch.no_grad()
@@ -172,7 +170,6 @@ class WatermarkPredictor:
     def _stage_images(self, images):
         """pack `images` into the static staging buffers (_ibuf, _idesc, _mdesc; _mbuf sized for their masks) -> (n, IMG_SIZE, descs,
         mask descs, areas, mask bytes)"""
-        from .data import descs_tensor, pack_images
         # pack into ONE persistent pinned buffer (pinned allocation is expensive), grown geometrically; the previous batch's upload
         # from it must have finished before it is overwritten
         need = sum((int(np.prod(im.shape)) + 3) // 4 * 4 for im in images)
