@@ -694,6 +694,30 @@ size_t uwm_mask_workspace_bytes(int N, int H, int W);
  * {components found, area of the largest (0 if none), foreground pixels of the output, id of the largest or -1} */
 int    uwm_optimize_mask(const uint8_t* in, uint8_t* out, int N, int H, int W, int mask_type, long long* summary,
                          void* workspace, size_t workspace_bytes, uwm_stream stream);
+/* The same on a ragged batch in ONE call, whatever the sizes: image i is descs[i].h x descs[i].w, one byte per pixel, at
+ * in + descs[i].offset (any alignment: the layout uwm_resize_threshold_ragged writes); its result goes to out + descs[i].offset and
+ * equals uwm_optimize_mask on that image alone bit for bit (ids are image-local, y * w_i + x).  out may be in.  UWM_MASK_NONE (this
+ * call only): binarise (> 127), no morphology, keep every component.  stats (device, may be NULL): long long [N][8] =
+ *   0 components found, 1 largest area, 2 foreground pixels of the output, 3 id of the largest or -1   (the summary above)
+ *   4 components kept, 5 largest kept area       (the output is a union of whole components, so these ARE its components: what
+ *                                                 cv2.connectedComponentsWithStats on the output counts; NONE: = entries 0, 1)
+ *   6 h_i * w_i, 7 status: 0 done, 1 misfit
+ * The descriptors are read on the device; the host arguments are capacities, so one captured call serves every batch of N images
+ * that fits them: max_pixels (1 .. 2^31 - 2) bounds h_i * w_i and sizes the grids, rows bounds the sum of h_i and, with mask_bytes,
+ * sizes the bit planes (image i takes h_i * ceil(w_i / 64) words; a plane holds mask_bytes / 64 + rows).  The launch count does
+ * not depend on N (N <= 65535).  Misfit: a side outside 1 .. 2^30, h_i * w_i > max_pixels, a region that leaves [0, mask_bytes),
+ * or, counting the images before it that pass those three tests, a sum of rows above `rows` or of plane words above the plane.  A
+ * misfit gets status 1 and entries 0..6 zero, its bytes are not written and it costs the others nothing.  Whatever the
+ * descriptors hold, no read leaves in / descs and no write leaves out + [0, mask_bytes), stats or the workspace; overlapping regions
+ * are the caller's error.  workspace: uwm_mask_ragged_workspace_bytes(N, mask_bytes, rows) bytes (0 and a message on a bad
+ * argument), descs / stats / workspace 8-byte aligned.  Every argument is checked before any launch; no host synchronisation,
+ * allocation or copy. */
+enum { UWM_MASK_NONE = 3 };
+size_t uwm_mask_ragged_workspace_bytes(int N, size_t mask_bytes, long long rows);
+int    uwm_optimize_masks_ragged(const uint8_t* in, uint8_t* out /* may alias in */, size_t mask_bytes,
+                                 const uwm_image_desc* descs /* device */, int N, int mask_type, long long max_pixels,
+                                 long long rows, long long* stats /* device [N][8], may be NULL */, void* workspace,
+                                 size_t workspace_bytes, uwm_stream stream);
 /* building blocks, for tests and other callers; out may alias in */
 int    uwm_op_morph(const uint8_t* in, uint8_t* out, int N, int H, int W, int dilate, int shape, int kw, int kh,
                     int iterations, void* workspace, size_t workspace_bytes, uwm_stream stream);

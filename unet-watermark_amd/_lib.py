@@ -146,6 +146,8 @@ SIGNATURES = {
     "uwm_mask_element": (I, [I, I, I, P]),
     "uwm_mask_workspace_bytes": (Z, [I, I, I]),
     "uwm_optimize_mask": (I, [P, P, I, I, I, I, P, P, Z, P]),
+    "uwm_mask_ragged_workspace_bytes": (Z, [I, Z, L]),
+    "uwm_optimize_masks_ragged": (I, [P, P, Z, P, I, I, L, L, P, P, Z, P]),
     "uwm_op_morph": (I, [P, P, I, I, I, I, I, I, I, I, P, Z, P]),
     "uwm_op_components": (I, [P, P, P, I, I, I, P, Z, P]),
     "uwm_set_side_stream": (I, [P, I]),

@@ -1,4 +1,4 @@
-"""`python main.py train|predict|masks|filter|synth ...` — counterpart of the reference's CLI for the model path
+"""`python main.py train|predict|masks|filter|select|synth ...` — counterpart of the reference's CLI for the model path
 (/root/reference/src/cli.py:368-395 flag names; train loop order /root/reference/src/train.py:207-499:
 epochs of train_epoch + validate (val batch = 2x train batch, :254), Adam | SGD (:265-279), ReduceLROnPlateau on the
 val loss | CosineAnnealingLR (:280-296,408-412), best / periodic checkpoints (:428-460), early stopping (:37-66,362-368)).
@@ -519,8 +519,28 @@ def filter_command(args):
     return stats
 
 
+def select_command(args):
+    """The reference's src/scripts/model_selector.py on the device: every checkpoint on a seeded sample of images, then the summary."""
+    from .select import ModelSelector
+    if not os.path.exists(args.input):
+        raise SystemExit(f"select: input path not found: {args.input}")
+    if not os.path.exists(args.model):
+        raise SystemExit(f"select: model path not found: {args.model}")
+    if args.config and not os.path.exists(args.config):
+        raise SystemExit(f"select: config file not found: {args.config}")
+    if not torch.cuda.is_available():
+        raise SystemExit("select needs a HIP device (this path has no CPU fallback)")
+    cfg = get_cfg_defaults()
+    if args.config:
+        update_config(cfg, args.config)
+    if args.encoder:
+        cfg.MODEL.ENCODER_NAME = args.encoder
+    sel = ModelSelector(args.input, args.model, args.output, args.num_samples, cfg, args.mask_type, args.batch_size, args.seed, args.save_masks)
+    return sel.run_evaluation()
+
+
 def build_parser():
-    ap = argparse.ArgumentParser(description="MI355X-native U-Net watermark segmentation (train | masks | filter | predict)")
+    ap = argparse.ArgumentParser(description="MI355X-native U-Net watermark segmentation (train | masks | filter | select | predict)")
     sub = ap.add_subparsers(dest="command")
     tp = sub.add_parser("train")
     tp.add_argument("--config", type=str, default=None)
@@ -600,6 +620,26 @@ def build_parser():
     act.add_argument("--delete", action="store_true", help="delete the images without a watermark (never done without this flag)")
     fp.add_argument("--dry-run", action="store_true", help="report what would be moved or deleted; touch nothing")
     fp.add_argument("--batch-size", type=int, default=None, help="images per captured call (default PREDICT.BATCH_SIZE)")
+    lp = sub.add_parser("select", help="rank checkpoints on a seeded sample of images (the reference's scripts/model_selector.py)",
+                        description="Run every .pth under --model on a seeded sample of the images under --input and write "
+                                    "model_evaluation_results.json (the reference's keys) to --output: per image the watermark ratio and "
+                                    "the component statistics of the post-processed mask, per model the detection rate (share of ratios "
+                                    "above 0.001), and the model with the highest.  A batch is one captured call on the device and 64 bytes "
+                                    "back per image.  Deliberate departures from the reference's script: masks are written only with "
+                                    "--save-masks (the reference writes one PNG per image and model); an image that cannot be read is a "
+                                    "failed prediction of every model, not fatal; a model is keyed by its path relative to --model (the "
+                                    "reference keys by file name, so same-named files of different sub-directories overwrite each other); "
+                                    "one process and one device, no worker processes.")
+    lp.add_argument("--input", type=str, required=True, help="the folder of images (png, jpg, jpeg, bmp, tiff), or one image")
+    lp.add_argument("--model", type=str, required=True, help="a directory searched recursively for .pth files, or one .pth file")
+    lp.add_argument("--output", type=str, required=True, help="where model_evaluation_results.json (and the masks) go")
+    lp.add_argument("--num-samples", type=int, default=100, help="images drawn with random.sample (the script's default)")
+    lp.add_argument("--seed", type=int, default=42); lp.add_argument("--config", type=str, default=None)
+    lp.add_argument("--encoder", type=str)
+    lp.add_argument("--mask-type", choices=["watermark", "text", "mixed"], default="watermark",
+                    help="the _optimize_mask type every mask goes through (predict_mask's default: watermark)")
+    lp.add_argument("--batch-size", type=int, default=None, help="images per captured call (default PREDICT.BATCH_SIZE)")
+    lp.add_argument("--save-masks", action="store_true", help="also write <image>_<model>_mask.png for every image and model")
     pp = sub.add_parser("predict")
     pp.add_argument("--input", type=str, required=True); pp.add_argument("--output", type=str, required=True)
     pp.add_argument("--model", type=str, required=True); pp.add_argument("--config", type=str, default=None)
@@ -627,4 +667,6 @@ def main(argv=None):
         return filter_command(args)
     if args.command == "synth":
         return synth_command(args)
+    if args.command == "select":
+        return select_command(args)
     ap.print_help()

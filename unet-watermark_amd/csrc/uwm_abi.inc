@@ -580,6 +580,31 @@ int uwm_optimize_mask(const uint8_t* in, uint8_t* out, int N, int H, int W, int 
   LCHK(launch_optimize_mask(in, out, N, H, W, mask_type, summary, ws, (hipStream_t)stream));
   return 0;
 }
+static int mask_ragged_caps_check(const char* fn, int N, size_t mask_bytes, long long rows) {
+  if (N < 1 || mask_bytes < 1 || rows < 1) return fail("%s: N, mask_bytes and rows must be >= 1 (got %d, %zu, %lld)", fn, N, mask_bytes, rows);
+  if (N > 65535) return fail("%s: N too large: at most 65535 masks per call (got %d)", fn, N);
+  if (mask_bytes > ((size_t)1 << 40) || rows > (1ll << 40)) return fail("%s: mask_bytes and rows too large: at most 2^40 (got %zu, %lld)", fn, mask_bytes, rows);
+  return 0;
+}
+size_t uwm_mask_ragged_workspace_bytes(int N, size_t mask_bytes, long long rows) {
+  if (mask_ragged_caps_check("uwm_mask_ragged_workspace_bytes", N, mask_bytes, rows)) return 0;
+  return mask_ragged_workspace_bytes(N, mask_bytes, rows);
+}
+int uwm_optimize_masks_ragged(const uint8_t* in, uint8_t* out, size_t mask_bytes, const uwm_image_desc* descs, int N, int mask_type,
+                              long long max_pixels, long long rows, long long* stats, void* ws, size_t ws_bytes, uwm_stream stream) {
+  const char* fn = "uwm_optimize_masks_ragged";
+  if (!in || !out || !descs || !ws) return fail("%s: null argument", fn);
+  if (mask_type != UWM_MASK_WATERMARK && mask_type != UWM_MASK_TEXT && mask_type != UWM_MASK_MIXED && mask_type != UWM_MASK_NONE)
+    return fail("%s: unknown mask type %d (UWM_MASK_WATERMARK = 0 | UWM_MASK_TEXT = 1 | UWM_MASK_MIXED = 2 | UWM_MASK_NONE = 3)", fn, mask_type);
+  if (mask_ragged_caps_check(fn, N, mask_bytes, rows)) return 1;
+  if (max_pixels < 1) return fail("%s: max_pixels must be >= 1 (got %lld)", fn, max_pixels);
+  if (max_pixels >= 2147483647ll) return fail("%s: max_pixels too large: it must be below 2^31 - 1 (got %lld)", fn, max_pixels);
+  if (((uintptr_t)descs | (uintptr_t)stats | (uintptr_t)ws) & 7) return fail("%s: descriptors, stats and the workspace must be 8-byte aligned", fn);
+  const size_t need = mask_ragged_workspace_bytes(N, mask_bytes, rows);
+  if (ws_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", fn, ws_bytes, need);
+  LCHK(launch_optimize_masks_ragged(in, out, mask_bytes, (const ImageDesc*)descs, N, mask_type, max_pixels, rows, stats, ws, (hipStream_t)stream));
+  return 0;
+}
 int uwm_op_morph(const uint8_t* in, uint8_t* out, int N, int H, int W, int dilate, int shape, int kw, int kh, int iterations,
                  void* ws, size_t ws_bytes, uwm_stream stream) {
   if (!in || !out) return fail("uwm_op_morph: null argument");

@@ -584,5 +584,10 @@ hipError_t launch_mask_morph(const uint8_t* in, uint8_t* out, int N, int H, int 
 hipError_t launch_mask_components(const uint8_t* in, int* labels, int* areas, int N, int H, int W, void* ws, hipStream_t st);
 hipError_t launch_optimize_mask(const uint8_t* in, uint8_t* out, int N, int H, int W, int mask_type, long long* summary, void* ws,
                                 hipStream_t st);
+// the same on a ragged batch (image i: descs[i], read on the device); mask_type 3 = no morphology, every component kept.
+// ws: mask_ragged_workspace_bytes(N, mask_bytes, rows) bytes; stats (may be null): [N][8], include/uwm.h
+size_t mask_ragged_workspace_bytes(int N, size_t mask_bytes, long long rows);
+hipError_t launch_optimize_masks_ragged(const uint8_t* in, uint8_t* out, size_t mask_bytes, const ImageDesc* descs, int N, int mask_type,
+                                        long long max_pixels, long long rows, long long* stats, void* ws, hipStream_t st);
 
 }  // namespace uwm

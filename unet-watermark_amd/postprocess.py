@@ -2,12 +2,14 @@
 (/root/reference/src/predict.py:161-301): binary morphology (open / close / dilate with elliptical and line elements), an
 8-connected component analysis and a selection by area, for the three mask types `watermark`, `text`, `mixed`.  The reference
 does this with OpenCV on the host; here it is HIP (csrc/mask_post.hip: uwm_optimize_mask and its building blocks), exact integer
-work whose results equal the specification in DESIGN.md §8b bit for bit.  No CPU fallback.
+work whose results equal the specification in DESIGN.md §8b bit for bit.  No CPU fallback.  optimize_masks_ragged is the same on
+a ragged batch of masks of any sizes in ONE call (uwm_optimize_masks_ragged), with eight statistics per image.
 
 The reference's automatic type detection (_detect_watermark_type: Canny / Sobel on the image) and _enhance_text_features stay out."""
 from __future__ import annotations
 
 import ctypes as C
+from typing import Optional
 
 import numpy as np
 import torch
@@ -95,6 +97,72 @@ def optimize_mask(mask_u8: torch.Tensor, mask_type: str = "watermark", return_su
     if return_summary:
         return res, (summary[0] if squeeze else summary)
     return res
+
+
+RAGGED_TYPES = {**MASK_TYPES, "none": 3}                 # 'none' (UWM_MASK_NONE): binarise, no morphology, every component kept
+STATS_FIELDS = ("components", "largest_area", "foreground", "largest_id", "kept_components", "largest_kept_area", "pixels", "status")
+_rws = {}                                                 # device -> workspace tensor of the ragged call (grown on demand)
+
+
+def ragged_workspace(device, n: int, mask_bytes: int, rows: int) -> torch.Tensor:
+    """The ragged call's scratch for the capacities (n, mask_bytes, rows): one buffer per device, kept and grown like `workspace`; a
+    captured graph holds the buffer it was captured with."""
+    need = L.lib().uwm_mask_ragged_workspace_bytes(int(n), int(mask_bytes), int(rows))
+    if need == 0:
+        raise RuntimeError(L.lib().uwm_last_error().decode(errors="replace"))
+    key = str(device)
+    ws = _rws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _rws[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws
+
+
+def optimize_masks_ragged(buf: torch.Tensor, descs, mask_type: str = "watermark", return_stats: bool = False, out=None, *,
+                          n: Optional[int] = None, max_pixels: Optional[int] = None, rows: Optional[int] = None, stats=None):
+    """A ragged batch of masks through ONE library call (uwm_optimize_masks_ragged), whatever their sizes.  buf: uint8 1-d device
+    tensor; image i is descs[i]'s (h, w), one byte per pixel, at buf[descs[i].offset:].  descs: a host record array with the fields
+    offset / h / w (uploaded here), or a device tensor of uwm_image_desc bytes — then n, max_pixels and rows must be given, nothing
+    about the batch is read on the host, and the call can be captured.  -> the uint8 buffer of the results at the same offsets
+    (`out`, which may be buf itself, or a new tensor; bytes outside the images are then zero), with return_stats also the int64
+    (n, 8) device tensor STATS_FIELDS (`stats`: a tensor to write them into).  mask_type: 'watermark' | 'text' | 'mixed' | 'none'.
+    max_pixels / rows: capacities, at least the largest h*w and the sum of h; an image beyond a capacity is a misfit (status 1)."""
+    if mask_type not in RAGGED_TYPES:
+        raise ValueError(f"mask_type must be one of 'watermark', 'text', 'mixed', 'none', got {mask_type!r}")
+    if not isinstance(buf, torch.Tensor) or buf.device.type != "cuda":
+        raise RuntimeError("uwm optimize_masks_ragged runs only on a HIP device (no CPU fallback)")
+    if buf.dtype != torch.uint8 or buf.dim() != 1 or buf.numel() == 0 or not buf.is_contiguous():
+        raise RuntimeError(f"expected a non-empty contiguous 1-d uint8 buffer, got {buf.dtype} {tuple(buf.shape)}")
+    if isinstance(descs, torch.Tensor):
+        if n is None or max_pixels is None or rows is None:
+            raise ValueError("optimize_masks_ragged: device descriptors need n, max_pixels and rows")
+        if descs.device != buf.device or descs.dtype != torch.uint8 or descs.numel() < 16 * int(n):
+            raise RuntimeError("optimize_masks_ragged: descs must be a uint8 tensor of 16 n bytes on the buffer's device")
+        d = descs
+    else:
+        from .data import descs_tensor
+        n = len(descs) if n is None else int(n)
+        if n < 1:
+            raise ValueError("optimize_masks_ragged: empty batch")
+        if max_pixels is None:
+            max_pixels = max(1, int((descs["h"].astype("int64") * descs["w"]).max()))
+        if rows is None:
+            rows = max(1, int(descs["h"].astype("int64").clip(min=0).sum()))
+        d = descs_tensor(descs).to(buf.device)
+    if out is None:
+        o = torch.zeros_like(buf)
+    else:
+        if out.dtype != torch.uint8 or out.device != buf.device or out.numel() != buf.numel() or not out.is_contiguous():
+            raise RuntimeError("optimize_masks_ragged: out must be a contiguous uint8 tensor of the buffer's size on the same device")
+        o = out
+    if return_stats and stats is None:
+        stats = torch.empty((int(n), 8), dtype=torch.int64, device=buf.device)
+    with L.on_device(buf):
+        ws = ragged_workspace(buf.device, n, buf.numel(), rows)
+        L.check(L.lib().uwm_optimize_masks_ragged(C.c_void_p(buf.data_ptr()), C.c_void_p(o.data_ptr()), buf.numel(), C.c_void_p(d.data_ptr()),
+                                                  int(n), RAGGED_TYPES[mask_type], int(max_pixels), int(rows),
+                                                  C.c_void_p(stats.data_ptr() if return_stats else 0), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                                  C.c_void_p(L.stream_ptr(buf.device))))
+    return (o, stats) if return_stats else o
 
 
 def morphology(mask_u8: torch.Tensor, op: str, shape, ksize, iterations: int = 1) -> torch.Tensor:

@@ -17,7 +17,7 @@ from .constants import IMAGENET_MEAN, IMAGENET_STD  # noqa: F401   (predict.IMAG
 from .data import descs_tensor, device_preprocess, pack_images
 from .metrics import threshold_mask
 from .model import create_model_from_config
-from .postprocess import mask_type_code, optimize_mask, workspace as mask_workspace
+from .postprocess import RAGGED_TYPES, mask_type_code, optimize_mask, optimize_masks_ragged, ragged_workspace, workspace as mask_workspace
 
 
 class WatermarkPredictor:
@@ -53,6 +53,10 @@ class WatermarkPredictor:
         self._igraph = None                   # predict_images: ONE graph per (N, H, W, apply_sigmoid, threshold), whatever the image sizes
         self._ikey = None
         self._ibuf = self._idesc = self._mdesc = self._mbuf = self._iws = None      # its static staging buffers
+        self._qgraph = None                   # predict_images(mask_type=...) / mask_stats: the same with the ragged post-processing
+        self._qkey = None
+        self._qws = self._sbuf = None         # ... its static (N, 8) stats, and the capacities of the post-processing in it
+        self._cap_pixels = self._cap_rows = 0
         self._cgraph = None                   # watermark_counts: ONE graph per (N, IMG_SIZE, threshold, post_process, with masks)
         self._ckey = None
         self._cbuf = self._cws = None         # its static counts buffer and workspaces
@@ -115,7 +119,7 @@ class WatermarkPredictor:
         captured on the old arena contents go."""
         if self.freeze and not self.model.frozen_serves(n, h, w):
             self.model.freeze(batch_shape=(n, h, w))
-            self._graph = self._gkey = self._ugraph = self._ukey = self._pgraph = self._pkey = self._igraph = self._ikey = self._cgraph = self._ckey = None
+            self._graph = self._gkey = self._ugraph = self._ukey = self._pgraph = self._pkey = self._igraph = self._ikey = self._qgraph = self._qkey = self._cgraph = self._ckey = None
 
     @torch.no_grad()
     def predict_mask_u8(self, images_u8_nhwc: torch.Tensor, out_size=None, apply_sigmoid: bool = False,
@@ -165,7 +169,7 @@ class WatermarkPredictor:
             return
         cap = max(need, 256 if buf is None else 2 * buf.numel())
         setattr(self, name, torch.zeros(cap, dtype=torch.uint8, device=self.device))
-        self._igraph = self._ikey = self._cgraph = self._ckey = None
+        self._igraph = self._ikey = self._qgraph = self._qkey = self._cgraph = self._ckey = None
 
     def _stage_images(self, images):
         """pack `images` into the static staging buffers (_ibuf, _idesc, _mdesc; _mbuf sized for their masks) -> (n, IMG_SIZE, descs,
@@ -194,38 +198,86 @@ class WatermarkPredictor:
         self._mdesc[:16 * n].copy_(descs_tensor(mdescs))
         return n, s, descs, mdescs, areas, mask_bytes
 
-    @torch.no_grad()
-    def predict_images(self, images, apply_sigmoid: bool = False, mask_type: Optional[str] = None, use_graph: bool = True):
-        """uint8 (h_i, w_i, C) images of ANY sizes (arrays or tensors) -> a list of uint8 {0,255} device masks, one per image at its
-        own size: the reference's predict path (src/predict.py:327-335,614-625) device-resident from the image bytes on — cv2's
-        INTER_LINEAR resize to IMG_SIZE (A.Resize) + Normalize, eval forward, bilinear resize of the logits back to (h_i, w_i) +
-        threshold, in ONE library call (uwm_predict_images_u8).  The per-image geometry lives in device memory, so one captured
-        graph per (N, IMG_SIZE, apply_sigmoid) serves every batch of N images; it is re-captured only when a staging buffer had
-        to grow or the frozen arena was re-made.  mask_type 'watermark' | 'text' | 'mixed': each mask then goes through
-        optimize_mask at its own size, outside the graph."""
-        if mask_type is not None:
-            mask_type_code(mask_type)
+    def _run_images(self, images, apply_sigmoid: bool, mask_type: Optional[str], use_graph: bool):
+        """stage `images`, run uwm_predict_images_u8 and, with a mask_type, uwm_optimize_masks_ragged in place on _mbuf — one captured
+        graph for both -> (descs, mask descs, areas, mask bytes, the int64 (n, 8) device stats or None).  The ragged call's
+        capacities (the largest h*w, the sum of h) are kept and grown geometrically like the staging buffers; they and the buffer
+        sizes are all the graph knows about a batch, so a batch that fits them replays it and one that exceeds one re-captures."""
         n, s, descs, mdescs, areas, mask_bytes = self._stage_images(images)
-        run = lambda: self.model.predict_images_u8(self._ibuf, self._idesc, self._mdesc, self._mbuf, n, (s, s), IMAGENET_MEAN,
-                                                   IMAGENET_STD, self.threshold, apply_sigmoid)
+        if mask_type is not None:
+            for name, need in (("_cap_pixels", int(areas.max())), ("_cap_rows", int(descs["h"].astype("int64").sum()))):
+                if getattr(self, name) < need:
+                    setattr(self, name, min(max(need, 2 * getattr(self, name)), 2 ** 31 - 2 if name == "_cap_pixels" else 2 ** 40))
+        caps = () if mask_type is None else (mask_type, self._cap_pixels, self._cap_rows)
+        stats = None
+
+        def run():
+            self.model.predict_images_u8(self._ibuf, self._idesc, self._mdesc, self._mbuf, n, (s, s), IMAGENET_MEAN, IMAGENET_STD,
+                                         self.threshold, apply_sigmoid)
+            if mask_type is not None:
+                optimize_masks_ragged(self._mbuf, self._mdesc, mask_type, True, out=self._mbuf, n=n, max_pixels=caps[1], rows=caps[2],
+                                      stats=stats)
         if not use_graph:
+            if mask_type is not None:
+                stats = torch.empty((n, 8), dtype=torch.int64, device=self.device)
             run()
         else:
-            key = (n, s, s, bool(apply_sigmoid), float(self.threshold))      # (the threshold is a captured kernel argument)
-            if self._ikey != key or self._igraph is None:
+            key = (n, s, s, bool(apply_sigmoid), float(self.threshold)) + caps      # (the threshold and the capacities are captured arguments)
+            slot = "_i" if mask_type is None else "_q"      # the graph without post-processing stays when the other is captured
+            if getattr(self, slot + "key") != key or getattr(self, slot + "graph") is None:
                 self._refreeze_for(n, s, s)
+                if mask_type is not None:
+                    stats = self._sbuf = torch.empty((n, 8), dtype=torch.int64, device=self.device)
                 run()                                 # eager warm-up: plans the workspace, sets kernel attributes
                 torch.cuda.synchronize(self.device)
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
                     run()
-                self._igraph, self._ikey, self._iws = g, key, self.model._ws
-            self._igraph.replay()
+                ws = self.model._ws                   # (the graph's workspaces stay alive with it)
+                if mask_type is not None:
+                    ws = (ws, ragged_workspace(self.device, n, self._mbuf.numel(), caps[2]))
+                setattr(self, slot + "graph", g); setattr(self, slot + "key", key); setattr(self, slot + "ws", ws)
+            stats = self._sbuf if mask_type is not None else None
+            getattr(self, slot + "graph").replay()
+        return descs, mdescs, areas, mask_bytes, stats
+
+    def _mask_views(self, descs, mdescs, areas, mask_bytes):
         out = self._mbuf[:mask_bytes].clone()         # (the staging buffer is overwritten by the next call)
-        masks = [out[int(o): int(o) + int(a)].view(int(h), int(w)) for o, a, h, w in zip(mdescs["offset"], areas, descs["h"], descs["w"])]
+        return [out[int(o): int(o) + int(a)].view(int(h), int(w)) for o, a, h, w in zip(mdescs["offset"], areas, descs["h"], descs["w"])]
+
+    @torch.no_grad()
+    def predict_images(self, images, apply_sigmoid: bool = False, mask_type: Optional[str] = None, use_graph: bool = True,
+                       return_stats: bool = False):
+        """uint8 (h_i, w_i, C) images of ANY sizes (arrays or tensors) -> a list of uint8 {0,255} device masks, one per image at its
+        own size: the reference's predict path (src/predict.py:327-335,614-625) device-resident from the image bytes on — cv2's
+        INTER_LINEAR resize to IMG_SIZE (A.Resize) + Normalize, eval forward, bilinear resize of the logits back to (h_i, w_i) +
+        threshold, in ONE library call (uwm_predict_images_u8).  The per-image geometry lives in device memory, so one captured
+        graph per (N, IMG_SIZE, apply_sigmoid) serves every batch of N images; it is re-captured only when a staging buffer had
+        to grow or the frozen arena was re-made.  mask_type 'watermark' | 'text' | 'mixed': every mask then goes through the
+        reference's _optimize_mask at its own size (uwm_optimize_masks_ragged), in place and inside the same graph; the graph is
+        then also re-captured when the largest image or the sum of the heights outgrows the capacity it was captured with.
+        return_stats (needs a mask_type): also the int64 (N, 8) HOST array of postprocess.STATS_FIELDS."""
         if mask_type is not None:
-            masks = [optimize_mask(m, mask_type) for m in masks]
-        return masks
+            mask_type_code(mask_type)
+        elif return_stats:
+            raise ValueError("return_stats needs a mask_type ('watermark', 'text' or 'mixed')")
+        descs, mdescs, areas, mask_bytes, stats = self._run_images(images, apply_sigmoid, mask_type, use_graph)
+        masks = self._mask_views(descs, mdescs, areas, mask_bytes)
+        return (masks, stats.cpu().numpy()) if return_stats else masks
+
+    @torch.no_grad()
+    def mask_stats(self, images, mask_type: str = "watermark", return_masks: bool = False, use_graph: bool = True):
+        """uint8 (h_i, w_i, C) images of ANY sizes -> the int64 (N, 8) HOST array of postprocess.STATS_FIELDS for the masks
+        predict_images(mask_type=...) returns: {components found, largest area, foreground pixels, id of the largest or -1,
+        components kept, largest kept area, h_i * w_i, status}.  Entries 2, 4, 5 and 6 are what the reference's model selector
+        computes from every mask on the host (src/scripts/model_selector.py:171-197).  One captured call and one device-to-host
+        copy of 64 N bytes; no mask leaves the device unless return_masks, which adds the list of device masks.  mask_type may also be
+        'none': the thresholded masks as they are."""
+        if mask_type not in RAGGED_TYPES:
+            raise ValueError(f"mask_type must be one of 'watermark', 'text', 'mixed', 'none', got {mask_type!r}")
+        descs, mdescs, areas, mask_bytes, stats = self._run_images(images, False, mask_type, use_graph)
+        host = stats.cpu().numpy()
+        return (host, self._mask_views(descs, mdescs, areas, mask_bytes)) if return_masks else host
 
     @torch.no_grad()
     def watermark_counts(self, images, post_process: Optional[bool] = None, return_masks: bool = False, use_graph: bool = True):
