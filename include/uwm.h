@@ -363,6 +363,36 @@ int  uwm_loss_apply(const float* logits, int ld, const void* target, int target_
                     float w_dice, float w_bce, float smooth, float eps, const void* scratch, float* loss_out,
                     float* dlogits, int ldd, float grad_scale, uwm_stream stream);
 
+/* The rest of the reference's loss menu (LOSS.NAME JaccardLoss | TverskyLoss | FocalLoss, and any weighted mix with Dice and BCE)
+ * on one fused pass.  The terms are smp's JaccardLoss / TverskyLoss / FocalLoss in mode='binary', from_logits=True (log_loss,
+ * normalized, reduced_threshold, ignore_index: not served), with I = sum p*t, P = sum p, T = sum t over the batch:
+ *   jaccard = 1 - (I + smooth) / max(P + T - I + smooth, eps)
+ *   tversky = (1 - (I + smooth) / max(I + alpha (P - I) + beta (T - I) + smooth, eps)) ^ gamma
+ *   focal   = mean_i a_i (1 - pt_i)^gamma bce_i,  pt_i = exp(-bce_i),  a_i = alpha t_i + (1 - alpha)(1 - t_i), or 1 without alpha
+ * Dice and BCE as in uwm_loss; the three region losses are 0 for a batch without foreground (T == 0).  smp's defaults: smooth 0,
+ * eps 1e-7, tversky alpha = beta 0.5, gamma 1, focal alpha none, gamma 2. */
+typedef struct uwm_loss_spec {
+  float w_dice, w_bce, w_jaccard, w_tversky, w_focal;
+  float dice_smooth, dice_eps, jaccard_smooth, jaccard_eps, tversky_smooth, tversky_eps;
+  float tversky_alpha, tversky_beta, tversky_gamma;   /* gamma > 0 */
+  float focal_alpha;                                  /* < 0: none; otherwise <= 1 */
+  float focal_gamma;                                  /* >= 0 */
+} uwm_loss_spec;
+/* loss = sum of the five weighted terms.  Arguments as uwm_loss, except: loss_out: 8 device floats {total, dice, bce, jaccard,
+ * tversky, focal, 0, 0} — every term is reported whatever its weight, but focal only when w_focal != 0 (its arithmetic is compiled
+ * out of both passes otherwise, and it reads 0); dlogits' padding channels 1..ldd-1 are written as zeros (one 16-byte store per
+ * pixel when ldd == 4 and dlogits is 16-byte aligned).  Nothing synchronises with the host.  uwm_loss_ext_sums leaves FIVE doubles
+ * {sum p*t, sum p, sum t, sum bce, sum focal} in scratch[0..4] (40 bytes to all-reduce); uwm_loss_ext_apply is the counterpart of
+ * uwm_loss_apply, with the same grad_scale = world_size rule.  Both halves must see the same spec. */
+int  uwm_loss_ext(const float* logits, int ld, const void* target, int target_dtype, long long npix, const uwm_loss_spec* spec,
+                  void* scratch /* >= 64 B */, float* loss_out /* 8 */, float* dlogits /* may be NULL */, int ldd, float grad_scale,
+                  uwm_stream stream);
+int  uwm_loss_ext_sums(const float* logits, int ld, const void* target, int target_dtype, long long npix, const uwm_loss_spec* spec,
+                       void* scratch, uwm_stream stream);
+int  uwm_loss_ext_apply(const float* logits, int ld, const void* target, int target_dtype, long long npix, long long npix_total,
+                        const uwm_loss_spec* spec, const void* scratch, float* loss_out, float* dlogits, int ldd, float grad_scale,
+                        uwm_stream stream);
+
 /* out[N][4] int64 = tp, fp, fn, tn of (v >= threshold), v = sigmoid(logit) if apply_sigmoid else logit */
 int  uwm_stats(const float* logits, int ld, const void* target, int target_dtype, int N, long long hw,
                float threshold, int apply_sigmoid, long long* out, uwm_stream stream);

@@ -18,7 +18,7 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 _PKG_DIR = Path(__file__).resolve().parent
 _CSRC = _PKG_DIR / "csrc"
 LIB_PATH = _PKG_DIR / "libuwm.so"
-SOURCES = ["uwm_route.hip", "conv_igemm.hip", "conv_patch.hip", "conv_patch16.hip", "conv_wino.hip", "conv_wino8.hip", "conv_wino_x3.hip", "conv_f16x3.hip", "conv_f16x3v2.hip", "conv_stem_f16x3.hip", "conv_up2.hip", "conv_up2_f16.hip", "conv_c16_f16.hip", "conv_gemm.hip", "conv_head.hip", "mbconv.hip", "wgrad_igemm.hip", "wgrad_patch.hip", "wgrad_wino.hip", "wgrad_f16x3.hip", "wgrad_c16.hip", "wgrad_gemm.hip", "wgrad_stem.hip", "elementwise.hip", "loss.hip", "mask_post.hip", "resize_u8.hip", "pair_mask_u8.hip", "synth_u8.hip", "filter_u8.hip", "augment_u8.hip", "augment_ext_u8.hip", "jpeg_u8.hip", "uwm_model.hip"]
+SOURCES = ["uwm_route.hip", "conv_igemm.hip", "conv_patch.hip", "conv_patch16.hip", "conv_wino.hip", "conv_wino8.hip", "conv_wino_x3.hip", "conv_f16x3.hip", "conv_f16x3v2.hip", "conv_stem_f16x3.hip", "conv_up2.hip", "conv_up2_f16.hip", "conv_c16_f16.hip", "conv_gemm.hip", "conv_head.hip", "mbconv.hip", "wgrad_igemm.hip", "wgrad_patch.hip", "wgrad_wino.hip", "wgrad_f16x3.hip", "wgrad_c16.hip", "wgrad_gemm.hip", "wgrad_stem.hip", "elementwise.hip", "loss.hip", "loss_ext.hip", "mask_post.hip", "resize_u8.hip", "pair_mask_u8.hip", "synth_u8.hip", "filter_u8.hip", "augment_u8.hip", "augment_ext_u8.hip", "jpeg_u8.hip", "uwm_model.hip"]
 HIP_ARCH = "gfx950"
 # per-file compiler flags.  The fp16x3 kernels interleave their staging VALU work with MFMAs; hipcc turns the f4 arithmetic of that
 # work into packed v_pk_{fma,mul,add}_f32, which cost more than two plain VALU instructions beside MFMAs (MI355X_MICROARCH.md,
@@ -44,6 +44,13 @@ class uwm_tensor_info(C.Structure):
 class uwm_src(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p),
                 ("C", C.c_int), ("H", C.c_int), ("W", C.c_int), ("up", C.c_int), ("relu", C.c_int)]
+
+
+class uwm_loss_spec(C.Structure):
+    """include/uwm.h: the weights and parameters of the five loss terms uwm_loss_ext serves (focal_alpha < 0: none)"""
+    _fields_ = [(n, C.c_float) for n in ("w_dice", "w_bce", "w_jaccard", "w_tversky", "w_focal", "dice_smooth", "dice_eps", "jaccard_smooth",
+                                         "jaccard_eps", "tversky_smooth", "tversky_eps", "tversky_alpha", "tversky_beta", "tversky_gamma",
+                                         "focal_alpha", "focal_gamma")]
 
 
 KIND_CONV_W, KIND_BIAS, KIND_BN_GAMMA, KIND_BN_BETA, KIND_BN_MEAN, KIND_BN_VAR = range(6)
@@ -97,6 +104,9 @@ SIGNATURES = {
     "uwm_loss": (I, [P, I, P, I, L, F, F, F, F, P, P, P, I, F, P]),
     "uwm_loss_sums": (I, [P, I, P, I, L, P, P]),
     "uwm_loss_apply": (I, [P, I, P, I, L, L, F, F, F, F, P, P, P, I, F, P]),
+    "uwm_loss_ext": (I, [P, I, P, I, L, C.POINTER(uwm_loss_spec), P, P, P, I, F, P]),
+    "uwm_loss_ext_sums": (I, [P, I, P, I, L, C.POINTER(uwm_loss_spec), P, P]),
+    "uwm_loss_ext_apply": (I, [P, I, P, I, L, L, C.POINTER(uwm_loss_spec), P, P, P, I, F, P]),
     "uwm_stats": (I, [P, I, P, I, I, L, F, I, P, P]),
     "uwm_threshold": (I, [P, I, L, F, I, P, P]),
     "uwm_adam": (I, [P, P, P, P, L, F, F, F, F, F, L, F, P]),

@@ -21,7 +21,7 @@ from .checkpoint import load_checkpoint, save_checkpoint
 from .config import get_cfg_defaults, update_config
 from .data import (AUG_RECIPES, AUG_RECIPES_EXT, DeviceInputPipeline, DeviceU8Dataset, FolderDataset, RawFolderDataset, RawPairDataset,
                    RawSynthDataset, SyntheticWatermarkDataset, list_collate)
-from .losses import get_loss_function
+from .losses import CombinedLoss, FocalLoss, criterion_spec, get_loss_function
 from .metrics import logits_metrics
 from .model import create_model_from_config
 from .predict import WatermarkPredictor
@@ -37,6 +37,40 @@ def _loss_weights(cfg):
     if name == "CombinedLoss":
         return float(cfg.LOSS.DICE_WEIGHT), float(cfg.LOSS.BCE_WEIGHT)
     raise ValueError(f"unsupported LOSS.NAME {name!r} (DiceLoss | BCEWithLogitsLoss | CombinedLoss)")
+
+
+def _criterion(cfg, args=None):
+    """The configured loss as a module: get_loss_function(cfg), plus the focal term of --focal-weight config|FLOAT.  The flag is
+    served with LOSS.NAME CombinedLoss only (the text-watermark recipe, whose FOCAL_WEIGHT the reference's own trainer ignores):
+    'config' takes the weight from LOSS.FOCAL_WEIGHT, a number is the weight; both read LOSS.FOCAL_ALPHA and LOSS.FOCAL_GAMMA."""
+    criterion = get_loss_function(cfg)
+    fw = getattr(args, "focal_weight", None)
+    if fw is None:
+        return criterion
+    if cfg.LOSS.NAME != "CombinedLoss":
+        raise ValueError(f"--focal-weight adds a focal term to LOSS.NAME 'CombinedLoss'; the config names {cfg.LOSS.NAME!r} "
+                         "(LOSS.NAME 'FocalLoss' trains on the focal loss alone)")
+    if fw == "config":
+        if cfg.LOSS.get("FOCAL_WEIGHT", None) is None:
+            raise ValueError("--focal-weight config: the config has no LOSS.FOCAL_WEIGHT")
+        weight = float(cfg.LOSS.FOCAL_WEIGHT)
+    else:
+        try:
+            weight = float(fw)
+        except ValueError:
+            raise ValueError(f"--focal-weight {fw!r}: 'config' or a number") from None
+    alpha = cfg.LOSS.get("FOCAL_ALPHA", None)
+    focal = FocalLoss(mode=getattr(cfg.LOSS, "MODE", "binary"), alpha=None if alpha is None else float(alpha),
+                      gamma=float(cfg.LOSS.get("FOCAL_GAMMA", 2.0)))
+    return CombinedLoss(criterion.losses + [focal], criterion.weights + [weight])
+
+
+def _loss_spec(cfg, args=None):
+    """The Trainer's loss_spec: None for the losses the Dice / BCE step serves (DiceLoss | BCEWithLogitsLoss | CombinedLoss without
+    --focal-weight: the Trainer then takes _loss_weights, as before), else the uwm_loss_spec of _criterion(cfg, args)."""
+    if cfg.LOSS.NAME in ("DiceLoss", "BCEWithLogitsLoss", "CombinedLoss") and getattr(args, "focal_weight", None) is None:
+        return None
+    return criterion_spec(_criterion(cfg, args))
 
 
 def _served_recipe(augment, cfg, jpeg="refuse"):
@@ -232,6 +266,8 @@ def train_command(args):
         raise ValueError(f"MODEL.NAME={cfg.MODEL.NAME!r}: this build serves 'Unet' and 'UnetPlusPlus'")
     if cfg.OPTIMIZER.NAME not in ("Adam", "AdamW", "SGD"):
         raise ValueError(f"unsupported optimizer: {cfg.OPTIMIZER.NAME}")           # /root/reference/src/train.py:279
+    criterion = _criterion(cfg, args)            # (an unserved LOSS.NAME or --focal-weight is refused here, before any device work)
+    loss_spec = _loss_spec(cfg, args)
     if cfg.MODEL.ENCODER_WEIGHTS is not None:
         print(f"note: ENCODER_WEIGHTS={cfg.MODEL.ENCODER_WEIGHTS!r} needs a download; training from seeded init")
         cfg.MODEL.ENCODER_WEIGHTS = None
@@ -253,12 +289,11 @@ def train_command(args):
         own_group = True
     torch.manual_seed(int(cfg.DATA.SEED))
     model = create_model_from_config(cfg).to(device)
-    wd, wb = _loss_weights(cfg)
+    wd, wb = (1.0, 0.0) if loss_spec is not None else _loss_weights(cfg)          # (a loss_spec replaces them)
     trainer = Trainer(model, w_dice=wd, w_bce=wb, smooth=float(cfg.LOSS.SMOOTH), lr=float(cfg.TRAIN.LR),
                       weight_decay=float(cfg.TRAIN.WEIGHT_DECAY), optimizer=cfg.OPTIMIZER.NAME,
                       max_grad_norm=(float(cfg.TRAIN.GRADIENT_CLIP) if args.grad_clip else None),
-                      global_dice=bool(getattr(args, "global_dice", False)))
-    criterion = get_loss_function(cfg)
+                      global_dice=bool(getattr(args, "global_dice", False)), loss_spec=loss_spec)
     sched = _make_scheduler(cfg, trainer.opt)
     start_epoch, best = 0, float("inf")
     tr_losses, va_losses, tr_hist, va_hist = [], [], [], []
@@ -575,6 +610,10 @@ def build_parser():
     tp.add_argument("--optimizer", choices=["Adam", "AdamW", "SGD"], default=None, help="OPTIMIZER.NAME")
     tp.add_argument("--global-dice", action="store_true",
                     help="data-parallel runs: Dice of the GLOBAL batch (loss sums all-reduced) instead of the mean of per-rank Dice losses")
+    tp.add_argument("--focal-weight", type=str, default=None, metavar="config|FLOAT",
+                    help="LOSS.NAME CombinedLoss: add a focal term (smp's FocalLoss with LOSS.FOCAL_ALPHA / LOSS.FOCAL_GAMMA) to the BCE + Dice "
+                         "sum, weighted by LOSS.FOCAL_WEIGHT ('config') or by the number given; absent (default) = no focal term, as in the "
+                         "reference's trainer")
     tp.add_argument("--lr-scheduler", choices=["ReduceLROnPlateau", "CosineAnnealingLR", "CosineAnnealingWarmRestarts", "none"],
                     default=None, help="OPTIMIZER.LR_SCHEDULER")
     tp.add_argument("--checkpoint-dir", type=str, default=None, help="TRAIN.CHECKPOINT_DIR")

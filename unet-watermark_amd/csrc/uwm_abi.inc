@@ -480,6 +480,41 @@ int uwm_loss_apply(const float* logits, int ld, const void* target, int tdt, lon
                          loss_out, dlogits, ldd, grad_scale, (hipStream_t)stream));
   return 0;
 }
+// the argument checks shared by uwm_loss_ext and its halves (0 = fine); nothing is launched before they pass
+static int loss_ext_check(const char* who, const float* logits, int ld, const void* target, int tdt, long long npix,
+                          const uwm_loss_spec* q, const void* scratch) {
+  if (!logits || !target || !q || !scratch || npix <= 0 || ld < 1) return fail("%s: bad argument", who);
+  if (tdt < 0 || tdt > 3) return fail("%s: unsupported target dtype %d", who, tdt);
+  if (!(q->tversky_gamma > 0.f)) return fail("%s: tversky_gamma must be positive", who);
+  if (!(q->focal_gamma >= 0.f)) return fail("%s: focal_gamma must not be negative", who);
+  if (!(q->focal_alpha <= 1.f)) return fail("%s: focal_alpha must be <= 1 (negative: none)", who);
+  return 0;
+}
+int uwm_loss_ext(const float* logits, int ld, const void* target, int tdt, long long npix, const uwm_loss_spec* spec, void* scratch,
+                 float* loss_out, float* dlogits, int ldd, float grad_scale, uwm_stream stream) {
+  if (loss_ext_check("uwm_loss_ext", logits, ld, target, tdt, npix, spec, scratch)) return 1;
+  if (!loss_out) return fail("uwm_loss_ext: bad argument");
+  if (dlogits && ldd < 1) return fail("uwm_loss_ext: bad dlogits stride");
+  LCHK(launch_loss_ext(logits, ld, target, tdt, (size_t)npix, *spec, (double*)scratch, loss_out, dlogits, ldd, grad_scale,
+                       (hipStream_t)stream));
+  return 0;
+}
+int uwm_loss_ext_sums(const float* logits, int ld, const void* target, int tdt, long long npix, const uwm_loss_spec* spec,
+                      void* scratch, uwm_stream stream) {
+  if (loss_ext_check("uwm_loss_ext_sums", logits, ld, target, tdt, npix, spec, scratch)) return 1;
+  LCHK(launch_loss_ext_sums(logits, ld, target, tdt, (size_t)npix, *spec, (double*)scratch, (hipStream_t)stream));
+  return 0;
+}
+int uwm_loss_ext_apply(const float* logits, int ld, const void* target, int tdt, long long npix, long long npix_total,
+                       const uwm_loss_spec* spec, const void* scratch, float* loss_out, float* dlogits, int ldd, float grad_scale,
+                       uwm_stream stream) {
+  if (loss_ext_check("uwm_loss_ext_apply", logits, ld, target, tdt, npix, spec, scratch)) return 1;
+  if (!loss_out || npix_total < npix) return fail("uwm_loss_ext_apply: bad argument");
+  if (dlogits && ldd < 1) return fail("uwm_loss_ext_apply: bad dlogits stride");
+  LCHK(launch_loss_ext_apply(logits, ld, target, tdt, (size_t)npix, (double)npix_total, *spec, (const double*)scratch, loss_out,
+                             dlogits, ldd, grad_scale, (hipStream_t)stream));
+  return 0;
+}
 int uwm_stats(const float* logits, int ld, const void* target, int tdt, int N, long long hw, float thr, int sig,
               long long* out, uwm_stream stream) {
   if (!logits || !target || !out || N < 1 || hw < 1) return fail("uwm_stats: bad argument");

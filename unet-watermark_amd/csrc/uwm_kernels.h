@@ -11,6 +11,8 @@
 #include <stddef.h>
 #include <atomic>
 
+struct uwm_loss_spec;        // include/uwm.h
+
 namespace uwm {
 
 struct Src {                 // one (possibly lazily transformed) NHWC activation
@@ -570,6 +572,14 @@ hipError_t launch_loss_sums(const float* logits, int ld, const void* target, int
 hipError_t launch_loss_apply(const float* logits, int ld, const void* target, int tdtype, size_t n, double ntotal, float w_dice, float w_bce,
                              float smooth, float eps, const double* scratch4, float* loss_out3, float* dlogits, int ldd,
                              float grad_scale, hipStream_t st);
+// Dice + BCE + Jaccard + Tversky + Focal (loss_ext.hip); scratch: 64 bytes (5 doubles in use, all 8 zeroed), loss_out8: 8 floats
+hipError_t launch_loss_ext(const float* logits, int ld, const void* target, int tdtype, size_t n, const uwm_loss_spec& spec,
+                           double* scratch, float* loss_out8, float* dlogits, int ldd, float grad_scale, hipStream_t st);
+hipError_t launch_loss_ext_sums(const float* logits, int ld, const void* target, int tdtype, size_t n, const uwm_loss_spec& spec,
+                                double* scratch, hipStream_t st);
+hipError_t launch_loss_ext_apply(const float* logits, int ld, const void* target, int tdtype, size_t n, double ntotal,
+                                 const uwm_loss_spec& spec, const double* scratch, float* loss_out8, float* dlogits, int ldd,
+                                 float grad_scale, hipStream_t st);
 hipError_t launch_stats(const float* logits, int ld, const void* target, int tdtype, int N, size_t hw,
                         float thr, int apply_sigmoid, long long* out4, hipStream_t st);
 hipError_t launch_threshold(const float* logits, int ld, size_t npix, float thr, int apply_sigmoid,

@@ -328,8 +328,19 @@ class Trainer:
     def __init__(self, model, w_dice: float = 1.0, w_bce: float = 0.0, smooth: float = 1e-5, eps: float = 1e-7,
                  lr: float = 1e-4, betas=(0.9, 0.999), adam_eps: float = 1e-8, weight_decay: float = 0.0,
                  group=None, overlap_comm: bool = True, force_ddp: bool = False, max_grad_norm=None,
-                 optimizer: str = "Adam", momentum: float = 0.9, global_dice: bool = False, use_graph: bool = False):
+                 optimizer: str = "Adam", momentum: float = 0.9, global_dice: bool = False, use_graph: bool = False,
+                 loss_spec=None):
         self.model = model
+        # loss_spec: a uwm_loss_spec (or a mapping of its fields, losses.make_loss_spec) naming any mix of Dice, BCE, Jaccard, Tversky
+        # and Focal; it then replaces w_dice / w_bce / smooth / eps.  With a Jaccard, Tversky or Focal weight the step's loss is
+        # uwm_loss_ext (eight terms, self.loss_terms); a Dice / BCE-only spec, like no spec, stays on uwm_loss.
+        self.loss_spec = None
+        if loss_spec is not None:
+            from .losses import make_loss_spec, spec_needs_ext
+            spec = make_loss_spec(loss_spec)
+            w_dice, w_bce, smooth, eps = spec.w_dice, spec.w_bce, spec.dice_smooth, spec.dice_eps
+            if spec_needs_ext(spec):
+                self.loss_spec = spec
         # use_graph: the whole step (forward, loss, staged backward with its weight-gradient side stream, Adam) is captured
         # ONCE per batch shape into a hipGraph and replayed ("hipGraph the step"): the ~150-1200 launches of
         # a step cost the host one graph launch.  Single-process Adam only; a data-parallel trainer keeps the eager path
@@ -359,6 +370,7 @@ class Trainer:
         self._dl = None
         self._scratch = None
         self._loss = None
+        self._terms = None
         self._shape_bufs = {}
         if self.world > 1:
             broadcast_model(model, 0, group)
@@ -371,9 +383,16 @@ class Trainer:
         ent = self._shape_bufs.get(key)
         if ent is None:
             ent = (torch.empty((n, h, w, cp), dtype=torch.float32, device=dev), torch.empty(8, dtype=torch.float64, device=dev),
-                   torch.empty(3, dtype=torch.float32, device=dev))
+                   torch.empty(8 if self.loss_spec is not None else 3, dtype=torch.float32, device=dev))
             self._shape_bufs[key] = ent
-        self._dl, self._scratch, self._loss = ent
+        self._dl, self._scratch, self._terms = ent
+        self._loss = self._terms[:3]
+
+    @property
+    def loss_terms(self):
+        """The last step's loss terms on the device (no host sync): {total, dice, bce, jaccard, tversky, focal, 0, 0} under a
+        loss_spec with a Jaccard, Tversky or Focal weight, else {total, dice, bce}; None before the first step."""
+        return self._terms
 
     def step(self, images: torch.Tensor, masks: torch.Tensor) -> torch.Tensor:
         """images (N,C,H,W) fp32, masks (N,H,W)|(N,1,H,W) int64|uint8|float32 on the HIP device.
@@ -420,7 +439,19 @@ class Trainer:
         if t.numel() != n * h * w:
             raise ValueError(f"masks have {t.numel()} elements, expected {n * h * w}")
         st = C.c_void_p(L.stream_ptr(dev))
-        if self.global_dice and self.ddp:
+        if self.loss_spec is not None:
+            lp, tp, tdt = C.c_void_p(logits.data_ptr()), C.c_void_p(t.data_ptr()), L.target_dtype_code(t)
+            spec, scr = C.byref(self.loss_spec), C.c_void_p(self._scratch.data_ptr())
+            out, dl = C.c_void_p(self._terms.data_ptr()), C.c_void_p(self._dl.data_ptr())
+            if self.global_dice and self.ddp:
+                L.check(L.lib().uwm_loss_ext_sums(lp, m._cp, tp, tdt, n * h * w, spec, scr, st))
+                dist.all_reduce(self._scratch[:5], group=self.group)      # SUM of {sum p*t, sum p, sum t, sum bce, sum focal}
+                # as below: the ranks' gradients of the global loss add up and the exchange averages, hence grad_scale = world
+                L.check(L.lib().uwm_loss_ext_apply(lp, m._cp, tp, tdt, n * h * w, n * h * w * self.world, spec, scr, out, dl, m._cp,
+                                                   float(self.world), st))
+            else:
+                L.check(L.lib().uwm_loss_ext(lp, m._cp, tp, tdt, n * h * w, spec, scr, out, dl, m._cp, 1.0, st))
+        elif self.global_dice and self.ddp:
             lp, tp, tdt = C.c_void_p(logits.data_ptr()), C.c_void_p(t.data_ptr()), L.target_dtype_code(t)
             L.check(L.lib().uwm_loss_sums(lp, m._cp, tp, tdt, n * h * w, C.c_void_p(self._scratch.data_ptr()), st))
             dist.all_reduce(self._scratch[:4], group=self.group)          # SUM of {sum p*t, sum p, sum t, sum bce}
