@@ -748,6 +748,44 @@ int    uwm_optimize_masks_ragged(const uint8_t* in, uint8_t* out /* may alias in
                                  const uwm_image_desc* descs /* device */, int N, int mask_type, long long max_pixels,
                                  long long rows, long long* stats /* device [N][8], may be NULL */, void* workspace,
                                  size_t workspace_bytes, uwm_stream stream);
+/* Mask enhancement on the device: the reference's enhance_mask (src/scripts/enhance_masks.py:16-67), which turns a tight
+ * segmentation mask into the rounded, enlarged one people train on.  A ragged batch in ONE call, as above: image i is descs[i].h x
+ * descs[i].w 8-bit grey pixels at in + descs[i].offset (any alignment), its result, in {0, 255}, goes to out + descs[i].offset; out
+ * may be in.  With e = expand_pixels, k = blur_kernel (an even k is raised by one, 0 = no blur), s = smooth_iterations:
+ *   1 m = grey close E(7,7) (dilate = max, then erode = min)     2 m = grey dilate E(2e+1, 2e+1)
+ *   3 f = float32(m), blurred by the k x k Gaussian when k > 0     4 s times: f = open E(5,5), then close E(5,5), on floats
+ *   5 u = f > 127 ? 255 : 0                                        6 u = bilateralFilter(u, 9, 75, 75), then u > 127 ? 255 : 0
+ * computed as the chain 1, 2, 3, 5, then s times a BINARY open and close E(5,5): thresholding commutes with min and max, and step
+ * 6 is the identity on a {0, 255} image (tests/test_enhance.py holds both against the literal chain).
+ *   elements    the ELLIPSE rule above at odd sides 1..63: row i of E(2r+1, 2r+1) spans columns [r - dx, r + dx + 1),
+ *               dx = round_half_even(r * sqrt((r*r - dy*dy) / (r*r))), dy = i - r; 1 x 1 is the identity; anchor at the centre;
+ *               pixels outside the image are ignored, by max and by min
+ *   taps        cv2.getGaussianKernel(k, 0, CV_32F): k = 1, 3, 5, 7 the fixed tables {1}, {.25, .5, .25}, {.0625, .25, .375, .25,
+ *               .0625}, {.03125, .109375, .21875, .28125, .21875, .109375, .03125}; k >= 9 in double, sigma = ((k-1)*0.5 - 1)*0.3
+ *               + 0.8, t_i = exp(-0.5 * x*x / sigma^2), x = i - (k-1)/2, divided by their double sum, rounded to float32
+ *   blur        this library's own arithmetic (OpenCV's float filter differs by build): row pass (result stored as float32),
+ *               then column pass, each acc = t[c]*x[0], then for i = 1 .. r in order acc += t[c+i] * (x[-i] + x[+i]), every
+ *               operation rounded to float32, no fused multiply-add; border BORDER_REFLECT_101 by borderInterpolate's loop
+ *               (length 1: index 0; else p = -p below 0 and p = 2*(len-1) - p from len on, repeated until inside)
+ * OpenCV is not available to this project: every OpenCV rule here is restated, not run against cv2; equality with cv2 is claimed
+ * only away from blurred values within a few ulp of 127.  Results are exact and the same on every run.
+ * stats (device, may be NULL): long long [N][4] = {foreground (> 127) pixels of the input, of the output, h_i * w_i, status: 0
+ * done, 1 misfit}.  The descriptors are read on the device; the host arguments are capacities, so one captured call serves every
+ * batch of N images that fits them: max_pixels (1 .. 2^31 - 2) bounds h_i * w_i and sizes the grids.  The launch count does not
+ * depend on N (N <= 65535).  Misfit: a side outside 1 .. 2^30, h_i * w_i > max_pixels, or a region that leaves [0, mask_bytes).  A
+ * misfit gets status 1 and entries 0..2 zero, its bytes are not written and it costs the others nothing.  Whatever the descriptors
+ * hold, no read leaves in / descs and no write leaves out + [0, mask_bytes), stats or the workspace; overlapping regions are the
+ * caller's error.  Ranges: expand_pixels 0..31, blur_kernel 0..63, smooth_iterations 0..8.  workspace:
+ * uwm_enhance_masks_workspace_bytes(N, mask_bytes) bytes (0 and a message on a bad argument), descs / stats / workspace 8-byte
+ * aligned.  Every argument is checked before any launch; no host synchronisation, allocation or copy. */
+size_t uwm_enhance_masks_workspace_bytes(int N, size_t mask_bytes);
+int    uwm_enhance_masks_ragged(const uint8_t* in, uint8_t* out /* may alias in */, size_t mask_bytes,
+                                const uwm_image_desc* descs /* device */, int N, int expand_pixels, int blur_kernel,
+                                int smooth_iterations, long long max_pixels, long long* stats /* device [N][4], may be NULL */,
+                                void* workspace, size_t workspace_bytes, uwm_stream stream);
+/* host only, no device: the taps the blur uses for blur_kernel 0..63 (0 and 1: the one tap {1}) -> out[0 .. k), returns the
+ * effective k (even + 1), or 0 and a message on a bad argument; out holds up to 63 floats */
+int    uwm_enhance_gauss_taps(int blur_kernel, float* out);
 /* building blocks, for tests and other callers; out may alias in */
 int    uwm_op_morph(const uint8_t* in, uint8_t* out, int N, int H, int W, int dilate, int shape, int kw, int kh,
                     int iterations, void* workspace, size_t workspace_bytes, uwm_stream stream);

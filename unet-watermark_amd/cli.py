@@ -574,8 +574,56 @@ def select_command(args):
     return sel.run_evaluation()
 
 
+def enhance_masks_command(args):
+    """The reference's src/scripts/enhance_masks.py (enhance_mask over a folder) on the device: every .png / .jpg / .jpeg of --mask-dir
+    through postprocess.enhance_masks_ragged, --batch-size files per call, written under the same name to --output-dir, or over the
+    input with --in-place.  One line per file with the foreground share before and after (from the call's stats)."""
+    import numpy as np
+    from PIL import Image
+    from .data import DESC_DTYPE, mask_descs_for
+    from .postprocess import enhance_masks_ragged
+    if not os.path.isdir(args.mask_dir):
+        raise SystemExit(f"enhance-masks: mask directory not found: {args.mask_dir}")
+    out_dir = args.mask_dir if args.in_place else args.output_dir
+    if not args.in_place and os.path.realpath(out_dir) == os.path.realpath(args.mask_dir):
+        raise SystemExit("enhance-masks: --output-dir is the mask directory: overwriting the masks needs --in-place")
+    if not torch.cuda.is_available():
+        raise SystemExit("enhance-masks needs a HIP device (this path has no CPU fallback)")
+    device = torch.device("cuda", torch.cuda.current_device())
+    files = sorted(f for f in os.listdir(args.mask_dir) if f.endswith((".png", ".jpg", ".jpeg")))        # the script's filter
+    os.makedirs(out_dir, exist_ok=True)
+    bs = max(1, int(args.batch_size or 16))
+    written = unreadable = 0
+    for b in range(0, len(files), bs):
+        names, masks = [], []
+        for f in files[b:b + bs]:
+            try:
+                with Image.open(os.path.join(args.mask_dir, f)) as im:
+                    masks.append(np.asarray(im if im.mode == "L" else im.convert("L"), dtype=np.uint8))
+                names.append(f)
+            except Exception as e:                                 # counted and left alone
+                unreadable += 1
+                print(f"{f}: unreadable ({e.__class__.__name__}), left as it is")
+        if not names:
+            continue
+        descs = np.zeros(len(masks), DESC_DTYPE)
+        descs["h"], descs["w"] = [m.shape[0] for m in masks], [m.shape[1] for m in masks]
+        descs = mask_descs_for(descs)                              # the masks back to back
+        flat = torch.from_numpy(np.concatenate([m.reshape(-1) for m in masks])).to(device)
+        out, stats = enhance_masks_ragged(flat, descs, args.expand_pixels, args.blur_kernel, args.smooth_iterations, return_stats=True)
+        out = out.cpu().numpy()
+        for f, d, row in zip(names, descs, stats.cpu().tolist()):
+            o, h, w = int(d["offset"]), int(d["h"]), int(d["w"])
+            Image.fromarray(out[o:o + h * w].reshape(h, w)).save(os.path.join(out_dir, f))
+            print(f"{f}: foreground {row[0] / row[2]:.4f} -> {row[1] / row[2]:.4f}")
+            written += 1
+    print(f"wrote {written} enhanced masks to {out_dir} (expand {args.expand_pixels}, blur {args.blur_kernel}, smooth "
+          f"{args.smooth_iterations}); {unreadable} unreadable")
+    return dict(written=written, unreadable=unreadable, output=out_dir)
+
+
 def build_parser():
-    ap = argparse.ArgumentParser(description="MI355X-native U-Net watermark segmentation (train | masks | filter | select | predict)")
+    ap = argparse.ArgumentParser(description="MI355X-native U-Net watermark segmentation (train | masks | enhance-masks | filter | select | predict)")
     sub = ap.add_subparsers(dest="command")
     tp = sub.add_parser("train")
     tp.add_argument("--config", type=str, default=None)
@@ -643,6 +691,20 @@ def build_parser():
     mp.add_argument("--config", type=str, default=None)
     mp.add_argument("--threshold", type=int, default=None, help="DATA.GENERATE_MASK_THRESHOLD (0..255)")
     mp.add_argument("--batch-size", type=int, default=None, help="pairs per launch (default 16)")
+    ep = sub.add_parser("enhance-masks", help="round and enlarge the masks of a folder (the reference's scripts/enhance_masks.py) on the device",
+                        description="enhance_mask of the reference's script for every .png / .jpg / .jpeg of --mask-dir: grey close, dilate "
+                                    "by --expand-pixels, Gaussian blur, threshold, smoothing; each result is written under the same name.  "
+                                    "The defaults are the function's (10 / 15 / 2); the script's main() uses 15 / 21 and overwrites "
+                                    "data/train/masks, which here needs --in-place.  Single-channel 8-bit files are read exactly; a colour "
+                                    "file is converted by Pillow's 'L' rule, not by OpenCV's.  An unreadable file is counted and left alone.")
+    ep.add_argument("--mask-dir", type=str, required=True, help="the folder of masks")
+    dst = ep.add_mutually_exclusive_group(required=True)
+    dst.add_argument("--output-dir", type=str, default=None, help="where the enhanced masks go")
+    dst.add_argument("--in-place", action="store_true", help="overwrite the masks of --mask-dir (never done without this flag)")
+    ep.add_argument("--expand-pixels", type=int, default=10, help="radius of the dilation, 0..31")
+    ep.add_argument("--blur-kernel", type=int, default=15, help="side of the Gaussian, 0..63 (0: no blur; an even value is raised by one)")
+    ep.add_argument("--smooth-iterations", type=int, default=2, help="open / close E(5,5) rounds, 0..8")
+    ep.add_argument("--batch-size", type=int, default=16, help="masks per call")
     fp = sub.add_parser("filter", help="sort a folder by predicted watermark area (the reference's scripts/watermark_filter.py)",
                         description="Predict every image's watermark mask on the device and move away (or delete) the images whose mask "
                                     "covers less than --threshold of the image.  Two deliberate departures from the reference's script: "
@@ -708,4 +770,6 @@ def main(argv=None):
         return synth_command(args)
     if args.command == "select":
         return select_command(args)
+    if args.command == "enhance-masks":
+        return enhance_masks_command(args)
     ap.print_help()

@@ -640,6 +640,40 @@ int uwm_optimize_masks_ragged(const uint8_t* in, uint8_t* out, size_t mask_bytes
   LCHK(launch_optimize_masks_ragged(in, out, mask_bytes, (const ImageDesc*)descs, N, mask_type, max_pixels, rows, stats, ws, (hipStream_t)stream));
   return 0;
 }
+// ---- mask enhancement (mask_enhance.hip): every argument is checked here, before any launch
+static int enhance_caps_check(const char* fn, int N, size_t mask_bytes) {
+  if (N < 1 || mask_bytes < 1) return fail("%s: N and mask_bytes must be >= 1 (got %d, %zu)", fn, N, mask_bytes);
+  if (N > 65535) return fail("%s: N too large: at most 65535 masks per call (got %d)", fn, N);
+  if (mask_bytes > ((size_t)1 << 40)) return fail("%s: mask_bytes too large: at most 2^40 (got %zu)", fn, mask_bytes);
+  return 0;
+}
+size_t uwm_enhance_masks_workspace_bytes(int N, size_t mask_bytes) {
+  if (enhance_caps_check("uwm_enhance_masks_workspace_bytes", N, mask_bytes)) return 0;
+  return enhance_workspace_bytes(N, mask_bytes);
+}
+int uwm_enhance_gauss_taps(int blur_kernel, float* out) {
+  if (!out) { fail("uwm_enhance_gauss_taps: null argument"); return 0; }
+  if (blur_kernel < 0 || blur_kernel > 63) { fail("uwm_enhance_gauss_taps: blur_kernel %d outside 0..63", blur_kernel); return 0; }
+  return enhance_gauss_taps(blur_kernel, out);
+}
+int uwm_enhance_masks_ragged(const uint8_t* in, uint8_t* out, size_t mask_bytes, const uwm_image_desc* descs, int N, int expand_pixels,
+                             int blur_kernel, int smooth_iterations, long long max_pixels, long long* stats, void* ws, size_t ws_bytes,
+                             uwm_stream stream) {
+  const char* fn = "uwm_enhance_masks_ragged";
+  if (!in || !out || !descs || !ws) return fail("%s: null argument", fn);
+  if (enhance_caps_check(fn, N, mask_bytes)) return 1;
+  if (expand_pixels < 0 || expand_pixels > 31) return fail("%s: expand_pixels %d outside 0..31", fn, expand_pixels);
+  if (blur_kernel < 0 || blur_kernel > 63) return fail("%s: blur_kernel %d outside 0..63", fn, blur_kernel);
+  if (smooth_iterations < 0 || smooth_iterations > 8) return fail("%s: smooth_iterations %d outside 0..8", fn, smooth_iterations);
+  if (max_pixels < 1) return fail("%s: max_pixels must be >= 1 (got %lld)", fn, max_pixels);
+  if (max_pixels >= 2147483647ll) return fail("%s: max_pixels too large: it must be below 2^31 - 1 (got %lld)", fn, max_pixels);
+  if (((uintptr_t)descs | (uintptr_t)stats | (uintptr_t)ws) & 7) return fail("%s: descriptors, stats and the workspace must be 8-byte aligned", fn);
+  const size_t need = enhance_workspace_bytes(N, mask_bytes);
+  if (ws_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", fn, ws_bytes, need);
+  LCHK(launch_enhance_masks_ragged(in, out, mask_bytes, (const ImageDesc*)descs, N, expand_pixels, blur_kernel, smooth_iterations, max_pixels,
+                                   stats, ws, (hipStream_t)stream));
+  return 0;
+}
 int uwm_op_morph(const uint8_t* in, uint8_t* out, int N, int H, int W, int dilate, int shape, int kw, int kh, int iterations,
                  void* ws, size_t ws_bytes, uwm_stream stream) {
   if (!in || !out) return fail("uwm_op_morph: null argument");

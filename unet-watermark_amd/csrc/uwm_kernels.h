@@ -600,4 +600,12 @@ size_t mask_ragged_workspace_bytes(int N, size_t mask_bytes, long long rows);
 hipError_t launch_optimize_masks_ragged(const uint8_t* in, uint8_t* out, size_t mask_bytes, const ImageDesc* descs, int N, int mask_type,
                                         long long max_pixels, long long rows, long long* stats, void* ws, hipStream_t st);
 
+// mask enhancement (mask_enhance.hip): the reference's enhance_mask on a ragged batch, grey morphology + float blur + binary
+// smoothing (the rule: include/uwm.h).  ws: enhance_workspace_bytes(N, mask_bytes) bytes; stats (may be null): [N][4]
+int enhance_gauss_taps(int blur_kernel, float* out);           // host: the taps (0..63; even + 1) -> their number, 0 on a bad argument
+size_t enhance_workspace_bytes(int N, size_t mask_bytes);
+hipError_t launch_enhance_masks_ragged(const uint8_t* in, uint8_t* out, size_t mask_bytes, const ImageDesc* descs, int N, int expand_pixels,
+                                       int blur_kernel, int smooth_iterations, long long max_pixels, long long* stats, void* ws,
+                                       hipStream_t st);
+
 }  // namespace uwm

@@ -4,6 +4,8 @@
 does this with OpenCV on the host; here it is HIP (csrc/mask_post.hip: uwm_optimize_mask and its building blocks), exact integer
 work whose results equal the specification in DESIGN.md §8b bit for bit.  No CPU fallback.  optimize_masks_ragged is the same on
 a ragged batch of masks of any sizes in ONE call (uwm_optimize_masks_ragged), with eight statistics per image.
+enhance_masks_ragged / enhance_mask are the reference's scripts/enhance_masks.py::enhance_mask (grey close and dilate, Gaussian blur,
+threshold, smoothing: csrc/mask_enhance.hip) on a ragged batch, again in one call.
 
 The reference's automatic type detection (_detect_watermark_type: Canny / Sobel on the image) and _enhance_text_features stay out."""
 from __future__ import annotations
@@ -163,6 +165,99 @@ def optimize_masks_ragged(buf: torch.Tensor, descs, mask_type: str = "watermark"
                                                   C.c_void_p(stats.data_ptr() if return_stats else 0), C.c_void_p(ws.data_ptr()), ws.numel(),
                                                   C.c_void_p(L.stream_ptr(buf.device))))
     return (o, stats) if return_stats else o
+
+
+ENHANCE_STATS_FIELDS = ("foreground_in", "foreground_out", "pixels", "status")
+_ews = {}                                                 # device -> workspace tensor of the enhancement (grown on demand)
+
+
+def enhance_workspace(device, n: int, mask_bytes: int) -> torch.Tensor:
+    """uwm_enhance_masks_ragged's scratch for the capacities (n, mask_bytes): one buffer per device, kept and grown like `workspace`;
+    a captured graph holds the buffer it was captured with."""
+    need = L.lib().uwm_enhance_masks_workspace_bytes(int(n), int(mask_bytes))
+    if need == 0:
+        raise RuntimeError(L.lib().uwm_last_error().decode(errors="replace"))
+    key = str(device)
+    ws = _ews.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _ews[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws
+
+
+def _enhance_params(expand_pixels, blur_kernel, smooth_iterations):
+    e, k, s = int(expand_pixels), int(blur_kernel), int(smooth_iterations)
+    if not 0 <= e <= 31:
+        raise ValueError(f"expand_pixels must be in 0..31, got {expand_pixels!r}")
+    if not 0 <= k <= 63:
+        raise ValueError(f"blur_kernel must be in 0..63, got {blur_kernel!r}")
+    if not 0 <= s <= 8:
+        raise ValueError(f"smooth_iterations must be in 0..8, got {smooth_iterations!r}")
+    return e, k, s
+
+
+def enhance_masks_ragged(buf: torch.Tensor, descs, expand_pixels: int = 10, blur_kernel: int = 15, smooth_iterations: int = 2,
+                         return_stats: bool = False, out=None, *, n: Optional[int] = None, max_pixels: Optional[int] = None, stats=None):
+    """The reference's enhance_mask (scripts/enhance_masks.py) on a ragged batch of 8-bit grey masks through ONE library call
+    (uwm_enhance_masks_ragged): close E(7,7), dilate by expand_pixels, Gaussian blur of side blur_kernel (0: none; even: + 1),
+    threshold at 127, smooth_iterations rounds of open / close E(5,5) -> masks in {0,255}.  buf, descs, out, n, max_pixels as
+    optimize_masks_ragged takes them (device descriptors need n and max_pixels; the call can then be captured).  return_stats: also
+    the int64 (n, 4) device tensor ENHANCE_STATS_FIELDS (`stats`: a tensor to write them into).  The rules are restated from
+    OpenCV's documented behaviour, not run against it (include/uwm.h)."""
+    e, k, s = _enhance_params(expand_pixels, blur_kernel, smooth_iterations)
+    if not isinstance(buf, torch.Tensor) or buf.device.type != "cuda":
+        raise RuntimeError("uwm enhance_masks_ragged runs only on a HIP device (no CPU fallback)")
+    if buf.dtype != torch.uint8 or buf.dim() != 1 or buf.numel() == 0 or not buf.is_contiguous():
+        raise RuntimeError(f"expected a non-empty contiguous 1-d uint8 buffer, got {buf.dtype} {tuple(buf.shape)}")
+    if isinstance(descs, torch.Tensor):
+        if n is None or max_pixels is None:
+            raise ValueError("enhance_masks_ragged: device descriptors need n and max_pixels")
+        if descs.device != buf.device or descs.dtype != torch.uint8 or descs.numel() < 16 * int(n):
+            raise RuntimeError("enhance_masks_ragged: descs must be a uint8 tensor of 16 n bytes on the buffer's device")
+        d = descs
+    else:
+        from .data import descs_tensor
+        n = len(descs) if n is None else int(n)
+        if n < 1:
+            raise ValueError("enhance_masks_ragged: empty batch")
+        if max_pixels is None:
+            max_pixels = max(1, int((descs["h"].astype("int64") * descs["w"]).max()))
+        d = descs_tensor(descs).to(buf.device)
+    if out is None:
+        o = torch.zeros_like(buf)
+    else:
+        if out.dtype != torch.uint8 or out.device != buf.device or out.numel() != buf.numel() or not out.is_contiguous():
+            raise RuntimeError("enhance_masks_ragged: out must be a contiguous uint8 tensor of the buffer's size on the same device")
+        o = out
+    if return_stats and stats is None:
+        stats = torch.empty((int(n), 4), dtype=torch.int64, device=buf.device)
+    with L.on_device(buf):
+        ws = enhance_workspace(buf.device, n, buf.numel())
+        L.check(L.lib().uwm_enhance_masks_ragged(C.c_void_p(buf.data_ptr()), C.c_void_p(o.data_ptr()), buf.numel(), C.c_void_p(d.data_ptr()),
+                                                 int(n), e, k, s, int(max_pixels), C.c_void_p(stats.data_ptr() if return_stats else 0),
+                                                 C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(L.stream_ptr(buf.device))))
+    return (o, stats) if return_stats else o
+
+
+def enhance_mask(mask_u8: torch.Tensor, expand_pixels: int = 10, blur_kernel: int = 15, smooth_iterations: int = 2,
+                 return_stats: bool = False, out=None):
+    """enhance_masks_ragged for uint8 (H,W) | (N,H,W) masks on the HIP device -> the enhanced masks, uint8 {0,255} of the same shape
+    (`out`: a contiguous uint8 tensor of that shape to write into, which may be the input); return_stats: also the int64 (N,4) | (4,)
+    device tensor ENHANCE_STATS_FIELDS."""
+    import numpy as np
+    from .data import DESC_DTYPE
+    _enhance_params(expand_pixels, blur_kernel, smooth_iterations)
+    m, squeeze = _masks(mask_u8, "enhance_mask")
+    n, h, w = m.shape
+    if out is not None and (out.dtype != torch.uint8 or out.device != m.device or out.numel() != m.numel() or not out.is_contiguous()):
+        raise RuntimeError("enhance_mask: out must be a contiguous uint8 tensor of the input's shape on the same device")
+    descs = np.zeros(n, DESC_DTYPE)
+    descs["offset"], descs["h"], descs["w"] = np.arange(n, dtype=np.int64) * (h * w), h, w
+    o = torch.empty_like(m) if out is None else out
+    res = enhance_masks_ragged(m.view(-1), descs, expand_pixels, blur_kernel, smooth_iterations, return_stats, o.view(-1))
+    o = o.view(mask_u8.shape) if out is None else out
+    if return_stats:
+        return o, (res[1][0] if squeeze else res[1])
+    return o
 
 
 def morphology(mask_u8: torch.Tensor, op: str, shape, ksize, iterations: int = 1) -> torch.Tensor:
