@@ -786,6 +786,71 @@ int    uwm_enhance_masks_ragged(const uint8_t* in, uint8_t* out /* may alias in 
 /* host only, no device: the taps the blur uses for blur_kernel 0..63 (0 and 1: the one tap {1}) -> out[0 .. k), returns the
  * effective k (even + 1), or 0 and a message on a bad argument; out holds up to 63 floats */
 int    uwm_enhance_gauss_taps(int blur_kernel, float* out);
+/* Watermark cut-outs from watermarked / clean pairs on the device: the reference's extract_watermarks.py (extract_watermark_from_pair,
+ * _extract_single_watermark / _extract_combined_watermark, _create_transparent_watermark), whose transparent RGBA cut-outs are the logos
+ * gen_data.py pastes.  Two calls with a small host plan between them (extract.plan_cutouts: centres, clustering, margins).
+ * STAGE 1, uwm_extract_regions_ragged.  wm, clean: ragged batches as above (uint8 RGB interleaved, C = 3); pair i at its OWN size:
+ *     g = gray(|wm - clean|), the rule of uwm_pair_mask_u8; m = g > threshold                     absdiff, cvtColor, threshold
+ *     m = open(close(m, RECT(3,3)), RECT(3,3)), one iteration each, the morphology of               morphologyEx(np.ones((3,3)))
+ *         uwm_optimize_mask: pixels outside the image are ignored
+ *     F = m plus every background pixel that is not 4-connected through background to the           findContours(RETR_EXTERNAL) +
+ *         outside of the image: holes are filled, islands in holes join the enclosing region       fillPoly of each outer contour
+ *     regions = the 8-connected components of F; id = y*w + x of the raster-first pixel
+ *     per region, over every 2 x 2 window of neighbouring pixels (top-left corner (x, y)):          contourArea / moments of the outer
+ *         4 corners in F: a00 += 2, a10 += 6x + 3, a01 += 6y + 3                                   contour = the polygon through the
+ *         3 corners in F: a00 += 1, a10 += the three corners' x, a01 += the three corners' y       pixel centres: area = a00/2,
+ *         fewer: nothing                                                                           m10 = a10/6, m01 = a01/6
+ *     kept = the regions with a00 > 2*min_area                                                     contourArea(c) > min_area
+ *   -> stats[i][4] = {regions found, regions kept, status, h_i*w_i}; table[i][254][9], one row per kept region in ascending id order =
+ *   {id, a00, a10, a01, x0, y0, x1, y1 (bounding box, inclusive), pixels of F}, the other rows zero; plane + plane_descs[i].offset <-
+ *   one byte per pixel: the row index of the kept region at that pixel, 255 for none.  status: 0 done; 1 misfit (a side outside
+ *   3 .. 2^30, sizes of wm / clean / plane that differ, h*w > max_pixels, a region that leaves its buffer, or a sum of h*w, over the
+ *   pairs up to this one that pass those tests, above total_pixels): found = kept = h*w = 0, its plane bytes are not written; 2 more than 254
+ *   kept regions: found and kept are reported, the table is empty and the plane all 255.  Every OpenCV rule here is restated, NOT
+ *   run against cv2; tests/test_extract.py holds the window sums and the fill to a literal border follower with the shoelace
+ *   formulas and to scipy's binary_fill_holes.  A pair whose two files differ in size is first brought to (min w, min h) by
+ *   uwm_resize_u8(UWM_INTER_LINEAR): the caller's step.
+ * STAGE 2, uwm_extract_cutouts_ragged.  Job j: the crop (x, y, w, h) of image `image`, written as w*h RGBA pixels at out + out_offset:
+ *   RGB from wm, A = 255 where member[plane byte] != 0 (the byte 255 is never a member), else 0; then, over RGB with alpha carried:
+ *     ImageEnhance.Contrast(1.3)     blend(d, p, 1.3f), d = (int)(sum of L over ALL crop pixels / (w*h) + 0.5) in float64,
+ *                                    L = (19595*R + 38470*G + 7471*B + 0x8000) >> 16
+ *     ImageEnhance.Sharpness(1.4)    blend(d, p, 1.4f), d = ImageFilter.SMOOTH of the contrast stage: k1 = 1.f/13.f, k5 = 5.f/13.f,
+ *                                    ss = 0.5f; for the rows y+1, y, y-1: ss += (l*k1 + c*kc) + r*k1 (kc = k5 on row y, else k1), every
+ *                                    operation rounded to float32, no fused multiply-add; d = 0 for ss <= 0, 255 for ss >= 255, else
+ *                                    (int)ss; the one-pixel frame of the crop is not filtered (d = p)
+ *     ImageEnhance.Brightness(1.1)   blend(0, p, 1.1f)
+ *     blend(d, p, f) in float32: t = d + f*(p - d); 0 for t <= 0, 255 for t >= 255, else (int)t      (Image.blend, as in uwm_synth_u8)
+ *   held to Pillow bit for bit by tests/test_extract.py.  status[j]: 0 done; 1 misfit, nothing written (an image index outside 0..N-1, an
+ *   image or plane descriptor that fails stage 1's tests, a crop side below 3 or a crop outside the image, w*h > max_crop_pixels,
+ *   out_offset negative, not a multiple of 4, or a region that leaves [0, out_bytes)).
+ * Both calls: descriptors and jobs are read on the device, the host arguments are capacities (max_pixels 1 .. 2^30 bounds h_i*w_i,
+ * total_pixels their sum, max_crop_pixels a crop; all size the grids and the workspace), so one captured call serves every batch that
+ * fits them; the launch count (18 and 3) does not depend on N or J (both <= 65535).  A misfit costs the others nothing.  Whatever the
+ * descriptors hold, no read leaves the inputs and no write leaves plane + [0, plane_bytes), out + [0, out_bytes), stats, table, status or
+ * the workspace; overlapping output regions are the caller's error.  workspace: uwm_extract_workspace_bytes(N, total_pixels, J) bytes
+ * serves both calls (N = 0 or J = 0: the other call alone; 0 and a message on a bad argument).  wm / clean / out 4-byte, descriptors /
+ * jobs / stats / table / workspace 8-byte aligned.  Every argument is checked before any launch; no host synchronisation, allocation
+ * or copy.  Integer sums and extrema have one result whatever their order, so runs are bit-identical. */
+enum { UWM_EXTRACT_MAX_REGIONS = 254, UWM_EXTRACT_ROW_INTS = 9 };
+typedef struct uwm_extract_job {
+  int image;                   /* index into the descriptors */
+  int x, y, w, h;              /* the crop, inside the image, sides >= 3 */
+  int reserved;
+  long long out_offset;        /* bytes, a multiple of 4 */
+  uint8_t member[256];         /* member[k] != 0: kept region k of the image belongs to this cut-out */
+} uwm_extract_job;
+size_t uwm_extract_workspace_bytes(int N, long long total_pixels, int J);
+int    uwm_extract_regions_ragged(const uint8_t* wm, size_t wm_bytes, const uwm_image_desc* wm_descs,
+                                  const uint8_t* clean, size_t clean_bytes, const uwm_image_desc* clean_descs,
+                                  int N, int C /* 3 */, int threshold /* 0..255 */, int min_area, long long max_pixels,
+                                  long long total_pixels, uint8_t* plane, size_t plane_bytes, const uwm_image_desc* plane_descs,
+                                  long long* stats /* device [N][4] */, long long* table /* device [N][254][9] */,
+                                  void* workspace, size_t workspace_bytes, uwm_stream stream);
+int    uwm_extract_cutouts_ragged(const uint8_t* wm, size_t wm_bytes, const uwm_image_desc* wm_descs,
+                                  const uint8_t* plane, size_t plane_bytes, const uwm_image_desc* plane_descs, int N,
+                                  const uwm_extract_job* jobs /* device [J] */, int J, long long max_crop_pixels,
+                                  uint8_t* out, size_t out_bytes, int* status /* device [J] */,
+                                  void* workspace, size_t workspace_bytes, uwm_stream stream);
 /* building blocks, for tests and other callers; out may alias in */
 int    uwm_op_morph(const uint8_t* in, uint8_t* out, int N, int H, int W, int dilate, int shape, int kw, int kh,
                     int iterations, void* workspace, size_t workspace_bytes, uwm_stream stream);

@@ -24,4 +24,5 @@ from .data import device_synth, sample_synth_jobs, sample_synth_choice, RawSynth
 from .filter import WatermarkFilter, filter_folder, batch_ratios, list_images  # noqa: F401,E402
 from .postprocess import optimize_masks_ragged  # noqa: F401,E402
 from .select import ModelSelector, run_selection  # noqa: F401,E402
+from .extract import WatermarkExtractor, extract_regions, plan_cutouts, extract_cutouts  # noqa: F401,E402
 from .train import FusedAdam, FusedAdamW  # noqa: F401,E402

@@ -18,7 +18,7 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 _PKG_DIR = Path(__file__).resolve().parent
 _CSRC = _PKG_DIR / "csrc"
 LIB_PATH = _PKG_DIR / "libuwm.so"
-SOURCES = ["uwm_route.hip", "conv_igemm.hip", "conv_patch.hip", "conv_patch16.hip", "conv_wino.hip", "conv_wino8.hip", "conv_wino_x3.hip", "conv_f16x3.hip", "conv_f16x3v2.hip", "conv_stem_f16x3.hip", "conv_up2.hip", "conv_up2_f16.hip", "conv_c16_f16.hip", "conv_gemm.hip", "conv_head.hip", "mbconv.hip", "wgrad_igemm.hip", "wgrad_patch.hip", "wgrad_wino.hip", "wgrad_f16x3.hip", "wgrad_c16.hip", "wgrad_gemm.hip", "wgrad_stem.hip", "elementwise.hip", "loss.hip", "loss_ext.hip", "mask_post.hip", "mask_enhance.hip", "resize_u8.hip", "pair_mask_u8.hip", "synth_u8.hip", "filter_u8.hip", "augment_u8.hip", "augment_ext_u8.hip", "jpeg_u8.hip", "uwm_model.hip"]
+SOURCES = ["uwm_route.hip", "conv_igemm.hip", "conv_patch.hip", "conv_patch16.hip", "conv_wino.hip", "conv_wino8.hip", "conv_wino_x3.hip", "conv_f16x3.hip", "conv_f16x3v2.hip", "conv_stem_f16x3.hip", "conv_up2.hip", "conv_up2_f16.hip", "conv_c16_f16.hip", "conv_gemm.hip", "conv_head.hip", "mbconv.hip", "wgrad_igemm.hip", "wgrad_patch.hip", "wgrad_wino.hip", "wgrad_f16x3.hip", "wgrad_c16.hip", "wgrad_gemm.hip", "wgrad_stem.hip", "elementwise.hip", "loss.hip", "loss_ext.hip", "mask_post.hip", "mask_enhance.hip", "resize_u8.hip", "pair_mask_u8.hip", "synth_u8.hip", "extract_u8.hip", "filter_u8.hip", "augment_u8.hip", "augment_ext_u8.hip", "jpeg_u8.hip", "uwm_model.hip"]
 HIP_ARCH = "gfx950"
 # per-file compiler flags.  The fp16x3 kernels interleave their staging VALU work with MFMAs; hipcc turns the f4 arithmetic of that
 # work into packed v_pk_{fma,mul,add}_f32, which cost more than two plain VALU instructions beside MFMAs (MI355X_MICROARCH.md,
@@ -29,6 +29,7 @@ EXTRA_FLAGS = {name: ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops
                for name in ("conv_f16x3.hip", "conv_f16x3v2.hip", "wgrad_f16x3.hip", "conv_stem_f16x3.hip")}
 # the synthesis kernels restate float arithmetic of Pillow and OpenCV operation by operation: no fused multiply-add
 EXTRA_FLAGS["synth_u8.hip"] = ["-ffp-contract=off"]
+EXTRA_FLAGS["extract_u8.hip"] = ["-ffp-contract=off"]      # Pillow's SMOOTH filter and Image.blend, operation by operation
 
 
 class uwm_unet_desc(C.Structure):
@@ -51,6 +52,12 @@ class uwm_loss_spec(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("w_dice", "w_bce", "w_jaccard", "w_tversky", "w_focal", "dice_smooth", "dice_eps", "jaccard_smooth",
                                          "jaccard_eps", "tversky_smooth", "tversky_eps", "tversky_alpha", "tversky_beta", "tversky_gamma",
                                          "focal_alpha", "focal_gamma")]
+
+
+class uwm_extract_job(C.Structure):
+    """include/uwm.h: one cut-out of uwm_extract_cutouts_ragged (288 bytes; extract.EXTRACT_JOB_DTYPE is its numpy twin)"""
+    _fields_ = [("image", C.c_int), ("x", C.c_int), ("y", C.c_int), ("w", C.c_int), ("h", C.c_int), ("reserved", C.c_int),
+                ("out_offset", C.c_longlong), ("member", C.c_uint8 * 256)]
 
 
 KIND_CONV_W, KIND_BIAS, KIND_BN_GAMMA, KIND_BN_BETA, KIND_BN_MEAN, KIND_BN_VAR = range(6)
@@ -161,6 +168,9 @@ SIGNATURES = {
     "uwm_enhance_masks_workspace_bytes": (Z, [I, Z]),
     "uwm_enhance_masks_ragged": (I, [P, P, Z, P, I, I, I, I, L, P, P, Z, P]),
     "uwm_enhance_gauss_taps": (I, [I, C.POINTER(C.c_float)]),
+    "uwm_extract_workspace_bytes": (Z, [I, L, I]),
+    "uwm_extract_regions_ragged": (I, [P, Z, P, P, Z, P, I, I, I, I, L, L, P, Z, P, P, P, P, Z, P]),
+    "uwm_extract_cutouts_ragged": (I, [P, Z, P, P, Z, P, I, P, I, L, P, Z, P, P, Z, P]),
     "uwm_op_morph": (I, [P, P, I, I, I, I, I, I, I, I, P, Z, P]),
     "uwm_op_components": (I, [P, P, P, I, I, I, P, Z, P]),
     "uwm_set_side_stream": (I, [P, I]),

@@ -1,4 +1,4 @@
-"""`python main.py train|predict|masks|filter|select|synth ...` — counterpart of the reference's CLI for the model path
+"""`python main.py train|predict|masks|filter|select|synth|extract ...` — counterpart of the reference's CLI for the model path
 (/root/reference/src/cli.py:368-395 flag names; train loop order /root/reference/src/train.py:207-499:
 epochs of train_epoch + validate (val batch = 2x train batch, :254), Adam | SGD (:265-279), ReduceLROnPlateau on the
 val loss | CosineAnnealingLR (:280-296,408-412), best / periodic checkpoints (:428-460), early stopping (:37-66,362-368)).
@@ -622,8 +622,24 @@ def enhance_masks_command(args):
     return dict(written=written, unreadable=unreadable, output=out_dir)
 
 
+def extract_command(args):
+    """The reference's extract_watermarks.py on the device: transparent RGBA cut-outs of the watermark regions of every
+    clean / watermarked pair, written where `--logos-dir` of `synth` and `train --synthesize` can read them."""
+    from .extract import WatermarkExtractor
+    for flag, d in (("--clean-dir", args.clean_dir), ("--watermarked-dir", args.watermarked_dir)):
+        if not os.path.isdir(d):
+            raise SystemExit(f"extract: {flag} not found: {d}")
+    if not torch.cuda.is_available():
+        raise SystemExit("extract needs a HIP device (this path has no CPU fallback)")
+    ex = WatermarkExtractor(args.clean_dir, args.watermarked_dir, args.output_dir, args.threshold, args.min_area, args.batch_size)
+    res = ex.process_all_images(args.limit, args.seed)
+    print(f"processed {res['processed']} pairs: {res['extracted']} yielded cut-outs, {res['written']} files written to {args.output_dir}, "
+          f"{res['errors']} errors")
+    return res
+
+
 def build_parser():
-    ap = argparse.ArgumentParser(description="MI355X-native U-Net watermark segmentation (train | masks | enhance-masks | filter | select | predict)")
+    ap = argparse.ArgumentParser(description="MI355X-native U-Net watermark segmentation (train | masks | enhance-masks | extract | filter | select | predict)")
     sub = ap.add_subparsers(dest="command")
     tp = sub.add_parser("train")
     tp.add_argument("--config", type=str, default=None)
@@ -705,6 +721,21 @@ def build_parser():
     ep.add_argument("--blur-kernel", type=int, default=15, help="side of the Gaussian, 0..63 (0: no blur; an even value is raised by one)")
     ep.add_argument("--smooth-iterations", type=int, default=2, help="open / close E(5,5) rounds, 0..8")
     ep.add_argument("--batch-size", type=int, default=16, help="masks per call")
+    xp = sub.add_parser("extract", help="cut the watermarks out of clean / watermarked pairs as transparent PNGs (the reference's extract_watermarks.py)",
+                        description="Compare every pair of --clean-dir and --watermarked-dir on the device, find the watermark regions "
+                                    "(difference, threshold, closing and opening, filled outer contours, area above --min-area), and write "
+                                    "each cluster of regions as an enhanced RGBA cut-out: <stem>_watermark.png, or <stem>_watermark_partK.png "
+                                    "where the regions lie further apart than a quarter of the diagonal.  Departures from the reference's "
+                                    "script: pairs are matched by stem over jpg, jpeg, png, bmp, tiff and tif (the script globs *.jpg); "
+                                    "--limit draws its sample from --seed; a pair that cannot be read counts under errors and stops "
+                                    "nothing; parts are numbered in ascending order of their first pixel, not in OpenCV's contour order.")
+    xp.add_argument("--clean-dir", type=str, required=True); xp.add_argument("--watermarked-dir", type=str, required=True)
+    xp.add_argument("--output-dir", type=str, required=True)
+    xp.add_argument("--threshold", type=int, default=30, help="least grey difference that counts as watermark (0..255)")
+    xp.add_argument("--min-area", type=int, default=100, help="a region is kept when its contour area exceeds this")
+    xp.add_argument("--limit", type=int, default=None, help="process a seeded random sample of this many pairs")
+    xp.add_argument("--seed", type=int, default=0, help="seed of the --limit sample")
+    xp.add_argument("--batch-size", type=int, default=16, help="pairs per device call")
     fp = sub.add_parser("filter", help="sort a folder by predicted watermark area (the reference's scripts/watermark_filter.py)",
                         description="Predict every image's watermark mask on the device and move away (or delete) the images whose mask "
                                     "covers less than --threshold of the image.  Two deliberate departures from the reference's script: "
@@ -772,4 +803,6 @@ def main(argv=None):
         return select_command(args)
     if args.command == "enhance-masks":
         return enhance_masks_command(args)
+    if args.command == "extract":
+        return extract_command(args)
     ap.print_help()

@@ -1262,4 +1262,58 @@ int uwm_op_maxpool(const uwm_src* in, int N, float* out, uint8_t* idx, uwm_strea
   return 0;
 }
 
+// ---- watermark cut-outs from pairs (extract_u8.hip): every argument is checked here, before any launch
+static int extract_caps_check(const char* fn, int N, long long total_pixels, int J) {
+  if (N < 0 || J < 0 || (N < 1 && J < 1)) return fail("%s: N and J must be >= 0 and one of them >= 1 (got %d, %d)", fn, N, J);
+  if (N > 65535 || J > 65535) return fail("%s: at most 65535 images and 65535 jobs per call (got %d, %d)", fn, N, J);
+  if (N >= 1 && (total_pixels < 1 || total_pixels > (1ll << 40))) return fail("%s: total_pixels must be 1 .. 2^40 (got %lld)", fn, total_pixels);
+  return 0;
+}
+size_t uwm_extract_workspace_bytes(int N, long long total_pixels, int J) {
+  if (extract_caps_check("uwm_extract_workspace_bytes", N, total_pixels, J)) return 0;
+  return extract_workspace_bytes(N, total_pixels, J);
+}
+int uwm_extract_regions_ragged(const uint8_t* wm, size_t wm_bytes, const uwm_image_desc* wm_descs, const uint8_t* clean, size_t clean_bytes,
+                               const uwm_image_desc* clean_descs, int N, int C, int threshold, int min_area, long long max_pixels,
+                               long long total_pixels, uint8_t* plane, size_t plane_bytes, const uwm_image_desc* plane_descs, long long* stats,
+                               long long* table, void* ws, size_t ws_bytes, uwm_stream stream) {
+  const char* fn = "uwm_extract_regions_ragged";
+  if (!wm || !wm_descs || !clean || !clean_descs || !plane || !plane_descs || !stats || !table || !ws) return fail("%s: null argument", fn);
+  if (C != 3) return fail("%s: C must be 3 (RGB pairs; got %d)", fn, C);
+  if (threshold < 0 || threshold > 255) return fail("%s: threshold must be 0..255 (got %d)", fn, threshold);
+  if (min_area < 0 || min_area > (1 << 30)) return fail("%s: min_area must be 0 .. 2^30 (got %d)", fn, min_area);
+  if (N < 1 || wm_bytes < 1 || clean_bytes < 1 || plane_bytes < 1)
+    return fail("%s: N, wm_bytes, clean_bytes and plane_bytes must be >= 1 (got %d, %zu, %zu, %zu)", fn, N, wm_bytes, clean_bytes, plane_bytes);
+  if (extract_caps_check(fn, N, total_pixels, 0)) return 1;
+  if (((uintptr_t)wm | (uintptr_t)clean) & 3) return fail("%s: wm and clean must be 4-byte aligned", fn);
+  if (max_pixels < 1 || max_pixels > (1ll << 30)) return fail("%s: max_pixels must be 1 .. 2^30 (got %lld)", fn, max_pixels);
+  if (((uintptr_t)wm_descs | (uintptr_t)clean_descs | (uintptr_t)plane_descs | (uintptr_t)stats | (uintptr_t)table | (uintptr_t)ws) & 7)
+    return fail("%s: descriptors, stats, table and the workspace must be 8-byte aligned", fn);
+  const size_t need = extract_workspace_bytes(N, total_pixels, 0);
+  if (ws_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", fn, ws_bytes, need);
+  LCHK(launch_extract_regions(wm, wm_bytes, (const ImageDesc*)wm_descs, clean, clean_bytes, (const ImageDesc*)clean_descs, N, threshold, min_area,
+                              max_pixels, total_pixels, plane, plane_bytes, (const ImageDesc*)plane_descs, stats, table, ws, (hipStream_t)stream));
+  return 0;
+}
+int uwm_extract_cutouts_ragged(const uint8_t* wm, size_t wm_bytes, const uwm_image_desc* wm_descs, const uint8_t* plane, size_t plane_bytes,
+                               const uwm_image_desc* plane_descs, int N, const uwm_extract_job* jobs, int J, long long max_crop_pixels,
+                               uint8_t* out, size_t out_bytes, int* status, void* ws, size_t ws_bytes, uwm_stream stream) {
+  const char* fn = "uwm_extract_cutouts_ragged";
+  static_assert(sizeof(uwm_extract_job) == sizeof(ExtractJob) && sizeof(ExtractJob) == 288, "uwm_extract_job layout");
+  if (!wm || !wm_descs || !plane || !plane_descs || !jobs || !out || !status || !ws) return fail("%s: null argument", fn);
+  if (N < 1 || J < 1 || wm_bytes < 1 || plane_bytes < 1 || out_bytes < 1)
+    return fail("%s: N, J, wm_bytes, plane_bytes and out_bytes must be >= 1 (got %d, %d, %zu, %zu, %zu)", fn, N, J, wm_bytes, plane_bytes, out_bytes);
+  if (extract_caps_check(fn, 0, 0, J)) return 1;
+  if (max_crop_pixels < 1 || max_crop_pixels > (1ll << 30)) return fail("%s: max_crop_pixels must be 1 .. 2^30 (got %lld)", fn, max_crop_pixels);
+  if (((uintptr_t)wm | (uintptr_t)out) & 3) return fail("%s: wm and out must be 4-byte aligned", fn);
+  if ((uintptr_t)status & 3) return fail("%s: status must be 4-byte aligned", fn);
+  if (((uintptr_t)wm_descs | (uintptr_t)plane_descs | (uintptr_t)jobs | (uintptr_t)ws) & 7)
+    return fail("%s: descriptors, jobs and the workspace must be 8-byte aligned", fn);
+  const size_t need = extract_workspace_bytes(0, 0, J);
+  if (ws_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", fn, ws_bytes, need);
+  LCHK(launch_extract_cutouts(wm, wm_bytes, (const ImageDesc*)wm_descs, plane, plane_bytes, (const ImageDesc*)plane_descs, N,
+                              (const ExtractJob*)jobs, J, max_crop_pixels, out, out_bytes, status, ws, (hipStream_t)stream));
+  return 0;
+}
+
 }  // extern "C"

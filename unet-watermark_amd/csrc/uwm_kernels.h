@@ -608,4 +608,26 @@ hipError_t launch_enhance_masks_ragged(const uint8_t* in, uint8_t* out, size_t m
                                        int blur_kernel, int smooth_iterations, long long max_pixels, long long* stats, void* ws,
                                        hipStream_t st);
 
+// watermark cut-outs from watermarked / clean pairs (extract_u8.hip): the reference's extract_watermarks.py on a ragged batch (the rule:
+// include/uwm.h).  ws: extract_workspace_bytes(N, total_pixels, J) bytes, the larger of the two stages' needs (N or J
+// below 1: that stage is left out); the callers (uwm_abi.inc) have checked every argument
+constexpr int kExtractMaxRegions = 254;              // kept regions of one image: the plane's byte 255 stands for "none"
+constexpr int kExtractRowInts = 9;                   // a table row: id, a00, a10, a01, x0, y0, x1, y1, pixels
+struct ExtractJob {                                  // = uwm_extract_job: one cut-out, in DEVICE memory
+  int image, x, y, w, h, reserved;
+  long long out_offset;
+  uint8_t member[256];
+};
+size_t extract_workspace_bytes(int N, long long total_pixels, int J);
+// stage 1: stats [N][4] = {regions found, regions kept, status, h*w}, table [N][254][9], plane + plane_descs[i].offset <- the index
+// of the kept region at each pixel or 255.  No read leaves the inputs, no write leaves the plane, stats, table or the workspace
+hipError_t launch_extract_regions(const uint8_t* wm, size_t wm_bytes, const ImageDesc* wm_descs, const uint8_t* clean, size_t clean_bytes,
+                                  const ImageDesc* clean_descs, int N, int threshold, int min_area, long long max_pixels, long long total_pixels,
+                                  uint8_t* plane, size_t plane_bytes, const ImageDesc* plane_descs, long long* stats, long long* table, void* ws,
+                                  hipStream_t st);
+// stage 2: job j's enhanced RGBA crop -> out + jobs[j].out_offset, status[j] = 0 done | 1 misfit (nothing written)
+hipError_t launch_extract_cutouts(const uint8_t* wm, size_t wm_bytes, const ImageDesc* wm_descs, const uint8_t* plane, size_t plane_bytes,
+                                  const ImageDesc* plane_descs, int N, const ExtractJob* jobs, int J, long long max_crop_pixels, uint8_t* out,
+                                  size_t out_bytes, int* status, void* ws, hipStream_t st);
+
 }  // namespace uwm
