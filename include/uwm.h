@@ -786,6 +786,47 @@ int    uwm_enhance_masks_ragged(const uint8_t* in, uint8_t* out /* may alias in 
 /* host only, no device: the taps the blur uses for blur_kernel 0..63 (0 and 1: the one tap {1}) -> out[0 .. k), returns the
  * effective k (even + 1), or 0 and a message on a bad argument; out holds up to 63 floats */
 int    uwm_enhance_gauss_taps(int blur_kernel, float* out);
+/* Text-feature enhancement on the device: the reference's WatermarkPredictor._enhance_text_features (src/predict.py:370-404), the
+ * OpenCV chain it runs on an image before the network sees it when the mask type is text or mixed.  A ragged batch in ONE call:
+ * image i is descs[i].h x descs[i].w x 3 interleaved RGB bytes at in + descs[i].offset (any alignment), its result goes to out +
+ * descs[i].offset; out must not overlap in (the last stage reads neighbours).  Six stages, each image at its own size:
+ *   1 grey     g = (R*9798 + G*19235 + B*3735 + 16384) >> 15                                       cvtColor(RGB2GRAY), 8 bit
+ *   2 CLAHE    createCLAHE(2.0, (8, 8)).apply(g): when h % 8 or w % 8 is non-zero the plane is extended at the bottom by 8 - h % 8
+ *              rows AND at the right by 8 - w % 8 columns (a side that divides grows by a full 8), BORDER_REFLECT_101; tile th x tw
+ *              = the (extended) size / 8; per tile the 256-bin histogram, clipped at max(int(2.0 * th*tw / 256), 1), the excess
+ *              handed out (excess / 256 to every bin, the rest one each to bins 0, s, 2s, ... with s = max(256 / rest, 1)), table[v] =
+ *              rint(float32(cumulative sum) * (255.0f / float32(th*tw))); per pixel f = y * (1.0f / th) - 0.5f, tiles floor(f) and
+ *              floor(f) + 1 clamped to 0..7, weight a = f - floor(f), likewise in x; c = rint((t11*(1-xa) + t12*xa)*(1-ya) +
+ *              (t21*(1-xa) + t22*xa)*ya), every float32 operation rounded on its own
+ *   3 Canny    Canny(c, 50, 150), aperture 3, L2gradient = false: dx, dy = the 3 x 3 Sobel derivatives, BORDER_REPLICATE; m = |dx| +
+ *              |dy|, 0 outside the image.  A pixel is a candidate when m > 50 and, with x = |dx|, y = |dy| << 15, t = x * 13573:
+ *              y < t: m > m(left) and m >= m(right); else y > t + (x << 16): m > m(above) and m >= m(below); else, s = -1 when
+ *              (dx ^ dy) < 0, otherwise 1: m > m(y-1, x-s) and m > m(y+1, x+s).  The edge image is 255 on the candidates that are
+ *              8-connected, through candidates, to a candidate with m > 150, else 0
+ *   4 dilate   with getStructuringElement(MORPH_ELLIPSE, (2, 2)) = [[0,1],[1,1]], anchor (1, 1): d(y, x) = max(e(y-1, x), e(y, x-1),
+ *              e(y, x)); pixels outside the image are ignored
+ *   5 boost    where d != 0 every channel value v becomes trunc(min(float32(v) * 1.2f, 255))
+ *   6 sharpen  filter2D with [[-1,-1,-1],[-1,9,-1],[-1,-1,-1]] per channel of the boosted image, BORDER_REFLECT_101, saturated
+ * Every OpenCV rule here is restated, NOT run against cv2 (DESIGN.md 8n lists them); tests/textenh_ref.py is the literal form the
+ * kernels are held to byte for byte.  edges (may be NULL; then edges_bytes and edge_descs are ignored): receives d, one byte per pixel
+ * in {0, 255}, at edges + edge_descs[i].offset; edge_descs[i] must carry image i's h and w.  The descriptors are read on the device;
+ * the host arguments are capacities, so one captured call serves every batch of N images that fits them: max_pixels (1 .. 2^30) bounds
+ * h_i * w_i and sizes the grids, total_pixels (1 .. 2^40) bounds the sum of h_i * w_i over the enhanced images and sizes the workspace.
+ * The launch count (11) does not depend on N (N <= 65535) or on what the images hold.  Per-image status: the first N ints of the
+ * workspace after the call = 0 enhanced | 1 misfit, nothing written (a side outside 1 .. 2^30, h*w > max_pixels, a region that leaves
+ * [0, bytes) or [0, edges_bytes), an edge descriptor of another size, or a sum of h*w over the enhanced images up to this one above
+ * total_pixels) | 2 a side below 16: the image is copied through unchanged and its edge plane is 0.  A misfit costs the others
+ * nothing.  Whatever the descriptors hold, no read leaves in / the descriptors and no write leaves out + [0, bytes), edges + [0,
+ * edges_bytes) or the workspace; overlapping regions are the caller's error.  workspace:
+ * uwm_text_enhance_workspace_bytes(total_pixels, N) bytes (0 and a message on a bad argument); descriptors and workspace 8-byte
+ * aligned.  Every argument is checked before any launch; no host synchronisation, allocation or copy.  Integer atomics only: runs
+ * are bit-identical. */
+enum { UWM_TEXT_ENHANCE_DONE = 0, UWM_TEXT_ENHANCE_MISFIT = 1, UWM_TEXT_ENHANCE_COPIED = 2, UWM_TEXT_ENHANCE_MIN_SIDE = 16 };
+size_t uwm_text_enhance_workspace_bytes(long long total_pixels, int N);
+int    uwm_text_enhance_ragged(const uint8_t* in, uint8_t* out, size_t bytes, const uwm_image_desc* descs /* device */, int N,
+                               int C /* 3 */, long long max_pixels, long long total_pixels,
+                               uint8_t* edges /* may be NULL */, size_t edges_bytes, const uwm_image_desc* edge_descs /* device */,
+                               void* workspace, size_t workspace_bytes, uwm_stream stream);
 /* Watermark cut-outs from watermarked / clean pairs on the device: the reference's extract_watermarks.py (extract_watermark_from_pair,
  * _extract_single_watermark / _extract_combined_watermark, _create_transparent_watermark), whose transparent RGBA cut-outs are the logos
  * gen_data.py pastes.  Two calls with a small host plan between them (extract.plan_cutouts: centres, clustering, margins).

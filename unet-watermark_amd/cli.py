@@ -398,6 +398,10 @@ def train_command(args):
 
 
 def predict_command(args):
+    text_enhance = bool(getattr(args, "text_enhance", False))
+    if text_enhance and args.resize != "device":
+        raise ValueError("--text-enhance needs --resize device: the reference's text-feature enhancement works on every image at its own "
+                         "size, which only the ragged device path serves (--resize host resizes on the host first)")
     cfg = get_cfg_defaults()
     if args.config and os.path.exists(args.config):
         update_config(cfg, args.config)
@@ -416,7 +420,7 @@ def predict_command(args):
         ims = [Image.open(os.path.join(args.input, f)).convert("RGB") for f in chunk]
         if args.resize == "device":                            # cv2-convention resize on the device, both ways, in one call
             masks = pred.predict_images([np.asarray(im, dtype=np.uint8) for im in ims], args.sigmoid, args.mask_type,
-                                        use_graph=len(chunk) == bs)
+                                        use_graph=len(chunk) == bs, text_enhance=text_enhance)
             for f, m in zip(chunk, masks):
                 Image.fromarray(m.cpu().numpy()).save(os.path.join(args.output, os.path.splitext(f)[0] + "_mask.png"))
             continue
@@ -783,6 +787,10 @@ def build_parser():
                     help="where images are resized to IMG_SIZE: 'device' = the reference's rule (cv2.resize INTER_LINEAR as A.Resize "
                          "does, restated in HIP; images of any size in one captured graph); 'host' (default) = PIL BILINEAR, which "
                          "widens its support on a downscale and so does NOT give the reference's pixels")
+    pp.add_argument("--text-enhance", action="store_true",
+                    help="run the reference's _enhance_text_features (CLAHE, Canny, dilate, x 1.2 on the edges, sharpen) on every image on "
+                         "the device before the network sees it; needs --resize device.  Independent of --mask-type: the reference's "
+                         "predict_text_watermark_mask is --mask-type text --text-enhance")
     return ap
 
 

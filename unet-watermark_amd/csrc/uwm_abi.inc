@@ -674,6 +674,40 @@ int uwm_enhance_masks_ragged(const uint8_t* in, uint8_t* out, size_t mask_bytes,
                                    stats, ws, (hipStream_t)stream));
   return 0;
 }
+// ---- text-feature enhancement (text_enhance.hip): every argument is checked here, before any launch
+static int text_enhance_caps_check(const char* fn, long long total_pixels, int N) {
+  if (N < 1 || N > 65535) return fail("%s: N must be 1 .. 65535 (got %d)", fn, N);
+  if (total_pixels < 1 || total_pixels > (1ll << 40)) return fail("%s: total_pixels must be 1 .. 2^40 (got %lld)", fn, total_pixels);
+  return 0;
+}
+size_t uwm_text_enhance_workspace_bytes(long long total_pixels, int N) {
+  if (text_enhance_caps_check("uwm_text_enhance_workspace_bytes", total_pixels, N)) return 0;
+  return text_enhance_workspace_bytes(total_pixels, N);
+}
+int uwm_text_enhance_ragged(const uint8_t* in, uint8_t* out, size_t bytes, const uwm_image_desc* descs, int N, int C, long long max_pixels,
+                            long long total_pixels, uint8_t* edges, size_t edges_bytes, const uwm_image_desc* edge_descs, void* ws,
+                            size_t ws_bytes, uwm_stream stream) {
+  const char* fn = "uwm_text_enhance_ragged";
+  if (!in || !out || !descs || !ws) return fail("%s: null argument", fn);
+  if (C != 3) return fail("%s: C must be 3 (RGB images; got %d)", fn, C);
+  if (bytes < 1 || bytes > ((size_t)1 << 42)) return fail("%s: bytes must be 1 .. 2^42 (got %zu)", fn, bytes);
+  if (text_enhance_caps_check(fn, total_pixels, N)) return 1;
+  if (max_pixels < 1 || max_pixels > (1ll << 30)) return fail("%s: max_pixels must be 1 .. 2^30 (got %lld)", fn, max_pixels);
+  if ((uintptr_t)in < (uintptr_t)out + bytes && (uintptr_t)out < (uintptr_t)in + bytes)
+    return fail("%s: out must not overlap in (the sharpening filter reads neighbours)", fn);
+  if (edges) {
+    if (!edge_descs) return fail("%s: edges needs edge_descs", fn);
+    if (edges_bytes < 1 || edges_bytes > ((size_t)1 << 40)) return fail("%s: edges_bytes must be 1 .. 2^40 (got %zu)", fn, edges_bytes);
+    if ((uintptr_t)edges < (uintptr_t)out + bytes && (uintptr_t)out < (uintptr_t)edges + edges_bytes)
+      return fail("%s: edges must not overlap out", fn);
+  }
+  if (((uintptr_t)descs | (uintptr_t)edge_descs | (uintptr_t)ws) & 7) return fail("%s: descriptors and the workspace must be 8-byte aligned", fn);
+  const size_t need = text_enhance_workspace_bytes(total_pixels, N);
+  if (ws_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", fn, ws_bytes, need);
+  LCHK(launch_text_enhance_ragged(in, out, bytes, (const ImageDesc*)descs, N, max_pixels, total_pixels, edges, edges ? edges_bytes : 0,
+                                  (const ImageDesc*)edge_descs, ws, (hipStream_t)stream));
+  return 0;
+}
 int uwm_op_morph(const uint8_t* in, uint8_t* out, int N, int H, int W, int dilate, int shape, int kw, int kh, int iterations,
                  void* ws, size_t ws_bytes, uwm_stream stream) {
   if (!in || !out) return fail("uwm_op_morph: null argument");

@@ -630,4 +630,12 @@ hipError_t launch_extract_cutouts(const uint8_t* wm, size_t wm_bytes, const Imag
                                   const ImageDesc* plane_descs, int N, const ExtractJob* jobs, int J, long long max_crop_pixels, uint8_t* out,
                                   size_t out_bytes, int* status, void* ws, hipStream_t st);
 
+// text-feature enhancement (text_enhance.hip): the reference's _enhance_text_features on a ragged batch of RGB images (the rule:
+// include/uwm.h).  ws: text_enhance_workspace_bytes(total_pixels, N) bytes, its first N ints the per-image status;
+// edges (may be null): the dilated edge plane.  The callers (uwm_abi.inc) have checked every argument
+size_t text_enhance_workspace_bytes(long long total_pixels, int N);
+hipError_t launch_text_enhance_ragged(const uint8_t* in, uint8_t* out, size_t bytes, const ImageDesc* descs, int N, long long max_pixels,
+                                      long long total_pixels, uint8_t* edges, size_t edges_bytes, const ImageDesc* edge_descs, void* ws,
+                                      hipStream_t st);
+
 }  // namespace uwm

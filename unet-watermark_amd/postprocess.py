@@ -7,7 +7,8 @@ a ragged batch of masks of any sizes in ONE call (uwm_optimize_masks_ragged, DES
 enhance_masks_ragged / enhance_mask are the reference's scripts/enhance_masks.py::enhance_mask (grey close and dilate, Gaussian blur,
 threshold, smoothing: csrc/mask_enhance.hip) on a ragged batch, again in one call.
 
-The reference's automatic type detection (_detect_watermark_type: Canny / Sobel on the image) and _enhance_text_features stay out."""
+The reference's _enhance_text_features (the image enhancement in front of the network for text watermarks) is served by textenh.py
+(csrc/text_enhance.hip); its automatic type detection (_detect_watermark_type: Canny / Sobel on the image) stays out."""
 from __future__ import annotations
 
 import ctypes as C

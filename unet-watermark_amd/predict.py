@@ -3,7 +3,9 @@ step1_batch_predict_watermark_masks (/root/reference/src/predict.py:68-99,303-36
 part of that path: checkpoint -> eval() -> logits -> threshold -> uint8 mask.  The reference runs batch 1
 per image; here a whole batch goes through ONE hipGraph replay of the eval forward (BASELINE config 5).
 The reference's mask post-processing (_optimize_mask, src/predict.py:161-301) is opt-in through `mask_type` and runs on the
-device inside the same graph (postprocess.py); its automatic type detection, IOPaint and OCR stay out of scope."""
+device inside the same graph (postprocess.py); its image enhancement for text watermarks (_enhance_text_features,
+src/predict.py:370-404) is opt-in through `text_enhance` and runs in front of the forward inside the same graph (textenh.py); its
+automatic type detection, IOPaint and OCR stay out of scope."""
 from __future__ import annotations
 
 from typing import Optional
@@ -17,6 +19,7 @@ from .constants import IMAGENET_MEAN, IMAGENET_STD  # noqa: F401   (predict.IMAG
 from .data import descs_tensor, device_preprocess, pack_images
 from .metrics import threshold_mask
 from .model import create_model_from_config
+from .textenh import text_enhance_ragged, text_enhance_workspace
 from .postprocess import RAGGED_TYPES, mask_type_code, optimize_mask, optimize_masks_ragged, ragged_workspace, workspace as mask_workspace
 
 
@@ -57,6 +60,11 @@ class WatermarkPredictor:
         self._qkey = None
         self._qws = self._sbuf = None         # ... its static (N, 8) stats, and the capacities of the post-processing in it
         self._cap_pixels = self._cap_rows = 0
+        self._tigraph = self._tqgraph = None  # the same two with text_enhance: graphs of their own, so the default ones stay as captured
+        self._tikey = self._tqkey = None
+        self._tiws = self._tqws = self._tsbuf = None
+        self._ebuf = None                     # ... the enhanced images: a second staging buffer of _ibuf's size
+        self._tcap_pixels = self._tcap_total = 0      # ... and the capacities of the enhancement in them
         self._cgraph = None                   # watermark_counts: ONE graph per (N, IMG_SIZE, threshold, post_process, with masks)
         self._ckey = None
         self._cbuf = self._cws = None         # its static counts buffer and workspaces
@@ -120,6 +128,7 @@ class WatermarkPredictor:
         if self.freeze and not self.model.frozen_serves(n, h, w):
             self.model.freeze(batch_shape=(n, h, w))
             self._graph = self._gkey = self._ugraph = self._ukey = self._pgraph = self._pkey = self._igraph = self._ikey = self._qgraph = self._qkey = self._cgraph = self._ckey = None
+            self._tigraph = self._tikey = self._tqgraph = self._tqkey = None
 
     @torch.no_grad()
     def predict_mask_u8(self, images_u8_nhwc: torch.Tensor, out_size=None, apply_sigmoid: bool = False,
@@ -170,6 +179,7 @@ class WatermarkPredictor:
         cap = max(need, 256 if buf is None else 2 * buf.numel())
         setattr(self, name, torch.zeros(cap, dtype=torch.uint8, device=self.device))
         self._igraph = self._ikey = self._qgraph = self._qkey = self._cgraph = self._ckey = None
+        self._tigraph = self._tikey = self._tqgraph = self._tqkey = None
 
     def _stage_images(self, images):
         """pack `images` into the static staging buffers (_ibuf, _idesc, _mdesc; _mbuf sized for their masks) -> (n, IMG_SIZE, descs,
@@ -198,12 +208,28 @@ class WatermarkPredictor:
         self._mdesc[:16 * n].copy_(descs_tensor(mdescs))
         return n, s, descs, mdescs, areas, mask_bytes
 
-    def _run_images(self, images, apply_sigmoid: bool, mask_type: Optional[str], use_graph: bool):
+    def _run_images(self, images, apply_sigmoid: bool, mask_type: Optional[str], use_graph: bool, text_enhance: bool = False):
         """stage `images`, run uwm_predict_images_u8 and, with a mask_type, uwm_optimize_masks_ragged in place on _mbuf — one captured
         graph for both -> (descs, mask descs, areas, mask bytes, the int64 (n, 8) device stats or None).  The ragged call's
         capacities (the largest h*w, the sum of h) are kept and grown geometrically like the staging buffers; they and the buffer
-        sizes are all the graph knows about a batch, so a batch that fits them replays it and one that exceeds one re-captures."""
+        sizes are all the graph knows about a batch, so a batch that fits them replays it and one that exceeds one re-captures.
+        text_enhance: the staged images first go through uwm_text_enhance_ragged into a second staging buffer (_ebuf), which the
+        forward then reads — the same graph, kept in slots of its own, with the enhancement's two capacities (the largest h*w, the
+        sum of h*w) in its key."""
         n, s, descs, mdescs, areas, mask_bytes = self._stage_images(images)
+        tcaps = ()
+        if text_enhance:
+            if self.model.in_channels != 3:
+                raise RuntimeError(f"text_enhance takes RGB images; the model takes {self.model.in_channels} channels")
+            if int(areas.max()) > 2 ** 30:
+                raise ValueError("text_enhance: an image of more than 2^30 pixels")
+            for name, need in (("_tcap_pixels", int(areas.max())), ("_tcap_total", int(areas.sum()))):
+                if getattr(self, name) < need:
+                    setattr(self, name, min(max(need, 2 * getattr(self, name)), 2 ** 30 if name == "_tcap_pixels" else 2 ** 40))
+            if self._ebuf is None or self._ebuf.numel() != self._ibuf.numel():
+                self._ebuf = torch.zeros_like(self._ibuf)
+                self._tigraph = self._tikey = self._tqgraph = self._tqkey = None
+            tcaps = ("text_enhance", self._tcap_pixels, self._tcap_total)
         if mask_type is not None:
             for name, need in (("_cap_pixels", int(areas.max())), ("_cap_rows", int(descs["h"].astype("int64").sum()))):
                 if getattr(self, name) < need:
@@ -212,8 +238,10 @@ class WatermarkPredictor:
         stats = None
 
         def run():
-            self.model.predict_images_u8(self._ibuf, self._idesc, self._mdesc, self._mbuf, n, (s, s), IMAGENET_MEAN, IMAGENET_STD,
-                                         self.threshold, apply_sigmoid)
+            if text_enhance:
+                text_enhance_ragged(self._ibuf, self._idesc, out=self._ebuf, n=n, max_pixels=tcaps[1], total_pixels=tcaps[2])
+            self.model.predict_images_u8(self._ebuf if text_enhance else self._ibuf, self._idesc, self._mdesc, self._mbuf, n, (s, s),
+                                         IMAGENET_MEAN, IMAGENET_STD, self.threshold, apply_sigmoid)
             if mask_type is not None:
                 optimize_masks_ragged(self._mbuf, self._mdesc, mask_type, True, out=self._mbuf, n=n, max_pixels=caps[1], rows=caps[2],
                                       stats=stats)
@@ -222,12 +250,16 @@ class WatermarkPredictor:
                 stats = torch.empty((n, 8), dtype=torch.int64, device=self.device)
             run()
         else:
-            key = (n, s, s, bool(apply_sigmoid), float(self.threshold)) + caps      # (the threshold and the capacities are captured arguments)
+            key = (n, s, s, bool(apply_sigmoid), float(self.threshold)) + caps + tcaps      # (the threshold and the capacities are captured arguments)
             slot = "_i" if mask_type is None else "_q"      # the graph without post-processing stays when the other is captured
+            sbuf = "_sbuf"
+            if text_enhance:
+                slot, sbuf = "_t" + slot[1:], "_tsbuf"
             if getattr(self, slot + "key") != key or getattr(self, slot + "graph") is None:
                 self._refreeze_for(n, s, s)
                 if mask_type is not None:
-                    stats = self._sbuf = torch.empty((n, 8), dtype=torch.int64, device=self.device)
+                    stats = torch.empty((n, 8), dtype=torch.int64, device=self.device)
+                    setattr(self, sbuf, stats)
                 run()                                 # eager warm-up: plans the workspace, sets kernel attributes
                 torch.cuda.synchronize(self.device)
                 g = torch.cuda.CUDAGraph()
@@ -236,8 +268,10 @@ class WatermarkPredictor:
                 ws = self.model._ws                   # (the graph's workspaces stay alive with it)
                 if mask_type is not None:
                     ws = (ws, ragged_workspace(self.device, n, self._mbuf.numel(), caps[2]))
+                if text_enhance:
+                    ws = (ws, text_enhance_workspace(self.device, tcaps[2], n))
                 setattr(self, slot + "graph", g); setattr(self, slot + "key", key); setattr(self, slot + "ws", ws)
-            stats = self._sbuf if mask_type is not None else None
+            stats = getattr(self, sbuf) if mask_type is not None else None
             getattr(self, slot + "graph").replay()
         return descs, mdescs, areas, mask_bytes, stats
 
@@ -247,7 +281,7 @@ class WatermarkPredictor:
 
     @torch.no_grad()
     def predict_images(self, images, apply_sigmoid: bool = False, mask_type: Optional[str] = None, use_graph: bool = True,
-                       return_stats: bool = False):
+                       return_stats: bool = False, text_enhance: bool = False):
         """uint8 (h_i, w_i, C) images of ANY sizes (arrays or tensors) -> a list of uint8 {0,255} device masks, one per image at its
         own size: the reference's predict path (src/predict.py:327-335,614-625) device-resident from the image bytes on — cv2's
         INTER_LINEAR resize to IMG_SIZE (A.Resize) + Normalize, eval forward, bilinear resize of the logits back to (h_i, w_i) +
@@ -256,26 +290,30 @@ class WatermarkPredictor:
         to grow or the frozen arena was re-made.  mask_type 'watermark' | 'text' | 'mixed': every mask then goes through the
         reference's _optimize_mask at its own size (uwm_optimize_masks_ragged), in place and inside the same graph; the graph is
         then also re-captured when the largest image or the sum of the heights outgrows the capacity it was captured with.
-        return_stats (needs a mask_type): also the int64 (N, 8) HOST array of postprocess.STATS_FIELDS."""
+        return_stats (needs a mask_type): also the int64 (N, 8) HOST array of postprocess.STATS_FIELDS.
+        text_enhance: every image first goes through the reference's _enhance_text_features at its own size
+        (uwm_text_enhance_ragged, textenh.py) and the network sees the enhanced image; an image with a side below 16 goes in as it
+        is.  Independent of mask_type: mask_type='text', text_enhance=True is the reference's predict_text_watermark_mask."""
         if mask_type is not None:
             mask_type_code(mask_type)
         elif return_stats:
             raise ValueError("return_stats needs a mask_type ('watermark', 'text' or 'mixed')")
-        descs, mdescs, areas, mask_bytes, stats = self._run_images(images, apply_sigmoid, mask_type, use_graph)
+        descs, mdescs, areas, mask_bytes, stats = self._run_images(images, apply_sigmoid, mask_type, use_graph, text_enhance)
         masks = self._mask_views(descs, mdescs, areas, mask_bytes)
         return (masks, stats.cpu().numpy()) if return_stats else masks
 
     @torch.no_grad()
-    def mask_stats(self, images, mask_type: str = "watermark", return_masks: bool = False, use_graph: bool = True):
+    def mask_stats(self, images, mask_type: str = "watermark", return_masks: bool = False, use_graph: bool = True,
+                   text_enhance: bool = False):
         """uint8 (h_i, w_i, C) images of ANY sizes -> the int64 (N, 8) HOST array of postprocess.STATS_FIELDS for the masks
         predict_images(mask_type=...) returns: {components found, largest area, foreground pixels, id of the largest or -1,
         components kept, largest kept area, h_i * w_i, status}.  Entries 2, 4, 5 and 6 are what the reference's model selector
         computes from every mask on the host (src/scripts/model_selector.py:171-197).  One captured call and one device-to-host
         copy of 64 N bytes; no mask leaves the device unless return_masks, which adds the list of device masks.  mask_type may also be
-        'none': the thresholded masks as they are."""
+        'none': the thresholded masks as they are.  text_enhance: as predict_images."""
         if mask_type not in RAGGED_TYPES:
             raise ValueError(f"mask_type must be one of 'watermark', 'text', 'mixed', 'none', got {mask_type!r}")
-        descs, mdescs, areas, mask_bytes, stats = self._run_images(images, False, mask_type, use_graph)
+        descs, mdescs, areas, mask_bytes, stats = self._run_images(images, False, mask_type, use_graph, text_enhance)
         host = stats.cpu().numpy()
         return (host, self._mask_views(descs, mdescs, areas, mask_bytes)) if return_masks else host
 
