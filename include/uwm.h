@@ -223,8 +223,8 @@ int  uwm_pair_mask_u8(const uint8_t* wm, size_t wm_bytes, const uwm_image_desc* 
 
 /* Logo-watermarked training samples: the LOGO branch of the reference's src/scripts/gen_data.py (apply_watermark_effects,
  * resize_watermark, generate_multiple_watermarks_image / generate_watermarked_image, calculate_overlap_area, and main()'s
- * single/multi and transparent/normal choices).  Text and mixed watermarks, the JPEG quality=95 save and a device-resident logo bank
- * are NOT served.  A JOB is one logo on one image.  The HOST draws every random number, computes every size and does the placement
+ * single/multi and transparent/normal choices).  Text and mixed watermarks are uwm_synth_text_u8's, below; the JPEG quality=95 save
+ * and a device-resident logo bank are NOT served.  A JOB is one logo on one image.  The HOST draws every random number, computes every size and does the placement
  * loop (data.sample_synth_jobs); the device only executes descriptors, so a batch is a pure function of its inputs.  Stages, in
  * order, on an RGBA patch (uint8, R G B A interleaved); MULDIV255(x, y) = (t = x*y + 128, ((t >> 8) + t) >> 8):
  *   1 RESIZE to (w1, h1) = Image.resize(LANCZOS) on RGBA.  Equal size: a copy.  Else premultiply c = MULDIV255(c, a); the horizontal
@@ -302,6 +302,63 @@ int  uwm_op_synth_patches(const uint8_t* logos, size_t logo_bytes, const uwm_ima
                           void* workspace, size_t workspace_bytes, uint8_t* out, size_t out_bytes, uwm_stream stream);
 int  uwm_lanczos_table_ints(int in, int out);         /* out*(ksize + 2); 0 for a side outside 1..32767 */
 int  uwm_op_lanczos_table(int in, int out, int* table /* device */, size_t table_ints, uwm_stream stream);
+
+/* Text-watermarked training samples: the TEXT branch of the reference's src/scripts/gen_data.py (apply_text_effects,
+ * generate_text_watermark) and the mask rule of generate_mixed_watermark.  A JOB is one text on one image.  The HOST chooses the text
+ * and the font, rasterises the text to a COVERAGE PLANE (one byte per pixel: font.getmask2(text, "L") placed on the canvas of the
+ * text's bounding box plus a margin of 20; data.render_text_plane), draws every random number and computes every size
+ * (data.sample_text_job); the device only executes descriptors.  Stages, in order, on an RGBA patch; "stage n" is uwm_synth_u8's:
+ *   A COLOUR   what ImageDraw.text(fill = ink) leaves on a transparent canvas: coverage c != 0 gives (ink[0], ink[1], ink[2], c),
+ *              c == 0 gives (0, 0, 0, 0).
+ *   B ROTATE   (rotate != 0) stage 2 to (w2, h2) with rot: Image.rotate(angle, expand=True, fillcolor=(0, 0, 0, 0)).
+ *   C SCALE    (scale != 0) stage 1 to (w3, h3): Image.resize(LANCZOS) on RGBA, premultiplied; an equal size is a copy.
+ *   D BLUR     (blur != 0) stage 4 with blur_r, blur_ww, blur_fw (the script draws radii 0.5..1.5).
+ *   E ENHANCE  Brightness (brighten != 0), then Contrast (recontrast != 0), by stage 6's rule; the Contrast mean is taken over the
+ *              brightened patch.  There is no Color step.  A step that is off is that step at factor 1, which is Image.blend's copy.
+ *   F OPACITY  stage 7: a = opacity[a].
+ *   G FIT      nfit (0..3) further LANCZOS resizes, in order, to fit[f] = {w, h}: the script's "wider than 0.8 W", "taller than
+ *              0.8 H" and "still does not fit" rescales, with the sizes the host derived.  An equal size is a copy.
+ *   H PASTE    stage 8 into the image at (x, y), clipped; the jobs of one image are applied in slot order.  The mask plane follows
+ *              mask_mode.  0: mask.paste(alpha, (x, y), alpha) over what the plane holds (text alone: the caller zeroes the plane).
+ *              1: the mixed rule: every byte m of the plane becomes max(m >> 1, t), t the alpha planes pasted from 0 — m >> 1 is
+ *              Image.blend(0, m, 0.5) followed by convert("L"); each byte is halved once whatever K is.
+ * An image none of whose K jobs runs is left as it is, mask plane included (in mode 1 too: no text, no mixed rule), so one call
+ * serves a batch in which only some images carry text.
+ * images: a ragged batch (uint8 RGB interleaved), worked on IN PLACE; masks (may be NULL): one byte per pixel, used where a mask's
+ * descriptor equals its image's.  planes: a ragged batch of one-channel uint8 images, each offset a multiple of 4.  jobs: [N][K] in
+ * device memory, K <= 8.  The workspace holds, per job, two patch buffers of max_patch_pixels pixels, eight coefficient tables of
+ * max_taps int32 and the partial sums of the Contrast mean.  A job with enabled == 0, or one that does not fit (a plane index or
+ * descriptor outside its buffer, an ink outside 0..255, a side outside 1..32767, the plane or an intermediate or final patch above
+ * max_patch_pixels, a table above max_taps, non-finite matrix entries, blur_r above 32, nfit outside 0..3) is skipped by every
+ * stage and costs only itself.  20 launches of N * K * 32 workgroups on the caller's stream, sized from N and K alone, no host
+ * synchronisation: capturable, and one captured call serves every batch of equal capacities.  Integer sums and spelt-out float
+ * operations only: runs are bit-identical.  uwm_op_text_patches runs stages A-G on J jobs and stores job j's finished patch at
+ * out + j*max_patch_pixels*4 (stage-level tests).  Every argument is checked before any launch.  No read leaves the inputs; no write
+ * leaves [images, +image_bytes), [masks, +mask_bytes) or the workspace.  Held to Pillow through tests/textsynth_ref.py. */
+typedef struct uwm_text_job {
+  int enabled;                 /* 0: an empty slot */
+  int glyph;                   /* index into plane_descs */
+  int ink[3];                  /* A */
+  int rotate, w2, h2;          /* B and its expanded size */
+  int scale, w3, h3;           /* C */
+  int blur, blur_r;            /* D */
+  unsigned blur_ww, blur_fw;
+  int brighten, recontrast;    /* E */
+  float brightness, contrast;
+  int nfit, fit[3][2];         /* G: {w, h} */
+  int x, y;                    /* H */
+  double rot[6];
+  uint8_t opacity[256];        /* F */
+} uwm_text_job;
+size_t uwm_synth_text_workspace_bytes(int N, int K, long long max_patch_pixels, long long max_taps);
+int  uwm_synth_text_u8(uint8_t* images, size_t image_bytes, const uwm_image_desc* image_descs,
+                       uint8_t* masks /* may be NULL */, size_t mask_bytes, const uwm_image_desc* mask_descs, int mask_mode,
+                       const uint8_t* planes, size_t plane_bytes, const uwm_image_desc* plane_descs, int num_planes,
+                       const uwm_text_job* jobs, int N, int K, long long max_patch_pixels, long long max_taps,
+                       void* workspace, size_t workspace_bytes, uwm_stream stream);
+int  uwm_op_text_patches(const uint8_t* planes, size_t plane_bytes, const uwm_image_desc* plane_descs, int num_planes,
+                         const uwm_text_job* jobs, int J, long long max_patch_pixels, long long max_taps,
+                         void* workspace, size_t workspace_bytes, uint8_t* out, size_t out_bytes, uwm_stream stream);
 
 /* The dataset filter: the reference's src/scripts/watermark_filter.py (predict_mask, _post_process_mask, has_watermark), which sorts a
  * folder by the share of each image that the model calls watermark.  Only one integer per image is wanted, so the mask need not leave

@@ -21,6 +21,7 @@ from .data import (sample_aug_recipe, identity_aug_ext_params, gamma_lut, motion
                    AUG_EXT_DTYPE)
 from .data import device_pair_mask, stage_clean, mask_descs_for, RawPairDataset  # noqa: F401,E402
 from .data import device_synth, sample_synth_jobs, sample_synth_choice, RawSynthDataset, SYNTH_JOB_DTYPE  # noqa: F401,E402
+from .data import device_synth_text, render_text_plane, sample_text_job, sample_synth_kind, TEXT_JOB_DTYPE  # noqa: F401,E402
 from .filter import WatermarkFilter, filter_folder, batch_ratios, list_images  # noqa: F401,E402
 from .postprocess import optimize_masks_ragged  # noqa: F401,E402
 from .select import ModelSelector, run_selection  # noqa: F401,E402

@@ -2,8 +2,9 @@
 (/root/reference/src/cli.py:368-395 flag names; train loop order /root/reference/src/train.py:207-499:
 epochs of train_epoch + validate (val batch = 2x train batch, :254), Adam | SGD (:265-279), ReduceLROnPlateau on the
 val loss | CosineAnnealingLR (:280-296,408-412), best / periodic checkpoints (:428-460), early stopping (:37-66,362-368)).
-`repair` / `auto` (IOPaint, OCR, video, text-watermark synthesis) are out of scope (SURVEY.md §2 rows 6,9,10); the logo branch of the
-data synthesis runs on the device (`train --synthesize`, `synth`).
+`repair` / `auto` (IOPaint, OCR, video) are out of scope (SURVEY.md §2 rows 6,9,10); the data synthesis runs on the device (`train
+--synthesize`, `synth`): logo watermarks and, with --text-watermark-ratio / --mixed-watermark-ratio, text and mixed
+ones (§8o; the OCR mask is not served, masks come from pairs or from the pasted alpha planes).
 Multi-GPU: launch with torch.distributed.run; every rank trains its shard, gradients are all-reduced."""
 from __future__ import annotations
 
@@ -141,15 +142,46 @@ def _check_synthesize(args, augment):
     if augment == "none":
         raise ValueError("--synthesize runs on the device input path (the logos are pasted at each image's own size, in front of the "
                          "device's resize, augmentation and Normalize): give --augment basic or --augment config")
-    if not args.clean_dir or not args.logos_dir:
-        raise ValueError("--synthesize needs --clean-dir (clean photographs) and --logos-dir (logo images)")
+    _check_text_ratios(args)
+    if not args.clean_dir or (not args.logos_dir and float(args.text_watermark_ratio) < 1):
+        raise ValueError("--synthesize needs --clean-dir (clean photographs) and --logos-dir (logo images; only --text-watermark-ratio 1 "
+                         "does without)")
+
+
+def _check_text_ratios(args):
+    """the refusals that the text and mixed shares bring, before any device work: the ratios' range, and freetype"""
+    from .data.datasets import check_synth_ratios
+    from .data import require_freetype
+    t, m = check_synth_ratios(args.text_watermark_ratio, args.mixed_watermark_ratio)
+    if t > 0 or m > 0:
+        require_freetype("--text-watermark-ratio / --mixed-watermark-ratio")
+
+
+def _add_text_arguments(p, prefix):
+    p.add_argument("--text-watermark-ratio", type=float, default=0.0,
+                   help=f"{prefix}share of samples that carry a text watermark (the text branch of gen_data.py).  The reference's default is "
+                        "0.3; 0 here, so that a command without the flag produces byte-identical results")
+    p.add_argument("--mixed-watermark-ratio", type=float, default=0.0,
+                   help=f"{prefix}share of samples with one or two logos and a text (the reference's default is 0.2; 0 here, as above)")
+    p.add_argument("--fonts-dir", type=str, default=None,
+                   help=f"{prefix}directory of ttf / otf / ttc fonts for the texts (default: Pillow's embedded scalable font)")
+    p.add_argument("--texts-file", type=str, default=None,
+                   help=f"{prefix}the texts: one per line, blank lines separate categories (default: a short built-in list)")
+
+
+def _synth_kinds_note(ds):
+    if not ds.with_text:
+        return "logo watermarks only"
+    return f"text watermarks on {ds.text_ratio:g} of the samples, logos and a text on {ds.mixed_ratio:g}, {len(ds.fonts.paths)} font(s)"
 
 
 def _synth_datasets(cfg, args):
     """train / validation splits of the clean images, as _datasets splits a folder; the training split draws new samples every epoch
     (set_epoch), the validation split is never told the epoch and so reproduces its samples"""
     kw = dict(seed=int(args.synth_seed), transparent_ratio=float(args.transparent_ratio), multi_watermark_ratio=float(args.multi_watermark_ratio),
-              max_watermarks=int(args.synth_max_watermarks), mask_threshold=int(cfg.DATA.GENERATE_MASK_THRESHOLD), mask_source=args.synth_mask)
+              max_watermarks=int(args.synth_max_watermarks), mask_threshold=int(cfg.DATA.GENERATE_MASK_THRESHOLD), mask_source=args.synth_mask,
+              text_watermark_ratio=float(args.text_watermark_ratio), mixed_watermark_ratio=float(args.mixed_watermark_ratio),
+              fonts_dir=args.fonts_dir, texts_file=args.texts_file)
     train, val = RawSynthDataset(args.clean_dir, args.logos_dir, **kw), RawSynthDataset(args.clean_dir, args.logos_dir, **kw)
     n = len(train)
     g = torch.Generator().manual_seed(int(cfg.DATA.SEED))
@@ -323,7 +355,8 @@ def train_command(args):
                       "one; nothing is written (`main.py masks` persists them)", flush=True)
             if synthesize:
                 print(f"synthesis: {len(tr_set.dataset)} clean images x {len(tr_set.dataset.logos)} logos, pasted on the device at each image's "
-                      f"own size (logo watermarks only; masks from {'the pasted alpha planes' if args.synth_mask == 'alpha' else 'synthesized / clean pairs'})",
+                      f"own size ({_synth_kinds_note(tr_set.dataset)}; masks from "
+                      f"{'the pasted alpha planes' if args.synth_mask == 'alpha' else 'synthesized / clean pairs'})",
                       flush=True)
     bs = int(cfg.TRAIN.BATCH_SIZE)
     sampler = DistributedSampler(tr_set, world, rank, shuffle=True, seed=int(cfg.DATA.SEED)) if world > 1 else None
@@ -481,17 +514,27 @@ def masks_command(args):
 
 
 def synth_command(args):
-    """The logo branch of the reference's src/scripts/gen_data.py on the device: --count samples into <output-dir>/watermarked (PNG, so
-    the pixels are the device's; the reference saves JPEG quality 95), a same-named copy of the clean image into <output-dir>/clean —
-    which is what lets RawPairDataset derive the masks — and, with --generate-mask, the pasted alpha planes into <output-dir>/masks."""
+    """The reference's src/scripts/gen_data.py on the device: --count samples into <output-dir>/watermarked (PNG, so the pixels are
+    the device's; the reference saves JPEG quality 95), a same-named copy of the clean image into <output-dir>/clean — which is what
+    lets RawPairDataset derive the masks — and, with --generate-mask, the script's own masks into <output-dir>/masks: the pasted alpha
+    planes, for a mixed sample the logos' plane halved and then the maximum with the text's.  (That halved part never survives the
+    reference dataset's binarisation at 127 — the script's quirk, kept — which is one reason why masks from pairs are the default
+    of `train --synthesize`.)  Text and mixed samples (--text-watermark-ratio, --mixed-watermark-ratio; both 0 by default) carry the
+    script's prefixes text_trans_ / text_norm_ / mixed_trans_ / mixed_norm_."""
     import random
     import numpy as np
     from PIL import Image
-    from .data import device_synth, mask_descs_for, pack_images
+    from .data import device_synth, device_synth_text, mask_descs_for, pack_images
+    from .data.datasets import read_u8
     if int(args.count) < 1:
         raise ValueError("synth: --count must be >= 1")
+    _check_text_ratios(args)
+    if not args.logos_dir and float(args.text_watermark_ratio) < 1:
+        raise ValueError("synth needs --logos-dir (logo images; only --text-watermark-ratio 1 does without)")
     ds = RawSynthDataset(args.clean_dir, args.logos_dir, seed=int(args.seed), transparent_ratio=float(args.transparent_ratio),
-                         multi_watermark_ratio=float(args.multi_watermark_ratio), max_watermarks=int(args.max_watermarks))
+                         multi_watermark_ratio=float(args.multi_watermark_ratio), max_watermarks=int(args.max_watermarks),
+                         text_watermark_ratio=float(args.text_watermark_ratio), mixed_watermark_ratio=float(args.mixed_watermark_ratio),
+                         fonts_dir=args.fonts_dir, texts_file=args.texts_file)
     if not torch.cuda.is_available():
         raise SystemExit("synth needs a HIP device (this path has no CPU fallback)")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -504,18 +547,26 @@ def synth_command(args):
     for b in range(0, int(args.count), bs):
         idx = list(range(b, min(b + bs, int(args.count))))
         which = [pick.randrange(len(ds)) for _ in idx]       # the script picks a clean image at random for every sample
-        cleans, logos, jobs, names = [], [], [], []
+        cleans, logos, jobs, planes, text_jobs, names = [], [], [], [], [], []
         for n, i in zip(idx, which):
             ds.set_epoch(n)                                   # sample n's draws: a function of (seed, n, clean image)
-            clean, lg, j = ds[i]
-            transparent = bool(ds.draw(i, (clean.shape[1], clean.shape[0]))[0])
+            clean = read_u8(ds.files[i], "RGB")
+            transparent, _, lg, j, kind, pl, tj = ds.draw_sample(i, (clean.shape[1], clean.shape[0]))
             j = np.array(j, copy=True); j["logo"] += len(logos)
-            cleans.append(clean); logos += list(lg); jobs.append(j)
+            tj = np.array(tj, copy=True); tj["glyph"] += len(planes)
+            cleans.append(clean); logos += list(lg); jobs.append(j); planes += [a[..., None] for a in pl]; text_jobs.append(tj)
             count = int((j["enabled"] != 0).sum())
-            names.append(f"{'multi_' if count > 1 else ''}{'trans' if transparent else 'norm'}_{n:06d}")
+            prefix = "multi_" if kind == "logo" and count > 1 else "" if kind == "logo" else kind + "_"
+            names.append(f"{prefix}{'trans' if transparent else 'norm'}_{n:06d}")
         pc, dc, _ = pack_images(cleans)
-        pl, dl, _ = pack_images(logos)
-        out, mask = device_synth(pc.to(device), dc, pl.to(device), dl, np.stack(jobs), with_mask=bool(args.generate_mask), inplace=True)
+        out, mask = pc.to(device), None
+        if logos:
+            pl, dl, _ = pack_images(logos)
+            out, mask = device_synth(out, dc, pl.to(device), dl, np.stack(jobs), with_mask=bool(args.generate_mask), inplace=True)
+        if planes:
+            pp, dp, _ = pack_images(planes)
+            out, mask = device_synth_text(out, dc, pp.to(device), dp, np.stack(text_jobs), inplace=True, mask_mode=1,
+                                          masks=(mask if mask is not None else True) if args.generate_mask else None)
         out = out.cpu().numpy()
         mask = mask.cpu().numpy() if mask is not None else None
         for name, clean, d, m in zip(names, cleans, dc, mask_descs_for(dc)):
@@ -699,13 +750,16 @@ def build_parser():
                     help="--synthesize: 'pair' (default) derives the mask from (synthesized, clean) as the reference's dataset does; 'alpha' "
                          "takes the pasted alpha planes, which the reference binarises at 127, so low-opacity samples get nearly empty masks")
     tp.add_argument("--synth-seed", type=int, default=42, help="--synthesize: seed of the draws")
-    sp = sub.add_parser("synth", help="write logo-watermarked samples (the logo branch of the reference's scripts/gen_data.py) made on the device")
-    sp.add_argument("--clean-dir", type=str, required=True); sp.add_argument("--logos-dir", type=str, required=True)
+    _add_text_arguments(tp, "--synthesize: ")
+    sp = sub.add_parser("synth", help="write logo-, text- and mixed-watermarked samples (the reference's scripts/gen_data.py) made on the device")
+    sp.add_argument("--clean-dir", type=str, required=True)
+    sp.add_argument("--logos-dir", type=str, default=None, help="directory of logos (required unless --text-watermark-ratio 1)")
     sp.add_argument("--output-dir", type=str, required=True); sp.add_argument("--count", type=int, required=True)
-    sp.add_argument("--generate-mask", action="store_true", help="also write the pasted alpha planes to masks/")
+    sp.add_argument("--generate-mask", action="store_true", help="also write the pasted alpha planes to masks/ (a mixed sample: the logos' plane halved, then the maximum with the text's)")
     sp.add_argument("--seed", type=int, default=42)
     sp.add_argument("--transparent-ratio", type=float, default=0.6); sp.add_argument("--multi-watermark-ratio", type=float, default=0.4)
     sp.add_argument("--max-watermarks", type=int, default=3); sp.add_argument("--batch-size", type=int, default=None)
+    _add_text_arguments(sp, "")
     mp = sub.add_parser("masks", help="derive masks/<stem>.png from watermarked / clean pairs on the device, for every pair without one")
     mp.add_argument("--data-dir", type=str, default=None, help="DATA.ROOT_DIR: the directory with watermarked/, clean/ and masks/")
     mp.add_argument("--config", type=str, default=None)

@@ -14,9 +14,8 @@ namespace uwm {
 
 namespace {
 
-constexpr int kB = kSynthBlocks;
-constexpr int kMaxSide = 32767;            // Pillow's affine_fixed holds below 32768; every product of two sides fits an int
-constexpr int kMaxBlurR = 32;
+#include "synth_stages.inc"
+
 enum { S_R1H = 0, S_R1V, S_ROT, S_R3H, S_R3V, S_SHEAR, S_BLUR0, S_FINISH = S_BLUR0 + 6, S_END };
 
 struct Plan {
@@ -26,13 +25,6 @@ struct Plan {
   bool run[S_END];
   int ks[4];                               // taps per output of the four LANCZOS tables (r1h, r1v, r3h, r3v)
 };
-
-__device__ __forceinline__ int lanczos_ksize(int in, int out) {
-  const double scale = (double)in / (double)out, fs = scale < 1.0 ? 1.0 : scale;
-  return (int)ceil(3.0 * fs) * 2 + 1;
-}
-
-__device__ __forceinline__ bool finite_small(double v) { return fabs(v) < 65536.0; }      // false for NaN
 
 // the one place that decides whether job j runs: true only if every read and write of every stage stays inside its buffer
 __device__ bool make_plan(const SynthJob& j, const ImageDesc* __restrict__ logo_descs, int num_logos, size_t logo_bytes, int P, int T, Plan& p) {
@@ -108,43 +100,7 @@ struct Args {
   const SynthJob* jobs; int J, P, T; void* ws;
 };
 
-// ---------------------------------------------------------------------------------------------- LANCZOS tables (Pillow's precompute_coeffs)
-__device__ __forceinline__ double sinc(double x) {
-  if (x == 0.0) return 1.0;
-  x = __dmul_rn(x, 3.14159265358979323846);
-  return sin(x) / x;
-}
-__device__ __forceinline__ double lanczos(double x) {
-  if (-3.0 <= x && x < 3.0) return __dmul_rn(sinc(x), sinc(x / 3.0));
-  return 0.0;
-}
-// row xx of the table in -> out: {xmin, xmax, ksize coefficients of 22 bits}; two passes over the taps, the sum in Pillow's order
-__device__ void lanczos_row(int in, int out, int ksize, int xx, int* __restrict__ row) {
-  const double scale = (double)in / (double)out, fs = scale < 1.0 ? 1.0 : scale;
-  const double support = __dmul_rn(3.0, fs), ss = 1.0 / fs;
-  const double center = __dmul_rn(__dadd_rn((double)xx, 0.5), scale);
-  int xmin = (int)__dadd_rn(__dadd_rn(center, -support), 0.5);
-  if (xmin < 0) xmin = 0;
-  int xmax = (int)__dadd_rn(__dadd_rn(center, support), 0.5);
-  if (xmax > in) xmax = in;
-  xmax -= xmin;
-  if (xmax > ksize) xmax = ksize;                      // (never by the arithmetic above; keeps the row inside its table whatever happens)
-  if (xmax < 0) xmax = 0;
-  double ww = 0.0;
-  for (int x = 0; x < xmax; ++x) ww = __dadd_rn(ww, lanczos(__dmul_rn(__dadd_rn(__dadd_rn((double)(x + xmin), -center), 0.5), ss)));
-  row[0] = xmin; row[1] = xmax;
-  for (int x = 0; x < ksize; ++x) {
-    int k = 0;
-    if (x < xmax) {
-      double w = lanczos(__dmul_rn(__dadd_rn(__dadd_rn((double)(x + xmin), -center), 0.5), ss));
-      if (ww != 0.0) w = w / ww;
-      const double v = __dmul_rn(w, 4194304.0);
-      k = w < 0 ? (int)__dadd_rn(v, -0.5) : (int)__dadd_rn(v, 0.5);
-    }
-    row[2 + x] = k;
-  }
-}
-
+// ---------------------------------------------------------------------------------------------- LANCZOS tables
 __global__ __launch_bounds__(256) void lanczos_table_kernel(int in, int out, int ksize, int* __restrict__ table) {
   const int xx = blockIdx.x * blockDim.x + threadIdx.x;
   if (xx < out) lanczos_row(in, out, ksize, xx, table + (size_t)xx * (ksize + 2));
@@ -161,15 +117,11 @@ __global__ __launch_bounds__(256) void synth_tables_kernel(Args a) {
     if (!p.run[s]) continue;
     const bool horiz = !(t & 1);
     const int in = horiz ? p.w[s] : p.h[s], out = horiz ? p.w[s + 1] : p.h[s + 1];
-    for (int xx = blk * 256 + threadIdx.x; xx < out; xx += kB * 256) lanczos_row(in, out, p.ks[t], xx, sl.tab[t] + (size_t)xx * (p.ks[t] + 2));
+    lanczos_rows(in, out, p.ks[t], sl.tab[t], blk);
   }
 }
 
 // ---------------------------------------------------------------------------------------------- stages 1 and 3a: one resample pass
-__device__ __forceinline__ int muldiv255(int x, int y) { const int t = x * y + 128; return ((t >> 8) + t) >> 8; }
-__device__ __forceinline__ int clip8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
-__device__ __forceinline__ uint32_t pack4(int r, int g, int b, int a) { return (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16) | ((uint32_t)a << 24); }
-
 __global__ __launch_bounds__(256) void synth_resample_kernel(Args a, int s) {
   const int job = blockIdx.x / kB, blk = blockIdx.x % kB;
   Plan p;
@@ -181,32 +133,10 @@ __global__ __launch_bounds__(256) void synth_resample_kernel(Args a, int s) {
   const bool unpremul = !horiz || !p.run[s + 1];       // the last one
   const uint32_t* __restrict__ src = stage_src(p, sl, a.logos, s);
   uint32_t* __restrict__ dst = stage_dst(p, sl, s);
-  const int sw = p.w[s], dw = p.w[s + 1], dh = p.h[s + 1], ks = p.ks[t];
-  const int* __restrict__ tab = sl.tab[t];
-  const int total = dw * dh;
-  for (int i = blk * 256 + threadIdx.x; i < total; i += kB * 256) {
-    const int y = i / dw, x = i - y * dw;
-    const int* __restrict__ row = tab + (size_t)(horiz ? x : y) * (ks + 2);
-    const int xmin = row[0], xmax = row[1];
-    int acc[4] = {1 << 21, 1 << 21, 1 << 21, 1 << 21};
-    for (int k = 0; k < xmax; ++k) {
-      const uint32_t v = horiz ? src[(size_t)y * sw + xmin + k] : src[(size_t)(xmin + k) * sw + x];
-      int c0 = v & 255, c1 = (v >> 8) & 255, c2 = (v >> 16) & 255;
-      const int c3 = v >> 24;
-      if (premul) { c0 = muldiv255(c0, c3); c1 = muldiv255(c1, c3); c2 = muldiv255(c2, c3); }
-      const int kk = row[2 + k];
-      acc[0] += c0 * kk; acc[1] += c1 * kk; acc[2] += c2 * kk; acc[3] += c3 * kk;
-    }
-    int r = clip8(acc[0] >> 22), g = clip8(acc[1] >> 22), b = clip8(acc[2] >> 22);
-    const int al = clip8(acc[3] >> 22);
-    if (unpremul && al != 0 && al != 255) { r = min(255, 255 * r / al); g = min(255, 255 * g / al); b = min(255, 255 * b / al); }
-    dst[i] = pack4(r, g, b, al);
-  }
+  resample_pass(src, dst, p.w[s], p.w[s + 1], p.h[s + 1], sl.tab[t], p.ks[t], horiz, premul, unpremul, blk);
 }
 
 // ---------------------------------------------------------------------------------------------- stage 2: Pillow's affine_fixed
-__device__ __forceinline__ long long fix16(double v) { return (long long)floor(__dadd_rn(__dmul_rn(v, 65536.0), 0.5)); }
-
 __global__ __launch_bounds__(256) void synth_rotate_kernel(Args a) {
   const int job = blockIdx.x / kB, blk = blockIdx.x % kB;
   const SynthJob& j = a.jobs[job];
@@ -215,16 +145,7 @@ __global__ __launch_bounds__(256) void synth_rotate_kernel(Args a) {
   const Slice sl = slice_of(a.ws, job, a.P, a.T);
   const uint32_t* __restrict__ src = stage_src(p, sl, a.logos, S_ROT);
   uint32_t* __restrict__ dst = stage_dst(p, sl, S_ROT);
-  const int sw = p.w[S_ROT], sh = p.h[S_ROT], dw = p.w[S_ROT + 1], dh = p.h[S_ROT + 1];
-  const long long a0 = fix16(j.rot[0]), a1 = fix16(j.rot[1]), a3 = fix16(j.rot[3]), a4 = fix16(j.rot[4]);
-  const long long a2 = fix16(__dadd_rn(__dadd_rn(j.rot[2], __dmul_rn(j.rot[0], 0.5)), __dmul_rn(j.rot[1], 0.5)));
-  const long long a5 = fix16(__dadd_rn(__dadd_rn(j.rot[5], __dmul_rn(j.rot[3], 0.5)), __dmul_rn(j.rot[4], 0.5)));
-  const int total = dw * dh;
-  for (int i = blk * 256 + threadIdx.x; i < total; i += kB * 256) {
-    const int y = i / dw, x = i - y * dw;
-    const long long xin = (a2 + a1 * y + a0 * x) >> 16, yin = (a5 + a4 * y + a3 * x) >> 16;
-    dst[i] = (xin >= 0 && xin < sw && yin >= 0 && yin < sh) ? src[(size_t)yin * sw + (size_t)xin] : 0u;
-  }
+  rotate_pass(src, dst, p.w[S_ROT], p.h[S_ROT], p.w[S_ROT + 1], p.h[S_ROT + 1], j.rot, blk);
 }
 
 // ---------------------------------------------------------------------------------------------- stage 3b: shear (restated; NOT run against cv2)
@@ -271,40 +192,10 @@ __global__ __launch_bounds__(256) void synth_blur_kernel(Args a, int pass) {
   const Slice sl = slice_of(a.ws, job, a.P, a.T);
   const uint32_t* __restrict__ src = stage_src(p, sl, a.logos, s);
   uint32_t* __restrict__ dst = stage_dst(p, sl, s);
-  const int w = p.w[s], h = p.h[s], R = j.blur_r;
-  const bool horiz = pass < 3;
-  const int n = horiz ? w : h, step = horiz ? 1 : w;
-  const unsigned long long ww = j.blur_ww, fw = j.blur_fw;
-  const int total = w * h;
-  for (int i = blk * 256 + threadIdx.x; i < total; i += kB * 256) {
-    const int y = i / w, x = i - y * w;
-    const int pos = horiz ? x : y;
-    const uint32_t* __restrict__ line = src + (horiz ? (size_t)y * w : (size_t)x);
-    unsigned acc[4] = {0u, 0u, 0u, 0u};
-    for (int d = -R; d <= R; ++d) {
-      const uint32_t v = line[(size_t)min(max(pos + d, 0), n - 1) * step];
-      acc[0] += v & 255; acc[1] += (v >> 8) & 255; acc[2] += (v >> 16) & 255; acc[3] += v >> 24;
-    }
-    const uint32_t lo = line[(size_t)min(max(pos - R - 1, 0), n - 1) * step], hi = line[(size_t)min(max(pos + R + 1, 0), n - 1) * step];
-    uint32_t out = 0u;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const unsigned far = ((lo >> (8 * c)) & 255) + ((hi >> (8 * c)) & 255);
-      out |= (uint32_t)(((ww * acc[c] + fw * far + (1ull << 23)) >> 24) & 255ull) << (8 * c);
-    }
-    dst[i] = out;
-  }
+  blur_pass(src, dst, p.w[s], p.h[s], j.blur_r, j.blur_ww, j.blur_fw, pass < 3, blk);
 }
 
 // ---------------------------------------------------------------------------------------------- stages 5-7
-// Image.blend(degenerate, image, f) on one channel value, in float32 with every rounding spelt out
-__device__ __forceinline__ int blend8(int d, int v, float f) {
-  const float t = __fadd_rn((float)d, __fmul_rn(f, __fsub_rn((float)v, (float)d)));
-  if (f >= 0.f && f <= 1.f) return (int)t & 255;
-  return t <= 0.f ? 0 : t >= 255.f ? 255 : (int)t;
-}
-__device__ __forceinline__ int luma8(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }
-
 // per-workgroup partial sums of L over the brightened patch (the Contrast degenerate is their mean); integer sums: any order, one result
 __global__ __launch_bounds__(256) void synth_luma_kernel(Args a) {
   __shared__ long long red[256];
@@ -314,20 +205,7 @@ __global__ __launch_bounds__(256) void synth_luma_kernel(Args a) {
   if (!make_plan(j, a.logo_descs, a.num_logos, a.logo_bytes, a.P, a.T, p) || !j.enhance) return;      // uniform over the workgroup
   const Slice sl = slice_of(a.ws, job, a.P, a.T);
   const uint32_t* __restrict__ src = stage_src(p, sl, a.logos, S_FINISH);
-  const int total = p.w[S_FINISH] * p.h[S_FINISH];
-  const float fb = j.brightness;
-  long long sum = 0;
-  for (int i = blk * 256 + threadIdx.x; i < total; i += kB * 256) {
-    const uint32_t v = src[i];
-    sum += luma8(blend8(0, v & 255, fb), blend8(0, (v >> 8) & 255, fb), blend8(0, (v >> 16) & 255, fb));
-  }
-  red[threadIdx.x] = sum;
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) sl.part[blk] = red[0];
+  luma_partial(src, p.w[S_FINISH] * p.h[S_FINISH], j.brightness, blk, red, sl.part + blk);
 }
 
 __global__ __launch_bounds__(256) void synth_finish_kernel(Args a) {
@@ -339,12 +217,7 @@ __global__ __launch_bounds__(256) void synth_finish_kernel(Args a) {
   const uint32_t* __restrict__ src = stage_src(p, sl, a.logos, S_FINISH);
   uint32_t* __restrict__ dst = stage_dst(p, sl, S_FINISH);
   const int w = p.w[S_FINISH], total = w * p.h[S_FINISH];
-  int mean = 0;
-  if (j.enhance) {
-    long long sum = 0;
-    for (int b = 0; b < kB; ++b) sum += sl.part[b];
-    mean = (int)__dadd_rn((double)sum / (double)total, 0.5);
-  }
+  const int mean = j.enhance ? luma_mean(sl.part, total) : 0;
   const float fb = j.brightness, fc = j.contrast, fs = j.color;
   for (int i = blk * 256 + threadIdx.x; i < total; i += kB * 256) {
     const int y = i / w, x = i - y * w;
@@ -364,8 +237,6 @@ __global__ __launch_bounds__(256) void synth_finish_kernel(Args a) {
 
 // ---------------------------------------------------------------------------------------------- stage 8: paste, one thread per IMAGE pixel
 // A pixel's thread applies the slots that cover it in slot order, so overlapping logos need no ordering between workgroups.
-__device__ __forceinline__ int blend255(int src, int dst, int al) { const int t = src * al + dst * (255 - al) + 128; return ((t >> 8) + t) >> 8; }
-
 __global__ __launch_bounds__(256) void synth_paste_kernel(Args a, int K, uint8_t* __restrict__ images, size_t image_bytes, const ImageDesc* __restrict__ image_descs,
                                                           uint8_t* __restrict__ masks, size_t mask_bytes, const ImageDesc* __restrict__ mask_descs) {
   __shared__ const uint32_t* patch[kSynthMaxSlots];
@@ -382,15 +253,12 @@ __global__ __launch_bounds__(256) void synth_paste_kernel(Args a, int K, uint8_t
   }
   __syncthreads();
   const ImageDesc d = image_descs[n];
-  if (d.h < 1 || d.w < 1 || d.h > kMaxSide || d.w > kMaxSide || d.offset < 0 || (unsigned long long)d.offset > image_bytes ||
-      (unsigned long long)d.h * d.w > (image_bytes - (unsigned long long)d.offset) / 3)
-    return;
+  if (!rgb_desc_ok(d, image_bytes)) return;
   bool with_mask = masks != nullptr;
   ImageDesc md = d;
   if (with_mask) {
     md = mask_descs[n];
-    with_mask = md.h == d.h && md.w == d.w && md.offset >= 0 && (unsigned long long)md.offset <= mask_bytes &&
-                (unsigned long long)md.h * md.w <= mask_bytes - (unsigned long long)md.offset;
+    with_mask = mask_desc_ok(md, d, mask_bytes);
   }
   uint8_t* __restrict__ img = images + d.offset;
   uint8_t* __restrict__ msk = with_mask ? masks + md.offset : nullptr;

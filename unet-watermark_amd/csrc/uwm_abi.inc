@@ -356,6 +356,56 @@ int uwm_op_lanczos_table(int in, int out, int* table, size_t table_ints, uwm_str
   LCHK(launch_lanczos_table(in, out, table, (hipStream_t)stream));
   return 0;
 }
+// ---- text-watermarked training samples (synth_text_u8.hip): checked as the logo entries are
+static_assert(sizeof(uwm_text_job) == sizeof(TextJob) && sizeof(uwm_text_job) == 416 && offsetof(uwm_text_job, rot) == 112 &&
+              offsetof(uwm_text_job, opacity) == offsetof(TextJob, opacity) && offsetof(uwm_text_job, x) == offsetof(TextJob, x) &&
+              offsetof(uwm_text_job, fit) == offsetof(TextJob, fit), "uwm_text_job layout");
+size_t uwm_synth_text_workspace_bytes(int N, int K, long long max_patch_pixels, long long max_taps) {
+  const size_t b = synth_text_workspace_bytes(N, K, max_patch_pixels, max_taps);
+  if (!b) (void)fail("uwm_synth_text_workspace_bytes: need N >= 1, K in 1..%d, max_patch_pixels in 1..%lld, max_taps in 1..%lld and N * K * %d within "
+                     "one launch (got %d, %d, %lld, %lld)", kSynthMaxSlots, kSynthMaxPatchPixels, kSynthMaxTaps, kSynthBlocks, N, K, max_patch_pixels, max_taps);
+  return b;
+}
+static int text_args_check(const char* fn, const void* planes, size_t plane_bytes, const void* plane_descs, int num_planes, const void* jobs, int N,
+                           int K, long long P, long long T, const void* ws, size_t ws_bytes) {
+  if (!planes || !plane_descs || !jobs || !ws) return fail("%s: null argument", fn);
+  if (num_planes < 1 || plane_bytes < 1) return fail("%s: num_planes and plane_bytes must be >= 1 (got %d, %zu)", fn, num_planes, plane_bytes);
+  const size_t need = synth_text_workspace_bytes(N, K, P, T);
+  if (!need) return fail("%s: need N >= 1, K in 1..%d, max_patch_pixels in 1..%lld, max_taps in 1..%lld and N * K * %d within one launch (got %d, %d, %lld, "
+                         "%lld)", fn, kSynthMaxSlots, kSynthMaxPatchPixels, kSynthMaxTaps, kSynthBlocks, N, K, P, T);
+  if (ws_bytes < need) return fail("%s: workspace of %zu bytes, need %zu (uwm_synth_text_workspace_bytes)", fn, ws_bytes, need);
+  if ((uintptr_t)planes & 3) return fail("%s: planes must be 4-byte aligned", fn);
+  if (((uintptr_t)plane_descs | (uintptr_t)jobs | (uintptr_t)ws) & 7) return fail("%s: descriptors, jobs and workspace must be 8-byte aligned", fn);
+  return 0;
+}
+int uwm_synth_text_u8(uint8_t* images, size_t image_bytes, const uwm_image_desc* image_descs, uint8_t* masks, size_t mask_bytes,
+                      const uwm_image_desc* mask_descs, int mask_mode, const uint8_t* planes, size_t plane_bytes,
+                      const uwm_image_desc* plane_descs, int num_planes, const uwm_text_job* jobs, int N, int K, long long max_patch_pixels,
+                      long long max_taps, void* ws, size_t ws_bytes, uwm_stream stream) {
+  if (!images || !image_descs) return fail("uwm_synth_text_u8: null argument");
+  if (text_args_check("uwm_synth_text_u8", planes, plane_bytes, plane_descs, num_planes, jobs, N, K, max_patch_pixels, max_taps, ws, ws_bytes)) return 1;
+  if (image_bytes < 1) return fail("uwm_synth_text_u8: image_bytes must be >= 1");
+  if ((uintptr_t)image_descs & 7) return fail("uwm_synth_text_u8: descriptors must be 8-byte aligned");
+  if (mask_mode != 0 && mask_mode != 1) return fail("uwm_synth_text_u8: mask_mode must be 0 (paste) or 1 (mixed) (got %d)", mask_mode);
+  if (masks && (!mask_descs || mask_bytes < 1 || ((uintptr_t)mask_descs & 7)))
+    return fail("uwm_synth_text_u8: masks need mask_descs (8-byte aligned) and mask_bytes >= 1");
+  LCHK(launch_synth_text_u8(images, image_bytes, (const ImageDesc*)image_descs, masks, mask_bytes, (const ImageDesc*)mask_descs, mask_mode, planes,
+                            plane_bytes, (const ImageDesc*)plane_descs, num_planes, (const TextJob*)jobs, N, K, max_patch_pixels, max_taps, ws,
+                            ws_bytes, (hipStream_t)stream));
+  return 0;
+}
+int uwm_op_text_patches(const uint8_t* planes, size_t plane_bytes, const uwm_image_desc* plane_descs, int num_planes, const uwm_text_job* jobs, int J,
+                        long long max_patch_pixels, long long max_taps, void* ws, size_t ws_bytes, uint8_t* out, size_t out_bytes,
+                        uwm_stream stream) {
+  if (!out) return fail("uwm_op_text_patches: null argument");
+  if (text_args_check("uwm_op_text_patches", planes, plane_bytes, plane_descs, num_planes, jobs, J, 1, max_patch_pixels, max_taps, ws, ws_bytes)) return 1;
+  if ((uintptr_t)out & 3) return fail("uwm_op_text_patches: out must be 4-byte aligned");
+  if (out_bytes / 4 / (size_t)max_patch_pixels < (size_t)J)
+    return fail("uwm_op_text_patches: out of %zu bytes, need J * max_patch_pixels * 4 = %zu", out_bytes, (size_t)J * (size_t)max_patch_pixels * 4);
+  LCHK(launch_text_patches(planes, plane_bytes, (const ImageDesc*)plane_descs, num_planes, (const TextJob*)jobs, J, max_patch_pixels, max_taps, ws,
+                           ws_bytes, out, out_bytes, (hipStream_t)stream));
+  return 0;
+}
 int uwm_predict_images_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, const uwm_image_desc* in_descs, const float* mean,
                           const float* std, float threshold, int apply_sigmoid, const uwm_image_desc* out_descs, uint8_t* mask,
                           size_t mask_bytes, float* logits, void* ws, size_t ws_bytes, int N, int H, int W, uwm_stream stream) {

@@ -529,6 +529,28 @@ hipError_t launch_synth_u8(uint8_t* images, size_t image_bytes, const ImageDesc*
 hipError_t launch_synth_patches(const uint8_t* logos, size_t logo_bytes, const ImageDesc* logo_descs, int num_logos, const SynthJob* jobs, int J,
                                 long long max_patch_pixels, long long max_taps, void* ws, size_t ws_bytes, uint8_t* out, size_t out_bytes,
                                 hipStream_t st);
+// ---- text-watermarked training samples (synth_text_u8.hip; the rule: include/uwm.h).  K, the workgroups per job and the
+// capacities are the logo chain's
+struct TextJob {                                     // = uwm_text_job: one per (image, slot), in DEVICE memory
+  int enabled, glyph, ink[3], rotate, w2, h2, scale, w3, h3, blur, blur_r;
+  unsigned blur_ww, blur_fw;
+  int brighten, recontrast;
+  float brightness, contrast;
+  int nfit, fit[3][2], x, y;
+  double rot[6];
+  uint8_t opacity[256];
+};
+size_t synth_text_workspace_bytes(int N, int K, long long max_patch_pixels, long long max_taps);      // 0 for arguments out of range
+// stages A-H of every job, in place on the ragged RGB batch; masks (may be nullptr) follow mask_mode (0: paste over the plane, 1: the
+// mixed rule).  No read leaves the inputs, no write leaves [images, +image_bytes), [masks, +mask_bytes) or the workspace
+hipError_t launch_synth_text_u8(uint8_t* images, size_t image_bytes, const ImageDesc* image_descs, uint8_t* masks, size_t mask_bytes,
+                                const ImageDesc* mask_descs, int mask_mode, const uint8_t* planes, size_t plane_bytes,
+                                const ImageDesc* plane_descs, int num_planes, const TextJob* jobs, int N, int K, long long max_patch_pixels,
+                                long long max_taps, void* ws, size_t ws_bytes, hipStream_t st);
+// stages A-G only: job j's finished RGBA patch -> out + j * max_patch_pixels * 4 (a job that is off or does not fit writes nothing)
+hipError_t launch_text_patches(const uint8_t* planes, size_t plane_bytes, const ImageDesc* plane_descs, int num_planes, const TextJob* jobs, int J,
+                               long long max_patch_pixels, long long max_taps, void* ws, size_t ws_bytes, uint8_t* out, size_t out_bytes,
+                               hipStream_t st);
 
 // EfficientNet MBConv pieces (mbconv.hip): swish, depthwise k x k conv (weights tap-major [k*k][C]) with static "same"
 // padding (pb = pad at the begin of H and W; the end pad is implied by Ho/Wo), squeeze-and-excitation, block output with drop-connect

@@ -6,7 +6,8 @@ reference's basic and enhanced albumentations recipes run on the device (augment
 baseline JPEG round trip on the device (device_jpeg, sample_transparent_recipe; `--augment config --jpeg device`).
 Images of any size travel as one packed buffer (ragged).  An image without a mask file gets the mask the reference derives from its
 clean counterpart, also on the device (pairmask: device_pair_mask; RawPairDataset), and logo-watermarked samples are
-synthesized there (synth: device_synth; RawSynthDataset).
+synthesized there (synth: device_synth; RawSynthDataset; DESIGN.md §8i), as are text and mixed ones (synthtext: device_synth_text;
+DESIGN.md §8o).
 Every name is used as data.NAME; the modules below say where it lives."""
 from __future__ import annotations
 
@@ -30,6 +31,9 @@ from .pairmask import device_pair_mask, stage_clean  # noqa: F401
 from .synth import (SYNTH_JOB_DTYPE, SYNTH_MAX_SIDE, SYNTH_MAX_SLOTS, SYNTH_SLOTS, _overlap_area, _plain_job, _sample_effects,  # noqa: F401
                     device_synth, empty_synth_jobs, sample_synth_choice, sample_synth_jobs, synth_blur_params, synth_job_needs,
                     synth_opacity_lut, synth_rotate_setup, synth_shear_inverse)
+from .synthtext import (DEFAULT_TEXTS, SYNTH_KINDS, TEXT_INKS, TEXT_JOB_DTYPE, TEXT_MARGIN, FontSet, device_synth_text,  # noqa: F401
+                        empty_text_jobs, has_cjk, load_texts, render_text_plane, require_freetype, sample_font_size, sample_synth_kind,
+                        sample_text, sample_text_item, sample_text_job, text_job_final_size, text_job_needs)
 from .datasets import (LOGO_EXTENSIONS, LOGO_SUBDIRS, PAIR_IMAGE_EXTENSIONS, DeviceU8Dataset, FolderDataset, RawFolderDataset,  # noqa: F401
                        RawPairDataset, RawSynthDataset, SyntheticWatermarkDataset, list_collate, list_logos)
 from .pipeline import DeviceInputPipeline  # noqa: F401

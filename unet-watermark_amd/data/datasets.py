@@ -10,6 +10,7 @@ from torch.utils.data import Dataset
 
 from ..constants import IMAGENET_MEAN, IMAGENET_STD
 from .synth import SYNTH_SLOTS, sample_synth_choice, sample_synth_jobs
+from .synthtext import FontSet, empty_text_jobs, load_texts, sample_synth_kind, sample_text_item
 
 FOLDER_IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg")                             # FolderDataset / RawFolderDataset
 PAIR_IMAGE_EXTENSIONS = (".jpg", ".jpeg", ".png", ".bmp", ".tiff", ".tif")      # the reference's _collect_image_files
@@ -190,16 +191,26 @@ class RawSynthDataset(Dataset):
     (sample_synth_choice, sample_synth_jobs); DeviceInputPipeline pastes the logos with uwm_synth_u8 and derives the masks.  The
     draws of item i are a function of (seed, epoch, i): set_epoch(e) before an epoch's loader is made gives that epoch new samples,
     and a dataset that is never told the epoch (a validation split) reproduces its samples every time.  Decoded logos are kept in a
-    per-process LRU of `cache` entries."""
+    per-process LRU of `cache` entries.
+
+    text_watermark_ratio / mixed_watermark_ratio (the reference's defaults are 0.3 / 0.2; 0 / 0 here, so that a dataset made without
+    them yields what it always has): the shares of samples that carry a text, or one or two logos and a text (sample_synth_kind).
+    With either above 0 an item is (clean, logos, jobs, planes, text_jobs): planes a list of at most one uint8 (ch, cw) coverage
+    plane that the worker rasterised (render_text_plane; fonts of fonts_dir or Pillow's embedded one, texts of texts_file or
+    DEFAULT_TEXTS), text_jobs [1] of TEXT_JOB_DTYPE; a text sample has no logo job, a logo sample no text job.  With both 0 nothing
+    more is drawn and items are the three-tuples above.  Not served: the temporary JPEG quality-95 file the script writes between the
+    logos and the text of a mixed sample."""
 
     def __init__(self, clean_dir, logos_dir, seed=42, transparent_ratio=0.6, multi_watermark_ratio=0.4, max_watermarks=3,
-                 mask_threshold=None, mask_source="pair", cache=64):
+                 mask_threshold=None, mask_source="pair", cache=64, text_watermark_ratio=0.0, mixed_watermark_ratio=0.0, fonts_dir=None,
+                 texts_file=None):
         from PIL import Image  # noqa: F401
+        self.text_ratio, self.mixed_ratio = check_synth_ratios(text_watermark_ratio, mixed_watermark_ratio)
         if not os.path.isdir(clean_dir):
             raise ValueError(f"RawSynthDataset: clean directory not found: {clean_dir}")
         self.files = list_files(clean_dir, LOGO_EXTENSIONS)
-        self.logos = list_logos(logos_dir)
-        if not self.files or not self.logos:
+        self.logos = list_logos(logos_dir) if logos_dir is not None else []
+        if not self.files or (not self.logos and self.text_ratio < 1):
             raise ValueError(f"RawSynthDataset: {len(self.files)} clean images in {clean_dir}, {len(self.logos)} logos in {logos_dir}: need both")
         if not 1 <= int(max_watermarks) <= SYNTH_SLOTS:
             raise ValueError(f"RawSynthDataset: max_watermarks must be 1..{SYNTH_SLOTS} (got {max_watermarks})")
@@ -210,6 +221,9 @@ class RawSynthDataset(Dataset):
         self.max_watermarks, self.mask_threshold, self.mask_source = int(max_watermarks), mask_threshold, mask_source
         self.cache = int(cache)
         self._lru = {}
+        self.with_text = self.text_ratio > 0 or self.mixed_ratio > 0
+        if self.with_text:                                   # refused here, before any device work, where freetype is missing
+            self.fonts, self.texts = FontSet(fonts_dir), load_texts(texts_file)
 
     def __len__(self):
         return len(self.files)
@@ -228,17 +242,39 @@ class RawSynthDataset(Dataset):
 
     def draw(self, i, image_size):
         """-> (enhance_transparent, logo indices, decoded logos, jobs) of item i at this epoch"""
+        return self.draw_sample(i, image_size)[:4]
+
+    def draw_sample(self, i, image_size):
+        """-> (enhance_transparent, logo indices, decoded logos, jobs, kind, planes, text_jobs) of item i at this epoch, in main()'s
+        order: transparency, the watermark type, then the type's own draws (mixed: the logos with max_watermarks 2, then the text)"""
         import random
         rng = random.Random(f"uwm-synth:{self.seed}:{self.epoch}:{int(i)}")
-        transparent, picked = sample_synth_choice(rng, len(self.logos), self.transparent_ratio, self.multi_watermark_ratio, self.max_watermarks)
+        transparent = rng.random() < self.transparent_ratio
+        kind = sample_synth_kind(rng, self.text_ratio, self.mixed_ratio)
+        picked = []
+        if kind != "text":
+            picked = sample_synth_choice(rng, len(self.logos), self.transparent_ratio, self.multi_watermark_ratio,
+                                         self.max_watermarks if kind == "logo" else min(2, self.max_watermarks), transparent=transparent)[1]
         logos = [self._logo(k) for k in picked]
         jobs = sample_synth_jobs(rng, image_size, [(a.shape[1], a.shape[0]) for a in logos], transparent)
-        return transparent, picked, logos, jobs
+        planes, text_jobs = [], empty_text_jobs(1)
+        if kind != "logo":
+            plane, text_jobs[0] = sample_text_item(rng, image_size, self.texts, self.fonts, transparent)
+            planes = [plane]
+        return transparent, picked, logos, jobs, kind, planes, text_jobs
 
     def __getitem__(self, i):
         clean = read_u8(self.files[i], "RGB")
-        _, _, logos, jobs = self.draw(i, (clean.shape[1], clean.shape[0]))
-        return clean, logos, jobs
+        _, _, logos, jobs, _, planes, text_jobs = self.draw_sample(i, (clean.shape[1], clean.shape[0]))
+        return (clean, logos, jobs, planes, text_jobs) if self.with_text else (clean, logos, jobs)
+
+
+def check_synth_ratios(text_ratio, mixed_ratio):
+    """-> the two ratios as floats; ValueError unless each is in [0, 1] and their sum at most 1"""
+    t, m = float(text_ratio), float(mixed_ratio)
+    if not (0.0 <= t <= 1.0 and 0.0 <= m <= 1.0) or t + m > 1.0:
+        raise ValueError(f"text_watermark_ratio and mixed_watermark_ratio must each be in [0, 1] and sum to at most 1 (got {text_ratio}, {mixed_ratio})")
+    return t, m
 
 
 def list_collate(batch):

@@ -8,6 +8,7 @@ from .datasets import DeviceU8Dataset, RawSynthDataset
 from .pairmask import device_pair_mask, stage_clean
 from .ragged import device_resize, mask_descs_for, pack_images
 from .synth import device_synth
+from .synthtext import device_synth_text
 
 
 class DeviceInputPipeline:
@@ -68,23 +69,38 @@ class DeviceInputPipeline:
         return x, m.view(len(items), self.size, self.size)
 
     def _synth_u8(self, items):
-        """RawSynthDataset items (clean, logos, jobs): upload the clean images and the logos the batch uses, paste the logos into a copy
-        of the clean batch (uwm_synth_u8), take the masks from (synthesized, clean) with uwm_pair_mask_u8 — the reference's default
-        flow, gen_data.py writes no masks unless asked — or, mask_source 'alpha', from the pasted alpha planes; then resize as ever"""
+        """RawSynthDataset items (clean, logos, jobs[, planes, text_jobs]): upload the clean images and the logos the batch uses, paste
+        the logos into a copy of the clean batch (uwm_synth_u8), then — only where the dataset makes text or mixed samples — upload the
+        coverage planes and paste the texts (uwm_synth_text_u8); take the masks from (synthesized, clean) with uwm_pair_mask_u8 — the
+        reference's default flow, gen_data.py writes no masks unless asked — or, mask_source 'alpha', from the pasted alpha planes
+        (mixed samples by the script's rule: the logos' plane halved, then the maximum with the text's); then resize as ever.  A
+        dataset with both ratios 0 yields three-tuples, and this path then launches exactly what it did without text synthesis."""
         cleans = [np.ascontiguousarray(it[0]) for it in items]
-        logos, jobs = [], []
+        logos, jobs, planes, text_jobs = [], [], [], []
         for it in items:
             j = np.array(it[2], copy=True)
             j["logo"] += len(logos)                              # item-local logo index -> index into the batch's logos
             logos += [np.ascontiguousarray(a) for a in it[1]]
             jobs.append(j)
+            if len(it) > 3:
+                t = np.array(it[4], copy=True)
+                t["glyph"] += len(planes)
+                planes += [np.ascontiguousarray(a)[..., None] for a in it[3]]
+                text_jobs.append(t)
         alpha = self.source.mask_source == "alpha"
         if not alpha and self.mask_threshold is None:
             raise ValueError("synthesized samples with masks from pairs need mask_threshold (DATA.GENERATE_MASK_THRESHOLD)")
         with torch.cuda.device(self.device):
             pc, dc = self._upload(cleans, 0)
-            pl, dl = self._upload(logos, 2)
-            synth, pm = device_synth(pc, dc, pl, dl, np.stack(jobs), with_mask=alpha)
+            if logos:
+                pl, dl = self._upload(logos, 2)
+                synth, pm = device_synth(pc, dc, pl, dl, np.stack(jobs), with_mask=alpha)
+            else:                                                # a batch of text samples only
+                synth = pc.clone()
+                pm = torch.zeros(sum(a.shape[0] * a.shape[1] for a in cleans), dtype=torch.uint8, device=self.device) if alpha else None
+            if planes:
+                pp, dp = self._upload(planes, 1)
+                synth, pm = device_synth_text(synth, dc, pp, dp, np.stack(text_jobs), masks=pm, mask_mode=1, inplace=True)
             if not alpha:
                 pm = device_pair_mask(synth, dc, pc, dc, self.mask_threshold)
             x = device_resize(synth, dc, self.size, 3, "linear")

@@ -184,11 +184,13 @@ def sample_synth_jobs(rng, image_size, logo_sizes, enhance_transparent=True, slo
     return jobs
 
 
-def sample_synth_choice(rng, num_logos, transparent_ratio=0.6, multi_watermark_ratio=0.4, max_watermarks=3):
+def sample_synth_choice(rng, num_logos, transparent_ratio=0.6, multi_watermark_ratio=0.4, max_watermarks=3, transparent=None):
     """gen_data.py main()'s choices for one sample, logo branch only -> (enhance_transparent, [indices of the logos to paste]).  One
     departure: main() also makes the first count*ratio samples transparent whatever the draw; that quota needs the run's state, so
-    here the draw alone decides."""
-    transparent = rng.random() < transparent_ratio
+    here the draw alone decides.  transparent: that draw's result when the caller has made it already (main() makes it in front of
+    the watermark-type draw, data.sample_synth_kind); it is then not made again."""
+    if transparent is None:
+        transparent = rng.random() < transparent_ratio
     single = rng.randrange(num_logos)
     if rng.random() < multi_watermark_ratio and num_logos > 1 and max_watermarks >= 2:
         chosen = rng.sample(range(num_logos), min(rng.randint(2, max_watermarks), num_logos))
