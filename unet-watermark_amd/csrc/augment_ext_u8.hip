@@ -106,22 +106,10 @@ __device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
 __device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
 __device__ __forceinline__ float sub_rn(float a, float b) { return a - b; }
 
-// ---- device helpers (reflect101 and div_rne as in augment_u8.hip)
-__device__ __forceinline__ int ext_reflect101(int c, int n) {
-  if ((unsigned)c < (unsigned)n) return c;
-  if (n == 1) return 0;
-  const int p = 2 * (n - 1);
-  int m = c % p;
-  if (m < 0) m += p;
-  return m < n ? m : p - m;
-}
-__device__ __forceinline__ int ext_div_rne(int a, int b) {
-  int q = a / b;
-  const int r2 = 2 * (a - q * b);
-  if (r2 > b || (r2 == b && (q & 1))) ++q;
-  return q;
-}
-__device__ __forceinline__ int clamp255(int v) { return min(max(v, 0), 255); }
+// ---- device helpers
+namespace {
+#include "image_common.inc"
+}  // namespace
 
 // lightness, the project's own integer rule: sRGB -> linear -> XYZ over the white point (rows sum to 4096) -> f()
 __device__ __forceinline__ void lab_f(int r, int g, int b, int& fx, int& fy, int& fz) {
@@ -153,15 +141,6 @@ __device__ __forceinline__ unsigned long long hash64(unsigned long long seed, un
 }
 
 struct ExtGeom { int th, tw; float inv_th, inv_tw, lut_scale; };      // CLAHE tile size, 1.0f / each, 255.0f / area: host float32 divisions
-
-// CLAHE's axis: y -> (tile, next tile, weight of the next); every operation rounded on its own
-__device__ __forceinline__ void clahe_axis(int y, float inv, int& t1, int& t2, float& a) {
-  const float f = sub_rn(mul_rn((float)y, inv), 0.5f), fl = floorf(f);
-  a = sub_rn(f, fl);
-  const int i = (int)fl;
-  t1 = min(max(i, 0), 7);
-  t2 = min(max(i + 1, 0), 7);
-}
 
 // The pre-blur value of pixel (y, x): stage byte -> tone -> noise.  tone: 0 none, 1 CLAHE (C = 1 or 3 only), 2 table.
 template <int C>
@@ -224,7 +203,7 @@ __global__ __launch_bounds__(256) void augment_ext_hist_kernel(const uint8_t* __
   const int y0 = (tile >> 3) * gm.th, x0 = (tile & 7) * gm.tw, area = gm.th * gm.tw;
   for (int i = t; i < area; i += 256) {
     const int dy = i / gm.tw, dx = i - dy * gm.tw;
-    const uint8_t* p = simg + ((size_t)ext_reflect101(y0 + dy, H) * W + ext_reflect101(x0 + dx, W)) * C;
+    const uint8_t* p = simg + ((size_t)reflect101(y0 + dy, H) * W + reflect101(x0 + dx, W)) * C;
     int l = p[0];
     if (C == 3) { int fx, fy, fz; lab_f(p[0], p[C > 1 ? 1 : 0], p[C > 2 ? 2 : 0], fx, fy, fz); l = lab_l8(fy); }
     atomicAdd(&hist[l], 1);
@@ -299,17 +278,17 @@ __global__ __launch_bounds__(256) void augment_ext_apply_kernel(const uint8_t* _
 #pragma unroll
         for (int c = 0; c < C; ++c) acc[c] = 0;
         for (int i = 0; i < 3; ++i) {
-          const int yy = ext_reflect101(y + i - 1, H);
+          const int yy = reflect101(y + i - 1, H);
           for (int j = 0; j < 3; ++j) {
             const int w = s_w[3 * i + j];
             if (w == 0) continue;                                          // uniform
-            ext_value<C>(simg, W, yy, ext_reflect101(x + j - 1, W), tone, lut2, luts_n, gm, sigma, seed, v);
+            ext_value<C>(simg, W, yy, reflect101(x + j - 1, W), tone, lut2, luts_n, gm, sigma, seed, v);
 #pragma unroll
             for (int c = 0; c < C; ++c) acc[c] += w * v[c];
           }
         }
 #pragma unroll
-        for (int c = 0; c < C; ++c) v[c] = blur == 2 ? (acc[c] + 8) >> 4 : ext_div_rne(acc[c], wsum);
+        for (int c = 0; c < C; ++c) v[c] = blur == 2 ? (acc[c] + 8) >> 4 : div_rne(acc[c], wsum);
       }
       const size_t pix = (size_t)y * W + x;
 #pragma unroll

@@ -11,6 +11,10 @@
 
 namespace uwm {
 
+namespace {
+#include "image_common.inc"
+}  // namespace
+
 constexpr int kAugRows = 4;                 // output rows of one workgroup: grid = N * ceil(H / kAugRows)
 constexpr double kAugCoordMax = 1073739776.0;      // 2^30 - 2048: two clamped terms and the rounding offset still add up inside int32
 
@@ -22,23 +26,6 @@ __device__ __forceinline__ int fix10(double v) {
 // coordinates, and only for some matrices)
 __device__ __forceinline__ int fix10_mul(double a, int x) { return fix10(__dmul_rn(a, (double)x)); }
 __device__ __forceinline__ int fix10_mad(double a, int y, double b) { return fix10(__dadd_rn(__dmul_rn(a, (double)y), b)); }
-
-// BORDER_REFLECT_101 of ANY coordinate into [0, n): period 2(n - 1); n = 1 -> 0
-__device__ __forceinline__ int reflect101(int c, int n) {
-  if ((unsigned)c < (unsigned)n) return c;
-  if (n == 1) return 0;
-  const int p = 2 * (n - 1);
-  int m = c % p;
-  if (m < 0) m += p;
-  return m < n ? m : p - m;
-}
-// a / b rounded half to even, a >= 0, b > 0
-__device__ __forceinline__ int div_rne(int a, int b) {
-  int q = a / b;
-  const int r2 = 2 * (a - q * b);
-  if (r2 > b || (r2 == b && (q & 1))) ++q;
-  return q;
-}
 
 // OpenCV's 8-bit RGB -> HSV (H in 0..179), the three shifts, and the project's integer way back (include/uwm.h)
 __device__ __forceinline__ void hsv_shift(int& r, int& g, int& b, int hue, int sat, int val, const int* __restrict__ sdiv,

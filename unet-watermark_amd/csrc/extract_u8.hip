@@ -20,6 +20,8 @@ typedef unsigned long long u64;
 
 namespace {
 
+#include "image_common.inc"
+
 constexpr int kT = 256;
 constexpr int kKept = kExtractMaxRegions;        // 254
 constexpr int kRow = kExtractRowInts;            // 9
@@ -40,8 +42,6 @@ struct XWs {
   unsigned* acc;
 };
 
-size_t rup256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct XLayout { size_t ctr, list, a, b, lab, acc, total; };
 XLayout x_layout(int N, long long total_pixels) {
   XLayout l;
@@ -60,12 +60,6 @@ XWs x_ws(void* ws, const XLayout& l) {
   return {(XRec*)p, (XCtr*)(p + l.ctr), (int*)(p + l.list), (uint8_t*)(p + l.a), (uint8_t*)(p + l.b), (int*)(p + l.lab), (unsigned*)(p + l.acc)};
 }
 
-// sides 3 .. 2^30, offset >= 0, offset + h*w*C <= bytes
-__device__ __forceinline__ bool x_desc_ok(const ImageDesc& d, int C, size_t bytes) {
-  if (d.h < 3 || d.w < 3 || d.h > (1 << 30) || d.w > (1 << 30) || d.offset < 0 || (u64)d.offset > bytes) return false;
-  return (u64)d.h * (u64)d.w <= (bytes - (u64)d.offset) / (unsigned)C;
-}
-
 // one workgroup: validates every pair and lays the working planes out one after the other (prefix sums over N in turns of kT)
 __global__ void __launch_bounds__(kT) extract_prep(const ImageDesc* __restrict__ wd, size_t wm_bytes, const ImageDesc* __restrict__ cd,
                                                    size_t clean_bytes, const ImageDesc* __restrict__ pd, size_t plane_bytes, XRec* __restrict__ recs,
@@ -79,7 +73,7 @@ __global__ void __launch_bounds__(kT) extract_prep(const ImageDesc* __restrict__
     XRec r = {0, 0, 0, 0, 0, 0};
     if (i < N) {
       const ImageDesc w = wd[i], c = cd[i], p = pd[i];
-      if (x_desc_ok(w, 3, wm_bytes) && x_desc_ok(c, 3, clean_bytes) && x_desc_ok(p, 1, plane_bytes) && c.h == w.h && c.w == w.w && p.h == w.h &&
+      if (region_ok(w, 3, wm_bytes, 3) && region_ok(c, 3, clean_bytes, 3) && region_ok(p, 1, plane_bytes, 3) && c.h == w.h && c.w == w.w && p.h == w.h &&
           p.w == w.w && (long long)w.h * w.w <= max_pixels) {
         r.wm = w.offset; r.clean = c.offset; r.plane = p.offset; r.h = w.h; r.w = w.w;
       }
@@ -87,14 +81,7 @@ __global__ void __launch_bounds__(kT) extract_prep(const ImageDesc* __restrict__
     }
     const long long mine = (long long)r.h * r.w;
     s_pix[t] = mine;
-    __syncthreads();
-    for (int d = 1; d < kT; d <<= 1) {                       // inclusive scan
-      long long a = 0;
-      if (t >= d) a = s_pix[t - d];
-      __syncthreads();
-      s_pix[t] += a;
-      __syncthreads();
-    }
+    block_scan_incl(s_pix, t);
     const long long to = s_carry + s_pix[t];
     if (to > total_pixels) r.h = r.w = 0;                    // beyond the capacity: a misfit (it still counts in the sums, as in mask_post.hip)
     r.ws = r.h ? to - mine : 0;
@@ -139,28 +126,7 @@ __global__ void __launch_bounds__(kT) extract_morph(const uint8_t* __restrict__ 
   dst[r.ws + p] = (uint8_t)v;
 }
 
-// ---------------------------------------------------------------- union-find on byte planes
-__device__ __forceinline__ int ld_label(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_label(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int x_find(const int* lab, int p) {
-  for (;;) {
-    const int q = ld_label(lab + p);
-    if (q == p) return p;
-    p = q;
-  }
-}
-__device__ __forceinline__ void x_union(int* lab, int a, int b) {
-  for (;;) {
-    a = x_find(lab, a);
-    b = x_find(lab, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(lab + a, b);                   // a's parent as it was
-    if (old == a) return;
-    a = old;
-  }
-}
-
+// ---------------------------------------------------------------- union-find on byte planes (image_common.inc's, labels = parent)
 // BG: the set is the plane's zeros (the background, for the fill), else its ones.  label = head of the pixel's run inside the wave's
 // 64 consecutive pixels (a run also ends where a row does), -1 outside the set; acc = 0
 template <bool BG>
@@ -185,8 +151,7 @@ __global__ void __launch_bounds__(kT) extract_cc_init(const uint8_t* __restrict_
   acc[r.ws + p] = 0;
 }
 
-// joins across wave boundaries and between rows.  A pixel whose left neighbour is in the set with the set above it leaves the join with
-// the row above to that neighbour, so each stretch of vertical contact joins once (mask_post.hip's mp_cc_merge)
+// joins across wave boundaries and between rows (cc_join)
 template <bool CONN8, bool BG>
 __global__ void __launch_bounds__(kT) extract_cc_merge(const uint8_t* __restrict__ plane, int* __restrict__ labels, const XRec* __restrict__ recs) {
   const XRec r = recs[blockIdx.y];
@@ -195,19 +160,7 @@ __global__ void __launch_bounds__(kT) extract_cc_merge(const uint8_t* __restrict
   const uint8_t* s = plane + r.ws;
   if ((s[p] != 0) == BG) return;
   const int w = r.w, y = p / w, x = p % w;
-  int* lab = labels + r.ws;
-  const bool left = x > 0 && (s[p - 1] != 0) != BG;
-  if (left && (threadIdx.x & 63) == 0) x_union(lab, (int)p, (int)p - 1);
-  if (y == 0) return;
-  const bool up = (s[p - w] != 0) != BG;
-  const bool upl = x > 0 && (s[p - w - 1] != 0) != BG;
-  if (up) {
-    if (!(left && upl)) x_union(lab, (int)p, (int)p - w);
-  } else if (CONN8) {
-    const bool upr = x + 1 < w && (s[p - w + 1] != 0) != BG;
-    if (upl && !left) x_union(lab, (int)p, (int)p - w - 1);
-    if (upr) x_union(lab, (int)p, (int)p - w + 1);
-  }
+  cc_join<CONN8, 0>(labels + r.ws, (int)p, x, y, w, [&](int dy, int dx) { return (s[(int)p + dy * w + dx] != 0) != BG; }, (threadIdx.x & 63) == 0);
 }
 
 // labels <- root
@@ -217,7 +170,7 @@ __global__ void __launch_bounds__(kT) extract_cc_flatten(int* __restrict__ label
   if (p >= (unsigned)r.h * r.w) return;
   int* lab = labels + r.ws;
   if (ld_label(lab + p) < 0) return;
-  st_label(lab + p, x_find(lab, (int)p));
+  st_label(lab + p, uf_find<0>(lab, (int)p));
 }
 
 // acc[root] = 1 for every background component that has a pixel on the image's border: it is 4-connected to the outside
@@ -430,7 +383,7 @@ __global__ void __launch_bounds__(kT) cutout_prep(const ImageDesc* __restrict__ 
   const long long off = jobs[j].out_offset;
   if (image >= 0 && image < N) {
     const ImageDesc a = wd[image], b = pd[image];
-    if (x_desc_ok(a, 3, wm_bytes) && x_desc_ok(b, 1, plane_bytes) && a.h == b.h && a.w == b.w && x >= 0 && y >= 0 && w >= 3 && h >= 3 &&
+    if (region_ok(a, 3, wm_bytes, 3) && region_ok(b, 1, plane_bytes, 3) && a.h == b.h && a.w == b.w && x >= 0 && y >= 0 && w >= 3 && h >= 3 &&
         (long long)x + w <= a.w && (long long)y + h <= a.h && (long long)w * h <= max_crop_pixels && off >= 0 && (off & 3) == 0 &&
         (u64)off <= out_bytes && (u64)w * (u64)h <= (out_bytes - (u64)off) / 4) {
       c.wm = a.offset; c.plane = b.offset; c.W = a.w; c.ok = 1;
@@ -440,14 +393,6 @@ __global__ void __launch_bounds__(kT) cutout_prep(const ImageDesc* __restrict__ 
   sums[j] = 0;
   status[j] = c.ok ? 0 : 1;
 }
-
-// Image.blend(degenerate, image, f) on one channel value (synth_u8.hip's blend8, restated): float32, every rounding spelt out
-__device__ __forceinline__ int blend8(int d, int v, float f) {
-  const float t = __fadd_rn((float)d, __fmul_rn(f, __fsub_rn((float)v, (float)d)));
-  if (f >= 0.f && f <= 1.f) return (int)t & 255;
-  return t <= 0.f ? 0 : t >= 255.f ? 255 : (int)t;
-}
-__device__ __forceinline__ int luma8(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }
 
 // sums[j] = the sum of L over the crop (the Contrast degenerate is its rounded mean); integer: any order, one result
 __global__ void __launch_bounds__(kT) cutout_luma(const uint8_t* __restrict__ wm, const ExtractJob* __restrict__ jobs, const CRec* __restrict__ recs,
@@ -525,8 +470,6 @@ size_t extract_workspace_bytes(int N, long long total_pixels, int J) {
   return a > b ? a : b;
 }
 
-#define XCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
-
 hipError_t launch_extract_regions(const uint8_t* wm, size_t wm_bytes, const ImageDesc* wm_descs, const uint8_t* clean, size_t clean_bytes,
                                   const ImageDesc* clean_descs, int N, int threshold, int min_area, long long max_pixels, long long total_pixels,
                                   uint8_t* plane, size_t plane_bytes, const ImageDesc* plane_descs, long long* stats, long long* table, void* ws,
@@ -535,20 +478,20 @@ hipError_t launch_extract_regions(const uint8_t* wm, size_t wm_bytes, const Imag
   const dim3 grid((unsigned)((max_pixels + kT - 1) / kT), (unsigned)N), block(kT);
   hipLaunchKernelGGL(extract_prep, dim3(1), block, 0, st, wm_descs, wm_bytes, clean_descs, clean_bytes, plane_descs, plane_bytes, x.recs, x.ctr, N,
                      max_pixels, total_pixels);
-  XCHK(hipGetLastError());
+  UWM_CHK(hipGetLastError());
   hipLaunchKernelGGL(extract_mask, grid, block, 0, st, wm, clean, x.recs, x.a, threshold);
   hipLaunchKernelGGL(extract_morph<true>, grid, block, 0, st, x.a, x.b, x.recs);       // close
   hipLaunchKernelGGL(extract_morph<false>, grid, block, 0, st, x.b, x.a, x.recs);
   hipLaunchKernelGGL(extract_morph<false>, grid, block, 0, st, x.a, x.b, x.recs);      // open
   hipLaunchKernelGGL(extract_morph<true>, grid, block, 0, st, x.b, x.a, x.recs);
-  XCHK(hipGetLastError());
+  UWM_CHK(hipGetLastError());
   // the fill: the 4-connected components of the background, those that touch the border marked
   hipLaunchKernelGGL(extract_cc_init<true>, grid, block, 0, st, x.a, x.lab, x.acc, x.recs);
   hipLaunchKernelGGL((extract_cc_merge<false, true>), grid, block, 0, st, x.a, x.lab, x.recs);
   hipLaunchKernelGGL(extract_cc_flatten, grid, block, 0, st, x.lab, x.recs);
   hipLaunchKernelGGL(extract_border, grid, block, 0, st, x.lab, x.acc, x.recs);
   hipLaunchKernelGGL(extract_fill, grid, block, 0, st, x.a, x.lab, x.acc, x.b, x.recs);
-  XCHK(hipGetLastError());
+  UWM_CHK(hipGetLastError());
   // the regions: the 8-connected components of F
   hipLaunchKernelGGL(extract_cc_init<false>, grid, block, 0, st, x.b, x.lab, x.acc, x.recs);
   hipLaunchKernelGGL((extract_cc_merge<true, false>), grid, block, 0, st, x.b, x.lab, x.recs);
@@ -569,7 +512,7 @@ hipError_t launch_extract_cutouts(const uint8_t* wm, size_t wm_bytes, const Imag
   const dim3 grid((unsigned)((max_crop_pixels + kT - 1) / kT), (unsigned)J), block(kT);
   hipLaunchKernelGGL(cutout_prep, dim3((unsigned)((J + kT - 1) / kT)), block, 0, st, wm_descs, wm_bytes, plane_descs, plane_bytes, N, jobs, J,
                      max_crop_pixels, out_bytes, recs, sums, status);
-  XCHK(hipGetLastError());
+  UWM_CHK(hipGetLastError());
   hipLaunchKernelGGL(cutout_luma, grid, block, 0, st, wm, jobs, recs, sums);
   hipLaunchKernelGGL(cutout_final, grid, block, 0, st, wm, plane, jobs, recs, sums, out);
   return hipGetLastError();

@@ -19,6 +19,8 @@ namespace uwm {
 
 namespace {
 
+#include "image_common.inc"
+
 constexpr int kPW = 128;                   // plane columns of a tile: image columns x0 - 4 .. x0 + 123, four to a dword
 constexpr int kGroups = kPlaneGroups;      // dwords per plane row
 constexpr int kTW = kFilterTileW;          // mask columns of a tile = plane columns 4 .. 123
@@ -27,14 +29,9 @@ constexpr int kHalo = 4;                   // erode, dilate, dilate, erode
 static_assert(kTW == kPW - 2 * kHalo && kGroups * 4 == kPW && kTH % 8 == 0, "tile geometry");
 
 __device__ __forceinline__ bool sides_ok(const ImageDesc& d) { return d.h >= 1 && d.w >= 1 && d.h <= (1 << 30) && d.w <= (1 << 30); }
-// offset >= 0 and offset + h*w <= bytes, for any positive h, w
-__device__ __forceinline__ bool region_fits(const ImageDesc& d, size_t bytes) {
-  if (d.h < 1 || d.w < 1 || d.offset < 0 || (unsigned long long)d.offset > bytes) return false;
-  return (unsigned long long)d.h * (unsigned long long)d.w <= bytes - (unsigned long long)d.offset;
-}
 // an image that is counted: sides in 1 .. 2^30 (every coordinate of a tile then fits an int) and, with a mask, a region inside it
 __device__ __forceinline__ bool filter_desc_ok(const ImageDesc& d, bool with_mask, size_t mask_bytes) {
-  return sides_ok(d) && (!with_mask || region_fits(d, mask_bytes));
+  return sides_ok(d) && (!with_mask || region_ok(d, 1, mask_bytes));
 }
 
 // pixels x .. x + 3 of row y of the H x W image: resize_prob > thr as bytes of 0 / 255; 0 for a column outside the image
@@ -58,7 +55,7 @@ __global__ __launch_bounds__(256) void prob_mask_count_kernel(const float* __res
   const int n = blockIdx.x / kFilterBlocks, blk = blockIdx.x % kFilterBlocks;
   const ImageDesc d = descs[n];
   if (!filter_desc_ok(d, mask != nullptr, mask_bytes)) {                       // (uniform over the workgroup)
-    if (mask && region_fits(d, mask_bytes)) {                                  // a side above 2^30 whose region still fits: zeros
+    if (mask && region_ok(d, 1, mask_bytes, 1, kAnySide)) {                                  // a side above 2^30 whose region still fits: zeros
       const size_t total = (size_t)d.h * d.w;
       for (size_t i = (size_t)blk * blockDim.x + threadIdx.x; i < total; i += (size_t)kFilterBlocks * blockDim.x) mask[d.offset + i] = 0;
     }

@@ -18,6 +18,10 @@
 
 namespace uwm {
 
+namespace {
+#include "image_common.inc"
+}  // namespace
+
 constexpr int kJpegMcus = 4;                 // MCUs of one pass-A workgroup: 4 * 64 quads = 256 threads, 24 blocks = 192 DCT lanes
 constexpr int kJpegBlkStride = 72;           // ints between two blocks in LDS (64 + 8: the column reads of four blocks miss each other's banks)
 
@@ -31,7 +35,6 @@ __device__ const unsigned char kJpegChrom[64] = {17, 18, 24, 47, 99, 99, 99, 99,
 
 __device__ __forceinline__ int jpeg_quality(const int* __restrict__ quality, int n) { return min(max(quality[n], 0), 100); }
 __device__ __forceinline__ int jpeg_descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
-__device__ __forceinline__ int jpeg_clamp255(int v) { return min(max(v, 0), 255); }
 
 // jfdctint's 1-D pass on d[0..7] in place.  kRows: the row pass (outputs scaled up by 4); else the column pass (scaled back down)
 template <bool kRows>
@@ -161,8 +164,8 @@ __global__ __launch_bounds__(256) void jpeg_blocks_kernel(const uint8_t* __restr
     uint32_t lo = 0, hi = 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      lo |= (uint32_t)jpeg_clamp255(d[i] + 128) << (8 * i);
-      hi |= (uint32_t)jpeg_clamp255(d[4 + i] + 128) << (8 * i);
+      lo |= (uint32_t)clamp255(d[i] + 128) << (8 * i);
+      hi |= (uint32_t)clamp255(d[4 + i] + 128) << (8 * i);
     }
     const int m = b / 6, k = b - m * 6;
     const int mcu = g * kJpegMcus + m;
@@ -217,9 +220,9 @@ __global__ __launch_bounds__(256) void jpeg_pixels_kernel(const uint8_t* __restr
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int yy = (int)((yw >> (8 * k)) & 255u), cb = ch[0][k], cr = ch[1][k];
-      v[k][0] = jpeg_clamp255(yy + ((91881 * cr + 32768) >> 16));
-      v[k][1] = jpeg_clamp255(yy + ((-22554 * cb - 46802 * cr + 32768) >> 16));
-      v[k][2] = jpeg_clamp255(yy + ((116130 * cb + 32768) >> 16));
+      v[k][0] = clamp255(yy + ((91881 * cr + 32768) >> 16));
+      v[k][1] = clamp255(yy + ((-22554 * cb - 46802 * cr + 32768) >> 16));
+      v[k][2] = clamp255(yy + ((116130 * cb + 32768) >> 16));
     }
   }
   if (out_u8) {

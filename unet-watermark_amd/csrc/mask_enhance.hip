@@ -16,8 +16,8 @@
 //
 // The binary smoothing rounds do not go through me_morph: me_smooth (below) runs two rounds, eight passes, in LDS per launch.
 //
-// Blur + threshold (me_blur): the same tile with a halo of the Gaussian's radius, fetched through reflect-101 (the loop of
-// borderInterpolate, so images narrower than the radius work); the row pass goes to a float32 LDS plane, the column pass reads
+// Blur + threshold (me_blur): the same tile with a halo of the Gaussian's radius, fetched through reflect-101 (of any
+// coordinate, so images narrower than the radius work); the row pass goes to a float32 LDS plane, the column pass reads
 // it and thresholds.  Each pass is acc = t[c] * x[0]; acc += t[c + i] * (x[-i] + x[+i]) for i = 1 .. r in order, every operation
 // rounded to float32 (__fmul_rn / __fadd_rn: no contraction).  blur_kernel 0 is the one-tap kernel {1}: x * 1 is x.
 #include "uwm_kernels.h"
@@ -27,6 +27,8 @@
 namespace uwm {
 
 namespace {
+
+#include "image_common.inc"
 
 constexpr int kThreads = 256;
 constexpr int kT = 64;                         // tile side
@@ -55,9 +57,8 @@ __global__ void __launch_bounds__(kThreads) me_prep(const ImageDesc* __restrict_
   if (i >= N) return;
   const ImageDesc d = descs[i];
   Rec r = {0, 0, 0};
-  const bool sides = d.h >= 1 && d.w >= 1 && d.h <= (1 << 30) && d.w <= (1 << 30);
-  const long long area = sides ? (long long)d.h * d.w : 0;
-  if (sides && area <= max_pixels && d.offset >= 0 && d.offset <= mask_bytes - area) { r.off = d.offset; r.h = d.h; r.w = d.w; }
+  const long long area = (long long)d.h * d.w;                  // (read only where region_ok holds)
+  if (region_ok(d, 1, (size_t)mask_bytes) && area <= max_pixels) { r.off = d.offset; r.h = d.h; r.w = d.w; }
   recs[i] = r;
   if (stats) {
     long long* s = stats + (size_t)i * 4;
@@ -86,12 +87,6 @@ __global__ void __launch_bounds__(kThreads) me_count(const uint8_t* __restrict__
     for (int k = 0; k < kThreads / 64; ++k) sum += s_cnt[k];
     if (sum) atomicAdd((unsigned long long*)(stats + (size_t)blockIdx.y * 4 + slot), sum);
   }
-}
-
-__device__ __forceinline__ int reflect101(int p, int len) {          // cv2.borderInterpolate, BORDER_REFLECT_101
-  if (len == 1) return 0;
-  while (p < 0 || p >= len) p = p < 0 ? -p : 2 * (len - 1) - p;
-  return p;
 }
 
 template <bool MAX>
@@ -350,8 +345,6 @@ __global__ void __launch_bounds__(kThreads) me_smooth(const uint8_t* __restrict_
   }
 }
 
-size_t rup256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 Ellipse make_ellipse(int r) {                              // mask_element's rule (mask_post.hip) at odd sides up to 63
   Ellipse el;
   el.r = r;
@@ -362,8 +355,6 @@ Ellipse make_ellipse(int r) {                              // mask_element's rul
   }
   return el;
 }
-
-#define ME_CHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
 
 }  // namespace
 
@@ -415,11 +406,11 @@ hipError_t launch_enhance_masks_ragged(const uint8_t* in, uint8_t* out, size_t m
   if (e5.dx[0] != 0 || e5.dx[1] != 2 || e5.dx[2] != 2 || e5.dx[3] != 2 || e5.dx[4] != 0) return hipErrorInvalidValue;      // me_smooth's E(5,5)
 
   hipLaunchKernelGGL(me_prep, dim3((N + kThreads - 1) / kThreads), block, 0, st, descs, recs, stats, N, (long long)mask_bytes, max_pixels);
-  ME_CHK(hipGetLastError());
+  UWM_CHK(hipGetLastError());
   if (stats) hipLaunchKernelGGL(me_count, counts, block, 0, st, in, recs, stats, 0);
   hipLaunchKernelGGL(me_morph<true>, tiles, block, 0, st, in, a, recs, e7);
   hipLaunchKernelGGL(me_morph<false>, tiles, block, 0, st, (const uint8_t*)a, b, recs, e7);
-  ME_CHK(hipGetLastError());
+  UWM_CHK(hipGetLastError());
   uint8_t* cur = b;
   uint8_t* oth = a;
   if (expand_pixels > 0) {                                 // (a 1 x 1 element is the identity)
@@ -427,7 +418,7 @@ hipError_t launch_enhance_masks_ragged(const uint8_t* in, uint8_t* out, size_t m
     uint8_t* t = cur; cur = oth; oth = t;
   }
   hipLaunchKernelGGL(me_blur, tiles, block, 0, st, (const uint8_t*)cur, smooth_iterations ? oth : out, recs, tp);
-  ME_CHK(hipGetLastError());
+  UWM_CHK(hipGetLastError());
   { uint8_t* t = cur; cur = oth; oth = t; }
   for (int left = smooth_iterations; left > 0;) {          // kSR rounds of open + close E(5,5) per launch
     const int rounds = left < kSR ? left : kSR;
@@ -435,7 +426,7 @@ hipError_t launch_enhance_masks_ragged(const uint8_t* in, uint8_t* out, size_t m
     hipLaunchKernelGGL(me_smooth, tiles, block, 0, st, (const uint8_t*)cur, left ? oth : out, recs, rounds);
     uint8_t* t = cur; cur = oth; oth = t;
   }
-  ME_CHK(hipGetLastError());
+  UWM_CHK(hipGetLastError());
   if (stats) hipLaunchKernelGGL(me_count, counts, block, 0, st, (const uint8_t*)out, recs, stats, 1);
   return hipGetLastError();
 }

@@ -25,6 +25,8 @@ typedef unsigned long long u64;
 
 namespace {
 
+#include "image_common.inc"
+
 constexpr int kThreads = 256;
 constexpr int kPer = 8;                    // pixels per thread of the kernels that end in an atomic sum (mp_cc_compress, mp_select)
 constexpr int kPix = kPer * kThreads;
@@ -142,30 +144,7 @@ __global__ void __launch_bounds__(kThreads) mp_morph(const u64* __restrict__ src
 }
 
 // ---------------------------------------------------------------- components
-__device__ __forceinline__ int ld_label(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_label(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// root of p: parents never exceed their children, so the walk strictly descends
-__device__ __forceinline__ int mp_find(const int* lab, int p) {
-  for (;;) {
-    const int q = ld_label(lab + p) - 1;
-    if (q == p) return p;
-    p = q;
-  }
-}
-// join the sets of a and b.  Every turn either ends or continues with max(a, b) strictly smaller.
-__device__ __forceinline__ void mp_union(int* lab, int a, int b) {
-  for (;;) {
-    a = mp_find(lab, a);
-    b = mp_find(lab, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(lab + a, b + 1) - 1;       // a's parent as it was
-    if (old == a) return;                                // a was a root and now hangs below b
-    a = old;                                             // a had got a parent meanwhile: that set still has to meet b's
-  }
-}
-
+// (the union-find is image_common.inc's, labels = parent + 1)
 __device__ __forceinline__ bool bit_at(const u64* plane, int WP, int y, int x) {
   return (plane[(size_t)y * WP + (x >> 6)] >> (x & 63)) & 1;
 }
@@ -192,8 +171,7 @@ __global__ void __launch_bounds__(kThreads) mp_cc_init(const u64* __restrict__ b
   areas[g.pix + p] = 0;
 }
 
-// joins across word boundaries and between rows.  A pixel whose left neighbour is foreground with foreground above it leaves
-// the join with the row above to that neighbour (they share a run), so each stretch of vertical contact joins once.
+// joins across word boundaries and between rows (cc_join, 8-connected)
 template <class G>
 __global__ void __launch_bounds__(kThreads) mp_cc_merge(const u64* __restrict__ bits, int* __restrict__ labels, G geo) {
   Img g;
@@ -204,19 +182,7 @@ __global__ void __launch_bounds__(kThreads) mp_cc_merge(const u64* __restrict__ 
   const int y = p / W, x = p % W;
   const u64* plane = bits + g.word;
   if (!bit_at(plane, WP, y, x)) return;
-  int* lab = labels + g.pix;
-  const bool left = x > 0 && bit_at(plane, WP, y, x - 1);
-  if (left && (x & 63) == 0) mp_union(lab, (int)p, (int)p - 1);
-  if (y == 0) return;
-  const bool up = bit_at(plane, WP, y - 1, x);
-  const bool upl = x > 0 && bit_at(plane, WP, y - 1, x - 1);
-  const bool upr = x + 1 < W && bit_at(plane, WP, y - 1, x + 1);
-  if (up) {
-    if (!(left && upl)) mp_union(lab, (int)p, (int)p - W);
-  } else {
-    if (upl && !left) mp_union(lab, (int)p, (int)p - W - 1);      // (with `left`, the left pixel has `up` = upl and joins)
-    if (upr) mp_union(lab, (int)p, (int)p - W + 1);
-  }
+  cc_join<true, 1>(labels + g.pix, (int)p, x, y, W, [&](int dy, int dx) { return bit_at(plane, WP, y + dy, x + dx); }, (x & 63) == 0);
 }
 
 // labels <- root + 1, areas[root] += pixel count.  A workgroup covers kPix consecutive pixels; each wave sums the lanes that share
@@ -237,7 +203,7 @@ __global__ void __launch_bounds__(kThreads) mp_cc_compress(int* __restrict__ lab
     const unsigned p = blockIdx.x * kPix + i * kThreads + threadIdx.x;
     int r = -1;
     if (p < (unsigned)H * W && ld_label(lab + p) != 0) {
-      r = mp_find(lab, (int)p);
+      r = uf_find<1>(lab, (int)p);
       st_label(lab + p, r + 1);
     }
     const u64 fg = __ballot(r >= 0);
@@ -371,22 +337,12 @@ __global__ void __launch_bounds__(kThreads) mp_ragged_prep(const ImageDesc* __re
     Rec r = {0, 0, 0, 0};
     if (i < N) {
       const ImageDesc d = descs[i];
-      const bool sides = d.h >= 1 && d.w >= 1 && d.h <= (1 << 30) && d.w <= (1 << 30);
-      const long long area = sides ? (long long)d.h * d.w : 0;
-      if (sides && area <= max_pixels && d.offset >= 0 && d.offset <= mask_bytes - area) { r.off = d.offset; r.h = d.h; r.w = d.w; }
+      if (region_ok(d, 1, (size_t)mask_bytes) && (long long)d.h * d.w <= max_pixels) { r.off = d.offset; r.h = d.h; r.w = d.w; }
     }
     const long long my_rows = r.h, my_words = (long long)r.h * ((r.w + 63) / 64);
     s_rows[t] = my_rows;
     s_words[t] = my_words;
-    __syncthreads();
-    for (int d = 1; d < kThreads; d <<= 1) {                 // inclusive scan
-      long long a = 0, b = 0;
-      if (t >= d) { a = s_rows[t - d]; b = s_words[t - d]; }
-      __syncthreads();
-      s_rows[t] += a;
-      s_words[t] += b;
-      __syncthreads();
-    }
+    block_scan_incl(s_rows, t, s_words);
     const long long rows_to = s_carry[0] + s_rows[t], words_to = s_carry[1] + s_words[t];
     if (rows_to > rows || words_to > cap_words) r.h = r.w = 0, r.off = 0;
     r.word = r.h ? words_to - my_words : 0;
@@ -397,8 +353,6 @@ __global__ void __launch_bounds__(kThreads) mp_ragged_prep(const ImageDesc* __re
 }
 
 // ---------------------------------------------------------------- host side
-size_t rup256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct Layout {                // workspace: three bit planes, labels, areas, per-image counters (each 256-byte aligned)
   size_t plane, labels, areas, counters, total;
 };
@@ -484,8 +438,6 @@ hipError_t components(const u64* bits, int* labels, int* areas, u64* counters, c
   return hipGetLastError();
 }
 
-#define MP_CHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
-
 // pack -> the type's morphology -> components -> largest -> select + write: what the uniform and the ragged call share.
 // a, b, c: three bit planes; the counters are left for the caller's summary
 template <class G>
@@ -493,32 +445,32 @@ hipError_t optimize(const uint8_t* in, uint8_t* out, const Batch<G>& bt, int mas
                     u64* counters, hipStream_t st) {
   const int E = 2, R = 0;
   MorphEl el;
-  MP_CHK(pack(in, a, bt, st));
+  UWM_CHK(pack(in, a, bt, st));
   if (mask_type == 0) {                                   // watermark
-    MP_CHK(open_close(&a, &b, bt, false, E, 3, 3, 1, st));
-    MP_CHK(open_close(&a, &b, bt, true, E, 7, 7, 3, st));
-    MP_CHK(open_close(&a, &b, bt, true, E, 11, 11, 2, st));
+    UWM_CHK(open_close(&a, &b, bt, false, E, 3, 3, 1, st));
+    UWM_CHK(open_close(&a, &b, bt, true, E, 7, 7, 3, st));
+    UWM_CHK(open_close(&a, &b, bt, true, E, 11, 11, 2, st));
     make_el(E, 9, 9, &el);
-    MP_CHK(morph_n(&a, &b, bt, true, el, 2, st));
+    UWM_CHK(morph_n(&a, &b, bt, true, el, 2, st));
   } else if (mask_type == 1) {                            // text
-    MP_CHK(open_close(&a, &b, bt, false, E, 2, 2, 1, st));
-    MP_CHK(open_close(&a, &b, bt, true, E, 3, 3, 2, st));
+    UWM_CHK(open_close(&a, &b, bt, false, E, 2, 2, 1, st));
+    UWM_CHK(open_close(&a, &b, bt, true, E, 3, 3, 2, st));
     // the two line closings read the same input (a): c = close(a, 5x1); a = close(a, 1x5) | c
     make_el(R, 5, 1, &el);
-    MP_CHK(morph_pass(a, b, (const u64*)nullptr, bt, true, el, st));
-    MP_CHK(morph_pass(b, c, (const u64*)nullptr, bt, false, el, st));
+    UWM_CHK(morph_pass(a, b, (const u64*)nullptr, bt, true, el, st));
+    UWM_CHK(morph_pass(b, c, (const u64*)nullptr, bt, false, el, st));
     make_el(R, 1, 5, &el);
-    MP_CHK(morph_pass(a, b, (const u64*)nullptr, bt, true, el, st));
-    MP_CHK(morph_pass(b, a, c, bt, false, el, st));
+    UWM_CHK(morph_pass(a, b, (const u64*)nullptr, bt, true, el, st));
+    UWM_CHK(morph_pass(b, a, c, bt, false, el, st));
     make_el(E, 4, 4, &el);
-    MP_CHK(morph_n(&a, &b, bt, true, el, 1, st));
+    UWM_CHK(morph_n(&a, &b, bt, true, el, 1, st));
   } else if (mask_type == 2) {                            // mixed
-    MP_CHK(open_close(&a, &b, bt, false, E, 2, 2, 1, st));
-    MP_CHK(open_close(&a, &b, bt, true, E, 5, 5, 2, st));
+    UWM_CHK(open_close(&a, &b, bt, false, E, 2, 2, 1, st));
+    UWM_CHK(open_close(&a, &b, bt, true, E, 5, 5, 2, st));
     make_el(E, 6, 6, &el);
-    MP_CHK(morph_n(&a, &b, bt, true, el, 1, st));
+    UWM_CHK(morph_n(&a, &b, bt, true, el, 1, st));
   }                                                       // (none, ragged only: the binarised plane as it is)
-  MP_CHK(components(a, labels, areas, counters, bt, st));
+  UWM_CHK(components(a, labels, areas, counters, bt, st));
   hipLaunchKernelGGL(mp_cc_largest<G>, bt.per_pixel(), dim3(kThreads), 0, st, labels, areas, counters, bt.geo, mask_type);
   hipLaunchKernelGGL(mp_select<G>, bt.per_kpix(), dim3(kThreads), 0, st, labels, areas, counters, out, bt.geo, mask_type);
   return hipGetLastError();
@@ -575,8 +527,8 @@ hipError_t launch_mask_morph(const uint8_t* in, uint8_t* out, int N, int H, int 
   u64* tmp = (u64*)((char*)ws + l.plane);
   MorphEl el;
   if (!make_el(shape, kw, kh, &el)) return hipErrorInvalidValue;
-  MP_CHK(pack(in, cur, bt, st));
-  MP_CHK(morph_n(&cur, &tmp, bt, dilate != 0, el, iterations, st));
+  UWM_CHK(pack(in, cur, bt, st));
+  UWM_CHK(morph_n(&cur, &tmp, bt, dilate != 0, el, iterations, st));
   hipLaunchKernelGGL(mp_unpack, bt.per_pixel(), dim3(kThreads), 0, st, cur, out, H, W, (W + 63) / 64);
   return hipGetLastError();
 }
@@ -584,7 +536,7 @@ hipError_t launch_mask_morph(const uint8_t* in, uint8_t* out, int N, int H, int 
 hipError_t launch_mask_components(const uint8_t* in, int* labels, int* areas, int N, int H, int W, void* ws, hipStream_t st) {
   const Layout l = layout(N, H, W);
   const Batch<Uniform> bt = uniform(N, H, W);
-  MP_CHK(pack(in, (u64*)ws, bt, st));
+  UWM_CHK(pack(in, (u64*)ws, bt, st));
   return components((u64*)ws, labels, areas, (u64*)((char*)ws + l.counters), bt, st);
 }
 
@@ -592,7 +544,7 @@ hipError_t launch_optimize_mask(const uint8_t* in, uint8_t* out, int N, int H, i
                                 hipStream_t st) {
   const Layout l = layout(N, H, W);
   u64* counters = (u64*)((char*)ws + l.counters);
-  MP_CHK(optimize(in, out, uniform(N, H, W), mask_type, (u64*)ws, (u64*)((char*)ws + l.plane), (u64*)((char*)ws + 2 * l.plane),
+  UWM_CHK(optimize(in, out, uniform(N, H, W), mask_type, (u64*)ws, (u64*)((char*)ws + l.plane), (u64*)((char*)ws + 2 * l.plane),
                   (int*)((char*)ws + l.labels), (int*)((char*)ws + l.areas), counters, st));
   if (summary) hipLaunchKernelGGL(mp_summary, dim3((N + 63) / 64), dim3(64), 0, st, counters, summary, N);
   return hipGetLastError();
@@ -606,8 +558,8 @@ hipError_t launch_optimize_masks_ragged(const uint8_t* in, uint8_t* out, size_t 
   u64* a = (u64*)((char*)ws + l.plane0);
   hipLaunchKernelGGL(mp_ragged_prep, dim3(1), dim3(kThreads), 0, st, descs, recs, N, (long long)mask_bytes, max_pixels, rows,
                      (long long)l.cap_words);
-  MP_CHK(hipGetLastError());
-  MP_CHK(optimize(in, out, ragged(recs, N, max_pixels), mask_type, a, (u64*)((char*)a + l.plane), (u64*)((char*)a + 2 * l.plane),
+  UWM_CHK(hipGetLastError());
+  UWM_CHK(optimize(in, out, ragged(recs, N, max_pixels), mask_type, a, (u64*)((char*)a + l.plane), (u64*)((char*)a + 2 * l.plane),
                   (int*)((char*)ws + l.labels), (int*)((char*)ws + l.areas), counters, st));
   if (stats) hipLaunchKernelGGL(mp_ragged_stats, dim3((N + 63) / 64), dim3(64), 0, st, counters, recs, stats, N, mask_type);
   return hipGetLastError();

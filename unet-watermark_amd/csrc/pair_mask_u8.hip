@@ -12,6 +12,8 @@ namespace uwm {
 
 namespace {
 
+#include "image_common.inc"
+
 constexpr int kPW = 128;                   // plane columns of a tile: image columns x0 - 4 .. x0 + 123, four to a dword
 constexpr int kGroups = kPlaneGroups;      // dwords per plane row (column_mask, cross, store_px4: uwm_kernels.h)
 constexpr int kTW = kPairMaskTileW;        // mask columns of a tile = plane columns 4 .. 123 (the halo of 2 is rounded up to a dword)
@@ -20,12 +22,6 @@ constexpr int kTRows = kTH + 4;            // thresholded plane: rows y0 - 2 .. 
 constexpr int kERows = kTH + 2;            // eroded plane:      rows y0 - 1 .. y0 + kTH
 constexpr int kRawDwords = (kPW * 3 + 3 + 3) / 4;      // a staged row: 384 bytes behind up to 3 bytes of misalignment (97 dwords)
 static_assert(kTW == kPW - 8 && kGroups == 32 && kRawDwords == 97, "tile geometry");
-
-// h, w in 1 .. 2^30 (every coordinate of a tile then fits an int), offset >= 0, offset + h*w*C <= bytes
-__device__ __forceinline__ bool pair_desc_ok(const ImageDesc& d, int C, size_t bytes) {
-  if (d.h < 1 || d.w < 1 || d.h > (1 << 30) || d.w > (1 << 30) || d.offset < 0 || (unsigned long long)d.offset > bytes) return false;
-  return (unsigned long long)d.h * (unsigned long long)d.w <= (bytes - (unsigned long long)d.offset) / (unsigned)C;
-}
 
 // one image row's bytes [g0, g0 + nbytes) -> LDS as aligned-down dwords, one per lane of ONE wave (coalesced); byte k of the range is
 // then at ((uint8_t*)dst)[(g0 & 3) + k].  A dword that would reach past src_bytes is read byte by byte.
@@ -79,10 +75,11 @@ __global__ __launch_bounds__(256) void pair_mask_u8_kernel(const uint8_t* __rest
   const ImageDesc cd = clean_descs[n];
   if (cd.h == 0) return;                               // no clean image: the mask bytes stay (everything below is uniform over the workgroup)
   const ImageDesc wd = wm_descs[n], md = mask_descs[n];
-  if (!pair_desc_ok(md, 1, mask_bytes)) return;        // nowhere to write
+  // (region_ok: h, w in 1 .. 2^30, so every coordinate of a tile fits an int)
+  if (!region_ok(md, 1, mask_bytes)) return;        // nowhere to write
   uint8_t* out = mask + md.offset;
   const int h = md.h, w = md.w;
-  if (!pair_desc_ok(wd, 3, wm_bytes) || !pair_desc_ok(cd, 3, clean_bytes) || wd.h != h || wd.w != w || cd.h != h || cd.w != w) {
+  if (!region_ok(wd, 3, wm_bytes) || !region_ok(cd, 3, clean_bytes) || wd.h != h || wd.w != w || cd.h != h || cd.w != w) {
     const size_t total = (size_t)h * w;
     for (size_t i = (size_t)blk * blockDim.x + threadIdx.x; i < total; i += (size_t)kPairMaskBlocks * blockDim.x) out[i] = 0;
     return;

@@ -11,6 +11,10 @@ namespace uwm {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
+namespace {
+#include "image_common.inc"
+}  // namespace
+
 // ---------------------------------------------------------------- taps of one axis
 // INTER_LINEAR, 11 coefficient bits: source index pair (s, s1) and the weights a0 + a1 (= 2048 up to the rounding of 1 - f).
 // The double expression is evaluated as written — multiply, then subtract, each rounded — which a fused multiply-add would not do.
@@ -40,12 +44,6 @@ __device__ __forceinline__ int nearest_tap(int d, double scale, int src) {
 // VResizeLinear's 8-bit rule on two horizontally interpolated sums
 __device__ __forceinline__ int vlin(int S0, int S1, int b0, int b1) {
   return (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
-}
-
-// a descriptor that keeps every read of its image inside [0, src_bytes): h, w >= 1, offset >= 0, offset + h*w*C <= src_bytes
-__device__ __forceinline__ bool desc_ok(const ImageDesc& d, int C, size_t src_bytes) {
-  if (d.h < 1 || d.w < 1 || d.offset < 0 || (unsigned long long)d.offset > src_bytes) return false;
-  return (unsigned long long)d.h * (unsigned long long)d.w <= (src_bytes - (unsigned long long)d.offset) / (unsigned)C;      // (h*w < 2^62)
 }
 
 constexpr int kRowsPerBlock = kResizeRowsPerBlock;      // output rows of one workgroup
@@ -114,7 +112,7 @@ __global__ __launch_bounds__(256) void resize_u8_kernel(const uint8_t* __restric
   const int n = blockIdx.x / tiles, y_begin = (blockIdx.x % tiles) * kRowsPerBlock;
   const int y_end = min(y_begin + kRowsPerBlock, H);
   const ImageDesc d = descs[n];
-  const bool ok = desc_ok(d, C, src_bytes);
+  const bool ok = region_ok(d, C, src_bytes, 1, kAnySide);       // every read of the image stays inside [0, src_bytes)
   const int h = ok ? d.h : 1, w = ok ? d.w : 1;
   const size_t base = ok ? (size_t)d.offset : 0;
   const size_t row_bytes = (size_t)w * C;
@@ -193,7 +191,7 @@ __global__ __launch_bounds__(256) void resize_threshold_ragged_kernel(const floa
                                                                       uint8_t* __restrict__ mask, size_t mask_bytes) {
   const int n = blockIdx.x / kRaggedBlocks, blk = blockIdx.x % kRaggedBlocks;
   const ImageDesc d = descs[n];
-  if (!desc_ok(d, 1, mask_bytes)) return;
+  if (!region_ok(d, 1, mask_bytes, 1, kAnySide)) return;
   const int H = d.h, W = d.w;
   const float sy = (float)h / (float)H, sx = (float)w / (float)W;
   const float* b = logits + (size_t)n * h * w * ld;

@@ -1,6 +1,6 @@
 // The stage arithmetic that the logo chain (synth_u8.hip) and the text chain (synth_text_u8.hip) share: Pillow's LANCZOS tables and
 // resample pass, affine_fixed rotation, extended box blur, Image.blend and the paste blend, each restated operation by operation
-// (include/uwm.h states the rules).  Included inside the anonymous namespace of a file built with -ffp-contract=off.  A stage body
+// (include/uwm.h states the rules).  Included, after image_common.inc, inside the anonymous namespace of a file built with -ffp-contract=off.  A stage body
 // works on one job's patch from workgroup `blk` of kB: thread t of that workgroup takes pixels blk*256 + t, + kB*256, ...
 
 constexpr int kB = kSynthBlocks;
@@ -57,7 +57,6 @@ __device__ __forceinline__ void lanczos_rows(int in, int out, int ksize, int* __
 
 // ---------------------------------------------------------------------------------------------- one resample pass of Image.resize(LANCZOS) on RGBA
 __device__ __forceinline__ int muldiv255(int x, int y) { const int t = x * y + 128; return ((t >> 8) + t) >> 8; }
-__device__ __forceinline__ int clip8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
 __device__ __forceinline__ uint32_t pack4(int r, int g, int b, int a) { return (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16) | ((uint32_t)a << 24); }
 
 // src (sw wide) -> dst (dw x dh) along x (horiz) or y; premul: the first pass of its resize that runs, unpremul: the last one
@@ -77,8 +76,8 @@ __device__ __forceinline__ void resample_pass(const uint32_t* __restrict__ src, 
       const int kk = row[2 + k];
       acc[0] += c0 * kk; acc[1] += c1 * kk; acc[2] += c2 * kk; acc[3] += c3 * kk;
     }
-    int r = clip8(acc[0] >> 22), g = clip8(acc[1] >> 22), b = clip8(acc[2] >> 22);
-    const int al = clip8(acc[3] >> 22);
+    int r = clamp255(acc[0] >> 22), g = clamp255(acc[1] >> 22), b = clamp255(acc[2] >> 22);
+    const int al = clamp255(acc[3] >> 22);
     if (unpremul && al != 0 && al != 255) { r = min(255, 255 * r / al); g = min(255, 255 * g / al); b = min(255, 255 * b / al); }
     dst[i] = pack4(r, g, b, al);
   }
@@ -126,14 +125,6 @@ __device__ __forceinline__ void blur_pass(const uint32_t* __restrict__ src, uint
 }
 
 // ---------------------------------------------------------------------------------------------- ImageEnhance and paste
-// Image.blend(degenerate, image, f) on one channel value, in float32 with every rounding spelt out
-__device__ __forceinline__ int blend8(int d, int v, float f) {
-  const float t = __fadd_rn((float)d, __fmul_rn(f, __fsub_rn((float)v, (float)d)));
-  if (f >= 0.f && f <= 1.f) return (int)t & 255;
-  return t <= 0.f ? 0 : t >= 255.f ? 255 : (int)t;
-}
-__device__ __forceinline__ int luma8(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }
-
 // this workgroup's partial sum of L over the brightened patch (the Contrast degenerate is the mean) -> *part; integer sums: any order,
 // one result.  Every thread of the workgroup must come here (it synchronises)
 __device__ __forceinline__ void luma_partial(const uint32_t* __restrict__ src, int total, float fb, int blk, long long* __restrict__ red,
@@ -158,14 +149,3 @@ __device__ __forceinline__ int luma_mean(const long long* __restrict__ part, int
   return (int)__dadd_rn((double)sum / (double)total, 0.5);
 }
 
-// Image.paste's blend of one channel value
-__device__ __forceinline__ int blend255(int src, int dst, int al) { const int t = src * al + dst * (255 - al) + 128; return ((t >> 8) + t) >> 8; }
-
-__device__ __forceinline__ bool rgb_desc_ok(const ImageDesc& d, size_t bytes) {
-  return d.h >= 1 && d.w >= 1 && d.h <= kMaxSide && d.w <= kMaxSide && d.offset >= 0 && (unsigned long long)d.offset <= bytes &&
-         (unsigned long long)d.h * d.w <= (bytes - (unsigned long long)d.offset) / 3;
-}
-__device__ __forceinline__ bool mask_desc_ok(const ImageDesc& md, const ImageDesc& d, size_t bytes) {
-  return md.h == d.h && md.w == d.w && md.offset >= 0 && (unsigned long long)md.offset <= bytes &&
-         (unsigned long long)md.h * md.w <= bytes - (unsigned long long)md.offset;
-}

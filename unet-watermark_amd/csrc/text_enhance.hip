@@ -25,6 +25,8 @@ namespace {
 
 typedef unsigned long long u64;
 
+#include "image_common.inc"
+
 constexpr int kThreads = 256;
 constexpr int kMinSide = 16;                 // an image with a shorter side is copied through (status 2)
 constexpr int kLow = 50, kHigh = 150;        // Canny's thresholds on |dx| + |dy|
@@ -36,11 +38,6 @@ struct Rec {                   // one per image, written by te_prep.  mode 0: mi
   int th, tw, clip;            // CLAHE: the tile of the padded image, the integer clip limit
   float inv_th, inv_tw, scale; // 1.0f / th, 1.0f / tw, 255.0f / (th * tw)
 };
-
-__device__ __forceinline__ int reflect101(int c, int n) {      // |c - (n - 1)| < n and c > -n here: one reflection
-  return c < 0 ? -c : c >= n ? 2 * (n - 1) - c : c;
-}
-__device__ __forceinline__ int clamp255(int v) { return min(max(v, 0), 255); }
 
 // ---------------------------------------------------------------- prep
 // One workgroup: validates every descriptor and gives each enhanced image its place in the planes (prefix sums over N in turns of
@@ -59,26 +56,19 @@ __global__ void __launch_bounds__(kThreads) te_prep(const ImageDesc* __restrict_
     long long area = 0;
     if (i < N) {
       const ImageDesc d = descs[i];
-      const bool sides = d.h >= 1 && d.w >= 1 && d.h <= (1 << 30) && d.w <= (1 << 30);
-      area = sides ? (long long)d.h * d.w : 0;
-      bool ok = sides && area <= max_pixels && d.offset >= 0 && 3 * area <= bytes && d.offset <= bytes - 3 * area;
+      bool ok = region_ok(d, 3, (size_t)bytes);
+      area = ok ? (long long)d.h * d.w : 0;
+      ok = ok && area <= max_pixels;
       if (ok && edescs) {
         const ImageDesc e = edescs[i];
-        ok = e.h == d.h && e.w == d.w && e.offset >= 0 && area <= edges_bytes && e.offset <= edges_bytes - area;
+        ok = e.h == d.h && e.w == d.w && region_ok(e, 1, (size_t)edges_bytes);
         r.eoff = ok ? e.offset : 0;
       }
       if (ok) { r.off = d.offset; r.h = d.h; r.w = d.w; r.mode = (d.h >= kMinSide && d.w >= kMinSide) ? 1 : 2; }
     }
     const long long mine = r.mode == 1 ? area : 0;
     s_pix[t] = mine;
-    __syncthreads();
-    for (int d = 1; d < kThreads; d <<= 1) {                 // inclusive scan
-      long long a = 0;
-      if (t >= d) a = s_pix[t - d];
-      __syncthreads();
-      s_pix[t] += a;
-      __syncthreads();
-    }
+    block_scan_incl(s_pix, t);
     const long long to = s_carry + s_pix[t];
     if (r.mode == 1) {
       if (to > total_pixels) { r = Rec{0, 0, 0, 0, 0, 0, 1, 1, 1, 1.0f, 1.0f, 1.0f}; }
@@ -137,7 +127,7 @@ __global__ void __launch_bounds__(256) te_hist(const uint8_t* __restrict__ grey,
   const int y0 = (tile >> 3) * th, x0 = (tile & 7) * tw, area = th * tw;
   for (int i = t; i < area; i += 256) {
     const int dy = i / tw, dx = i - dy * tw;
-    atomicAdd(&hist[img[(size_t)reflect101(y0 + dy, H) * W + reflect101(x0 + dx, W)]], 1);
+    atomicAdd(&hist[img[(size_t)reflect101_near(y0 + dy, H) * W + reflect101_near(x0 + dx, W)]], 1);
   }
   __syncthreads();
   const int clip = rc.clip;
@@ -160,15 +150,6 @@ __global__ void __launch_bounds__(256) te_hist(const uint8_t* __restrict__ grey,
     __syncthreads();
   }
   luts[((size_t)n * 64 + tile) * 256 + t] = (uint8_t)clamp255(__float2int_rn((float)scan[cur][t] * rc.scale));
-}
-
-// an axis of the blend: y -> (tile, next tile, weight of the next); every operation rounded on its own
-__device__ __forceinline__ void clahe_axis(int y, float inv, int& t1, int& t2, float& a) {
-  const float f = (float)y * inv - 0.5f, fl = floorf(f);
-  a = f - fl;
-  const int i = (int)fl;
-  t1 = min(max(i, 0), 7);
-  t2 = min(max(i + 1, 0), 7);
 }
 
 __global__ void __launch_bounds__(kThreads) te_clahe(const uint8_t* __restrict__ grey, const Rec* __restrict__ recs, const uint8_t* __restrict__ luts,
@@ -212,30 +193,6 @@ __global__ void __launch_bounds__(kThreads) te_sobel(const uint8_t* __restrict__
   int dx, dy;
   sobel(cl + rc.pix, rc.h, rc.w, y, x, dx, dy);
   mag[rc.pix + p] = (unsigned short)(abs(dx) + abs(dy));       // at most 2040
-}
-
-__device__ __forceinline__ int ld_label(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_label(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// root of p: parents never exceed their children, so the walk strictly descends
-__device__ __forceinline__ int te_find(const int* lab, int p) {
-  for (;;) {
-    const int q = ld_label(lab + p) - 1;
-    if (q == p) return p;
-    p = q;
-  }
-}
-// join the sets of a and b.  Every turn either ends or continues with max(a, b) strictly smaller.
-__device__ __forceinline__ void te_union(int* lab, int a, int b) {
-  for (;;) {
-    a = te_find(lab, a);
-    b = te_find(lab, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(lab + a, b + 1) - 1;       // a's parent as it was
-    if (old == a) return;                                // a was a root and now hangs below b
-    a = old;                                             // a had got a parent meanwhile: that set still has to meet b's
-  }
 }
 
 // Non-maximum suppression -> labels: 0, or for a candidate the start of its run inside the wave's 64 pixels (+ 1); flags = 0.
@@ -289,8 +246,7 @@ __global__ void __launch_bounds__(kThreads) te_nms(const uint8_t* __restrict__ c
   flags[rc.pix + p] = 0;
 }
 
-// joins across the 64-pixel groups and between rows.  A pixel whose left neighbour is a candidate with a candidate above it leaves
-// the join with the row above to that neighbour (they share a run), so each stretch of vertical contact joins once.
+// joins across the 64-pixel groups and between rows (cc_join, 8-connected; the set is the candidates: label != 0)
 __global__ void __launch_bounds__(kThreads) te_merge(const Rec* __restrict__ recs, int* __restrict__ labels) {
   const Rec rc = recs[blockIdx.y];
   if (rc.mode != 1) return;
@@ -300,18 +256,7 @@ __global__ void __launch_bounds__(kThreads) te_merge(const Rec* __restrict__ rec
   const int p = (int)pl, y = p / W, x = p - y * W;
   int* lab = labels + rc.pix;
   if (ld_label(lab + p) == 0) return;
-  const bool left = x > 0 && ld_label(lab + p - 1) != 0;
-  if (left && (p & 63) == 0) te_union(lab, p, p - 1);
-  if (y == 0) return;
-  const bool up = ld_label(lab + p - W) != 0;
-  const bool upl = x > 0 && ld_label(lab + p - W - 1) != 0;
-  const bool upr = x + 1 < W && ld_label(lab + p - W + 1) != 0;
-  if (up) {
-    if (!(left && upl)) te_union(lab, p, p - W);
-  } else {
-    if (upl && !left) te_union(lab, p, p - W - 1);             // (with `left`, the left pixel has `up` = upl and joins)
-    if (upr) te_union(lab, p, p - W + 1);
-  }
+  cc_join<true, 1>(lab, p, x, y, W, [&](int dy, int dx) { return ld_label(lab + p + dy * W + dx) != 0; }, (p & 63) == 0);
 }
 
 // labels <- root + 1 (a root is an ancestor of everything a walk meets on its way, so the stores of other threads only shorten
@@ -324,7 +269,7 @@ __global__ void __launch_bounds__(kThreads) te_strong(const unsigned short* __re
   if (p >= total) return;
   int* lab = labels + rc.pix;
   if (ld_label(lab + p) == 0) return;
-  const int r = te_find(lab, (int)p);
+  const int r = uf_find<1>(lab, (int)p);
   st_label(lab + p, r + 1);
   if (mag[rc.pix + p] > kHigh) atomicMax(flags + rc.pix + r, 1);
 }
@@ -372,10 +317,10 @@ __global__ void __launch_bounds__(kThreads) te_final(const uint8_t* __restrict__
   int sum[3] = {0, 0, 0}, ctr[3] = {0, 0, 0};
 #pragma unroll
   for (int j = -1; j <= 1; ++j) {
-    const int yy = reflect101(y + j, H);
+    const int yy = reflect101_near(y + j, H);
 #pragma unroll
     for (int i = -1; i <= 1; ++i) {
-      const int xx = reflect101(x + i, W);
+      const int xx = reflect101_near(x + i, W);
       const size_t q = (size_t)yy * W + xx;
       const bool e = d[q] != 0;
       const uint8_t* px = img + 3 * q;
@@ -393,8 +338,6 @@ __global__ void __launch_bounds__(kThreads) te_final(const uint8_t* __restrict__
 }
 
 // ---------------------------------------------------------------- host side
-size_t rup256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct Layout {                // workspace: status, records, tables, grey / edge plane, CLAHE / dilated plane, magnitudes, labels, flags
   size_t recs, luts, grey, cl, mag, labels, flags, total;
 };
