@@ -224,7 +224,7 @@ int  uwm_pair_mask_u8(const uint8_t* wm, size_t wm_bytes, const uwm_image_desc* 
 /* Logo-watermarked training samples: the LOGO branch of the reference's src/scripts/gen_data.py (apply_watermark_effects,
  * resize_watermark, generate_multiple_watermarks_image / generate_watermarked_image, calculate_overlap_area, and main()'s
  * single/multi and transparent/normal choices).  Text and mixed watermarks are uwm_synth_text_u8's, below; the JPEG quality=95 save
- * and a device-resident logo bank are NOT served.  A JOB is one logo on one image.  The HOST draws every random number, computes every size and does the placement
+ * is uwm_jpeg_ragged_u8's; a device-resident logo bank is NOT served.  A JOB is one logo on one image.  The HOST draws every random number, computes every size and does the placement
  * loop (data.sample_synth_jobs); the device only executes descriptors, so a batch is a pure function of its inputs.  Stages, in
  * order, on an RGBA patch (uint8, R G B A interleaved); MULDIV255(x, y) = (t = x*y + 128, ((t >> 8) + t) >> 8):
  *   1 RESIZE to (w1, h1) = Image.resize(LANCZOS) on RGBA.  Equal size: a copy.  Else premultiply c = MULDIV255(c, a); the horizontal
@@ -645,6 +645,31 @@ int  uwm_aug_lab_tables(int which, const void** data, int* count, int* elem_byte
 size_t uwm_jpeg_workspace_bytes(int N, int H, int W);      /* 0 (and an error message) for a bad shape */
 int  uwm_jpeg_u8(const uint8_t* images, const int* quality, int N, int H, int W, const float* mean, const float* std, void* workspace,
                  size_t workspace_bytes, float* out_nchw, uint8_t* out_u8, uwm_stream stream);
+/* The JPEG save of the reference's gen_data.py (quality 95: the final save, gen_data.py:908, and the temporary file between the logos
+ * and the text of a mixed sample, gen_data.py:402-410): uwm_jpeg_u8's round trip for a RAGGED batch, every image at its own size, any
+ * h and w >= 1.  in / out: packed uint8 RGB images of `bytes` bytes (4-byte aligned) with one uwm_image_desc each (DEVICE memory,
+ * 8-byte aligned); out may be in itself, and must not overlap it otherwise.  quality: DEVICE int[N] (4-byte aligned), 0 = the image is
+ * left as it is, else 1..100 (the kernels clamp to 0..100; a host wrapper should refuse other values).  C must be 3.  max_pixels: an
+ * upper bound of h*w over the batch, below 2^31 - 1; it sizes the launches.  workspace: device memory, 8-byte aligned, at least
+ * uwm_jpeg_ragged_workspace_bytes(N, bytes) = bytes bytes, apart from in and out: image i's reconstructed planes (Y [h][w], Cb and Cr
+ * [hc][wc], hc = ceil(h/2), wc = ceil(w/2)) lie back to back at the image's own offset, h*w + 2*hc*wc <= 3*h*w.  Two launches of
+ * N * K workgroups on the caller's stream, K from max_pixels alone, geometry read on the device, no host synchronisation: one captured
+ * graph serves every batch of N images with these `bytes` and `max_pixels`.  An image whose descriptor does not fit (a side < 1, more than
+ * max_pixels pixels, not inside `bytes`) is skipped: nothing of it is read or written.  No read leaves [in, in+bytes), no write
+ * [out, out+bytes) or the workspace.
+ *   The rule is uwm_jpeg_u8's (tables, colour conversion, DCTs, quantisation) with libjpeg's edges (tests/jpeg_any_ref.py is the numpy
+ * form, held to Pillow bit for bit); c8(x) = x rounded up to a multiple of 8:
+ *   Y: the last column and the last row are replicated out to c8(h) x c8(w); its 8 x 8 blocks go through the luminance table; crop.
+ *   Cb, Cr: COLUMNS are replicated at full resolution, in front of the down-sampling, and so is an odd last row; ROWS are replicated
+ *     behind it.  Down-sampled sample (r, c) of the c8(hc) x c8(wc) plane is the 2 x 2 mean (bias 1 in even c, 2 in odd c) of image
+ *     rows 2r' and min(2r'+1, h-1), r' = min(r, hc-1), and columns min(2c, w-1) and min(2c+1, w-1).  Its blocks go through the
+ *     chrominance table; crop to hc x wc.
+ *   up-sampling: wc > 2: the "fancy" filter above on the cropped hc x wc plane, neighbours clamped to it, cropped to h x w;
+ *     wc <= 2: libjpeg falls back to replication, every chroma sample fills its 2 x 2 pixels. */
+size_t uwm_jpeg_ragged_workspace_bytes(int N, size_t bytes);      /* 0 (and an error message) for arguments out of range */
+int  uwm_jpeg_ragged_u8(const uint8_t* in, uint8_t* out /* may be in */, size_t bytes, const uwm_image_desc* descs /* device */,
+                        const int* quality /* device int[N] */, int N, int C /* 3 */, long long max_pixels, void* workspace,
+                        size_t workspace_bytes, uwm_stream stream);
 /* 3x3/stride-1 convolutions (forward, dgrad and weight gradient) run as Winograd F(2x2,3x3) on the fp32 MFMA path by
  * default (2.25x fewer multiplies, results within a few fp32 ulps of the direct form); mode 0 selects the direct
  * kernels everywhere; 2 (tests) prefers the 512-thread Winograd variant wherever its shape rules allow, whatever the

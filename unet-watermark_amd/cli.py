@@ -134,7 +134,10 @@ def _datasets(cfg, synthetic, device_input=None):
 
 def _check_synthesize(args, augment):
     """the refusals of `train --synthesize`, before any device work"""
+    quality = _check_jpeg_quality(getattr(args, "synth_jpeg_quality", 0), "--synth-jpeg-quality")
     if not getattr(args, "synthesize", False):
+        if quality:
+            raise ValueError("--synth-jpeg-quality is the JPEG save of the samples that --synthesize makes: give --synthesize as well")
         return
     if args.synthetic:
         raise ValueError("--synthesize and --synthetic exclude each other: --synthetic N trains on a toy generator's images, --synthesize "
@@ -146,6 +149,18 @@ def _check_synthesize(args, augment):
     if not args.clean_dir or (not args.logos_dir and float(args.text_watermark_ratio) < 1):
         raise ValueError("--synthesize needs --clean-dir (clean photographs) and --logos-dir (logo images; only --text-watermark-ratio 1 "
                          "does without)")
+
+
+def _check_jpeg_quality(value, flag):
+    """-> the quality of a synthesis flag as an int; ValueError, before any device work, unless it is 0 (no round trip) or 1..100"""
+    from .data import check_jpeg_quality
+    return check_jpeg_quality(value, flag)
+
+
+_JPEG_QUALITY_HELP = ("send every synthesized image through a baseline 4:2:0 JPEG round trip of this quality on the device (1..100), at "
+                      "its own size, bit-equal to Pillow's save and reload; a mixed sample also once between its logos and its text.  The "
+                      "reference's value is 95 (gen_data.py saves every sample so); 0 (default) = no round trip, and a command without the "
+                      "flag produces byte-identical results")
 
 
 def _check_text_ratios(args):
@@ -181,7 +196,7 @@ def _synth_datasets(cfg, args):
     kw = dict(seed=int(args.synth_seed), transparent_ratio=float(args.transparent_ratio), multi_watermark_ratio=float(args.multi_watermark_ratio),
               max_watermarks=int(args.synth_max_watermarks), mask_threshold=int(cfg.DATA.GENERATE_MASK_THRESHOLD), mask_source=args.synth_mask,
               text_watermark_ratio=float(args.text_watermark_ratio), mixed_watermark_ratio=float(args.mixed_watermark_ratio),
-              fonts_dir=args.fonts_dir, texts_file=args.texts_file)
+              fonts_dir=args.fonts_dir, texts_file=args.texts_file, jpeg_quality=int(getattr(args, "synth_jpeg_quality", 0)))
     train, val = RawSynthDataset(args.clean_dir, args.logos_dir, **kw), RawSynthDataset(args.clean_dir, args.logos_dir, **kw)
     n = len(train)
     g = torch.Generator().manual_seed(int(cfg.DATA.SEED))
@@ -515,7 +530,8 @@ def masks_command(args):
 
 def synth_command(args):
     """The reference's src/scripts/gen_data.py on the device: --count samples into <output-dir>/watermarked (PNG, so the pixels are
-    the device's; the reference saves JPEG quality 95), a same-named copy of the clean image into <output-dir>/clean — which is what
+    the device's; the reference saves JPEG quality 95, and --jpeg-quality 95 puts exactly that round trip into the pixels on the device:
+    the files then hold what `train --synthesize --synth-jpeg-quality 95` sees), a same-named copy of the clean image into <output-dir>/clean — which is what
     lets RawPairDataset derive the masks — and, with --generate-mask, the script's own masks into <output-dir>/masks: the pasted alpha
     planes, for a mixed sample the logos' plane halved and then the maximum with the text's.  (That halved part never survives the
     reference dataset's binarisation at 127 — the script's quirk, kept — which is one reason why masks from pairs are the default
@@ -524,8 +540,9 @@ def synth_command(args):
     import random
     import numpy as np
     from PIL import Image
-    from .data import device_synth, device_synth_text, mask_descs_for, pack_images
+    from .data import device_jpeg_ragged, device_synth, device_synth_text, mask_descs_for, pack_images
     from .data.datasets import read_u8
+    quality = _check_jpeg_quality(getattr(args, "jpeg_quality", 0), "--jpeg-quality")
     if int(args.count) < 1:
         raise ValueError("synth: --count must be >= 1")
     _check_text_ratios(args)
@@ -547,7 +564,7 @@ def synth_command(args):
     for b in range(0, int(args.count), bs):
         idx = list(range(b, min(b + bs, int(args.count))))
         which = [pick.randrange(len(ds)) for _ in idx]       # the script picks a clean image at random for every sample
-        cleans, logos, jobs, planes, text_jobs, names = [], [], [], [], [], []
+        cleans, logos, jobs, planes, text_jobs, names, mixed = [], [], [], [], [], [], []
         for n, i in zip(idx, which):
             ds.set_epoch(n)                                   # sample n's draws: a function of (seed, n, clean image)
             clean = read_u8(ds.files[i], "RGB")
@@ -555,6 +572,7 @@ def synth_command(args):
             j = np.array(j, copy=True); j["logo"] += len(logos)
             tj = np.array(tj, copy=True); tj["glyph"] += len(planes)
             cleans.append(clean); logos += list(lg); jobs.append(j); planes += [a[..., None] for a in pl]; text_jobs.append(tj)
+            mixed.append(len(pl) > 0 and bool((j["enabled"] != 0).any()))
             count = int((j["enabled"] != 0).sum())
             prefix = "multi_" if kind == "logo" and count > 1 else "" if kind == "logo" else kind + "_"
             names.append(f"{prefix}{'trans' if transparent else 'norm'}_{n:06d}")
@@ -563,10 +581,14 @@ def synth_command(args):
         if logos:
             pl, dl, _ = pack_images(logos)
             out, mask = device_synth(out, dc, pl.to(device), dl, np.stack(jobs), with_mask=bool(args.generate_mask), inplace=True)
+        if quality and any(mixed):                            # the temporary file between the logos and the text of a mixed sample
+            out = device_jpeg_ragged(out, dc, np.where(mixed, quality, 0), inplace=True)
         if planes:
             pp, dp, _ = pack_images(planes)
             out, mask = device_synth_text(out, dc, pp.to(device), dp, np.stack(text_jobs), inplace=True, mask_mode=1,
                                           masks=(mask if mask is not None else True) if args.generate_mask else None)
+        if quality:                                           # the save of the finished sample
+            out = device_jpeg_ragged(out, dc, np.full(len(idx), quality), inplace=True)
         out = out.cpu().numpy()
         mask = mask.cpu().numpy() if mask is not None else None
         for name, clean, d, m in zip(names, cleans, dc, mask_descs_for(dc)):
@@ -751,6 +773,7 @@ def build_parser():
                          "takes the pasted alpha planes, which the reference binarises at 127, so low-opacity samples get nearly empty masks")
     tp.add_argument("--synth-seed", type=int, default=42, help="--synthesize: seed of the draws")
     _add_text_arguments(tp, "--synthesize: ")
+    tp.add_argument("--synth-jpeg-quality", type=int, default=0, help="--synthesize: " + _JPEG_QUALITY_HELP)
     sp = sub.add_parser("synth", help="write logo-, text- and mixed-watermarked samples (the reference's scripts/gen_data.py) made on the device")
     sp.add_argument("--clean-dir", type=str, required=True)
     sp.add_argument("--logos-dir", type=str, default=None, help="directory of logos (required unless --text-watermark-ratio 1)")
@@ -760,6 +783,7 @@ def build_parser():
     sp.add_argument("--transparent-ratio", type=float, default=0.6); sp.add_argument("--multi-watermark-ratio", type=float, default=0.4)
     sp.add_argument("--max-watermarks", type=int, default=3); sp.add_argument("--batch-size", type=int, default=None)
     _add_text_arguments(sp, "")
+    sp.add_argument("--jpeg-quality", type=int, default=0, help=_JPEG_QUALITY_HELP + "; the files stay PNG, so they hold exactly these pixels")
     mp = sub.add_parser("masks", help="derive masks/<stem>.png from watermarked / clean pairs on the device, for every pair without one")
     mp.add_argument("--data-dir", type=str, default=None, help="DATA.ROOT_DIR: the directory with watermarked/, clean/ and masks/")
     mp.add_argument("--config", type=str, default=None)

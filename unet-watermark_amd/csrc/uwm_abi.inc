@@ -867,6 +867,37 @@ int uwm_jpeg_u8(const uint8_t* images, const int* quality, int N, int H, int W, 
   LCHK(launch_jpeg_u8(images, quality, N, H, W, mean, std, workspace, workspace_bytes, out_nchw, out_u8, (hipStream_t)stream));
   return 0;
 }
+// ---- the JPEG save of the synthesis chain (jpeg_ragged_u8.hip): every refusal comes before any launch
+static int jpeg_ragged_caps_check(const char* fn, int N, size_t bytes) {
+  if (N < 1 || N > 65535) return fail("%s: N must be 1 .. 65535 (got %d)", fn, N);
+  if (bytes < 1 || bytes > ((size_t)1 << 42)) return fail("%s: bytes must be 1 .. 2^42 (got %zu)", fn, bytes);
+  return 0;
+}
+size_t uwm_jpeg_ragged_workspace_bytes(int N, size_t bytes) {
+  if (jpeg_ragged_caps_check("uwm_jpeg_ragged_workspace_bytes", N, bytes)) return 0;
+  return bytes;                                                              // image i's planes lie at the image's own offset
+}
+int uwm_jpeg_ragged_u8(const uint8_t* in, uint8_t* out, size_t bytes, const uwm_image_desc* descs, const int* quality, int N, int C,
+                       long long max_pixels, void* workspace, size_t workspace_bytes, uwm_stream stream) {
+  const char* fn = "uwm_jpeg_ragged_u8";
+  if (!in || !out || !descs || !quality || !workspace) return fail("%s: null argument", fn);
+  if (C != 3) return fail("%s: C must be 3 (RGB images; got %d)", fn, C);
+  if (jpeg_ragged_caps_check(fn, N, bytes)) return 1;
+  if (max_pixels < 1) return fail("%s: max_pixels must be >= 1 (got %lld)", fn, max_pixels);
+  if (max_pixels >= 2147483647ll) return fail("%s: max_pixels too large: it must be below 2^31 - 1 (got %lld)", fn, max_pixels);
+  if (in != out && (uintptr_t)in < (uintptr_t)out + bytes && (uintptr_t)out < (uintptr_t)in + bytes)
+    return fail("%s: out must be in itself or not overlap it", fn);
+  if (((uintptr_t)in | (uintptr_t)out) & 3) return fail("%s: in and out must be 4-byte aligned", fn);
+  if ((uintptr_t)quality & 3) return fail("%s: quality must be 4-byte aligned", fn);
+  if (((uintptr_t)descs | (uintptr_t)workspace) & 7) return fail("%s: descriptors and the workspace must be 8-byte aligned", fn);
+  if (workspace_bytes < bytes) return fail("%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes, bytes);
+  if ((uintptr_t)workspace < (uintptr_t)out + bytes && (uintptr_t)out < (uintptr_t)workspace + bytes)
+    return fail("%s: the workspace must not overlap out", fn);
+  if ((uintptr_t)workspace < (uintptr_t)in + bytes && (uintptr_t)in < (uintptr_t)workspace + bytes)
+    return fail("%s: the workspace must not overlap in", fn);
+  LCHK(launch_jpeg_ragged_u8(in, out, bytes, (const ImageDesc*)descs, quality, N, max_pixels, workspace, workspace_bytes, (hipStream_t)stream));
+  return 0;
+}
 int uwm_scale(float* p, long long n, float s, uwm_stream stream) {
   if (!p || n < 1) return fail("uwm_scale: bad argument");
   LCHK(launch_scale(p, (size_t)n, s, (hipStream_t)stream));

@@ -415,6 +415,15 @@ size_t jpeg_workspace_bytes(int N, int H, int W);      // 0 for a bad shape (H, 
 // images [N][H][W][3], quality DEVICE int[N] (0 = unchanged, else 1..100) -> out_f fp32 NCHW (Normalize = pre_norm) and / or the bytes out_u8
 hipError_t launch_jpeg_u8(const uint8_t* img, const int* quality, int N, int H, int W, const float* mean, const float* std, void* workspace,
                           size_t workspace_bytes, float* out_f, uint8_t* out_u8, hipStream_t st);
+// ---- the same round trip for a ragged batch, every image at its own size (jpeg_ragged_u8.hip; the edge rule: include/uwm.h)
+struct ImageDesc;
+constexpr int kJpegRaggedMaxBlocks = 512;              // most workgroups per image in either pass
+constexpr long long kJpegRaggedPixelsPerBlock = 2048;  // K = ceil(max_pixels / this), 1 .. kJpegRaggedMaxBlocks: grid = N * K (measured)
+int jpeg_ragged_blocks_per_image(long long max_pixels);
+// image i of the packed batch (descs, quality: DEVICE memory; quality 0 = unchanged, else 1..100) -> out + descs[i].offset; out may be
+// in.  The workspace holds `bytes` bytes.  No read leaves [in, in + bytes), no write [out, out + bytes) or the workspace
+hipError_t launch_jpeg_ragged_u8(const uint8_t* in, uint8_t* out, size_t bytes, const ImageDesc* descs, const int* quality, int N,
+                                 long long max_pixels, void* workspace, size_t workspace_bytes, hipStream_t st);
 // One output pixel (Y, X) of the bilinear resize of a logit plane b[h][w] (element stride ld) by sy = h / H, sx = w / W: ONE function
 // for resize_threshold_kernel (loss.hip) and resize_threshold_ragged_kernel (resize_u8.hip), so that a ragged batch's masks are the
 // uniform call's bit for bit

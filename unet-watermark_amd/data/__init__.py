@@ -7,7 +7,8 @@ baseline JPEG round trip on the device (device_jpeg, sample_transparent_recipe; 
 Images of any size travel as one packed buffer (ragged).  An image without a mask file gets the mask the reference derives from its
 clean counterpart, also on the device (pairmask: device_pair_mask; RawPairDataset), and logo-watermarked samples are
 synthesized there (synth: device_synth; RawSynthDataset; DESIGN.md §8i), as are text and mixed ones (synthtext: device_synth_text;
-DESIGN.md §8o).
+DESIGN.md §8o); the JPEG save the reference ends its synthesis with runs there at each image's own size (jpegragged:
+device_jpeg_ragged).
 Every name is used as data.NAME; the modules below say where it lives."""
 from __future__ import annotations
 
@@ -28,6 +29,7 @@ from .augment import (AUG_DESC_DTYPE, AUG_EXT_DTYPE, AUG_HFLIP, AUG_RECIPES, AUG
                       identity_aug_params, motion_kernel, random_aug_flags, sample_aug_params, sample_aug_recipe, sample_recipe,
                       sample_transparent_recipe)
 from .pairmask import device_pair_mask, stage_clean  # noqa: F401
+from .jpegragged import SYNTH_JPEG_QUALITY, check_jpeg_quality, device_jpeg_ragged  # noqa: F401
 from .synth import (SYNTH_JOB_DTYPE, SYNTH_MAX_SIDE, SYNTH_MAX_SLOTS, SYNTH_SLOTS, _overlap_area, _plain_job, _sample_effects,  # noqa: F401
                     device_synth, empty_synth_jobs, sample_synth_choice, sample_synth_jobs, synth_blur_params, synth_job_needs,
                     synth_opacity_lut, synth_rotate_setup, synth_shear_inverse)

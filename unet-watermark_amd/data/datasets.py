@@ -9,6 +9,7 @@ import torch
 from torch.utils.data import Dataset
 
 from ..constants import IMAGENET_MEAN, IMAGENET_STD
+from .jpegragged import check_jpeg_quality
 from .synth import SYNTH_SLOTS, sample_synth_choice, sample_synth_jobs
 from .synthtext import FontSet, empty_text_jobs, load_texts, sample_synth_kind, sample_text_item
 
@@ -198,13 +199,18 @@ class RawSynthDataset(Dataset):
     With either above 0 an item is (clean, logos, jobs, planes, text_jobs): planes a list of at most one uint8 (ch, cw) coverage
     plane that the worker rasterised (render_text_plane; fonts of fonts_dir or Pillow's embedded one, texts of texts_file or
     DEFAULT_TEXTS), text_jobs [1] of TEXT_JOB_DTYPE; a text sample has no logo job, a logo sample no text job.  With both 0 nothing
-    more is drawn and items are the three-tuples above.  Not served: the temporary JPEG quality-95 file the script writes between the
-    logos and the text of a mixed sample."""
+    more is drawn and items are the three-tuples above.
+
+    jpeg_quality (the reference saves at 95; 0 here = no round trip, so that a dataset made without it yields what it always has): the
+    items stay what they are; DeviceInputPipeline sends every synthesized image through uwm_jpeg_ragged_u8 at this quality behind the
+    last stage — in front of the masks from pairs, as the reference's dataset sees its files — and a mixed sample once more between its
+    logos and its text (the temporary file the script writes there)."""
 
     def __init__(self, clean_dir, logos_dir, seed=42, transparent_ratio=0.6, multi_watermark_ratio=0.4, max_watermarks=3,
                  mask_threshold=None, mask_source="pair", cache=64, text_watermark_ratio=0.0, mixed_watermark_ratio=0.0, fonts_dir=None,
-                 texts_file=None):
+                 texts_file=None, jpeg_quality=0):
         from PIL import Image  # noqa: F401
+        self.jpeg_quality = check_jpeg_quality(jpeg_quality, "RawSynthDataset: jpeg_quality")
         self.text_ratio, self.mixed_ratio = check_synth_ratios(text_watermark_ratio, mixed_watermark_ratio)
         if not os.path.isdir(clean_dir):
             raise ValueError(f"RawSynthDataset: clean directory not found: {clean_dir}")

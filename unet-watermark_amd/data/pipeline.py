@@ -5,6 +5,7 @@ import torch
 from ..constants import IMAGENET_MEAN, IMAGENET_STD
 from .augment import device_augment, device_jpeg, device_preprocess, sample_recipe
 from .datasets import DeviceU8Dataset, RawSynthDataset
+from .jpegragged import device_jpeg_ragged
 from .pairmask import device_pair_mask, stage_clean
 from .ragged import device_resize, mask_descs_for, pack_images
 from .synth import device_synth
@@ -74,7 +75,11 @@ class DeviceInputPipeline:
         coverage planes and paste the texts (uwm_synth_text_u8); take the masks from (synthesized, clean) with uwm_pair_mask_u8 — the
         reference's default flow, gen_data.py writes no masks unless asked — or, mask_source 'alpha', from the pasted alpha planes
         (mixed samples by the script's rule: the logos' plane halved, then the maximum with the text's); then resize as ever.  A
-        dataset with both ratios 0 yields three-tuples, and this path then launches exactly what it did without text synthesis."""
+        dataset with both ratios 0 yields three-tuples, and this path then launches exactly what it did without text synthesis.
+        A dataset with a jpeg_quality sends every image through uwm_jpeg_ragged_u8 behind the last stage — in front of the masks from
+        pairs, so those come from the compressed image as the reference's dataset takes them; masks from the alpha planes stay — and
+        the mixed samples of the batch (an enabled logo job and a text) once more between the logos and the text; with quality 0
+        neither launch happens."""
         cleans = [np.ascontiguousarray(it[0]) for it in items]
         logos, jobs, planes, text_jobs = [], [], [], []
         for it in items:
@@ -88,6 +93,8 @@ class DeviceInputPipeline:
                 planes += [np.ascontiguousarray(a)[..., None] for a in it[3]]
                 text_jobs.append(t)
         alpha = self.source.mask_source == "alpha"
+        quality = int(getattr(self.source, "jpeg_quality", 0))
+        mixed = [len(it) > 3 and len(it[3]) > 0 and bool((it[2]["enabled"] != 0).any()) for it in items]
         if not alpha and self.mask_threshold is None:
             raise ValueError("synthesized samples with masks from pairs need mask_threshold (DATA.GENERATE_MASK_THRESHOLD)")
         with torch.cuda.device(self.device):
@@ -98,9 +105,13 @@ class DeviceInputPipeline:
             else:                                                # a batch of text samples only
                 synth = pc.clone()
                 pm = torch.zeros(sum(a.shape[0] * a.shape[1] for a in cleans), dtype=torch.uint8, device=self.device) if alpha else None
+            if quality and any(mixed):                           # the temporary file between the logos and the text
+                synth = device_jpeg_ragged(synth, dc, np.where(mixed, quality, 0), inplace=True)
             if planes:
                 pp, dp = self._upload(planes, 1)
                 synth, pm = device_synth_text(synth, dc, pp, dp, np.stack(text_jobs), masks=pm, mask_mode=1, inplace=True)
+            if quality:                                          # the save of the finished sample
+                synth = device_jpeg_ragged(synth, dc, np.full(len(items), quality), inplace=True)
             if not alpha:
                 pm = device_pair_mask(synth, dc, pc, dc, self.mask_threshold)
             x = device_resize(synth, dc, self.size, 3, "linear")
