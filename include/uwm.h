@@ -197,6 +197,51 @@ int  uwm_predict_images_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, c
                            size_t mask_bytes, float* logits, void* workspace, size_t workspace_bytes, int N, int H, int W,
                            uwm_stream stream);
 
+/* Prediction at NATIVE resolution (no counterpart in the reference, which always resizes to IMG_SIZE): every image of a ragged batch
+ * (as above) is cut into model-sized overlapping tiles on the device, the tiles go through the eval forward in batches of N, and the
+ * tile logits are blended into one plane per image at the image's own size.  (the host side of the plan:
+ * unet_watermark_amd/tiling.py.)
+ *   The plan, per axis of length len with tile side T (<= 1024) and S = T - overlap, overlap an integer in [0, T / 2]:
+ *     len <= T : one tile at origin 0;   len > T : n = ceil((len - T) / S) + 1 tiles at o_j = min(j * S, len - T)
+ *   Tiles of an image are ordered row-major (jy outer, jx inner).  The tile table holds one uwm_tile_desc per tile, all images' plans
+ *   back to back (`first`: the index of the image's first tile), padded to K entries with image = -1; one uwm_tile_image per image
+ *   holds {first, ny, nx}.  Both live in DEVICE memory (4-byte aligned) and are checked there.
+ * uwm_op_tile_norm_u8_nhwc4 (the gather): out[k][y][x][c] = Normalize(image[R(y0 + y, h)][R(x0 + x, w)][c]) as fp32 [K][T_h][T_w][4]
+ *   (16-byte aligned, padding channels zero), the arithmetic of uwm_op_preprocess_u8_nhwc4; R = BORDER_REFLECT_101
+ *   (cv2.borderInterpolate: period 2 (len - 1), len 1 gives 0), which only moves a coordinate where the tile leaves the image.  A tile
+ *   is written as zeros when image = -1 or out of range, when its origin is negative or beyond the image, or when the image's
+ *   descriptor does not fit [0, src_bytes).  The grid is sized from K and T_h; no read leaves [src, src + src_bytes).
+ * uwm_tile_blend_threshold_ragged (the blend): tile_logits is the store [K][T_h][T_w].  Output pixel (y, x) of image i collects the
+ *   tiles that cover it in ascending (jy, jx) order; the covering range of an axis follows from (n, S, T, len) by arithmetic.  With
+ *   w1(t) = min(t + 1, T - t), t the coordinate inside the tile, and the integer weight w = w1(ty) * w1(tx):
+ *     one covering tile:  v = its logit, unchanged
+ *     otherwise:          acc = w_0 * l_0;  acc += w_k * l_k in order;  v = acc / sum(w)      every operation rounded to fp32 on its own
+ *   mask[out_descs[i].offset + y * w + x] = (apply_sigmoid ? 1.f / (1.f + expf(-v)) : v) > threshold ? 255 : 0, and, where logits_out
+ *   is not NULL, logits_out[out_descs[i].offset + y * w + x] = v (a buffer of mask_bytes floats).  One thread per pixel gathers: no
+ *   atomics, the result does not depend on the schedule.  An image whose mask region does not fit [0, mask_bytes) is skipped; one
+ *   whose plan entry disagrees with the formula or does not fit K, or whose in_descs entry (in_descs may be NULL: not checked) has
+ *   another size or does not fit [0, src_bytes) at C bytes per pixel, gets zeros.  No write leaves the outputs.
+ * uwm_predict_tiled_u8: for each of the K / N chunks of the tile table (K a multiple of N) the gather into the forward's input, the
+ *   eval forward of (N, T_h, T_w) (frozen or not), and a copy of the N logit planes into the store; then one blend.  The workspace
+ *   (16-byte aligned, uwm_predict_tiled_workspace_bytes) holds the forward's and, as its last K * T_h * T_w floats, the store.
+ *   Capturable: no host synchronisation, allocation or copy; the launch count depends on K / N alone.  Every argument is checked
+ *   before any launch. */
+typedef struct { int image, y0, x0, first; } uwm_tile_desc;
+typedef struct { int first, ny, nx, reserved; } uwm_tile_image;
+int    uwm_op_tile_norm_u8_nhwc4(const uint8_t* src, size_t src_bytes, const uwm_image_desc* descs, int num_images,
+                                 const uwm_tile_desc* tiles, int K, int C, int T_h, int T_w, const float* mean, const float* std,
+                                 float* out, uwm_stream stream);
+int    uwm_tile_blend_threshold_ragged(const float* tile_logits, int K, const uwm_tile_image* plans, int num_images, int T_h, int T_w,
+                                       int overlap, const uwm_image_desc* in_descs /* may be NULL */, size_t src_bytes, int C,
+                                       const uwm_image_desc* out_descs, float threshold, int apply_sigmoid, uint8_t* mask,
+                                       size_t mask_bytes, float* logits_out /* may be NULL */, uwm_stream stream);
+size_t uwm_predict_tiled_workspace_bytes(uwm_handle h, int N, int K, int T_h, int T_w);
+int    uwm_predict_tiled_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, const uwm_image_desc* in_descs, int num_images,
+                            const uwm_tile_desc* tiles, int K, const uwm_tile_image* plans, int T_h, int T_w, int overlap,
+                            const float* mean, const float* std, float threshold, int apply_sigmoid, const uwm_image_desc* out_descs,
+                            uint8_t* mask, size_t mask_bytes, float* logits_out, void* workspace, size_t workspace_bytes, int N,
+                            uwm_stream stream);
+
 /* Masks from watermarked / clean pairs: the reference's WatermarkDataset._generate_mask with use_blurred_mask = False
  * (src/utils/dataset.py:197-211,277-278), which serves every image that has a clean counterpart and no mask file.  wm, clean and mask
  * are ragged batches as above (uint8 RGB interleaved, C = 3; masks one byte per pixel at any alignment); image i, at its OWN size:

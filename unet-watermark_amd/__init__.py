@@ -28,3 +28,4 @@ from .select import ModelSelector, run_selection  # noqa: F401,E402
 from .extract import WatermarkExtractor, extract_regions, plan_cutouts, extract_cutouts  # noqa: F401,E402
 from .textenh import enhance_text_features, text_enhance_ragged  # noqa: F401,E402
 from .train import FusedAdam, FusedAdamW  # noqa: F401,E402
+from .tiling import plan_tiles, plan_batch  # noqa: F401,E402

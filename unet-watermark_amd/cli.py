@@ -450,6 +450,13 @@ def predict_command(args):
     if text_enhance and args.resize != "device":
         raise ValueError("--text-enhance needs --resize device: the reference's text-feature enhancement works on every image at its own "
                          "size, which only the ragged device path serves (--resize host resizes on the host first)")
+    tile = bool(getattr(args, "tile", False))
+    if tile and args.resize != "device":
+        raise ValueError("--tile needs --resize device: tiles are cut from every image at its own size, which only the ragged device "
+                         "path serves (--resize host resizes on the host first)")
+    if tile and text_enhance:
+        raise ValueError("--tile cannot be combined with --text-enhance: enhancing the images before they are cut into tiles is not "
+                         "built yet; run one or the other")
     cfg = get_cfg_defaults()
     if args.config and os.path.exists(args.config):
         update_config(cfg, args.config)
@@ -466,6 +473,12 @@ def predict_command(args):
     for i in range(0, len(files), bs):
         chunk = files[i:i + bs]
         ims = [Image.open(os.path.join(args.input, f)).convert("RGB") for f in chunk]
+        if tile:                                               # native resolution: overlapping IMG_SIZE tiles, blended on the device
+            masks = pred.predict_images_tiled([np.asarray(im, dtype=np.uint8) for im in ims], int(args.tile_overlap), args.sigmoid,
+                                              args.mask_type, use_graph=len(chunk) == bs, tile_batch=bs)
+            for f, m in zip(chunk, masks):
+                Image.fromarray(m.cpu().numpy()).save(os.path.join(args.output, os.path.splitext(f)[0] + "_mask.png"))
+            continue
         if args.resize == "device":                            # cv2-convention resize on the device, both ways, in one call
             masks = pred.predict_images([np.asarray(im, dtype=np.uint8) for im in ims], args.sigmoid, args.mask_type,
                                         use_graph=len(chunk) == bs, text_enhance=text_enhance)
@@ -869,6 +882,11 @@ def build_parser():
                     help="run the reference's _enhance_text_features (CLAHE, Canny, dilate, x 1.2 on the edges, sharpen) on every image on "
                          "the device before the network sees it; needs --resize device.  Independent of --mask-type: the reference's "
                          "predict_text_watermark_mask is --mask-type text --text-enhance")
+    pp.add_argument("--tile", action="store_true",
+                    help="predict at native resolution: cut every image into overlapping IMG_SIZE x IMG_SIZE tiles on the device, run them "
+                         "through the network --batch-size at a time and blend the tile logits into one mask at the image's own size "
+                         "(no counterpart in the reference, which always resizes); needs --resize device, not with --text-enhance")
+    pp.add_argument("--tile-overlap", type=int, default=64, help="pixels neighbouring tiles share, 0 .. IMG_SIZE / 2 (with --tile)")
     return ap
 
 

@@ -430,6 +430,101 @@ int uwm_predict_images_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, co
   LCHK(launch_resize_threshold_ragged(lg, h->CP, N, H, W, (const ImageDesc*)out_descs, threshold, apply_sigmoid, mask, mask_bytes, st));
   return 0;
 }
+// ---- prediction at native resolution (tile_u8.hip): every argument is checked here, before any launch (the tile table, the plans and
+// the descriptors are device memory: the kernels check them)
+static_assert(sizeof(uwm_tile_desc) == sizeof(TileDesc) && sizeof(uwm_tile_desc) == 16 && offsetof(uwm_tile_desc, first) == offsetof(TileDesc, first) &&
+              sizeof(uwm_tile_image) == sizeof(TileImage) && sizeof(uwm_tile_image) == 16 && offsetof(uwm_tile_image, nx) == offsetof(TileImage, nx),
+              "uwm_tile_desc / uwm_tile_image layout");
+static int tile_shape_check(const char* fn, int K, int T_h, int T_w, int overlap) {
+  if (K < 1) return fail("%s: K must be >= 1 (got %d)", fn, K);
+  if (T_h < 1 || T_w < 1 || T_h > kTileMaxSide || T_w > kTileMaxSide) return fail("%s: tile sides must be 1..%d (got %d x %d)", fn, kTileMaxSide, T_h, T_w);
+  if (overlap < 0 || 2 * overlap > (T_h < T_w ? T_h : T_w)) return fail("%s: overlap must lie in [0, T / 2] on both axes (tile %d x %d, got %d)", fn, T_h, T_w, overlap);
+  if ((long long)K * ((T_h + kTileRowsPerBlock - 1) / kTileRowsPerBlock) > 2147483647ll) return fail("%s: K * T_h too large for one launch (%d x %d)", fn, K, T_h);
+  return 0;
+}
+int uwm_op_tile_norm_u8_nhwc4(const uint8_t* src, size_t src_bytes, const uwm_image_desc* descs, int num_images, const uwm_tile_desc* tiles, int K,
+                              int C, int T_h, int T_w, const float* mean, const float* std, float* out, uwm_stream stream) {
+  if (!src || !descs || !tiles || !mean || !std || !out) return fail("uwm_op_tile_norm_u8_nhwc4: null argument");
+  if (tile_shape_check("uwm_op_tile_norm_u8_nhwc4", K, T_h, T_w, 0)) return 1;
+  if (C < 1 || C > 4) return fail("uwm_op_tile_norm_u8_nhwc4: C must be 1..4 (got %d)", C);
+  if (num_images < 1 || src_bytes < 1) return fail("uwm_op_tile_norm_u8_nhwc4: num_images and src_bytes must be >= 1 (got %d, %zu)", num_images, src_bytes);
+  if ((uintptr_t)src & 3) return fail("uwm_op_tile_norm_u8_nhwc4: src must be 4-byte aligned");
+  if (((uintptr_t)descs & 7) || ((uintptr_t)tiles & 3)) return fail("uwm_op_tile_norm_u8_nhwc4: descriptors must be 8-byte, tiles 4-byte aligned");
+  if ((uintptr_t)out & 15) return fail("uwm_op_tile_norm_u8_nhwc4: out must be 16-byte aligned");
+  for (int c = 0; c < C; ++c) if (!(std[c] > 0.f)) return fail("uwm_op_tile_norm_u8_nhwc4: std[%d] must be positive", c);
+  LCHK(launch_tile_norm_u8_nhwc4(src, src_bytes, (const ImageDesc*)descs, num_images, (const TileDesc*)tiles, K, C, T_h, T_w, mean, std, out,
+                                 (hipStream_t)stream));
+  return 0;
+}
+static int tile_blend_args_check(const char* fn, int K, const void* plans, int num_images, int T_h, int T_w, int overlap, const void* in_descs,
+                                 int C, const void* out_descs, float threshold, const void* mask, size_t mask_bytes, const void* logits_out) {
+  if (!plans || !out_descs || !mask) return fail("%s: null argument", fn);
+  if (tile_shape_check(fn, K, T_h, T_w, overlap)) return 1;
+  if (num_images < 1 || mask_bytes < 1) return fail("%s: num_images and mask_bytes must be >= 1 (got %d, %zu)", fn, num_images, mask_bytes);
+  if (num_images > 2147483647 / kTileBlendBlocks) return fail("%s: too many images for one launch (%d)", fn, num_images);
+  if (!std::isfinite(threshold)) return fail("%s: threshold must be finite", fn);
+  if (in_descs && (C < 1 || C > 4)) return fail("%s: C must be 1..4 (got %d)", fn, C);
+  if (((uintptr_t)in_descs | (uintptr_t)out_descs) & 7) return fail("%s: descriptors must be 8-byte aligned", fn);
+  if (((uintptr_t)plans | (uintptr_t)logits_out) & 3) return fail("%s: plans and logits_out must be 4-byte aligned", fn);
+  return 0;
+}
+int uwm_tile_blend_threshold_ragged(const float* tile_logits, int K, const uwm_tile_image* plans, int num_images, int T_h, int T_w, int overlap,
+                                    const uwm_image_desc* in_descs, size_t src_bytes, int C, const uwm_image_desc* out_descs, float threshold,
+                                    int apply_sigmoid, uint8_t* mask, size_t mask_bytes, float* logits_out, uwm_stream stream) {
+  if (!tile_logits) return fail("uwm_tile_blend_threshold_ragged: null argument");
+  if ((uintptr_t)tile_logits & 3) return fail("uwm_tile_blend_threshold_ragged: tile_logits must be 4-byte aligned");
+  if (tile_blend_args_check("uwm_tile_blend_threshold_ragged", K, plans, num_images, T_h, T_w, overlap, in_descs, C, out_descs, threshold, mask,
+                            mask_bytes, logits_out))
+    return 1;
+  LCHK(launch_tile_blend_threshold_ragged(tile_logits, K, (const TileImage*)plans, num_images, T_h, T_w, overlap, (const ImageDesc*)in_descs, src_bytes,
+                                          C, (const ImageDesc*)out_descs, threshold, apply_sigmoid, mask, mask_bytes, logits_out, (hipStream_t)stream));
+  return 0;
+}
+// the workspace of uwm_predict_tiled_u8: the eval plan of (N, T_h, T_w) with the forward's logits behind it, then (256-byte aligned)
+// the tile-logit store [K][T_h][T_w], which is the workspace's tail
+size_t uwm_predict_tiled_workspace_bytes(uwm_handle h, int N, int K, int T_h, int T_w) {
+  if (K < 1 || T_h < 1 || T_w < 1) { (void)fail("uwm_predict_tiled_workspace_bytes: K and the tile sides must be >= 1 (got %d, %d x %d)", K, T_h, T_w); return 0; }
+  const size_t fwd = uwm_predict_workspace_bytes(h, N, T_h, T_w, 1);
+  if (!fwd) return 0;
+  return ((fwd + 255) & ~(size_t)255) + (size_t)K * T_h * T_w * sizeof(float);
+}
+int uwm_predict_tiled_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, const uwm_image_desc* in_descs, int num_images,
+                         const uwm_tile_desc* tiles, int K, const uwm_tile_image* plans, int T_h, int T_w, int overlap, const float* mean,
+                         const float* std, float threshold, int apply_sigmoid, const uwm_image_desc* out_descs, uint8_t* mask, size_t mask_bytes,
+                         float* logits_out, void* ws, size_t ws_bytes, int N, uwm_stream stream) {
+  if (!h || !src || !in_descs || !tiles || !mean || !std || !ws) return fail("uwm_predict_tiled_u8: null argument");
+  if (check_shape(N, T_h, T_w)) return 1;
+  if (tile_blend_args_check("uwm_predict_tiled_u8", K, plans, num_images, T_h, T_w, overlap, in_descs, h->desc.in_channels, out_descs, threshold, mask,
+                            mask_bytes, logits_out))
+    return 1;
+  if (K % N) return fail("uwm_predict_tiled_u8: K must be a multiple of the forward batch N (got %d, %d)", K, N);
+  if (!h->params || !h->buffers) return fail("uwm_predict_tiled_u8: call uwm_bind first");
+  if (src_bytes < 1) return fail("uwm_predict_tiled_u8: src_bytes must be >= 1");
+  const int C = h->desc.in_channels;
+  if (C < 1 || C > 4) return fail("uwm_predict_tiled_u8: the model takes %d channels; images have 1..4", C);
+  for (int c = 0; c < C; ++c) if (!(std[c] > 0.f)) return fail("uwm_predict_tiled_u8: std[%d] must be positive", c);
+  if ((uintptr_t)src & 3) return fail("uwm_predict_tiled_u8: src must be 4-byte aligned");
+  if ((uintptr_t)tiles & 3) return fail("uwm_predict_tiled_u8: tiles must be 4-byte aligned");
+  if ((uintptr_t)ws & 15) return fail("uwm_predict_tiled_u8: workspace must be 16-byte aligned");
+  const size_t need = uwm_predict_tiled_workspace_bytes(h, N, K, T_h, T_w);      // (also plans the eval forward of (N, T_h, T_w))
+  if (!need) return 1;
+  if (ws_bytes < need) return fail("uwm_predict_tiled_u8: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+  const size_t plane = (size_t)T_h * T_w;
+  float* lg = (float*)ws + h->plan.bytes / sizeof(float);                        // the forward's logits: behind the plan
+  float* store = (float*)((char*)ws + (need - (size_t)K * plane * sizeof(float)));
+  h->have_fwd = false;
+  DeviceGuard guard(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  for (int k0 = 0; k0 < K; k0 += N) {
+    LCHK(launch_tile_norm_u8_nhwc4(src, src_bytes, (const ImageDesc*)in_descs, num_images, (const TileDesc*)tiles + k0, N, C, T_h, T_w, mean, std,
+                                   (float*)ws + h->plan.x4, st));
+    if (do_forward(h, nullptr, lg, (float*)ws, N, T_h, T_w, 0, st)) return 1;
+    LCHK(launch_tile_store(lg, h->CP, (size_t)N * plane, store + (size_t)k0 * plane, st));
+  }
+  LCHK(launch_tile_blend_threshold_ragged(store, K, (const TileImage*)plans, num_images, T_h, T_w, overlap, (const ImageDesc*)in_descs, src_bytes, C,
+                                          (const ImageDesc*)out_descs, threshold, apply_sigmoid, mask, mask_bytes, logits_out, st));
+  return 0;
+}
 // ---- the dataset filter (filter_u8.hip): every argument is checked here, before any launch
 size_t uwm_filter_workspace_bytes(int N) {
   const size_t need = filter_workspace_bytes(N);

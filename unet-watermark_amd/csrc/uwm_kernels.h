@@ -453,8 +453,26 @@ hipError_t launch_resize_norm_u8_nhwc4(const uint8_t* src, size_t src_bytes, con
 // logit plane [N][h][w] (stride ld) -> image i's own (h_i, w_i) at mask + offset_i, thresholded; nothing is written outside [mask, mask + mask_bytes)
 hipError_t launch_resize_threshold_ragged(const float* logits, int ld, int N, int h, int w, const ImageDesc* out_descs, float thr,
                                           int apply_sigmoid, uint8_t* mask, size_t mask_bytes, hipStream_t st);
+// ---- prediction at native resolution: overlapping tiles, blended (tile_u8.hip; the rule: include/uwm.h)
+constexpr int kTileRowsPerBlock = 4;                 // tile rows of one gather workgroup: grid = K * ceil(T_h / this)
+constexpr int kTileBlendBlocks = 128;                // workgroups per image in the blend: grid = num_images * this
+constexpr int kTileMaxSide = 1024;                   // the blend's integer weights and their sums are exact in float32 up to this tile side
+struct TileDesc { int image, y0, x0, first; };       // = uwm_tile_desc: one per tile, in DEVICE memory
+struct TileImage { int first, ny, nx, reserved; };   // = uwm_tile_image: one per image, in DEVICE memory
+// tile k = (image, y0, x0) of the packed batch -> Normalize (pre_norm) as fp32 [K][T_h][T_w][4], reflect-101 where the tile leaves the
+// image, zeros for an entry that does not check out.  No read leaves [src, src + src_bytes)
+hipError_t launch_tile_norm_u8_nhwc4(const uint8_t* src, size_t src_bytes, const ImageDesc* descs, int num_images, const TileDesc* tiles, int K,
+                                     int C, int T_h, int T_w, const float* mean, const float* std, float* out, hipStream_t st);
+// channel 0 of logits [npix][ld] -> store [npix]
+hipError_t launch_tile_store(const float* logits, int ld, size_t npix, float* store, hipStream_t st);
+// store [K][T_h][T_w] -> image i's blended plane at its own size, thresholded into mask + out_descs[i].offset and, where logits_out !=
+// nullptr, as floats at logits_out + out_descs[i].offset (mask_bytes floats).  in_descs (may be nullptr): the images the tiles were cut
+// from; one that does not fit [0, src_bytes) gives a zero mask.  Nothing is written outside [mask, mask + mask_bytes)
+hipError_t launch_tile_blend_threshold_ragged(const float* store, int K, const TileImage* plans, int num_images, int T_h, int T_w, int overlap,
+                                              const ImageDesc* in_descs, size_t src_bytes, int C, const ImageDesc* out_descs, float thr,
+                                              int apply_sigmoid, uint8_t* mask, size_t mask_bytes, float* logits_out, hipStream_t st);
 // ---- masks from watermarked / clean pairs (pair_mask_u8.hip; the rule: include/uwm.h)
-constexpr int kPairMaskBlocks = 64;                  // workgroups per image, each walking that image's tiles: grid = N * this
+constexpr int kPairMaskBlocks = 64;                 // workgroups per image, each walking that image's tiles: grid = N * this
 constexpr int kPairMaskTileW = 120, kPairMaskTileH = 32;      // mask pixels of one tile
 // image i: mask + mask_descs[i].offset <- open3(gray(|wm_i - clean_i|) > threshold) (open == 0: without the opening); clean_descs[i].h == 0
 // skips the image, any other misfit zeroes its mask.  No read leaves the two source buffers, no write leaves [mask, mask + mask_bytes)

@@ -476,6 +476,61 @@ class Unet(nn.Module):
         return (mask, self._logits_view(logits)) if return_logits else mask
 
     @torch.no_grad()
+    def predict_tiled_u8(self, packed: torch.Tensor, in_descs: torch.Tensor, out_descs: torch.Tensor, mask: torch.Tensor, n: int,
+                         tiles: torch.Tensor, plans: torch.Tensor, k: int, batch: int, size, overlap: int, mean, std,
+                         threshold: float = 0.5, apply_sigmoid: bool = False, logits_out: Optional[torch.Tensor] = None):
+        """A packed ragged batch of n uint8 images (as predict_images_u8 takes it) at NATIVE resolution, in ONE library call
+        (uwm_predict_tiled_u8): `tiles` / `plans` are the bytes of tiling.plan_batch's tables on the HIP device, `k` the number of
+        tile entries (a multiple of the forward batch `batch`), `size` = (T_h, T_w) the tile = the model's input size.  Per chunk of
+        `batch` tiles: gather + Normalize into the forward's input, eval forward (frozen or not), the logit planes into the tile-logit
+        store; then one blend into `mask` at out_descs' offsets and, where given, into the float32 tensor `logits_out` (mask.numel()
+        floats, the same offsets).  Nothing in the call depends on the image sizes beyond k, so a graph captured around it serves every
+        batch of n images with k tile entries.  Returns `mask`; the store [k][T_h][T_w] of the call stays readable as
+        `self._tile_store` (a view of the workspace's tail)."""
+        if self.training:
+            raise RuntimeError("predict_tiled_u8 is an eval-mode path: call .eval() first")
+        for t in (packed, in_descs, out_descs, mask, tiles, plans):
+            self._require_gpu(t)
+            if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+                raise RuntimeError("predict_tiled_u8 takes flat contiguous uint8 tensors (data.pack_images / data.descs_tensor / tiling.table_tensor)")
+        n, k, batch = int(n), int(k), int(batch)
+        if n < 1 or in_descs.numel() < 16 * n or out_descs.numel() < 16 * n or plans.numel() < 16 * n:
+            raise RuntimeError(f"predict_tiled_u8: {n} images need {16 * n} descriptor bytes each way and as many plan bytes")
+        if k < 1 or batch < 1 or k % batch or tiles.numel() < 16 * k:
+            raise RuntimeError(f"predict_tiled_u8: k = {k} tile entries must be a multiple of the batch {batch} and need {16 * k} table bytes")
+        if logits_out is not None:
+            self._require_gpu(logits_out)
+            if logits_out.dtype != torch.float32 or not logits_out.is_contiguous() or logits_out.numel() < mask.numel():
+                raise RuntimeError(f"predict_tiled_u8: logits_out must be a contiguous float32 tensor of at least {mask.numel()} elements")
+        h, w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+        self.check_input_shape(torch.empty((0, self.in_channels, h, w)))
+        self._ensure_bound()
+        if self._frozen and not L.lib().uwm_is_frozen(self._h):
+            self._freeze_now(batch, h, w)
+        need = L.lib().uwm_predict_tiled_workspace_bytes(self._h, batch, k, h, w)
+        if need == 0:
+            raise SegmentationModelError(L.lib().uwm_last_error().decode())
+        if self._ws is None or self._ws.numel() < need or self._ws.device != self.device:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)      # (a captured graph's owner keeps its own reference)
+        self._ws_key = (batch, h, w, False)
+        ws = self._ws
+        self._tile_store = ws[need - 4 * k * h * w: need].view(torch.float32).view(k, h, w)
+        self._fwd_gen += 1
+        if self._n_mb:
+            self._set_drop_connect(batch, False, packed.device)
+        c = self.in_channels
+        mean_c = (C.c_float * c)(*[float(v) for v in mean[:c]]); std_c = (C.c_float * c)(*[float(v) for v in std[:c]])
+        with L.on_device(packed):
+            L.check(L.lib().uwm_predict_tiled_u8(self._h, C.c_void_p(packed.data_ptr()), packed.numel(), C.c_void_p(in_descs.data_ptr()), n,
+                                                 C.c_void_p(tiles.data_ptr()), k, C.c_void_p(plans.data_ptr()), h, w, int(overlap),
+                                                 mean_c, std_c, float(threshold), int(apply_sigmoid), C.c_void_p(out_descs.data_ptr()),
+                                                 C.c_void_p(mask.data_ptr()), mask.numel(),
+                                                 C.c_void_p(logits_out.data_ptr() if logits_out is not None else 0),
+                                                 C.c_void_p(ws.data_ptr()), need, batch, C.c_void_p(L.stream_ptr(packed.device))),
+                    SegmentationModelError)
+        return mask
+
+    @torch.no_grad()
     def filter_images_u8(self, packed: torch.Tensor, in_descs: torch.Tensor, out_descs: torch.Tensor, counts: torch.Tensor, n: int,
                          size, mean, std, threshold: float = 0.5, post_process: bool = True, mask: Optional[torch.Tensor] = None,
                          return_logits: bool = False):

@@ -68,6 +68,8 @@ class WatermarkPredictor:
         self._cgraph = None                   # watermark_counts: ONE graph per (N, IMG_SIZE, threshold, post_process, with masks)
         self._ckey = None
         self._cbuf = self._cws = None         # its static counts buffer and workspaces
+        self._xgraphs = {}                    # predict_images_tiled: ONE graph per (images, chunk count, ...), beside the ones above
+        self._xtiles = self._xplans = self._xlbuf = None      # its static tile table, per-image plans and ragged logit plane
         self._hbuf = self._hevt = None        # pinned host staging of the packed bytes + the event of its last upload
         self.freeze = bool(freeze)
         if self.freeze:
@@ -129,6 +131,7 @@ class WatermarkPredictor:
             self.model.freeze(batch_shape=(n, h, w))
             self._graph = self._gkey = self._ugraph = self._ukey = self._pgraph = self._pkey = self._igraph = self._ikey = self._qgraph = self._qkey = self._cgraph = self._ckey = None
             self._tigraph = self._tikey = self._tqgraph = self._tqkey = None
+            self._xgraphs = {}
 
     @torch.no_grad()
     def predict_mask_u8(self, images_u8_nhwc: torch.Tensor, out_size=None, apply_sigmoid: bool = False,
@@ -180,6 +183,7 @@ class WatermarkPredictor:
         setattr(self, name, torch.zeros(cap, dtype=torch.uint8, device=self.device))
         self._igraph = self._ikey = self._qgraph = self._qkey = self._cgraph = self._ckey = None
         self._tigraph = self._tikey = self._tqgraph = self._tqkey = None
+        self._xgraphs = {}
 
     def _stage_images(self, images):
         """pack `images` into the static staging buffers (_ibuf, _idesc, _mdesc; _mbuf sized for their masks) -> (n, IMG_SIZE, descs,
@@ -301,6 +305,80 @@ class WatermarkPredictor:
         descs, mdescs, areas, mask_bytes, stats = self._run_images(images, apply_sigmoid, mask_type, use_graph, text_enhance)
         masks = self._mask_views(descs, mdescs, areas, mask_bytes)
         return (masks, stats.cpu().numpy()) if return_stats else masks
+
+    def _tiled_static(self, name: str, need: int, dtype=torch.uint8):
+        """the static device buffer `name` of predict_images_tiled holds at least `need` elements; grown geometrically, and the tiled
+        graphs captured on the old buffer go with it"""
+        buf = getattr(self, name)
+        if buf is not None and buf.numel() >= need:
+            return
+        setattr(self, name, torch.zeros(max(need, 256 if buf is None else 2 * buf.numel()), dtype=dtype, device=self.device))
+        self._xgraphs = {}
+
+    @torch.no_grad()
+    def predict_images_tiled(self, images, overlap: int = 64, apply_sigmoid: bool = False, mask_type: Optional[str] = None,
+                             return_logits: bool = False, use_graph: bool = True, tile_batch: Optional[int] = None):
+        """uint8 (h_i, w_i, C) images of ANY sizes -> a list of uint8 {0,255} device masks, one per image at its own size, predicted at
+        NATIVE resolution: instead of resizing an image to IMG_SIZE it is cut into IMG_SIZE x IMG_SIZE tiles that overlap by
+        `overlap` pixels (tiling.plan_tiles; an image smaller than a tile is padded by reflection), the tiles of the whole batch go
+        through the eval forward `tile_batch` at a time (default PREDICT.BATCH_SIZE), and the tile logits are blended into one plane
+        per image with weights that rise from the rim of a tile to its middle (uwm_predict_tiled_u8; the rule: DESIGN.md 8r).  A
+        pixel under one tile keeps that tile's logit bit for bit.  The reference has no counterpart: it always resizes.
+        One captured graph per (number of images, number of forward chunks) serves every batch with those counts, whatever the
+        image sizes; it is re-captured when a staging buffer had to grow or the frozen arena was re-made.  mask_type 'watermark' |
+        'text' | 'mixed': every blended mask then goes through the reference's _optimize_mask at its own size
+        (uwm_optimize_masks_ragged), in place and inside the same graph.  return_logits: also the list of float32 (h_i, w_i) planes
+        of blended logits the masks were thresholded from."""
+        from .tiling import check_overlap, plan_batch, table_tensor
+        if mask_type is not None:
+            mask_type_code(mask_type)
+        T = int(self.cfg.DATA.IMG_SIZE)
+        batch = int(self.cfg.PREDICT.BATCH_SIZE if tile_batch is None else tile_batch)
+        overlap = check_overlap(T, T, overlap)
+        n, s, descs, mdescs, areas, mask_bytes = self._stage_images(images)
+        tiles, plans = plan_batch(list(zip(descs["h"].tolist(), descs["w"].tolist())), T, T, overlap, batch)
+        k = len(tiles)
+        self._tiled_static("_xtiles", 16 * k)
+        self._tiled_static("_xplans", 16 * n)
+        if return_logits and (self._xlbuf is None or self._xlbuf.numel() < self._mbuf.numel()):
+            self._xlbuf = None
+            self._tiled_static("_xlbuf", self._mbuf.numel(), torch.float32)
+        self._xtiles[:16 * k].copy_(table_tensor(tiles))
+        self._xplans[:16 * n].copy_(table_tensor(plans))
+        if mask_type is not None:
+            for name, need in (("_cap_pixels", int(areas.max())), ("_cap_rows", int(descs["h"].astype("int64").sum()))):
+                if getattr(self, name) < need:
+                    setattr(self, name, min(max(need, 2 * getattr(self, name)), 2 ** 31 - 2 if name == "_cap_pixels" else 2 ** 40))
+        caps = () if mask_type is None else (mask_type, self._cap_pixels, self._cap_rows)
+        lbuf = self._xlbuf if return_logits else None
+
+        def run():
+            self.model.predict_tiled_u8(self._ibuf, self._idesc, self._mdesc, self._mbuf, n, self._xtiles, self._xplans, k, batch, (T, T),
+                                        overlap, IMAGENET_MEAN, IMAGENET_STD, self.threshold, apply_sigmoid, lbuf)
+            if mask_type is not None:
+                optimize_masks_ragged(self._mbuf, self._mdesc, mask_type, False, out=self._mbuf, n=n, max_pixels=caps[1], rows=caps[2])
+        if not use_graph:
+            run()
+        else:
+            # (the counts, the threshold, the capacities and the logit plane's pointer are captured arguments)
+            key = (n, k // batch, batch, T, overlap, bool(apply_sigmoid), float(self.threshold), bool(return_logits)) + caps
+            if key not in self._xgraphs:
+                self._refreeze_for(batch, T, T)
+                run()                                 # eager warm-up: plans the workspace, sets kernel attributes
+                torch.cuda.synchronize(self.device)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    run()
+                ws = self.model._ws                   # (the graph's workspaces stay alive with it)
+                if mask_type is not None:
+                    ws = (ws, ragged_workspace(self.device, n, self._mbuf.numel(), caps[2]))
+                self._xgraphs[key] = (g, ws)
+            self._xgraphs[key][0].replay()
+        masks = self._mask_views(descs, mdescs, areas, mask_bytes)
+        if not return_logits:
+            return masks
+        lg = self._xlbuf[:mask_bytes].clone()
+        return masks, [lg[int(o): int(o) + int(a)].view(int(h), int(w)) for o, a, h, w in zip(mdescs["offset"], areas, descs["h"], descs["w"])]
 
     @torch.no_grad()
     def mask_stats(self, images, mask_type: str = "watermark", return_masks: bool = False, use_graph: bool = True,
