@@ -1072,7 +1072,13 @@ typedef struct {
  *    700        sub-pixel kernel for a 3x3 over a nearest-x2 upsampled 32-channel source with 16 outputs (conv_up2.hip; with
  *               uwm_op_set_igemm_f16x3(1): conv_up2_f16.hip)
  *    710, 711   3x3 16 -> 16 / 32 -> 32 at full resolution in fp16x3 arithmetic (conv_c16_f16.hip)
- *    800, 864, 928  persistent LDS-DMA GEMM for 1x1 / stride-1 layers with Cin % 32 == 0 (conv_gemm.hip): auto | 64 | 128 channel tile */
+ *    800, 864, 928  persistent LDS-DMA GEMM for 1x1 / stride-1 layers with Cin % 32 == 0 (conv_gemm.hip): auto | 64 | 128 channel tile
+ * Two test hooks go with the 600..607 codes:
+ *    uwm_op_set_f16x3_products(n)   split products per tile (ConvArgs::nprod) of every later uwm_op_conv cfg 600..607 and
+ *               uwm_op_dgrad_f16x3 launch: 3 = hi*hi' + hi*lo' + lo*hi' (the default), 2 = without the pixel operand's low half,
+ *               1 = hi*hi' only; anything else is an error.  The model takes its count from the precision mode, never from here.
+ *    uwm_op_dgrad_f16x3(...)        the DGRAD role of the same kernels, as the model's backward launches it: see its declaration.
+ * A 600..607 call whose coded kernel does not take the shape returns an error before anything is launched. */
 /* preprocess_u8_nhwc4 alone (uwm_predict_u8's input kernel): uint8 [npix][C] (4-byte aligned, C 1..4) -> Normalize as fp32 [npix][4]
  * (16-byte aligned), padding channels zero; any pixel count */
 int  uwm_op_preprocess_u8_nhwc4(const uint8_t* images, long long npix, int C, const float* mean, const float* std, float* out,
@@ -1087,6 +1093,20 @@ int  uwm_op_conv(const uwm_src* s0, const uwm_src* s1, const float* w, int wrows
 int  uwm_op_dgrad(const float* dy, int N, int Ho, int Wo, int Cout, const float* wd, int Cin, int KpadD, int kh, int kw,
                   int stride, int pad, int H, int W, const float* addend, const float* mask, const float* mscale,
                   const float* mshift, float* dx, uwm_stream stream);
+int  uwm_op_set_f16x3_products(int n);   /* tests: n = 1 | 2 | 3 split products in the op-level fp16x3 direct launches (see cfg above); default 3 */
+/* dx[N][H][W][Cin] = the 3x3 / stride-1 / pad-1 input gradient on an fp16x3 direct kernel (cfg = 600 | 601 | 602 | 603 | 605 | 607, as
+ * uwm_op_conv's; 600 = conv_f16x3v2.hip where the model would take it for this layer, else conv_f16x3.hip), launched as the model's
+ * backward launches it.  dy [N][H][W][CoutP] (CoutP % 32 == 0, channels >= Cout zero); w = the FORWARD weights [Cout][Kpad],
+ * k = tap * Cin + c, from which the tap-mirrored filter bank is packed; dY is staged times the power of two that puts max|dY|
+ * (a one-off reduction) into [2^13, 2^14).  Epilogue: dx = (conv + addend) where (mask * mscale + mshift) > 0, else 0 (each optional;
+ * mscale / mshift [Cin] come together).  bnb_mean / bnb_rstd [Cin] (optional): the fused BatchNorm-backward sums — sums[c] += dx,
+ * sums[Cin + c] += dx * (y - mean) * rstd with y = bnb_y if given, else the mask tensor — workgroup b adding into replica
+ * b & (nrep - 1) at sums + replica * sums_stride doubles (nrep a power of two; the caller zeroes every replica).  sums without
+ * bnb_mean: (sum, sum of squares) of dx.  A shape the coded kernel does not take is an error and nothing is launched. */
+int  uwm_op_dgrad_f16x3(const float* dy, int N, int H, int W, int Cout, int CoutP, const float* w, int Kpad, int Cin,
+                        const float* addend, const float* mask, const float* mscale, const float* mshift, const float* bnb_mean,
+                        const float* bnb_rstd, const float* bnb_y, double* sums, int nrep, long long sums_stride, float* dx, int cfg,
+                        uwm_stream stream);
 /* force_igemm (tests / timing), low byte: 0 = the library's routing (Winograd-domain / sub-pixel / 16-channel / stem / 1x1-GEMM /
  * fp16x3 kernels where they apply); 1 = flattened implicit GEMM only; 2 = none of the dedicated kernels but wgrad_patch.hip; 4 =
  * wgrad_gemm.hip (an error where it does not apply); 6 = the dedicated fp16x3 kernels (wgrad_f16x3.hip: 3x3 stride 1, channels % 32 == 0,

@@ -194,6 +194,8 @@ SIGNATURES = {
     "uwm_op_set_igemm_f16x3": (I, [I]),
     "uwm_op_conv": (I, [C.POINTER(uwm_src), C.POINTER(uwm_src), P, I, I, I, I, I, I, I, I, P, P, P, I, P]),
     "uwm_op_dgrad": (I, [P, I, I, I, I, P, I, I, I, I, I, I, I, I, P, P, P, P, P, P]),
+    "uwm_op_set_f16x3_products": (I, [I]),
+    "uwm_op_dgrad_f16x3": (I, [P, I, I, I, I, I, P, I, I, P, P, P, P, P, P, P, P, I, L, P, I, P]),
     "uwm_op_wgrad": (I, [C.POINTER(uwm_src), C.POINTER(uwm_src), P, I, I, I, I, I, I, I, I, I, I, P, I, P]),
     "uwm_op_pack_dgrad": (I, [P, I, I, I, I, P, I, I, P]),
     "uwm_op_maxpool": (I, [C.POINTER(uwm_src), I, P, P, P]),

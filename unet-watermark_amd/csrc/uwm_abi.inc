@@ -1101,6 +1101,11 @@ static int op_wino_prepare(ConvArgs& a, int mirror, hipStream_t st, bool x3 = fa
   a.wu = buf; a.wu_ncb = wino_ncb(a.wrows);
   return 0;
 }
+static int g_op_f3_nprod = 3;                     // ConvArgs::nprod of the op-level fp16x3 direct launches (uwm_op_conv cfg 600..607, uwm_op_dgrad_f16x3)
+int uwm_op_set_f16x3_products(int n) {            // tests: split products per tile of those launches (the model takes its count from the precision mode)
+  if (n < 1 || n > 3) return fail("uwm_op_set_f16x3_products: n must be 1, 2 or 3, got %d", n);
+  g_op_f3_nprod = n; return 0;
+}
 // fp16x3 bank for the op-level entry point (tests / timing): cfg 600
 static int op_f16x3_prepare(ConvArgs& a, hipStream_t st, int variant = 0, bool reuse = false) {
   static float* buf = nullptr; static size_t cap = 0;
@@ -1117,9 +1122,11 @@ static int op_f16x3_prepare(ConvArgs& a, hipStream_t st, int variant = 0, bool r
   // bank layout: 601-603 force a conv_f16x3.hip kernel (layout 0), 605 / 607 a conv_f16x3v2.hip one (layout 1), 600 = what the model would take
   const int layout = variant >= 4 ? 1 : (variant == 0 && f16x3v2_shape(a.Ho, a.Wo, a.wrows, a.Ctot) && a.wrows == a.Cout ? 1 : 0);
   j.w = a.w; j.ut = buf; j.rows = a.wrows; j.chans = a.Ctot; j.Kpad = a.Kpad; j.mode = 0; j.src_rows = a.wrows; j.pad_ = layout;
+  a.wu = buf; a.wu_layout = layout; a.wu_ncb = layout == 1 ? f16x3v2_nf(a.wrows) : f16x3_nj(a.wrows); a.wu_rinv_off = (int)f16x3_rinv_off(a.wrows, a.Ctot); a.prec = 2;
+  a.nprod = g_op_f3_nprod;
+  if (conv_route(a, 600 + variant).k == kConvInvalid) return fail("uwm_op_conv: cfg %d: the coded fp16x3 kernel does not take this shape", 600 + variant);      // (before the bank launch: a rejected call launches nothing)
   if (!(reuse && last_w == a.w && last_rows == a.wrows && last_chans == a.Ctot && last_layout == layout)) LCHK(launch_f16x3_weights_multi(jobs, st));
   last_w = a.w; last_rows = a.wrows; last_chans = a.Ctot; last_layout = layout;
-  a.wu = buf; a.wu_layout = layout; a.wu_ncb = layout == 1 ? f16x3v2_nf(a.wrows) : f16x3_nj(a.wrows); a.wu_rinv_off = (int)f16x3_rinv_off(a.wrows, a.Ctot); a.prec = 2;
   return 0;
 }
 static bool op_wino_shape(const ConvArgs& a, int kh, int kw, int stride, int pad) {
@@ -1374,6 +1381,54 @@ int uwm_op_dgrad(const float* dy, int N, int Ho, int Wo, int Cout, const float* 
     if ((k == kConvIgemm || k == kConvS2Dgrad) && op_ig_bank(wd, Cin, KpadD, 0, (hipStream_t)stream, &a.wbank)) return 1;
   }
   LCHK(launch_conv(a, (hipStream_t)stream));
+  return 0;
+}
+// The dgrad role of the fp16x3 direct kernels (conv_f16x3.hip / conv_f16x3v2.hip), as run_dgrad launches it: ConvArgs of a 3x3 /
+// stride-1 / pad-1 input gradient, the bank packed straight from the FORWARD weights (bank job mode 2), max|dY| through a one-off reduction
+int uwm_op_dgrad_f16x3(const float* dy, int N, int H, int W, int Cout, int CoutP, const float* w, int Kpad, int Cin,
+                       const float* addend, const float* mask, const float* mscale, const float* mshift, const float* bnb_mean,
+                       const float* bnb_rstd, const float* bnb_y, double* sums, int nrep, long long sums_stride, float* dx, int cfg,
+                       uwm_stream stream) {
+  if (!dy || !w || !dx) return fail("uwm_op_dgrad_f16x3: null argument");
+  if (cfg == 604 || cfg == 606) return fail("uwm_op_dgrad_f16x3: cfg %d names a removed conv_f16x3v2 form (607 is its kernel)", cfg);
+  if (cfg < 600 || cfg > 607) return fail("uwm_op_dgrad_f16x3: cfg must be 600..603, 605 or 607, got %d", cfg);
+  if (N < 1 || H < 8 || W < 16 || Cout < 1 || CoutP < Cout || (CoutP & 31) || Cin < 16 || (Cin & 3) || (Kpad & 31) || (long long)Kpad < 9LL * Cin)
+    return fail("uwm_op_dgrad_f16x3: needs H >= 8, W >= 16, padded dY channels %% 32 == 0, Cin %% 4 == 0, forward weights [Cout][Kpad >= 9 * Cin] (k = tap * Cin + c)");
+  if ((mscale == nullptr) != (mshift == nullptr) || (mscale && !mask)) return fail("uwm_op_dgrad_f16x3: mscale / mshift come together, with a mask");
+  if (!bnb_mean && (bnb_rstd || bnb_y)) return fail("uwm_op_dgrad_f16x3: bnb_rstd / bnb_y without bnb_mean");
+  if (bnb_mean && (!bnb_rstd || !sums || !(bnb_y || mask))) return fail("uwm_op_dgrad_f16x3: the fused BatchNorm-backward sums need bnb_rstd, a sums buffer and a mask or bnb_y");
+  if (sums && (nrep < 1 || (nrep & (nrep - 1)) || (nrep > 1 && (sums_stride < 2LL * Cin || sums_stride > 0x7fffffffLL)))) return fail("uwm_op_dgrad_f16x3: nrep must be a power of two, replicas at least 2 * Cin doubles apart");
+  hipStream_t st = (hipStream_t)stream;
+  static float* buf = nullptr; static size_t cap = 0;
+  static float* xm = nullptr;
+  const size_t need = f16x3_bank_floats(Cin, CoutP);
+  if (need > cap) {
+    HIPCHK(hipDeviceSynchronize());
+    if (buf) HIPCHK(hipFree(buf));
+    buf = nullptr; cap = 0;
+    HIPCHK(hipMalloc((void**)&buf, need * sizeof(float))); cap = need;
+  }
+  if (!xm) HIPCHK(hipMalloc((void**)&xm, 32 * sizeof(float)));
+  const int variant = cfg - 600;
+  const int layout = variant >= 4 ? 1 : (variant == 0 && f16x3v2_shape(H, W, Cin, CoutP) ? 1 : 0);      // as op_f16x3_prepare
+  ConvArgs a; memset(&a, 0, sizeof(a));
+  a.s0 = mk_src(dy, CoutP, H, W); a.s1 = a.s0; a.C0 = CoutP; a.Ctot = CoutP;
+  a.w = w; a.wrows = Cin; a.Kpad = Kpad; a.ntaps = 9; a.kw = 3;
+  a.N = N; a.Ho = H; a.Wo = W; a.Cout = Cin; a.M = N * H * W;
+  a.Hl = H; a.Wl = W; a.smul = 1; a.rmul = -1; a.off = 1; a.sdiv = 1;
+  a.out = dx; a.addend = addend; a.mask = mask; a.mscale = mscale; a.mshift = mshift; a.live_ch = Cout;
+  a.dv_ctot = make_fastdiv(a.Ctot); a.dv_kw = make_fastdiv(a.kw);
+  a.wu = buf; a.wu_layout = layout; a.wu_ncb = layout == 1 ? f16x3v2_nf(Cin) : f16x3_nj(Cin); a.wu_rinv_off = (int)f16x3_rinv_off(Cin, CoutP);
+  a.prec = 2; a.nprod = g_op_f3_nprod; a.xmax = xm;
+  a.bnb_mean = bnb_mean; a.bnb_rstd = bnb_rstd; a.bnb_y = bnb_y;
+  if (sums) { a.ssum = sums; a.ssq = sums + Cin; a.srep = nrep; a.sstride = (int)sums_stride; }
+  if (conv_route(a, cfg).k == kConvInvalid) return fail("uwm_op_dgrad_f16x3: cfg %d: the coded fp16x3 kernel does not take this shape", cfg);      // (nothing launched)
+  WinoJobs jobs; jobs.n = 1;
+  WinoJob& j = jobs.j[0];
+  j.w = w; j.ut = buf; j.rows = Cin; j.chans = CoutP; j.Kpad = Kpad; j.mode = 2; j.src_rows = Cout; j.pad_ = layout;
+  LCHK(launch_f16x3_weights_multi(jobs, st));
+  LCHK(launch_absmax32(dy, (size_t)N * H * W * CoutP, xm, st));
+  LCHK(launch_conv(a, st, cfg));
   return 0;
 }
 int uwm_op_dgrad_upsplit(const float* dy, int N, int H, int W, int Cout, const float* wd, int C0, int C1, int KpadD,
