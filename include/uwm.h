@@ -1077,6 +1077,8 @@ typedef struct {
  *    uwm_op_set_f16x3_products(n)   split products per tile (ConvArgs::nprod) of every later uwm_op_conv cfg 600..607 and
  *               uwm_op_dgrad_f16x3 launch: 3 = hi*hi' + hi*lo' + lo*hi' (the default), 2 = without the pixel operand's low half,
  *               1 = hi*hi' only; anything else is an error.  The model takes its count from the precision mode, never from here.
+ *               The same count goes to uwm_op_wgrad force_igemm 6 / 7 (WgradArgs::nprod), where wgrad_f16x3.hip reads it:
+ *               3 = dy_hi*x_hi + dy_hi*x_lo + dy_lo*x_hi, 2 = without dy_lo*x_hi, 1 = dy_hi*x_hi only.
  *    uwm_op_dgrad_f16x3(...)        the DGRAD role of the same kernels, as the model's backward launches it: see its declaration.
  * A 600..607 call whose coded kernel does not take the shape returns an error before anything is launched. */
 /* preprocess_u8_nhwc4 alone (uwm_predict_u8's input kernel): uint8 [npix][C] (4-byte aligned, C 1..4) -> Normalize as fp32 [npix][4]
@@ -1093,7 +1095,7 @@ int  uwm_op_conv(const uwm_src* s0, const uwm_src* s1, const float* w, int wrows
 int  uwm_op_dgrad(const float* dy, int N, int Ho, int Wo, int Cout, const float* wd, int Cin, int KpadD, int kh, int kw,
                   int stride, int pad, int H, int W, const float* addend, const float* mask, const float* mscale,
                   const float* mshift, float* dx, uwm_stream stream);
-int  uwm_op_set_f16x3_products(int n);   /* tests: n = 1 | 2 | 3 split products in the op-level fp16x3 direct launches (see cfg above); default 3 */
+int  uwm_op_set_f16x3_products(int n);   /* tests: n = 1 | 2 | 3 split products in the op-level fp16x3 direct launches (see cfg above) and in uwm_op_wgrad force_igemm 6 on wgrad_f16x3.hip; default 3 */
 /* dx[N][H][W][Cin] = the 3x3 / stride-1 / pad-1 input gradient on an fp16x3 direct kernel (cfg = 600 | 601 | 602 | 603 | 605 | 607, as
  * uwm_op_conv's; 600 = conv_f16x3v2.hip where the model would take it for this layer, else conv_f16x3.hip), launched as the model's
  * backward launches it.  dy [N][H][W][CoutP] (CoutP % 32 == 0, channels >= Cout zero); w = the FORWARD weights [Cout][Kpad],
@@ -1111,7 +1113,8 @@ int  uwm_op_dgrad_f16x3(const float* dy, int N, int H, int W, int Cout, int Cout
  * fp16x3 kernels where they apply); 1 = flattened implicit GEMM only; 2 = none of the dedicated kernels but wgrad_patch.hip; 4 =
  * wgrad_gemm.hip (an error where it does not apply); 6 = the dedicated fp16x3 kernels (wgrad_f16x3.hip: 3x3 stride 1, channels % 32 == 0,
  * Wo % 32 == 0, Ho % 4 == 0; the sub-pixel, stem and 16-channel kernels in their fp16x3 forms; an error elsewhere); 7 = the flattened
- * implicit GEMM in its fp16x3 form.  6 and 7 take max|dy| through a one-off reduction. */
+ * implicit GEMM in its fp16x3 form.  6 and 7 take max|dy| through a one-off reduction, and the split products per tile from
+ * uwm_op_set_f16x3_products (default 3; wgrad_f16x3.hip alone has the 1- and 2-product forms, the other kernels ignore the count). */
 int  uwm_op_wgrad(const uwm_src* s0, const uwm_src* s1, const float* dy, int N, int Ho, int Wo, int Cout, int wrows,
                   int Kpad, int kh, int kw, int stride, int pad, float* dw, int force_igemm, uwm_stream stream);
 int  uwm_op_pack_dgrad(const float* w, int Cout, int Kpad, int ntaps, int Cin, float* wd, int KpadD, int CoutP,

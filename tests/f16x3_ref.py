@@ -16,7 +16,10 @@ Row scale: the kernels put a row's largest |element| into [2^13, 2^14) (`top=14`
 does not depend on that choice (top=11 gives the same numbers to 1e-3 of the GPU bar), so no test has to copy the rule.  xs puts
 max|dY| into [2^13, 2^14) (uwm_launch.inc, "The max|dY| contract").
 
-Everything is NCHW / OIHW on the CPU; tests/test_f16x3v2_ops_gpu.py packs it for the library.
+`wgrad_emu` is the same for wgrad_f16x3.hip's weight gradient (further down: there the two split operands are X, unscaled, and dY
+times xs).
+
+Everything is NCHW / OIHW on the CPU; tests/test_f16x3v2_ops_gpu.py and tests/test_wgrad_f16x3_ops_gpu.py pack it for the library.
 """
 import functools
 import zlib
@@ -216,3 +219,127 @@ def dgrad_ref(shape, form, nprod, mag=DY_SMALL, top=14):
 
 def out_range(ref):
     return float(ref.abs().max())
+
+
+# ---------------------------------------------------------------------------------------------------------------- weight gradient
+# wgrad_f16x3.hip: dW[co][ci][tap] = sum over pixels of dY[p][co] * X[p + tap][ci].  X = the staged sources, clamped to +-65504 and
+# NOT scaled; D = dY times the power of two xs that puts max|dY| into [2^13, 2^14) (1 when dY is all zero).  dW is bilinear in
+# (X, D), so with G(X, D) = the fp64 weight gradient of F.conv2d(X, w, None, 1, 1):
+#     nprod 1: G(hi X, hi D)      nprod 2: + G(lo X, hi D)      nprod 3: + G(hi X, lo D)           all divided by xs
+WGRAD_BAR = 3e-5      # GPU bar: WGRAD_BAR * range of the true gradient — test_wgrad_f16x3_direct's (tests/test_ops_gpu.py)
+
+
+def wgrad64(X, D):
+    """fp64 autograd weight gradient [Cout][Cin][3][3] of the 3x3 / stride-1 / pad-1 conv of X [N][Cin][H][W] with output gradient D"""
+    w = torch.zeros(D.shape[1], X.shape[1], 3, 3, dtype=torch.float64, requires_grad=True)
+    return torch.autograd.grad(F.conv2d(X, w, None, 1, 1), w, D)[0]
+
+
+def wgrad_emu(sources, dy, nprod, top=14):
+    """weight gradient of the staged sources on nprod split products; nprod 0 = fp64 truth (nothing rounded, clamped or split)"""
+    X, D = staged(sources, exact=nprod == 0), dy.double()
+    if nprod == 0:
+        return wgrad64(X, D)
+    X = X.clamp(-65504.0, 65504.0)
+    xs = float(pow2_scale(D.abs().max().reshape(1), top)[0])
+    D = D * xs
+    Xh, Dh = hi(X), hi(D)
+    acc = wgrad64(Xh, Dh)
+    if nprod >= 2:
+        acc = acc + wgrad64(lo(X), Dh)
+    if nprod >= 3:
+        acc = acc + wgrad64(Xh, lo(D))
+    return acc / xs
+
+
+def wgrad_splits(pairs, nstages, cus):
+    """the launcher's pixel split (launch_wgrad_f16x3; cu_share 0, scratch not binding) -> (nsplit, stages per split)"""
+    nsplit = max(1, min(-(-cus // pairs), nstages // 4))
+    sps = -(-nstages // nsplit)
+    return -(-nstages // sps), sps
+
+
+def wgrad_geometry(cin, wrows, h, w, n):
+    """(stage width, (64-row, 32-channel) tile pairs, stages of 128 pixels) of a layer; None where the kernel does not take the image"""
+    wx = 32 if w % 32 == 0 and h % 4 == 0 else 16 if w % 16 == 0 and h % 8 == 0 else 0
+    if not wx:
+        return None
+    return wx, -(-wrows // 64) * (cin // 32), n * (h // (128 // wx)) * (w // wx)
+
+
+# One shape per branch of the kernel's stage walk, tile walk and grid: name -> (Cin, wrows, dY channels, N, H, W), the smallest that
+# reaches it.  WGRAD_CLAIMS: (stage width, workgroups, splits, stages per split) of each, on any card of 64 CUs or more
+# (tests/test_f16x3_ref.py::test_wgrad_case_table).
+WGRAD_SHAPES = {
+    "one_stage": (32, 32, 32, 1, 4, 32),      # 1 stage, no split: += straight into dW; a half-empty 64-row tile; 1 workgroup
+    "two_stage": (32, 64, 64, 2, 4, 32),      # 2 stages: the even tail of the two-buffer walk
+    "three_stage": (64, 64, 64, 3, 4, 32),    # 3 stages: the odd tail; two input-channel tiles share dY
+    "seven": (32, 32, 32, 1, 28, 32),         # 7 stages in one workgroup: steady state, prefetch index clamped at the end
+    "uneven": (32, 96, 96, 1, 36, 32),        # 9 stages -> splits of 5 + 4 (the shorter last split); rows 64..95 in a second, half-empty tile; partial images + reduce
+    "halo": (96, 40, 40, 1, 8, 64),           # 2 x 2 stage tiles: halo rows and columns from neighbours; 40 rows overhang; 3 workgroups
+    "xcd12": (96, 40, 40, 4, 8, 64),          # 16 stages -> 4 splits; 12 workgroups (q8 = 1, r8 = 4)
+    "xcd8": (128, 64, 64, 2, 16, 32),         # 8 stages -> 2 splits; 8 workgroups (q8 = 1, r8 = 0)
+    "padrows": (32, 38, 40, 2, 4, 32),        # wrows < Cout: dY padded to whole channel quads, dW with fewer rows
+    "wx16_one": (64, 32, 32, 1, 8, 16),       # 8 x 16-pixel stages: 1 stage
+    "wx16_split": (32, 64, 64, 5, 16, 16),    # ... 10 stages -> 2 x 5, two tile rows per image
+    "wx16_w48": (32, 32, 32, 1, 8, 48),       # ... on a width that is no multiple of 32: 3 stages
+}
+WGRAD_CLAIMS = {
+    "one_stage": (32, 1, 1, 1), "two_stage": (32, 1, 1, 2), "three_stage": (32, 2, 1, 3), "seven": (32, 1, 1, 7), "uneven": (32, 4, 2, 5),
+    "halo": (32, 3, 1, 4), "xcd12": (32, 12, 4, 4), "xcd8": (32, 8, 2, 4), "padrows": (32, 1, 1, 2), "wx16_one": (16, 2, 1, 1),
+    "wx16_split": (16, 2, 2, 5), "wx16_w48": (16, 1, 1, 3),
+    "cat1x8x32/upcat": (32, 2, 1, 2), "cat1x8x32/upcat_plain_skip": (32, 3, 1, 2),
+    "cat2x8x64/upcat": (32, 4, 2, 4), "cat2x8x64/upcat_plain_skip": (32, 6, 2, 4),
+}
+WGRAD_FORMS = ("plain", "lazy")                                # every shape
+WGRAD_FORMS_MORE = {"three_stage": ("lazy_norelu",), "wx16_w48": ("lazy_norelu",)}
+WGRAD_CAT_SHAPES = {"cat1x8x32": (1, 8, 32), "cat2x8x64": (2, 8, 64)}      # cat(nearest x2 of source 0, source 1) -> 64 rows at N, H, W
+WGRAD_CAT_FORMS = {                                            # (C0, C1, source 1 lazy): source 0 always lazy + ReLU at half resolution
+    "upcat": (32, 32, True),                  # the concat boundary on the first 32-channel tile; source 1 with its own scale, shift and ReLU
+    "upcat_plain_skip": (64, 32, False),
+}
+WGRAD_RANGES = (                                               # (shape, form, dY magnitude, X magnitude) of test_wgrad_ranges
+    ("halo", "lazy", DY_LARGE, 1.0),
+    ("halo", "lazy", DY_SMALL, 300.0),
+    ("halo", "lazy", DY_SMALL, 1e-3),
+)
+
+
+def wgrad_cases():
+    out = [(s, f) for s in WGRAD_SHAPES for f in WGRAD_FORMS + WGRAD_FORMS_MORE.get(s, ())]
+    return out + [(s, f) for s in WGRAD_CAT_SHAPES for f in WGRAD_CAT_FORMS]
+
+
+def wgrad_dims(shape, form):
+    """(Cin in total, wrows, dY channels, N, H, W)"""
+    if shape in WGRAD_CAT_SHAPES:
+        c0, c1, _ = WGRAD_CAT_FORMS[form]
+        return (c0 + c1, 64, 64) + WGRAD_CAT_SHAPES[shape]
+    return WGRAD_SHAPES[shape]
+
+
+@functools.lru_cache(maxsize=None)
+def wgrad_case(shape, form, mag=DY_SMALL, xmag=1.0):
+    """operands of a weight-gradient case: dict(sources, dy [N][wrows][H][W], cin, wrows, coutp, n, h, w_).  dY ~ mag with the left
+    half of the image a further 1e-3 smaller (mag 0: all zero); X ~ xmag (a lazy shift scaled along).  The unit operands of a
+    (shape, form) are the same at every magnitude."""
+    g = _gen(f"wgrad/{shape}/{form}")
+    cin, wrows, coutp, n, h, w = wgrad_dims(shape, form)
+    if shape in WGRAD_CAT_SHAPES:
+        c0, c1, lazy1 = WGRAD_CAT_FORMS[form]
+        sources = [_source(g, n, c0, h // 2, w // 2, lazy=True, up=1), _source(g, n, c1, h, w, lazy=lazy1)]
+    else:
+        sources = [_source(g, n, cin, h, w, lazy=form.startswith("lazy"), relu=form != "lazy_norelu")]
+    for s in sources:
+        s["x"] = s["x"] * xmag
+        if s["shift"] is not None:
+            s["shift"] = s["shift"] * xmag
+    dy = torch.randn(n, wrows, h, w, generator=g) * mag
+    dy[:, :, :, : w // 2] *= 1e-3
+    return {"sources": sources, "dy": dy, "cin": cin, "wrows": wrows, "coutp": coutp, "n": n, "h": h, "w_": w}
+
+
+@functools.lru_cache(maxsize=None)
+def wgrad_ref(shape, form, nprod, mag=DY_SMALL, xmag=1.0, top=14):
+    c = wgrad_case(shape, form, mag, xmag)
+    return wgrad_emu(c["sources"], c["dy"], nprod, top)

@@ -1101,7 +1101,7 @@ static int op_wino_prepare(ConvArgs& a, int mirror, hipStream_t st, bool x3 = fa
   a.wu = buf; a.wu_ncb = wino_ncb(a.wrows);
   return 0;
 }
-static int g_op_f3_nprod = 3;                     // ConvArgs::nprod of the op-level fp16x3 direct launches (uwm_op_conv cfg 600..607, uwm_op_dgrad_f16x3)
+static int g_op_f3_nprod = 3;                     // ConvArgs::nprod of the op-level fp16x3 direct launches (uwm_op_conv cfg 600..607, uwm_op_dgrad_f16x3) and WgradArgs::nprod of uwm_op_wgrad force 6 / 7
 int uwm_op_set_f16x3_products(int n) {            // tests: split products per tile of those launches (the model takes its count from the precision mode)
   if (n < 1 || n > 3) return fail("uwm_op_set_f16x3_products: n must be 1, 2 or 3, got %d", n);
   g_op_f3_nprod = n; return 0;
@@ -1468,7 +1468,7 @@ int uwm_op_wgrad(const uwm_src* s0, const uwm_src* s1, const float* dy, int N, i
     static float* xm = nullptr;
     if (!xm) HIPCHK(hipMalloc((void**)&xm, 32 * sizeof(float)));
     LCHK(launch_absmax32(dy, (size_t)N * Ho * Wo * Cout, xm, (hipStream_t)stream));
-    a.prec = 2; a.xmax = xm;
+    a.prec = 2; a.nprod = g_op_f3_nprod; a.xmax = xm;      // (nprod: wgrad_f16x3.hip's product count; the other fp16x3 weight-gradient kernels have one form)
   }
   LCHK(launch_wgrad(a, (hipStream_t)stream));
   return 0;
