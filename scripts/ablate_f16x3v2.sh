@@ -1,6 +1,6 @@
 #!/bin/bash
 # Timing-ablation builds of conv_f16x3v2.hip (compile-time bits UWM_F16V2_ABL: 1 no MFMA, 2 no filter-fragment loads, 4 no pixel-fragment
-# LDS reads, 8 no patch staging) as unet-watermark_amd/abl/libuwm_v2_<bits>.so; on the GPU box: UWM_LIB=<that file> python scripts/time_f16x3.py 607.
+# LDS reads, 8 no patch staging, 64 no filter-block DMA in the 8-wave kernel: its LDS reads stay) as unet-watermark_amd/abl/libuwm_v2_<bits>.so; on the GPU box: UWM_LIB=<that file> python scripts/time_f16x3.py 607.
 # Results of such builds are garbage by construction.  Extra -D flags: EXTRA="-DFOO=1" scripts/ablate_f16x3v2.sh <bits> ...
 set -e
 cd "$(dirname "$0")/.."

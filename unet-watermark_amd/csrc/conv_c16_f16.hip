@@ -39,12 +39,7 @@ __global__ __launch_bounds__(256, 2) void conv_c16_f16_kernel(const ConvArgs a, 
   const bool dg = a.rmul < 0;
 
   float xs = 1.f;                                         // dgrad: power-of-two scale of dY
-  if (dg && a.xmax) {
-    float mx = a.xmax[lane & 31];
-#pragma unroll
-    for (int d = 16; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-    if (mx > 0.f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); xs = ldexpf(1.f, 14 - e); }
-  }
+  if (dg && a.xmax) xs = uwm_dy_scale(a.xmax);
 
   // ---- staging: 340 px x 4 quads = 1360 units, 6 rounds
   const int unit = tid & 3;
@@ -106,10 +101,8 @@ __global__ __launch_bounds__(256, 2) void conv_c16_f16_kernel(const ConvArgs a, 
     }
     w0 = w0 * kWScale; w1 = w1 * kWScale;
     uwm_u2 h0, l0, h1, l1;
-    uwm_split4(__builtin_amdgcn_fmed3f(w0.x, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(w0.y, -65504.f, 65504.f),
-               __builtin_amdgcn_fmed3f(w0.z, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(w0.w, -65504.f, 65504.f), h0, l0);
-    uwm_split4(__builtin_amdgcn_fmed3f(w1.x, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(w1.y, -65504.f, 65504.f),
-               __builtin_amdgcn_fmed3f(w1.z, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(w1.w, -65504.f, 65504.f), h1, l1);
+    uwm_split4_clamped(w0.x, w0.y, w0.z, w0.w, h0, l0);
+    uwm_split4_clamped(w1.x, w1.y, w1.z, w1.w, h1, l1);
     uwm_u2* const ph = (uwm_u2*)(bank + ((j * 2 + 0) * 64 + L) * 16);
     uwm_u2* const pl = (uwm_u2*)(bank + ((j * 2 + 1) * 64 + L) * 16);
     ph[0] = h0; ph[1] = h1; pl[0] = l0; pl[1] = l1;
@@ -258,12 +251,7 @@ __global__ __launch_bounds__(512, 1) void conv_c32_f16_kernel(const ConvArgs a, 
   const bool dg = a.rmul < 0;
 
   float xs = 1.f;
-  if (dg && a.xmax) {
-    float mx = a.xmax[lane & 31];
-#pragma unroll
-    for (int d = 16; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-    if (mx > 0.f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); xs = ldexpf(1.f, 14 - e); }
-  }
+  if (dg && a.xmax) xs = uwm_dy_scale(a.xmax);
 
   // ---- staging: 340 px x 8 quads = 2720 units, 6 rounds of 512 threads
   const int unit = tid & 7;
@@ -324,10 +312,8 @@ __global__ __launch_bounds__(512, 1) void conv_c32_f16_kernel(const ConvArgs a, 
     }
     w0 = w0 * kWScale; w1 = w1 * kWScale;
     uwm_u2 h0, l0, h1, l1;
-    uwm_split4(__builtin_amdgcn_fmed3f(w0.x, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(w0.y, -65504.f, 65504.f),
-               __builtin_amdgcn_fmed3f(w0.z, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(w0.w, -65504.f, 65504.f), h0, l0);
-    uwm_split4(__builtin_amdgcn_fmed3f(w1.x, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(w1.y, -65504.f, 65504.f),
-               __builtin_amdgcn_fmed3f(w1.z, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(w1.w, -65504.f, 65504.f), h1, l1);
+    uwm_split4_clamped(w0.x, w0.y, w0.z, w0.w, h0, l0);
+    uwm_split4_clamped(w1.x, w1.y, w1.z, w1.w, h1, l1);
     uwm_u2* const ph = (uwm_u2*)(bank + ((tm * 2 + 0) * 64 + L) * 16);
     uwm_u2* const pl = (uwm_u2*)(bank + ((tm * 2 + 1) * 64 + L) * 16);
     ph[0] = h0; ph[1] = h1; pl[0] = l0; pl[1] = l1;

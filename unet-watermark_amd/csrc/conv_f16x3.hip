@@ -114,8 +114,7 @@ __global__ __launch_bounds__(256) void f16x3_rowscale_kernel(const WinoJobs jobs
   if (row >= nJ * 16) return;
   float* rinv = jb.ut + f16x3_rinv_off_floats(jb.rows, jb.chans);
   const float mx = rinv[row];                          // (the maximum, left there by f16x3_rowmax_kernel; 0 for padding rows)
-  float s = 1.f;
-  if (mx > 0.f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); s = ldexpf(1.f, 14 - e); }
+  const float s = uwm_pow2_scale(mx);
   rinv[row] = 1.f / s;                                 // (exact: a power of two)
 }
 __global__ __launch_bounds__(256) void f16x3_weights_multi_kernel(const WinoJobs jobs) {
@@ -227,7 +226,34 @@ __device__ __forceinline__ void f16x3_split_epilogue(const ConvArgs& a, const fl
 }
 
 // ---------------------------------------------------------------- main kernel
-__device__ __forceinline__ float clamp_h(float v) { return __builtin_amdgcn_fmed3f(v, -65504.f, 65504.f); }      // (one v_med3_f32; fminf(fmaxf()) adds a canonicalising v_max per value)
+// workgroup -> channel tile n0 (of CO channels), pixel tile (h0, w0), image n: channel tile fastest inside an XCD's range (uwm_xcd_tile)
+template <int CO>
+__device__ __forceinline__ void f16x3_tile(const ConvArgs& a, int& n0, int& h0, int& w0, int& n) {
+  unsigned tile = uwm_xcd_tile();
+  const int tilesN = (a.Cout + CO - 1) / CO;
+  const int tilesW = (a.Wo + kFT - 1) / kFT, tilesH = (a.Ho + kFT - 1) / kFT;
+  const int tn = tile % tilesN; tile /= tilesN;
+  const int tw = tile % tilesW; tile /= tilesW;
+  const int th = tile % tilesH; n = tile / tilesH;
+  n0 = tn * CO; h0 = th * kFT; w0 = tw * kFT;
+}
+// four staged values, clamped to fp16's range, as hi / lo fp16 halves (plain conversions: this form keeps its lows in fp16 arithmetic)
+__device__ __forceinline__ void f16x3_split4(f4 v, h4& hi, h4& lo) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float x = uwm_clamp_h(v[e]);
+    const _Float16 h = (_Float16)x;
+    hi[e] = h; lo[e] = (_Float16)(x - (float)h);
+  }
+}
+// accumulators -> the wave's epilogue block R ([64 px][LD floats]): D[row = co 4g + e][col = pixel px16]
+template <int NJ, int LD>
+__device__ __forceinline__ void f16x3_spill(float* R, const f4 (&acc)[4][NJ], int px16, int g) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) *(f4*)(R + (i * 16 + px16) * LD + j * 16 + g * 4) = acc[i][j];
+}
 
 // NJ = 16-channel fragments per workgroup: 4 (64 output channels) or 2 (32: the 32-output layers of decoder block 3 — half of a
 // 64-channel tile's MFMAs and filter loads were padding there: 400 / 162 us forward against 416 / 152 on the fp32 Winograd kernel)
@@ -246,15 +272,8 @@ __global__ __launch_bounds__(256, (NJ == 1 ? 4 : 2)) void conv_f16x3_kernel(cons
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int px16 = lane & 15, g = lane >> 4;
 
-  const unsigned nblk = gridDim.x, bid = blockIdx.x;
-  const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-  unsigned tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int tilesN = (a.Cout + kCo - 1) / kCo;
-  const int tilesW = (a.Wo + kFT - 1) / kFT, tilesH = (a.Ho + kFT - 1) / kFT;
-  const int tn = tile % tilesN; tile /= tilesN;
-  const int tw = tile % tilesW; tile /= tilesW;
-  const int th = tile % tilesH; const int n = tile / tilesH;
-  const int n0 = tn * kCo, h0 = th * kFT, w0 = tw * kFT;
+  int n0, h0, w0, n;
+  f16x3_tile<kCo>(a, n0, h0, w0, n);
   const int nJ = a.wu_ncb;
 
   f4 acc[4][NJ];
@@ -286,12 +305,7 @@ __global__ __launch_bounds__(256, (NJ == 1 ? 4 : 2)) void conv_f16x3_kernel(cons
   // dgrad: dY is tiny (1e-3 ... 1e-9): it is staged times the power of two that puts max|dY| into [2^13, 2^14) (exact; undone in
   // the epilogue).  max|dY| = the maximum of the 32 slots bn_bwd_apply filled; activations are staged as they are
   float xs = 1.f;
-  if (a.xmax) {
-    float mx = a.xmax[lane & 31];
-#pragma unroll
-    for (int d = 16; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-    if (mx > 0.f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); xs = ldexpf(1.f, 14 - e); }
-  }
+  if (a.xmax) xs = uwm_dy_scale(a.xmax);
   // ONE register set of raw patch values (a round's register is re-loaded for chunk c+2 right after its chunk-c+1 contents have been
   // stored) and one set of lazy-transform coefficients (those of the chunk being stored).  The store side is branch-free and cut into rounds, so that a round's
   // conversion work (about 30 VALU instructions + 2 LDS stores) can sit in the shadow of a tap pair's MFMAs — the matrix pipe
@@ -326,12 +340,7 @@ __global__ __launch_bounds__(256, (NJ == 1 ? 4 : 2)) void conv_f16x3_kernel(cons
     v = v * xs;
     if (!((gflags >> rd) & 1u)) v = (f4){0.f, 0.f, 0.f, 0.f};
     h4 hi, lo;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float x = clamp_h(v[e]);
-      const _Float16 h = (_Float16)x;
-      hi[e] = h; lo[e] = (_Float16)(x - (float)h);
-    }
+    f16x3_split4(v, hi, lo);
     const int u = rd * 256 + tid;
     _Float16* d = hsm + buf * kFBuf + (u >> 2) * kFPix + (u & 3) * 4;
     *(h4*)d = hi;
@@ -453,10 +462,7 @@ __global__ __launch_bounds__(256, (NJ == 1 ? 4 : 2)) void conv_f16x3_kernel(cons
   // constant channel quad (row un-scale, bias, mask coefficients and the statistics stay in registers)
   constexpr int kQLd = kOne ? 20 : 68;
   float* const R = (float*)hsm + wave * 64 * kQLd;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) *(f4*)(R + (i * 16 + px16) * kQLd + j * 16 + g * 4) = acc[i][j];
+  f16x3_spill<NJ, kQLd>(R, acc, px16, g);
   __syncthreads();
   const float* rinv = (const float*)a.wu + a.wu_rinv_off;
   const float ixs = 1.f / xs;
@@ -546,25 +552,13 @@ __global__ __launch_bounds__(512, 1) void conv_f16x3s_kernel(const ConvArgs a) {
   const int ltid = tid & 255;                         // thread index inside its role
   const int px16 = lane & 15, g = lane >> 4;
 
-  const unsigned nblk = gridDim.x, bid = blockIdx.x;
-  const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-  unsigned tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int tilesN = (a.Cout + 63) / 64;
-  const int tilesW = (a.Wo + kFT - 1) / kFT, tilesH = (a.Ho + kFT - 1) / kFT;
-  const int tn = tile % tilesN; tile /= tilesN;
-  const int tw = tile % tilesW; tile /= tilesW;
-  const int th = tile % tilesH; const int n = tile / tilesH;
-  const int n0 = tn * 64, h0 = th * kFT, w0 = tw * kFT;
+  int n0, h0, w0, n;
+  f16x3_tile<64>(a, n0, h0, w0, n);
   const int nJ = a.wu_ncb;
   const int nchunk = a.Ctot >> 4, nsteps = nchunk * kFKs;
 
   float xs = 1.f;
-  if (a.xmax) {
-    float mx = a.xmax[lane & 31];
-#pragma unroll
-    for (int d = 16; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-    if (mx > 0.f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); xs = ldexpf(1.f, 14 - e); }
-  }
+  if (a.xmax) xs = uwm_dy_scale(a.xmax);
 
   f4 acc[4][4];
 #pragma unroll
@@ -614,12 +608,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16x3s_kernel(const ConvArgs a) {
         if (!((gflags >> (2 * rd)) & 1u)) v = (f4){0.f, 0.f, 0.f, 0.f};
         if ((gflags >> (2 * rd)) & 2u) {
           h4 hi, lo;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float x = clamp_h(v[e]);
-            const _Float16 h = (_Float16)x;
-            hi[e] = h; lo[e] = (_Float16)(x - (float)h);
-          }
+          f16x3_split4(v, hi, lo);
           const int u = rd * 256 + ltid;
           _Float16* d = hsm + buf * kFBuf + (u >> 2) * kFPix + (u & 3) * 4;
           *(h4*)d = hi;
@@ -709,13 +698,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16x3s_kernel(const ConvArgs a) {
   // ---------------- epilogue (conv_f16x3_kernel's, spread over eight waves): an MMA wave's 64 px x 64 ch block goes through its
   // LDS region; waves w and w + 4 read back its pixels [0, 32) and [32, 64) with lanes along the channels
   constexpr int kQLd = 68;
-  if (is_mma) {
-    float* const Rw = (float*)hsm + mw * 64 * kQLd;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) *(f4*)(Rw + (i * 16 + px16) * kQLd + j * 16 + g * 4) = acc[i][j];
-  }
+  if (is_mma) f16x3_spill<4, kQLd>((float*)hsm + mw * 64 * kQLd, acc, px16, g);
   __syncthreads();
   const float* const R = (const float*)hsm + mw * 64 * kQLd;
   const float* rinv = (const float*)a.wu + a.wu_rinv_off;

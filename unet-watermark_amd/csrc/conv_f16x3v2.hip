@@ -26,19 +26,16 @@
 // Reference semantics replaced: the 3x3 convolutions of smp.Unet's encoder / decoder forward and their input gradients
 // (/root/reference/src/models/unet_model.py:64-71 -> SURVEY.md §8 a5-a8, a10, a14).
 #include "uwm_kernels.h"
-#include <type_traits>
 
 namespace uwm {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f16v __attribute__((ext_vector_type(16)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef unsigned u2 __attribute__((ext_vector_type(2)));
 
 #ifndef UWM_F16V2_ABL
-#define UWM_F16V2_ABL 0       // compile-time timing ablations: 1 no MFMA, 2 no filter loads, 4 no pixel-fragment LDS reads, 8 no patch loads / stores, (8-wave kernel) 16 no global patch loads, 32 no patch conversion / LDS stores, 64 no filter DMA (LDS reads stay); 0 in the product build
+#define UWM_F16V2_ABL 0       // compile-time timing ablations: 1 no MFMA, 2 no filter loads, 4 no pixel-fragment LDS reads, 8 no patch loads / stores, 64 (8-wave kernel) no filter DMA (LDS reads stay); 0 in the product build
 #endif
 #ifndef UWM_V2_COSLOW_BYTES
 #define UWM_V2_COSLOW_BYTES (2u << 20)      // filter bytes of all channel tiles beyond which the tile walk keeps one channel tile per XCD
@@ -110,23 +107,6 @@ hipError_t launch_f16x3v2_weights_multi(const WinoJobs& jobs, hipStream_t st) { 
   if (mx == 0) return hipSuccess;
   hipLaunchKernelGGL(f16x3v2_weights_multi_kernel, dim3((unsigned)((mx + 255) / 256), (unsigned)jobs.n), dim3(256), 0, st, jobs);
   return hipGetLastError();
-}
-
-// ---------------------------------------------------------------- split of four fp32 values into hi / lo fp16 halves
-// hi = rn_f16(x) (v_cvt_pk_f16_f32, two values per instruction), lo = rn_f16(x - hi) as ONE v_fma_mix{lo,hi}_f16 per value:
-// fma(hi_as_f32, -1.0, x) rounded to fp16 into one half of the destination, the fp16 operand selected out of the packed register
-// by op_sel (lane-exact: the difference of an fp32 value and its fp16 rounding is representable in fp32).
-__device__ __forceinline__ void split4(f4 x, u2& hi, u2& lo) {
-  const h2 a = {(_Float16)x.x, (_Float16)x.y}, b = {(_Float16)x.z, (_Float16)x.w};
-  hi.x = __builtin_bit_cast(unsigned, a); hi.y = __builtin_bit_cast(unsigned, b);
-  unsigned l0, l1;
-  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-      : "=&v"(l0) : "v"(hi.x), "v"(x.x), "v"(x.y));
-  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-      : "=&v"(l1) : "v"(hi.y), "v"(x.z), "v"(x.w));
-  lo.x = l0; lo.y = l1;
 }
 
 // ---------------------------------------------------------------- epilogue (shared by the 4-wave and the 8-wave kernel)
@@ -203,6 +183,29 @@ __device__ __forceinline__ void v2_stats(const ConvArgs& a, float* red, f4 ps_, 
   }
 }
 
+// ---------------------------------------------------------------- pieces the 4-wave and the 8-wave kernel share
+// staging of four raw values: lazy BatchNorm (the range scale folded into sc / sh), then ReLU + range clamp + halo zeroing in one
+// v_med3 per value ([lo_c, hi_c] = [0 | -65504, 65504], or [0, 0] for a halo pixel outside the image)
+__device__ __forceinline__ f4 v2_stage4(f4 raw, f4 sc, f4 sh, float lo_c, float hi_c) {
+  f4 v;
+  v.x = __builtin_amdgcn_fmed3f(__builtin_fmaf(raw.x, sc.x, sh.x), lo_c, hi_c);
+  v.y = __builtin_amdgcn_fmed3f(__builtin_fmaf(raw.y, sc.y, sh.y), lo_c, hi_c);
+  v.z = __builtin_amdgcn_fmed3f(__builtin_fmaf(raw.z, sc.z, sh.z), lo_c, hi_c);
+  v.w = __builtin_amdgcn_fmed3f(__builtin_fmaf(raw.w, sc.w, sh.w), lo_c, hi_c);
+  return v;
+}
+// pixel fragments of tap (dy, dx) for the wave's two rows: pb = the lane's place (pixel column, channel octet, first row) in the
+// chunk's patch buffer; one 16-byte read per plane
+__device__ __forceinline__ void v2_x_load(const char* pb, int tap, h8 (&xh)[2], h8 (&xl)[2]) {
+  const int off = ((tap / 3) * kVPW + tap % 3) * 16;
+  const char* pp = pb + off;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    if (UWM_F16V2_ABL & 4) { xh[i] = (h8){1, 1, 1, 1, 1, 1, 1, 1}; xl[i] = xh[i]; continue; }
+    xh[i] = *(const h8*)(pp + i * kVPW * 16); xl[i] = *(const h8*)(pp + i * kVPW * 16 + 2 * kVPlane);
+  }
+}
+
 // ---------------------------------------------------------------- 4-wave kernel (forced code 605 only: tests / timing)
 // The routing never takes it.  It stays compiled, with 32-channel tiles (NCF = 1), because the 8-wave kernel below shares
 // v2_epilogue<1> with it: with this second caller gone hipcc specialises the epilogue for the one that is left and emits a
@@ -218,9 +221,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3v2_kernel(const ConvArgs a) 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int pcol = lane & 31, kh = lane >> 5;
 
-  const unsigned nblk = gridDim.x, bid = blockIdx.x;
-  const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-  unsigned tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  unsigned tile = uwm_xcd_tile();
   const int tilesN = (a.Cout + kCo - 1) / kCo;
   const int tilesW = a.Wo / kVW, tilesH = a.Ho / kVH;
   // tile order inside an XCD's contiguous range: channel tile fastest (the channel tiles of one pixel tile share the patch in L2)
@@ -270,12 +271,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3v2_kernel(const ConvArgs a) 
   }
   // dgrad: dY is staged times the power of two that puts max|dY| into [2^13, 2^14) (exact; undone in the epilogue)
   float xs = 1.f;
-  if (a.xmax) {
-    float mx = a.xmax[lane & 31];
-#pragma unroll
-    for (int d = 16; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-    if (mx > 0.f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); xs = ldexpf(1.f, 14 - e); }
-  }
+  if (a.xmax) xs = uwm_dy_scale(a.xmax);
   f4 pv[kVRounds];
   f4 psc = {1.f, 1.f, 1.f, 1.f}, psh = {0.f, 0.f, 0.f, 0.f};
   float pfloor = -65504.f;                               // ReLU + range clamp in one v_med3: [0 | -65504, 65504]; a halo pixel outside the image: [0, 0]
@@ -300,13 +296,9 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3v2_kernel(const ConvArgs a) 
   auto store_unit = [&](int buf, int rd, f4 raw) {
     const bool ok = (gflags >> rd) & 1u;
     const float lo_c = ok ? pfloor : 0.f, hi_c = ok ? 65504.f : 0.f;
-    f4 v;
-    v.x = __builtin_amdgcn_fmed3f(__builtin_fmaf(raw.x, psc.x, psh.x), lo_c, hi_c);
-    v.y = __builtin_amdgcn_fmed3f(__builtin_fmaf(raw.y, psc.y, psh.y), lo_c, hi_c);
-    v.z = __builtin_amdgcn_fmed3f(__builtin_fmaf(raw.z, psc.z, psh.z), lo_c, hi_c);
-    v.w = __builtin_amdgcn_fmed3f(__builtin_fmaf(raw.w, psc.w, psh.w), lo_c, hi_c);
+    const f4 v = v2_stage4(raw, psc, psh, lo_c, hi_c);
     u2 hi, lo;
-    split4(v, hi, lo);
+    uwm_split4(v.x, v.y, v.z, v.w, hi, lo);
     const int u = rd * 256 + tid;
     char* d = vsm + buf * kVBuf + ((u >> 1) & 1) * kVPlane + (u >> 2) * 16 + (u & 1) * 8;
     *(u2*)d = hi;
@@ -322,17 +314,8 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3v2_kernel(const ConvArgs a) 
 #pragma unroll
     for (int j = 0; j < NCF; ++j) { whi[j] = *(const h8*)(p + j * 1024); wlo[j] = *(const h8*)(p + j * 1024 + 512); }
   };
-  // ---- pixel fragments: lane (pixel column pcol, channel octet kh) of row 2 * wave + i, tap (dy, dx): one 16-byte read per plane
+  // ---- pixel fragments (v2_x_load): lane (pixel column pcol, channel octet kh) of rows 2 * wave, 2 * wave + 1
   const int pbase = kh * kVPlane + ((2 * wave) * kVPW + pcol) * 16;
-  auto x_load = [&](int tap, const char* pc, h8 (&xh)[2], h8 (&xl)[2]) {
-    const int off = ((tap / 3) * kVPW + tap % 3) * 16;
-    const char* pp = pc + pbase + off;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      if (dbg & 4) { xh[i] = (h8){1, 1, 1, 1, 1, 1, 1, 1}; xl[i] = xh[i]; continue; }
-      xh[i] = *(const h8*)(pp + i * kVPW * 16); xl[i] = *(const h8*)(pp + i * kVPW * 16 + 2 * kVPlane);
-    }
-  };
   auto mma = [&](const h8 (&whi)[NCF], const h8 (&wlo)[NCF], const h8 (&xh)[2], const h8 (&xl)[2]) {
     if (dbg & 1) { acc[0][0][0] += (float)xh[0][0] + (float)xl[1][1] + (float)whi[0][2] + (float)wlo[NCF - 1][3] + (float)xh[1][0]; return; }
 #pragma unroll
@@ -379,7 +362,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3v2_kernel(const ConvArgs a) 
   // Iteration c multiplies chunk c (buffer c & 1) and, between the MFMAs of taps 0-5, converts and stores the six rounds of
   // chunk c+1 (raw values fetched during iteration c-1) into the other buffer, re-issuing each round's global load for chunk c+2.
   // kTrip chunks per loop trip so that every register set index is static (taps per trip % kAD == 0, chunks per trip even).
-  constexpr int kTrip = (kAD == 3) ? 2 : 2;              // (9 * 2) % 2 == 0 and (9 * 2) % 3 == 0
+  constexpr int kTrip = 2;                               // (9 * 2) % 2 == 0 and (9 * 2) % 3 == 0
   for (int cc = 0; cc < nchunk; cc += kTrip) {
 #pragma unroll
     for (int hh = 0; hh < kTrip; ++hh) {
@@ -388,7 +371,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3v2_kernel(const ConvArgs a) 
       coef_load(more1 ? c + 1 : c);
       chunk_src(c + 2 < nchunk ? c + 2 : nchunk - 1);      // (past the end: a harmless re-fetch)
       const char* pc = vsm + cur * kVBuf;
-      x_load(0, pc, x_h[0], x_l[0]);
+      v2_x_load(pc + pbase, 0, x_h[0], x_l[0]);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int ks = 0; ks < 9; ++ks) {
@@ -397,7 +380,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3v2_kernel(const ConvArgs a) 
         const int ws = (hh * 9 + ks) % kAD, wl = (hh * 9 + ks + kAD - 1) % kAD, xsn = ks & 1;
         // operands ahead first: filter fragments from L1 / L2 (kAD - 1 taps ahead), pixel fragments from LDS (next tap)
         w_load(tp, w_hi[wl], w_lo[wl]);
-        if (ks < 8) x_load(ks + 1, pc, x_h[xsn ^ 1], x_l[xsn ^ 1]);
+        if (ks < 8) v2_x_load(pc + pbase, ks + 1, x_h[xsn ^ 1], x_l[xsn ^ 1]);
         mma(w_hi[ws], w_lo[ws], x_h[xsn], x_l[xsn]);
         if (!(dbg & 8) && ks < kVRounds) {
           if (ks < kVRounds - 1) {
@@ -446,39 +429,24 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3v2_kernel(const ConvArgs a) 
 // 32^2, + pixel-fragment LDS reads 93, + filter loads 103, + patch staging alone 98 — but all of them together 152): a wave's
 // vector-memory operations retire IN ORDER, so the filter fragments of the next tap (an L2 hit) cannot be consumed before the HBM
 // loads of the patch staging issued ahead of them have landed; six taps out of nine wait for an HBM round trip.  Here ONE
-// 512-thread workgroup per CU gives each SIMD an MMA wave and a LOADER wave: waves 0-3 only load filter fragments (kSD taps ahead,
-// nothing else on their memory counter), read pixel fragments and issue MFMAs; waves 4-7 only stage patches (global -> registers
-// two chunks ahead -> lazy BatchNorm / ReLU / split -> LDS).  One barrier per chunk; all eight waves share the epilogue.
-#ifndef UWM_V2_ALDS
-#define UWM_V2_ALDS 1         // 8-wave kernel: 1 = the filter fragments of a chunk reach the MMA waves through LDS (loader waves' LDS-DMA, one copy per workgroup); 0 = every MMA wave loads them from L1 / L2 itself
-#endif
+// 512-thread workgroup per CU gives each SIMD an MMA wave and a LOADER wave: waves 0-3 only copy a chunk's filter fragments into LDS
+// (LDS-DMA, one copy per workgroup, nothing else on their memory counter), read filter and pixel fragments from LDS one tap ahead
+// and issue MFMAs; waves 4-7 only stage patches (global -> registers two chunks ahead -> lazy BatchNorm / ReLU / split -> LDS).
+// One barrier per chunk; all eight waves share the epilogue.
 typedef __attribute__((address_space(3))) void v2_lds_void;
 typedef const __attribute__((address_space(1))) void v2_gbl_void;
-#ifndef UWM_V2_W128
-#define UWM_V2_W128 1         // 8-wave kernel: loader units of 8 channels, 16-byte LDS stores (0: 4 channels, 8-byte stores)
-#endif
-#ifndef UWM_V2_PD
-#define UWM_V2_PD 1           // 8-wave kernel, filters through LDS: fragment prefetch distance of the MMA waves (taps)
-#endif
 #ifndef UWM_V2_LS
 #define UWM_V2_LS 2           // 8-wave kernel: register stages of the loader waves (chunks of load latency budget)
-#endif
-#ifndef UWM_V2_SD
-#define UWM_V2_SD 4           // filter-fragment register sets of the MMA waves (prefetch distance UWM_V2_SD - 1 taps)
 #endif
 template <int NCF, int NP = 3>
 __global__ __launch_bounds__(512, 1) void conv_f16x3v2s_kernel(const ConvArgs a) {
   constexpr int kCo = 32 * NCF;
-  constexpr int kSD = UWM_V2_SD;
   constexpr int dbg = UWM_F16V2_ABL;
-  constexpr bool kALds = UWM_V2_ALDS != 0;
   constexpr int kAPieces = 9 * NCF * 2;                // 1-KB fragment planes of a chunk's filter block: [tap][fragment][hi | lo][64 lanes][16 B]
   constexpr int kABuf = kAPieces * 1024;               // 18 432 bytes at NCF = 1
 
-  constexpr int kTrip = (kSD == 4 || kSD == 2) ? (kSD == 4 ? 4 : 2) : (kSD == 3 ? 1 : 0);      // chunks per loop trip: (9 * kTrip) % kSD == 0
-  static_assert(kTrip > 0 && (9 * kTrip) % kSD == 0, "UWM_V2_SD must be 2, 3 or 4");
   extern __shared__ __attribute__((aligned(16))) char vsm[];      // [2][kVBuf] patch buffers; the epilogue's [4][64][VQ<NCF>::kLd] floats
-  char* const asm_ = vsm + 2 * kVBuf;                  // [2][kABuf] behind the patch buffers (kALds)
+  char* const asm_ = vsm + 2 * kVBuf;                  // [2][kABuf] filter blocks behind the patch buffers
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool is_mma = wave < 4;
@@ -486,9 +454,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16x3v2s_kernel(const ConvArgs a)
   const int ltid = tid & 255;                         // thread index inside its role
   const int pcol = lane & 31, kh = lane >> 5;
 
-  const unsigned nblk = gridDim.x, bid = blockIdx.x;
-  const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-  unsigned tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  unsigned tile = uwm_xcd_tile();
   const int tilesN = (a.Cout + kCo - 1) / kCo;
   const int tilesW = a.Wo / kVW, tilesH = a.Ho / kVH;
   // tile order inside an XCD's contiguous range: channel tile fastest (the channel tiles of one pixel tile share the patch in L2)
@@ -507,15 +473,10 @@ __global__ __launch_bounds__(512, 1) void conv_f16x3v2s_kernel(const ConvArgs a)
   }
   const int n0 = tn * kCo, h0 = th * kVH, w0 = tw * kVW;
   const int nF = a.wu_ncb;
-  const int nchunk = a.Ctot >> 4, nsteps = nchunk * 9;
+  const int nchunk = a.Ctot >> 4;
 
   float xs = 1.f;
-  if (a.xmax) {
-    float mx = a.xmax[lane & 31];
-#pragma unroll
-    for (int d = 16; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-    if (mx > 0.f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); xs = ldexpf(1.f, 14 - e); }
-  }
+  if (a.xmax) xs = uwm_dy_scale(a.xmax);
 
   f16v acc[2][NCF];
 #pragma unroll
@@ -527,7 +488,6 @@ __global__ __launch_bounds__(512, 1) void conv_f16x3v2s_kernel(const ConvArgs a)
 
   if (!is_mma) {
     // ================= loader waves =================
-#if UWM_V2_W128
     // unit u = rd * 256 + ltid -> pixel u >> 1 of the 10 x 34 patch, channel OCTET u & 1 (= ltid & 1): two 16-byte loads, and the
     // eight hi / lo halfs leave as ONE 16-byte LDS store each (half the store instructions of the quad form: the LDS stores of the
     // loader waves, not their loads or their arithmetic, are what the MMA waves feel — profiles/r04_t_*)
@@ -576,13 +536,8 @@ __global__ __launch_bounds__(512, 1) void conv_f16x3v2s_kernel(const ConvArgs a)
         u2 hi[2], lo[2];
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-          const f4 raw = st.pv[rd][e];
-          f4 v;
-          v.x = __builtin_amdgcn_fmed3f(__builtin_fmaf(raw.x, st.sc[e].x, st.sh[e].x), lo_c, hi_c);
-          v.y = __builtin_amdgcn_fmed3f(__builtin_fmaf(raw.y, st.sc[e].y, st.sh[e].y), lo_c, hi_c);
-          v.z = __builtin_amdgcn_fmed3f(__builtin_fmaf(raw.z, st.sc[e].z, st.sh[e].z), lo_c, hi_c);
-          v.w = __builtin_amdgcn_fmed3f(__builtin_fmaf(raw.w, st.sc[e].w, st.sh[e].w), lo_c, hi_c);
-          split4(v, hi[e], lo[e]);
+          const f4 v = v2_stage4(st.pv[rd][e], st.sc[e], st.sh[e], lo_c, hi_c);
+          uwm_split4(v.x, v.y, v.z, v.w, hi[e], lo[e]);
         }
         const int u = rd * 256 + ltid;
         char* d = vsm + buf * kVBuf + (u & 1) * kVPlane + (u >> 1) * 16;
@@ -591,63 +546,6 @@ __global__ __launch_bounds__(512, 1) void conv_f16x3v2s_kernel(const ConvArgs a)
         *(u4*)(d + 2 * kVPlane) = (u4){lo[0].x, lo[0].y, lo[1].x, lo[1].y};
       }
     };
-#else
-    int goff0[kVRounds], goff1[kVRounds];                // chunk-invariant source offsets of a round, per source of the concat
-    unsigned gflags = 0;
-    const bool has_x = ltid < kVUnits - (kVRounds - 1) * 256;
-#pragma unroll
-    for (int rd = 0; rd < kVRounds; ++rd) {
-      const int u = rd * 256 + ltid;
-      const bool act = u < kVUnits;
-      const int pp = act ? (u >> 2) : 0;
-      const int py = pp / kVPW, pxx = pp - py * kVPW;
-      const int hl = h0 - 1 + py, wl = w0 - 1 + pxx;
-      const bool ok = act && hl >= 0 && hl < a.Hl && wl >= 0 && wl < a.Wl;
-      const int hc = min(max(hl, 0), a.Hl - 1), wc = min(max(wl, 0), a.Wl - 1);
-      goff0[rd] = ((n * a.s0.H + (hc >> a.s0.up)) * a.s0.W + (wc >> a.s0.up)) * a.s0.C;
-      goff1[rd] = a.C0 < a.Ctot ? ((n * a.s1.H + (hc >> a.s1.up)) * a.s1.W + (wc >> a.s1.up)) * a.s1.C : goff0[rd];
-      gflags |= (ok ? 1u : 0u) << rd;
-    }
-    struct Stage { f4 pv[kVRounds]; f4 sc, sh; float floor_; };
-    auto patch_load = [&](int cc, Stage& st) {
-      if (dbg & 8) return;
-      if ((dbg & 16) && cc > 2) return;
-      const int c = cc * 16;
-      const bool first = c < a.C0;
-      const Src& s = first ? a.s0 : a.s1;
-      const int cl = (first ? c : c - a.C0) + (ltid & 3) * 4;
-      if (s.scale != nullptr) { st.sc = *(const f4*)(s.scale + cl) * xs; st.sh = *(const f4*)(s.shift + cl) * xs; st.floor_ = s.relu ? 0.f : -65504.f; }
-      else { st.sc = (f4){xs, xs, xs, xs}; st.sh = (f4){0.f, 0.f, 0.f, 0.f}; st.floor_ = -65504.f; }
-      const float* sp = s.ptr + cl;
-#pragma unroll
-      for (int rd = 0; rd < kVRounds; ++rd) st.pv[rd] = *(const f4*)(sp + (first ? goff0[rd] : goff1[rd]));      // (every wave issues all six: the counted wait below relies on it; the offsets of inactive units are valid duplicates)
-    };
-    auto patch_store = [&](int buf, const Stage& st) {
-      if (dbg & 8) return;
-      if ((dbg & 32) && buf >= 0) { asm volatile("" :: "v"(st.pv[0].x), "v"(st.pv[5].w)); return; }
-#pragma unroll
-      for (int rd = 0; rd < kVRounds; ++rd) {
-        if (rd == kVRounds - 1 && !has_x) break;
-        const bool ok = (gflags >> rd) & 1u;
-        const float lo_c = ok ? st.floor_ : 0.f, hi_c = ok ? 65504.f : 0.f;
-        const f4 raw = st.pv[rd];
-        f4 v;
-        v.x = __builtin_amdgcn_fmed3f(__builtin_fmaf(raw.x, st.sc.x, st.sh.x), lo_c, hi_c);
-        v.y = __builtin_amdgcn_fmed3f(__builtin_fmaf(raw.y, st.sc.y, st.sh.y), lo_c, hi_c);
-        v.z = __builtin_amdgcn_fmed3f(__builtin_fmaf(raw.z, st.sc.z, st.sh.z), lo_c, hi_c);
-        v.w = __builtin_amdgcn_fmed3f(__builtin_fmaf(raw.w, st.sc.w, st.sh.w), lo_c, hi_c);
-        u2 hi, lo;
-        if (dbg & 256) { hi = (u2){__builtin_bit_cast(unsigned, raw.x), __builtin_bit_cast(unsigned, raw.y)}; lo = (u2){__builtin_bit_cast(unsigned, raw.z), __builtin_bit_cast(unsigned, raw.w)}; }
-        else split4(v, hi, lo);
-        const int u = rd * 256 + ltid;
-        char* d = vsm + buf * kVBuf + ((u >> 1) & 1) * kVPlane + (u >> 2) * 16 + (u & 1) * 8;
-        if (dbg & 128) { asm volatile("" :: "v"(hi.x), "v"(hi.y), "v"(lo.x), "v"(lo.y)); continue; }
-        *(u2*)d = hi;
-        *(u2*)(d + 2 * kVPlane) = lo;
-      }
-    };
-#endif
-    if (dbg & 512) __builtin_amdgcn_s_setprio(3);
     // kLS register stages: chunk c+1 is stored while chunk c is multiplied, its loads were issued kLS - 1 iterations earlier
     // (UWM_V2_LS = 2: two chunks of latency budget; 3: three)
     constexpr int kLS = UWM_V2_LS;
@@ -674,17 +572,11 @@ __global__ __launch_bounds__(512, 1) void conv_f16x3v2s_kernel(const ConvArgs a)
   } else {
     // ================= MMA waves =================
     const _Float16* const wb = (const _Float16*)a.wu + (size_t)(n0 / 32) * 1024 + lane * 8;
-    auto w_load = [&](int t, h8 (&whi)[NCF], h8 (&wlo)[NCF]) {
-      if ((dbg & 2) && t >= kSD) return;
-      const _Float16* p = wb + (size_t)t * nF * 1024;
-#pragma unroll
-      for (int j = 0; j < NCF; ++j) { whi[j] = *(const h8*)(p + j * 1024); wlo[j] = *(const h8*)(p + j * 1024 + 512); }
-    };
-    // kALds: filter fragments of chunk cc -> LDS block cc & 1 by LDS-DMA, piece k (1 KB = one fragment plane, lane-linear on both
+    // filter fragments of chunk cc -> LDS block cc & 1 by LDS-DMA, piece k (1 KB = one fragment plane, lane-linear on both
     // sides) through MMA wave k & 3.  Issued at the START of chunk cc - 1: the MMA waves have no other vector-memory traffic, so the
     // pieces have a whole chunk of MFMAs to land and the vmcnt(0) of the chunk's closing __syncthreads() finds them done
     auto a_dma = [&](int cc) {
-      if (!kALds || (dbg & 2) || (dbg & 64)) return;
+      if (dbg & (2 | 64)) return;
       char* const dst = asm_ + (cc & 1) * kABuf;
 #pragma unroll
       for (int i = 0; i < (kAPieces + 3) / 4; ++i) {
@@ -696,22 +588,13 @@ __global__ __launch_bounds__(512, 1) void conv_f16x3v2s_kernel(const ConvArgs a)
         }
       }
     };
-    auto w_lds = [&](int c, int tap, h8 (&whi)[NCF], h8 (&wlo)[NCF]) {      // kALds: the same fragments out of the chunk's LDS block
+    auto w_lds = [&](int c, int tap, h8 (&whi)[NCF], h8 (&wlo)[NCF]) {      // the same fragments out of the chunk's LDS block
       if (dbg & 2) { whi[0] = (h8){1, 1, 1, 1, 1, 1, 1, 1}; wlo[0] = whi[0]; if (NCF > 1) { whi[NCF - 1] = whi[0]; wlo[NCF - 1] = whi[0]; } return; }
       const char* p = asm_ + (c & 1) * kABuf + tap * (2 * NCF) * 1024 + lane * 16;
 #pragma unroll
       for (int j = 0; j < NCF; ++j) { whi[j] = *(const h8*)(p + (2 * j) * 1024); wlo[j] = *(const h8*)(p + (2 * j + 1) * 1024); }
     };
     const int pbase = kh * kVPlane + ((2 * mw) * kVPW + pcol) * 16;
-    auto x_load = [&](int tap, const char* pc, h8 (&xh)[2], h8 (&xl)[2]) {
-      const int off = ((tap / 3) * kVPW + tap % 3) * 16;
-      const char* pp = pc + pbase + off;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        if (dbg & 4) { xh[i] = (h8){1, 1, 1, 1, 1, 1, 1, 1}; xl[i] = xh[i]; continue; }
-        xh[i] = *(const h8*)(pp + i * kVPW * 16); xl[i] = *(const h8*)(pp + i * kVPW * 16 + 2 * kVPlane);
-      }
-    };
     auto mma = [&](const h8 (&whi)[NCF], const h8 (&wlo)[NCF], const h8 (&xh)[2], const h8 (&xl)[2]) {
       if (dbg & 1) { acc[0][0][0] += (float)xh[0][0] + (float)xl[1][1] + (float)whi[0][2] + (float)wlo[NCF - 1][3] + (float)xh[1][0]; return; }
 #pragma unroll
@@ -731,59 +614,29 @@ __global__ __launch_bounds__(512, 1) void conv_f16x3v2s_kernel(const ConvArgs a)
           for (int j = 0; j < NCF; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlo[j], xh[i], acc[i][j], 0, 0, 0);
       }
     };
-    constexpr int kPD = UWM_V2_PD;                       // LDS prefetch distance of the MMA waves in taps (1 or 2)
-    h8 w_hi[kSD][NCF], w_lo[kSD][NCF];
-    h8 x_h[3][2], x_l[3][2];
-    if (!kALds) {
-#pragma unroll
-      for (int d = 0; d < kSD - 1; ++d) w_load(d < nsteps ? d : nsteps - 1, w_hi[d], w_lo[d]);
-    } else a_dma(0);
+    h8 w_hi[2][NCF], w_lo[2][NCF];
+    h8 x_h[2][2], x_l[2][2];
+    a_dma(0);
     __syncthreads();                                       // chunk 0 staged (patch and filter block)
-    // one chunk of the walk; `base` = (taps done so far) % kSD, a compile-time constant after unrolling
-    auto chunk = [&](int c, auto base_c) {
-      constexpr int base = decltype(base_c)::value;
+    auto chunk = [&](int c) {
       const char* pc = vsm + (c & 1) * kVBuf;
-      if (kALds && c + 1 < nchunk) a_dma(c + 1);
-      x_load(0, pc, x_h[0], x_l[0]);
-      if (kALds) w_lds(c, 0, w_hi[0], w_lo[0]);
-      if (kALds && kPD == 2) { x_load(1, pc, x_h[1], x_l[1]); w_lds(c, 1, w_hi[1], w_lo[1]); }
+      if (c + 1 < nchunk) a_dma(c + 1);
+      v2_x_load(pc + pbase, 0, x_h[0], x_l[0]);
+      w_lds(c, 0, w_hi[0], w_lo[0]);
 #pragma unroll
-      for (int ks = 0; ks < 9; ++ks) {
-        const int t = c * 9 + ks;
+      for (int ks = 0; ks < 9; ++ks) {                     // both operands from LDS, one tap ahead
         const int xsn = ks & 1;
-        if (kALds && kPD == 2) {                           // both operands from LDS, TWO taps ahead (three register sets: 9 taps = 3 x 3)
-          const int cur = ks % 3, nx2 = (ks + 2) % 3;
-          if (ks < 7) { w_lds(c, ks + 2, w_hi[nx2], w_lo[nx2]); x_load(ks + 2, pc, x_h[nx2], x_l[nx2]); }
-          __builtin_amdgcn_sched_barrier(0);
-          mma(w_hi[cur], w_lo[cur], x_h[cur], x_l[cur]);
-        } else if (kALds) {                                // both operands from LDS, one tap ahead
-          if (ks < 8) { w_lds(c, ks + 1, w_hi[xsn ^ 1], w_lo[xsn ^ 1]); x_load(ks + 1, pc, x_h[xsn ^ 1], x_l[xsn ^ 1]); }
-          __builtin_amdgcn_sched_barrier(0);
-          mma(w_hi[xsn], w_lo[xsn], x_h[xsn], x_l[xsn]);
-        } else {
-          const int tp = t + kSD - 1 < nsteps ? t + kSD - 1 : nsteps - 1;
-          const int ws = (base + ks) % kSD, wl = (base + ks + kSD - 1) % kSD;
-          w_load(tp, w_hi[wl], w_lo[wl]);
-          if (ks < 8) x_load(ks + 1, pc, x_h[xsn ^ 1], x_l[xsn ^ 1]);
-          __builtin_amdgcn_sched_barrier(0);               // (operand loads are ISSUED ahead of the MFMA block, not sunk behind it)
-          mma(w_hi[ws], w_lo[ws], x_h[xsn], x_l[xsn]);
-        }
+        if (ks < 8) { w_lds(c, ks + 1, w_hi[xsn ^ 1], w_lo[xsn ^ 1]); v2_x_load(pc + pbase, ks + 1, x_h[xsn ^ 1], x_l[xsn ^ 1]); }
+        __builtin_amdgcn_sched_barrier(0);                 // (operand loads are ISSUED ahead of the MFMA block, not sunk behind it)
+        mma(w_hi[xsn], w_lo[xsn], x_h[xsn], x_l[xsn]);
         __builtin_amdgcn_sched_barrier(0);
       }
       __syncthreads();
     };
+    // four chunks per trip and a tail of two (Ctot % 32 == 0: nchunk is even) — the walk's unrolling is part of the kernel's schedule
     int c = 0;
-    if (kTrip == 4) {
-      for (; c + 4 <= nchunk; c += 4) {
-        chunk(c, std::integral_constant<int, 0>{}); chunk(c + 1, std::integral_constant<int, 9 % kSD>{});
-        chunk(c + 2, std::integral_constant<int, 18 % kSD>{}); chunk(c + 3, std::integral_constant<int, 27 % kSD>{});
-      }
-      if (c < nchunk) { chunk(c, std::integral_constant<int, 0>{}); chunk(c + 1, std::integral_constant<int, 9 % kSD>{}); }      // (nchunk is even)
-    } else if (kTrip == 2) {
-      for (; c < nchunk; c += 2) { chunk(c, std::integral_constant<int, 0>{}); chunk(c + 1, std::integral_constant<int, 9 % kSD>{}); }
-    } else {
-      for (; c < nchunk; c += 2) { chunk(c, std::integral_constant<int, 0>{}); chunk(c + 1, std::integral_constant<int, 0>{}); }
-    }
+    for (; c + 4 <= nchunk; c += 4) { chunk(c); chunk(c + 1); chunk(c + 2); chunk(c + 3); }
+    if (c < nchunk) { chunk(c); chunk(c + 1); }
   }
 
   // ---------------- epilogue (the 4-wave kernel's, spread over eight waves): an MMA wave's 64 px x kCo block goes through its LDS
@@ -841,8 +694,8 @@ hipError_t launch_conv_f16x3v2(const ConvArgs& a, hipStream_t st, bool four_wave
     const size_t lds = main_lds > q_lds ? main_lds : q_lds;
     return np == 3 ? launch_v2<1, 3>(a, st, grid, lds) : np == 2 ? launch_v2<1, 2>(a, st, grid, lds) : launch_v2<1, 1>(a, st, grid, lds);
   }
-  const size_t s_lds = UWM_V2_ALDS ? (size_t)2 * kVBuf + (size_t)2 * 9 * 2 * 1024 : 0;      // patch buffers + two filter-fragment blocks
-  const size_t lds = s_lds > q_lds ? s_lds : q_lds;
+  const size_t lds = (size_t)2 * kVBuf + (size_t)2 * 9 * 2 * 1024;      // patch buffers + two filter-fragment blocks (the epilogue blocks reuse them)
+  static_assert((size_t)2 * kVBuf >= (size_t)4 * 64 * VQ<1>::kLd * sizeof(float), "the epilogue blocks fit the patch buffers");
   return np == 3 ? launch_v2s<1, 3>(a, st, grid, lds) : np == 2 ? launch_v2s<1, 2>(a, st, grid, lds) : launch_v2s<1, 1>(a, st, grid, lds);
 }
 

@@ -42,10 +42,8 @@ typedef unsigned g_u4 __attribute__((ext_vector_type(4)));
 // 8 consecutive channels (two f4) -> the hi and lo fp16 fragments of one v_mfma_f32_16x16x32_f16 operand lane
 __device__ __forceinline__ void gemm_split8(f4 a0, f4 a1, g_h8& hi, g_h8& lo) {
   uwm_u2 h0, l0, h1, l1;
-  uwm_split4(__builtin_amdgcn_fmed3f(a0.x, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(a0.y, -65504.f, 65504.f),
-             __builtin_amdgcn_fmed3f(a0.z, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(a0.w, -65504.f, 65504.f), h0, l0);
-  uwm_split4(__builtin_amdgcn_fmed3f(a1.x, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(a1.y, -65504.f, 65504.f),
-             __builtin_amdgcn_fmed3f(a1.z, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(a1.w, -65504.f, 65504.f), h1, l1);
+  uwm_split4_clamped(a0.x, a0.y, a0.z, a0.w, h0, l0);
+  uwm_split4_clamped(a1.x, a1.y, a1.z, a1.w, h1, l1);
   hi = __builtin_bit_cast(g_h8, (g_u4){h0.x, h0.y, h1.x, h1.y});
   lo = __builtin_bit_cast(g_h8, (g_u4){l0.x, l0.y, l1.x, l1.y});
 }
@@ -107,12 +105,7 @@ __global__ __launch_bounds__(256, (BN == 64 ? 3 : 2)) void conv_gemm_kernel(cons
     }
   };
   float dys = 1.f;                                // F16: power-of-two scale of a dgrad's dY
-  if (F16 && a.xmax) {
-    float mx = a.xmax[lane & 31];
-#pragma unroll
-    for (int d = 16; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-    if (mx > 0.f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); dys = ldexpf(1.f, 14 - e); }
-  }
+  if (F16 && a.xmax) dys = uwm_dy_scale(a.xmax);
   const float unscale = F16 ? 1.f / (kGWScale * dys) : 1.f;
 
   f4 acc[MI][NI];

@@ -57,9 +57,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvArgs a) {
 
   // XCD-aware bijective block remap: blocks that share an XCD (bid % 8) get a contiguous range
   // of tiles, so halo rows / the weight panel stay in that XCD's L2.
-  const unsigned nblk = gridDim.x, bid = blockIdx.x;
-  const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-  const unsigned tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const unsigned tile = uwm_xcd_tile();
   const int tilesN = (a.Cout + BN - 1) / BN;
   const int tm = tile / tilesN, tn = tile - tm * tilesN;
   const int m0 = tm * BM, n0 = tn * BN;
@@ -90,12 +88,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvArgs a) {
 #pragma unroll
     for (int j = 0; j < NI; ++j) acc[i][j] = (f4){0.f, 0.f, 0.f, 0.f};
   float xs = 1.f;                                      // F16: power-of-two scale of a dgrad's dY
-  if (F16 && a.xmax) {
-    float mx = a.xmax[lane & 31];
-#pragma unroll
-    for (int d = 16; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-    if (mx > 0.f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); xs = ldexpf(1.f, 14 - e); }
-  }
+  if (F16 && a.xmax) xs = uwm_dy_scale(a.xmax);
 
   f4 xr[XR], wr[WR], tsc, tsh;
   unsigned xvalid = 0; int trelu = 0; bool thas = false;
@@ -157,8 +150,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvArgs a) {
       if (F16) {          // hi halfs of k = 4 unit .. +3 -> bytes [8 unit, 8 unit + 8) of the row's hi half, lo halfs -> the same place in the lo half
         uwm_u2 hi, lo;
         const float sc = xs_;
-        uwm_split4(__builtin_amdgcn_fmed3f(v.x * sc, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(v.y * sc, -65504.f, 65504.f),
-                   __builtin_amdgcn_fmed3f(v.z * sc, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(v.w * sc, -65504.f, 65504.f), hi, lo);
+        uwm_split4(uwm_clamp_h(v.x * sc), uwm_clamp_h(v.y * sc), uwm_clamp_h(v.z * sc), uwm_clamp_h(v.w * sc), hi, lo);
         char* rb = (char*)(xs + row * 32);
         const int sw = (row >> 1) & 7;
         *(uwm_u2*)(rb + (((unit >> 1) ^ sw) << 4) + (unit & 1) * 8) = hi;
@@ -175,8 +167,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvArgs a) {
         if (BN >= 32 || r0 < BN) {
           uwm_u2 hi, lo;
           const f4 w4 = wr[i] * kIgWScale;
-          uwm_split4(__builtin_amdgcn_fmed3f(w4.x, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(w4.y, -65504.f, 65504.f),
-                     __builtin_amdgcn_fmed3f(w4.z, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(w4.w, -65504.f, 65504.f), hi, lo);
+          uwm_split4_clamped(w4.x, w4.y, w4.z, w4.w, hi, lo);
           char* rb = (char*)(ws + row * 32);
           const int sw = (row >> 1) & 7;
           *(uwm_u2*)(rb + (((unit >> 1) ^ sw) << 4) + (unit & 1) * 8) = hi;

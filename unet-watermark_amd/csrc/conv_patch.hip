@@ -38,9 +38,7 @@ __global__ __launch_bounds__(256, BN >= 128 ? 2 : 3) void conv_patch_kernel(cons
 
   // one tile per workgroup (measured: a persistent multi-tile walk with cross-tile prefetch was ~8 %
   // slower — dynamic dispatch balances and de-synchronises workgroups better); XCD-aware bijective remap
-  const unsigned nblk = gridDim.x, bid = blockIdx.x;
-  const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-  unsigned tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  unsigned tile = uwm_xcd_tile();
   const int tilesN = (a.Cout + BN - 1) / BN;
   const int tilesW = (a.Wo + kTW - 1) / kTW, tilesH = (a.Ho + kTH - 1) / kTH;
   const int tn = tile % tilesN; tile /= tilesN;

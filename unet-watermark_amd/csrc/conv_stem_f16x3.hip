@@ -46,8 +46,7 @@ __global__ __launch_bounds__(256) void stem_f16x3_weights_kernel(const float* __
     for (int i = q; i < 49 * cin_p; i += 16) mx = fmaxf(mx, fabsf(wr[i]));
 #pragma unroll
     for (int d = 1; d < 16; d <<= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-    float s = 1.f;
-    if (mx > 0.f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); s = ldexpf(1.f, 14 - e); }
+    const float s = uwm_pow2_scale(mx);
     if (q == 0) { sc[r] = s; bank[stem_rinv_off_floats() + j * 16 + r] = 1.f / s; }
   }
   __syncthreads();
@@ -74,7 +73,6 @@ hipError_t launch_stem_f16x3_weights(const float* w, int Kpad, int cin_p, float*
   return hipGetLastError();
 }
 
-__device__ __forceinline__ float clamp_hs(float v) { return __builtin_amdgcn_fmed3f(v, -65504.f, 65504.f); }
 
 __global__ __launch_bounds__(256, 2) void conv_stem_f16x3_kernel(const ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) _Float16 ssm[];      // [hi | lo][37][40][4]; the epilogue's [4][64][68] floats alias it
@@ -119,7 +117,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem_f16x3_kernel(const ConvArgs 
       h4 hi, lo;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float x = clamp_hs(pv[rd][e]);
+        const float x = uwm_clamp_h(pv[rd][e]);
         const _Float16 h = (_Float16)x;
         hi[e] = h; lo[e] = (_Float16)(x - (float)h);
       }

@@ -37,23 +37,11 @@ __device__ __forceinline__ int t1d(int t) { return t == 0 ? 2 : (t == 1 ? 2 : (t
 
 __device__ __forceinline__ void put_frag(char* bank, int frag, int lane, const float* v) {
   uwm_u2 h0, l0, h1, l1;
-  uwm_split4(__builtin_amdgcn_fmed3f(v[0] * kWScale, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(v[1] * kWScale, -65504.f, 65504.f),
-             __builtin_amdgcn_fmed3f(v[2] * kWScale, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(v[3] * kWScale, -65504.f, 65504.f), h0, l0);
-  uwm_split4(__builtin_amdgcn_fmed3f(v[4] * kWScale, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(v[5] * kWScale, -65504.f, 65504.f),
-             __builtin_amdgcn_fmed3f(v[6] * kWScale, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(v[7] * kWScale, -65504.f, 65504.f), h1, l1);
+  uwm_split4(uwm_clamp_h(v[0] * kWScale), uwm_clamp_h(v[1] * kWScale), uwm_clamp_h(v[2] * kWScale), uwm_clamp_h(v[3] * kWScale), h0, l0);
+  uwm_split4(uwm_clamp_h(v[4] * kWScale), uwm_clamp_h(v[5] * kWScale), uwm_clamp_h(v[6] * kWScale), uwm_clamp_h(v[7] * kWScale), h1, l1);
   uwm_u2* const ph = (uwm_u2*)(bank + ((frag * 2 + 0) * 64 + lane) * 16);
   uwm_u2* const pl = (uwm_u2*)(bank + ((frag * 2 + 1) * 64 + lane) * 16);
   ph[0] = h0; ph[1] = h1; pl[0] = l0; pl[1] = l1;
-}
-__device__ __forceinline__ float dy_scale(const float* xmax, int lane) {
-  float xs = 1.f;
-  if (xmax) {
-    float mx = xmax[lane & 31];
-#pragma unroll
-    for (int d = 16; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-    if (mx > 0.f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); xs = ldexpf(1.f, 14 - e); }
-  }
-  return xs;
 }
 }  // namespace
 
@@ -241,7 +229,7 @@ __global__ __launch_bounds__(256, 2) void conv_up2_dgrad_f16_kernel(const ConvAr
   const int lrow = lane & 15, lq = lane >> 4;
   const int Hs = a.Ho >> 1, Wsrc = a.Wo >> 1;
   const int tilesW = Wsrc / kDW, tilesH = Hs / kDH;
-  const float xs = dy_scale(a.xmax, lane);
+  const float xs = a.xmax ? uwm_dy_scale(a.xmax) : 1.f;
 
   // ---- staging geometry: 10 rows x 34 columns x 4 units (4 co each) = 1360 units, 6 rounds
   const int unit = tid & 3;
@@ -278,8 +266,7 @@ __global__ __launch_bounds__(256, 2) void conv_up2_dgrad_f16_kernel(const ConvAr
     for (int rd = 0; rd < 6; ++rd) {
       const f4 v = pv[rd] * xs;
       uwm_u2 hi, lo;
-      uwm_split4(__builtin_amdgcn_fmed3f(v.x, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(v.y, -65504.f, 65504.f),
-                 __builtin_amdgcn_fmed3f(v.z, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(v.w, -65504.f, 65504.f), hi, lo);
+      uwm_split4_clamped(v.x, v.y, v.z, v.w, hi, lo);
       if (rd < 5 || last_live) { *(uwm_u2*)(pb_ + spos[rd]) = hi; *(uwm_u2*)(pb_ + (spos[rd] ^ 64)) = lo; }
     }
   };
@@ -413,15 +400,6 @@ hipError_t launch_conv_up2_dgrad_f16(const ConvArgs& a, hipStream_t st) {
 // co | lo], X~ [4][34][hi 32 ch | lo]; the stride-2 walk over dY and the neighbourhood shifts are lane addresses).  Tile = 2 x 32
 // low-resolution pixels; wave = (tile row, 16-channel block cb): 16 accumulators, 48 MFMAs per tile.  Persistent, stages
 // double-buffered.  The workgroup partial has wgrad_up2_kernel's layout: wgrad_up2_reduce_kernel folds both.
-typedef __fp16 u_fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-typedef __attribute__((address_space(3))) u_fp16x4 u_lds_fp16x4;
-__device__ __forceinline__ h8 u_tr_pair(const char* base, int o0, int o1) {
-  const u_fp16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16((u_lds_fp16x4*)(uintptr_t)(base + o0));
-  const u_fp16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16((u_lds_fp16x4*)(uintptr_t)(base + o1));
-  typedef __fp16 fp16x8 __attribute__((__vector_size__(8 * sizeof(__fp16))));
-  const fp16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(h8, v);
-}
 namespace {
 constexpr int kWH = 2, kWW = 32;                                   // low-resolution pixels per tile
 constexpr int kWPW = kWW + 2, kWPix = (kWH + 2) * kWPW;            // 4 x 34 = 136 patch pixels
@@ -437,7 +415,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_up2_f16_kernel(const WgradArgs a
   const int kr = wave >> 1, cb = wave & 1;
   const int Hs = a.s0.H, Wsrc = a.s0.W;
   const int tilesW = Wsrc / kWW, tilesH = Hs / kWH;
-  const float xs = dy_scale(a.xmax, lane);
+  const float xs = a.xmax ? uwm_dy_scale(a.xmax) : 1.f;
 
   // ---- staging: X~ 136 px x 8 quads = 1088 units (5 rounds), dY 256 px x 4 quads = 1024 units (4 rounds)
   const int xunit = tid & 7, yunit = tid & 3;
@@ -526,14 +504,14 @@ __global__ __launch_bounds__(256, 2) void wgrad_up2_f16_kernel(const WgradArgs a
 #pragma unroll
       for (int pb = 0; pb < 2; ++pb) {
         const char* const ya = yb + yo + (pa * 64 + pb) * 64;
-        ah[pa][pb] = u_tr_pair(ya, 0, 512); al[pa][pb] = u_tr_pair(ya, 32, 512 + 32);
+        ah[pa][pb] = uwm_tr_pair(ya, 0, 512); al[pa][pb] = uwm_tr_pair(ya, 32, 512 + 32);
       }
 #pragma unroll
     for (int py = 0; py < 3; ++py)
 #pragma unroll
       for (int px = 0; px < 3; ++px) {
         const char* const xa = xb + xo + (py * kWPW + px) * 128;
-        const h8 bh = u_tr_pair(xa, 0, 512), bl = u_tr_pair(xa, 64, 512 + 64);
+        const h8 bh = uwm_tr_pair(xa, 0, 512), bl = uwm_tr_pair(xa, 64, 512 + 64);
         // (py, px) = (pa + dy_, pb + dx_): the class products this neighbourhood pixel feeds
 #pragma unroll
         for (int pa = 0; pa < 2; ++pa)

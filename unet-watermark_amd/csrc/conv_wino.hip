@@ -150,9 +150,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const ConvArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int t16 = lane & 15, lq = lane >> 4;
 
-  const unsigned nblk = gridDim.x, bid = blockIdx.x;
-  const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-  unsigned tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  unsigned tile = uwm_xcd_tile();
   const int tilesN = (a.Cout + BN - 1) / BN;
   const int tilesW = (a.Wo + kTW - 1) / kTW, tilesH = (a.Ho + kTH - 1) / kTH;
   const int tn = tile % tilesN; tile /= tilesN;

@@ -36,9 +36,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino8_kernel(const ConvArgs a) {
   const int wrow = wave & 3, half = wave >> 2;
   const int t16 = lane & 15, lq = lane >> 4;
 
-  const unsigned nblk = gridDim.x, bid = blockIdx.x;
-  const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-  unsigned tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  unsigned tile = uwm_xcd_tile();
   const int tilesN = (a.Cout + 63) / 64;
   const int tilesW = (a.Wo + kT8 - 1) / kT8, tilesH = (a.Ho + kT8 - 1) / kT8;
   const int tn = tile % tilesN; tile /= tilesN;

@@ -107,6 +107,50 @@ template <class A> static inline int route_N(const A& a) { return a.route_n > 0 
 template <class A> static inline long route_M(const A& a) { return a.N > 0 ? (long)a.M / a.N * route_N(a) : (long)a.M; }
 
 #if defined(__HIPCC__)
+// ---- device helpers the convolution and weight-gradient kernels share ----
+typedef _Float16 uwm_h8 __attribute__((ext_vector_type(8)));
+
+// Power-of-two range scale of the fp16x3 arithmetic: the factor 2^(14 - e) that puts a maximum mx = m * 2^e (m in [0.5, 1)) into
+// [2^13, 2^14) — high in fp16's range (largest finite value 65504), so the hi / lo halves of the small values beside it stay
+// normal numbers.  Exact (a power of two), undone in the epilogue.  1 for a zero, infinite or NaN maximum.
+__device__ __forceinline__ float uwm_pow2_scale(float mx) {
+  float s = 1.f;
+  if (mx > 0.f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); s = ldexpf(1.f, 14 - e); }
+  return s;
+}
+// Range scale of a dgrad's dY: max|dY| = the maximum of the 32 floats at xmax (ConvArgs::xmax, filled by bn_bwd_apply), every
+// lane of the wave gets the same value (32-lane butterfly; workgroups are one-dimensional).  xmax is not null: whether a launch
+// scales at all is the caller's guard.  The lane index is taken here, not passed in: handing the kernel's `lane` through a
+// parameter changed the instruction order of wgrad_f16x3_kernel<16> and wgrad_stem_f16_kernel (scripts/isa_identity.py).
+__device__ __forceinline__ float uwm_dy_scale(const float* xmax) {
+  float mx = xmax[threadIdx.x & 31];
+#pragma unroll
+  for (int d = 16; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
+  return uwm_pow2_scale(mx);
+}
+// XCD-aware walk: the hardware deals workgroups round-robin over the 8 XCDs, so consecutive blockIdx.x values — neighbouring tiles
+// that stream the SAME operand block — land on eight different L2s and fetch it eight times (wgrad_f16x3, PMC: 235 MB fetched
+// per launch against 83 MB algorithmic).  This bijective remap of blockIdx.x gives every XCD a contiguous range of the linear
+// tile order (the first gridDim.x % 8 XCDs one tile more), so the tiles that share an operand meet in one L2.
+__device__ __forceinline__ unsigned uwm_xcd_tile() {
+  const unsigned nblk = gridDim.x, bid = blockIdx.x;
+  const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+}
+// Two transposed LDS reads (ds_read_b64_tr_b16: a 4 x 16 block of halfs per 16 lanes, delivered column-major) joined into one
+// 8-half MFMA operand fragment
+__device__ __forceinline__ uwm_h8 uwm_tr_pair(const char* base, int o0, int o1) {
+  typedef __fp16 fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
+  typedef __fp16 fp16x8 __attribute__((__vector_size__(8 * sizeof(__fp16))));
+  typedef __attribute__((address_space(3))) fp16x4 lds_fp16x4;
+  const fp16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_fp16x4*)(uintptr_t)(base + o0));
+  const fp16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_fp16x4*)(uintptr_t)(base + o1));
+  const fp16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  return __builtin_bit_cast(uwm_h8, v);
+}
+// Clamp to fp16's finite range in one v_med3_f32 (fminf(fmaxf()) adds a canonicalising v_max per value)
+__device__ __forceinline__ float uwm_clamp_h(float v) { return __builtin_amdgcn_fmed3f(v, -65504.f, 65504.f); }
+
 // Split of four fp32 values into hi / lo fp16 halves (the fp16x3 operand form): hi = rn_f16(x) (v_cvt_pk_f16_f32, two values per
 // instruction), lo = rn_f16(x - hi) as ONE v_fma_mix{lo,hi}_f16 per value — fma(hi_as_f32, -1.0, x) rounded to fp16 into one half
 // of the destination, the fp16 operand selected out of the packed register by op_sel (exact: an fp32 value minus its fp16 rounding
@@ -125,6 +169,10 @@ __device__ __forceinline__ void uwm_split4(float x0, float x1, float x2, float x
       : "=&v"(l1) : "v"(hi.y), "v"(x2), "v"(x3));
   lo.x = l0; lo.y = l1;
 }
+// ... of values that may leave fp16's range (weights times their scale, raw activations): clamped first, so hi stays finite
+__device__ __forceinline__ void uwm_split4_clamped(float x0, float x1, float x2, float x3, uwm_u2& hi, uwm_u2& lo) {
+  uwm_split4(uwm_clamp_h(x0), uwm_clamp_h(x1), uwm_clamp_h(x2), uwm_clamp_h(x3), hi, lo);
+}
 // The weight operand of conv_igemm.hip's fp16x3 form, pre-split: unit i = floats [4i, 4i + 4) of a [rows][Kpad] matrix (Kpad % 32 == 0)
 // goes times 2^12, clamped, as hi / lo fp16 halves to its place in the 128-byte LDS row image of its 32-float chunk (32 hi halfs |
 // 32 lo halfs, 16-byte slots XOR-swizzled by (row >> 1) & 7) — the very arithmetic and layout of conv_igemm_kernel's staging code,
@@ -136,8 +184,7 @@ __device__ __forceinline__ void ig_bank_unit(const float* __restrict__ src, floa
   const int unit = (int)(i & 7), row = (int)((g * 32) / (size_t)Kpad);
   const f4_ w4 = *(const f4_*)(src + i * 4) * kIgWScale;
   uwm_u2 hi, lo;
-  uwm_split4(__builtin_amdgcn_fmed3f(w4.x, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(w4.y, -65504.f, 65504.f),
-             __builtin_amdgcn_fmed3f(w4.z, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(w4.w, -65504.f, 65504.f), hi, lo);
+  uwm_split4_clamped(w4.x, w4.y, w4.z, w4.w, hi, lo);
   char* rb = (char*)(dst + g * 32);
   const int sw = (row >> 1) & 7;
   *(uwm_u2*)(rb + (((unit >> 1) ^ sw) << 4) + (unit & 1) * 8) = hi;

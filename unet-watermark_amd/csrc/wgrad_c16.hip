@@ -196,16 +196,6 @@ __global__ __launch_bounds__(256, 3) void wgrad_head_kernel(const WgradArgs a, c
 // pixel-major images [px][hi 16 ch | lo 16 ch] (64 B per pixel) — a tap shift is just another row address.  Persistent workgroups,
 // the stage (dY tile + x~ halo patch, split while staging) double-buffered: the next tile's global loads are in flight behind this
 // tile's MFMAs, one barrier per tile.
-typedef _Float16 c_h8 __attribute__((ext_vector_type(8)));
-typedef __fp16 c_fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-typedef __attribute__((address_space(3))) c_fp16x4 c_lds_fp16x4;
-__device__ __forceinline__ c_h8 c_tr_pair(const char* base, int o0, int o1) {
-  const c_fp16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16((c_lds_fp16x4*)(uintptr_t)(base + o0));
-  const c_fp16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16((c_lds_fp16x4*)(uintptr_t)(base + o1));
-  typedef __fp16 fp16x8 __attribute__((__vector_size__(8 * sizeof(__fp16))));
-  const fp16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(c_h8, v);
-}
 constexpr int kFDy = kRows * kCols * 64;                     // bytes of the dY image (16 KB)
 constexpr int kFX = kPR * kPC * 64;                          // bytes of the x~ image (21 760)
 constexpr int kFBuf = kFDy + kFX;
@@ -215,12 +205,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_c16_f16_kernel(const WgradArgs a
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = a.Ho, W = a.Wo;
   float xs = 1.f;
-  if (a.xmax) {
-    float mx = a.xmax[lane & 31];
-#pragma unroll
-    for (int d = 16; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-    if (mx > 0.f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); xs = ldexpf(1.f, 14 - e); }
-  }
+  if (a.xmax) xs = uwm_dy_scale(a.xmax);
   // ---- staging geometry: thread = (pixel, channel quad); x~ 340 px x 4 = 1360 units (6 rounds), dY 256 px x 4 = 1024 units (4 rounds)
   const int chu = tid & 3;
   f4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
@@ -305,13 +290,13 @@ __global__ __launch_bounds__(256, 2) void wgrad_c16_f16_kernel(const WgradArgs a
     for (int rr = 0; rr < 2; ++rr) {
       const int row = wave * 2 + rr;
       const char* const ya = yb + row * kCols * 64 + fo;
-      const c_h8 ah = c_tr_pair(ya, 0, 256), al = c_tr_pair(ya, 32, 256 + 32);
+      const uwm_h8 ah = uwm_tr_pair(ya, 0, 256), al = uwm_tr_pair(ya, 32, 256 + 32);
 #pragma unroll
       for (int r3 = 0; r3 < 3; ++r3)
 #pragma unroll
         for (int s3 = 0; s3 < 3; ++s3) {
           const char* const xa = xb + ((row + r3) * kPC + s3) * 64 + fo;
-          const c_h8 bh = c_tr_pair(xa, 0, 256), bl = c_tr_pair(xa, 32, 256 + 32);
+          const uwm_h8 bh = uwm_tr_pair(xa, 0, 256), bl = uwm_tr_pair(xa, 32, 256 + 32);
           f4 c = acc[r3 * 3 + s3];
           c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, c, 0, 0, 0);
           c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, c, 0, 0, 0);

@@ -28,8 +28,6 @@ namespace uwm {
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef __fp16 fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-typedef __attribute__((address_space(3))) fp16x4 lds_fp16x4;
 
 #ifndef UWM_WG16_ABL
 #define UWM_WG16_ABL 0      // compile-time timing ablations (scripts/ablate_f16x3.sh wgrad ...): 1 no MFMA, 2 no X fragment reads, 4 no loader work after the first stage, 8 no partial-image stores; 0 in the product build
@@ -51,14 +49,6 @@ constexpr int kWLT = 512;                                              // loader
 constexpr int kWDyRounds = 128 * 16 / kWLT;                            // dY 16-byte units per loader thread: 4
 
 __device__ __forceinline__ int off_dy(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
-__device__ __forceinline__ float clamp_hw(float v) { return __builtin_amdgcn_fmed3f(v, -65504.f, 65504.f); }      // (one v_med3_f32; fminf(fmaxf()) adds a canonicalising v_max per value)
-__device__ __forceinline__ h8 tr_pair(const char* base, int o0, int o1) {      // two transposed reads -> one 8-half operand fragment
-  const fp16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_fp16x4*)(uintptr_t)(base + o0));
-  const fp16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_fp16x4*)(uintptr_t)(base + o1));
-  typedef __fp16 fp16x8 __attribute__((__vector_size__(8 * sizeof(__fp16))));
-  const fp16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(h8, v);
-}
 
 // NP = split products per tile (WgradArgs::nprod): 3 = dy_hi*x_hi + dy_hi*x_lo + dy_lo*x_hi; 2 = dY as ONE fp16 (no dy_lo*x_hi); 1 = dy_hi*x_hi only
 template <int WX, int NP = 3>
@@ -72,14 +62,10 @@ __global__ __launch_bounds__(768, 1) void wgrad_f16x3_kernel(const WgradArgs a, 
 
   const int tilesA = (a.wrows + 63) / 64, tilesB = a.Ctot / 32;
   const int pairs = tilesA * tilesB;
-  // XCD-aware walk (round 4): workgroups are dealt round-robin over the 8 XCDs, so consecutive blockIdx values — the input-channel
-  // tiles that stream the SAME dY block — used to land on eight different L2s and fetch it eight times (PMC: 235 MB fetched per
-  // launch against 83 MB algorithmic).  The bijective remap gives every XCD a contiguous range of the (split, co tile, ci tile)
-  // order: the siblings that share a dY block (and, next, the co tiles that share an X patch) meet in one L2.
+  // XCD-aware walk (uwm_xcd_tile) of the (split, co tile, ci tile) order: the input-channel tiles that stream the SAME dY block
+  // (and, next, the co tiles that share an X patch) meet in one L2
 #if UWM_WG16_XCD
-  const unsigned nblk = gridDim.x, bid = blockIdx.x;
-  const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-  const int lin = (int)((xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3));
+  const int lin = (int)uwm_xcd_tile();
 #else
   const int lin = blockIdx.x;
 #endif
@@ -90,12 +76,7 @@ __global__ __launch_bounds__(768, 1) void wgrad_f16x3_kernel(const WgradArgs a, 
   const int tilesX = a.Wo / kWX, tilesY = a.Ho / kWR;
 
   float xs = 1.f;                                      // power-of-two scale of dY (conv_f16x3.hip)
-  if (a.xmax) {
-    float mx = a.xmax[lane & 31];
-#pragma unroll
-    for (int d = 16; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-    if (mx > 0.f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); xs = ldexpf(1.f, 14 - e); }
-  }
+  if (a.xmax) xs = uwm_dy_scale(a.xmax);
 
   f4 acc[2][9];
 #pragma unroll
@@ -160,7 +141,7 @@ __global__ __launch_bounds__(768, 1) void wgrad_f16x3_kernel(const WgradArgs a, 
       h4 hi, lo;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float x = clamp ? clamp_hw(v[e]) : v[e];
+        const float x = clamp ? uwm_clamp_h(v[e]) : v[e];
         const _Float16 h = (_Float16)x;
         hi[e] = h; lo[e] = (_Float16)(x - (float)h);
       }
@@ -228,8 +209,8 @@ __global__ __launch_bounds__(768, 1) void wgrad_f16x3_kernel(const WgradArgs a, 
         h8 ah[2], al[2];
 #pragma unroll
         for (int cf = 0; cf < 2; ++cf) {
-          ah[cf] = tr_pair(dyb + kr * 32 * 256, dyo[cf][0], dyo[cf][1]);
-          al[cf] = tr_pair(dyb + kr * 32 * 256, dyo[cf][0] ^ 128, dyo[cf][1] ^ 128);
+          ah[cf] = uwm_tr_pair(dyb + kr * 32 * 256, dyo[cf][0], dyo[cf][1]);
+          al[cf] = uwm_tr_pair(dyb + kr * 32 * 256, dyo[cf][0] ^ 128, dyo[cf][1] ^ 128);
         }
         // Iteration it: the X fragments of tap it+1 are read (one tap ahead of their first use), hh of tap it and hl, lh of tap
         // it-1 are issued, interleaved over the two channel fragments so that the three products of a tile — they update the SAME
@@ -239,8 +220,8 @@ __global__ __launch_bounds__(768, 1) void wgrad_f16x3_kernel(const WgradArgs a, 
         auto x_read = [&](int t) {
           const int r = t / 3, sx = t % 3;
           const char* xp = xb + ((kr * kRK + r) * kWPW + sx) * kWXS + xo;
-          xh[t % 3] = (UWM_WG16_ABL & 2) ? ah[0] : tr_pair(xp, 0, 4 * kWXS);
-          xl[t % 3] = (UWM_WG16_ABL & 2) ? al[1] : tr_pair(xp, 64, 4 * kWXS + 64);
+          xh[t % 3] = (UWM_WG16_ABL & 2) ? ah[0] : uwm_tr_pair(xp, 0, 4 * kWXS);
+          xl[t % 3] = (UWM_WG16_ABL & 2) ? al[1] : uwm_tr_pair(xp, 64, 4 * kWXS + 64);
         };
         x_read(0);
 #pragma unroll

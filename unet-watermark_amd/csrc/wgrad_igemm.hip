@@ -31,16 +31,6 @@ __device__ __forceinline__ unsigned fdivw(unsigned n, FastDiv f) {
   return f.d <= 1 ? n : __umulhi(n, f.mg);
 }
 
-typedef _Float16 wi_h8 __attribute__((ext_vector_type(8)));
-typedef __fp16 wi_fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-typedef __attribute__((address_space(3))) wi_fp16x4 wi_lds_fp16x4;
-__device__ __forceinline__ wi_h8 wi_tr_pair(const char* base, int o0, int o1) {      // two transposed reads -> one 8-half operand fragment
-  const wi_fp16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16((wi_lds_fp16x4*)(uintptr_t)(base + o0));
-  const wi_fp16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16((wi_lds_fp16x4*)(uintptr_t)(base + o1));
-  typedef __fp16 fp16x8 __attribute__((__vector_size__(8 * sizeof(__fp16))));
-  const fp16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(wi_h8, v);
-}
 
 template <int TA, int TB, int WA, int WB, bool F16 = false>
 __global__ __launch_bounds__(256, 2) void wgrad_igemm_kernel(const WgradArgs a) {
@@ -61,9 +51,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_igemm_kernel(const WgradArgs a) 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wa = wave / WB, wb = wave % WB;
 
-  const unsigned nblk = gridDim.x, bid = blockIdx.x;
-  const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-  const unsigned t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const unsigned t = uwm_xcd_tile();
   const int tilesA = (a.wrows + TA - 1) / TA, tilesB = (a.Kpad + TB - 1) / TB;
   const int split = t / (tilesA * tilesB);
   const int tt = t - split * (tilesA * tilesB);
@@ -108,12 +96,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_igemm_kernel(const WgradArgs a) 
   f4 ar[PA], br[PB];
   unsigned bvalid = 0;
   float xs = 1.f;                                    // F16: power-of-two scale of dY
-  if (F16 && a.xmax) {
-    float mx = a.xmax[lane & 31];
-#pragma unroll
-    for (int d = 16; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-    if (mx > 0.f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); xs = ldexpf(1.f, 14 - e); }
-  }
+  if (F16 && a.xmax) xs = uwm_dy_scale(a.xmax);
 
   // one thread per pixel row decomposes m -> (n, ho, wo) for a whole step; everyone else reads LDS
   auto row_info = [&](int st) {
@@ -172,8 +155,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_igemm_kernel(const WgradArgs a) 
             if (!((bvalid >> i) & 1u)) v = (f4){0.f, 0.f, 0.f, 0.f};
           }
           uwm_u2 hi, lo;
-          uwm_split4(__builtin_amdgcn_fmed3f(v.x, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(v.y, -65504.f, 65504.f),
-                     __builtin_amdgcn_fmed3f(v.z, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(v.w, -65504.f, 65504.f), hi, lo);
+          uwm_split4_clamped(v.x, v.y, v.z, v.w, hi, lo);
           char* const p_ = hb + 2 * PLA + (rb + RB * i) * RSB + ub * 8;
           *(uwm_u2*)p_ = hi; *(uwm_u2*)(p_ + PLB) = lo;
         }
@@ -219,12 +201,12 @@ __global__ __launch_bounds__(256, 2) void wgrad_igemm_kernel(const WgradArgs a) 
       const char* const hb = Hs + cur * STG;
       const char* const pa = hb + (8 * kg + q) * RSA + (wa * (TA / WA)) * 2 + p * 8;
       const char* const pb = hb + 2 * PLA + (8 * kg + q) * RSB + (wb * (TB / WB)) * 2 + p * 8;
-      wi_h8 ah[MI], al[MI];
+      uwm_h8 ah[MI], al[MI];
 #pragma unroll
-      for (int i = 0; i < MI; ++i) { ah[i] = wi_tr_pair(pa + i * 32, 0, 4 * RSA); al[i] = wi_tr_pair(pa + i * 32 + PLA, 0, 4 * RSA); }
+      for (int i = 0; i < MI; ++i) { ah[i] = uwm_tr_pair(pa + i * 32, 0, 4 * RSA); al[i] = uwm_tr_pair(pa + i * 32 + PLA, 0, 4 * RSA); }
 #pragma unroll
       for (int j = 0; j < NI; ++j) {
-        const wi_h8 bh = wi_tr_pair(pb + j * 32, 0, 4 * RSB), bl = wi_tr_pair(pb + j * 32 + PLB, 0, 4 * RSB);
+        const uwm_h8 bh = uwm_tr_pair(pb + j * 32, 0, 4 * RSB), bl = uwm_tr_pair(pb + j * 32 + PLB, 0, 4 * RSB);
 #pragma unroll
         for (int i = 0; i < MI; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl, acc[i][j], 0, 0, 0);
 #pragma unroll

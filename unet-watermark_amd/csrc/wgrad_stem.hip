@@ -179,16 +179,6 @@ __global__ __launch_bounds__(256) void wgrad_stem_reduce_kernel(const float* __r
 // straight out of the input patch [px][4 channels] (8 bytes per pixel: one lane address per (pixel, tap) — the stride-2 gather
 // and the tap shift are just addresses).  Columns j = tap*4 + c (196 -> 13 blocks of four taps; the stored zero channel rides
 // along), which IS dW's layout.  84 MFMAs of 16 cycles per tile and wave.
-typedef _Float16 s_h8 __attribute__((ext_vector_type(8)));
-typedef __fp16 s_fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-typedef __attribute__((address_space(3))) s_fp16x4 s_lds_fp16x4;
-__device__ __forceinline__ s_h8 s_tr_pair(const char* base, int o0, int o1) {      // two transposed reads -> one 8-half operand fragment
-  const s_fp16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16((s_lds_fp16x4*)(uintptr_t)(base + o0));
-  const s_fp16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16((s_lds_fp16x4*)(uintptr_t)(base + o1));
-  typedef __fp16 fp16x8 __attribute__((__vector_size__(8 * sizeof(__fp16))));
-  const fp16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(s_h8, v);
-}
 constexpr int kHPix = kSPH * kSPW;                         // 621 patch pixels
 constexpr int kHPlane = 5120;                              // bytes of one half-plane of the patch: 621 x 8 + zero bytes (the taps past 48), two planes = a multiple of 256
 constexpr int kHDy = kSR * kSC * 256;                      // bytes of the dY image: [64 px][hi 128 B | lo 128 B]
@@ -205,12 +195,7 @@ __global__ __launch_bounds__(256, 3) void wgrad_stem_f16_kernel(const WgradArgs 
   const int H = a.s0.H, W = a.s0.W;
   const int tilesW = a.Wo / kSC, tilesH = a.Ho / kSR;
   float xs = 1.f;
-  if (a.xmax) {
-    float mx = a.xmax[lane & 31];
-#pragma unroll
-    for (int d = 16; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-    if (mx > 0.f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); xs = ldexpf(1.f, 14 - e); }
-  }
+  if (a.xmax) xs = uwm_dy_scale(a.xmax);
 
   // ---- fragment addresses (bytes): lane = (k-group kg, row-in-group q, column quad p)
   const int kg = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
@@ -268,8 +253,7 @@ __global__ __launch_bounds__(256, 3) void wgrad_stem_f16_kernel(const WgradArgs 
 #pragma unroll
     for (int rd = 0; rd < 3; ++rd) {
       uwm_u2 hi, lo;
-      uwm_split4(__builtin_amdgcn_fmed3f(pv[rd].x, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(pv[rd].y, -65504.f, 65504.f),
-                 __builtin_amdgcn_fmed3f(pv[rd].z, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(pv[rd].w, -65504.f, 65504.f), hi, lo);
+      uwm_split4_clamped(pv[rd].x, pv[rd].y, pv[rd].z, pv[rd].w, hi, lo);
       if (rd < 2 || last_live) { *(uwm_u2*)(b_ + (rd * 256 + tid) * 8) = hi; *(uwm_u2*)(b_ + kHPlane + (rd * 256 + tid) * 8) = lo; }
     }
     char* const d_ = b_ + 2 * kHPlane;
@@ -306,11 +290,11 @@ __global__ __launch_bounds__(256, 3) void wgrad_stem_f16_kernel(const WgradArgs 
     const char* const ds = ps + 2 * kHPlane;
 #pragma unroll
     for (int kr = 0; kr < kSR; ++kr) {                     // k-step = the 32 output pixels of tile row kr
-      s_h8 ah[2], al[2];
+      uwm_h8 ah[2], al[2];
 #pragma unroll
       for (int cf = 0; cf < 2; ++cf) {
-        ah[cf] = s_tr_pair(ds + kr * 32 * 256, dyo[cf][0], dyo[cf][1]);
-        al[cf] = s_tr_pair(ds + kr * 32 * 256, dyo[cf][0] ^ 128, dyo[cf][1] ^ 128);
+        ah[cf] = uwm_tr_pair(ds + kr * 32 * 256, dyo[cf][0], dyo[cf][1]);
+        al[cf] = uwm_tr_pair(ds + kr * 32 * 256, dyo[cf][0] ^ 128, dyo[cf][1] ^ 128);
       }
       const char* const pk = ps + kr * 2 * kSPW * 8;
 #pragma unroll
@@ -319,8 +303,8 @@ __global__ __launch_bounds__(256, 3) void wgrad_stem_f16_kernel(const WgradArgs 
           const bool z = boff[jb] == kHPix * 8;           // (zero slot: no row / pixel offsets)
           const char* const pb = z ? ps : pk;
           const int st2 = z ? 0 : bstep;
-          const s_h8 bh = s_tr_pair(pb, boff[jb], boff[jb] + st2);
-          const s_h8 bl = s_tr_pair(pb + kHPlane, boff[jb], boff[jb] + st2);
+          const uwm_h8 bh = uwm_tr_pair(pb, boff[jb], boff[jb] + st2);
+          const uwm_h8 bl = uwm_tr_pair(pb + kHPlane, boff[jb], boff[jb] + st2);
 #pragma unroll
           for (int cf = 0; cf < 2; ++cf) acc[cf][jb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[cf], bl, acc[cf][jb], 0, 0, 0);
 #pragma unroll
