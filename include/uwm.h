@@ -875,6 +875,32 @@ int    uwm_optimize_masks_ragged(const uint8_t* in, uint8_t* out /* may alias in
                                  const uwm_image_desc* descs /* device */, int N, int mask_type, long long max_pixels,
                                  long long rows, long long* stats /* device [N][8], may be NULL */, void* workspace,
                                  size_t workspace_bytes, uwm_stream stream);
+/* Scoring predicted masks against ground truth (mask_score.hip): a ragged batch of mask PAIRS in ONE call.  pred and
+ * truth are two buffers of mask_bytes bytes under the same descriptors: image i is descs[i].h x descs[i].w, one byte per pixel, at
+ * + descs[i].offset in both (any alignment: the layout uwm_resize_threshold_ragged writes).  Both are binarised as > 127, so raw
+ * grey truth bytes go in as they are; pred may be truth.  With P, G the two binary masks of image i and d = radius[i]:
+ *   E_d(M)[y][x] = 1 iff the whole (2d+1) x (2d+1) window centred on (y, x) lies inside the image and is set (the 3 x 3 square
+ *                  erosion iterated d times, everything outside the image unset: Boundary IoU's mask_to_boundary)
+ *   B_d(M)       = M & ~E_d(M)
+ *   counts[i]    = long long [8]: 0 tp |P & G|, 1 fp |P & ~G|, 2 fn |~P & G|, 3 tn |~P & ~G|, 4 |B_d(P) & B_d(G)|, 5 |B_d(P)|,
+ *                  6 |B_d(G)|, 7 status: 0 done, 1 misfit
+ * d = 0 skips the boundary part (entries 4..6 are 0); 2d + 1 above a side makes E_d empty, so B_d(M) = M.  The cost does not depend
+ * on d beyond the log2(2d + 1) doubling steps of the row erosion.  Counts are integers summed with integer atomics: the same on
+ * every run.  The descriptors and radii are read on the device; the host arguments are capacities, so one captured call serves every
+ * batch of N pairs that fits them: max_pixels (1 .. 2^31 - 2) bounds h_i * w_i and sizes the grids, rows bounds the sum of h_i and,
+ * with mask_bytes, sizes the bit planes (image i takes h_i * ceil(w_i / 64) words; a plane holds mask_bytes / 64 + rows).  Five
+ * launches whatever N (N <= 65535) and the radii are.  Misfit: a side outside 1 .. 2^30, h_i * w_i > max_pixels, a region that
+ * leaves [0, mask_bytes), d outside 0 .. 32767, or, counting the images before it that pass those four tests, a sum of rows above
+ * `rows` or of plane words above the plane.  A misfit gets status 1 and entries 0..6 zero, and it costs the others nothing.
+ * Whatever the descriptors and radii hold, no read leaves pred / truth / descs / radius and no write leaves counts or the
+ * workspace.  workspace: uwm_score_masks_workspace_bytes(N, mask_bytes, rows) bytes (0 and a message on a bad argument); descs /
+ * counts / workspace 8-byte aligned, radius 4-byte aligned.  Every argument is checked before any launch; no host
+ * synchronisation, allocation or copy. */
+size_t uwm_score_masks_workspace_bytes(int N, size_t mask_bytes, long long rows);
+int    uwm_score_masks_ragged(const uint8_t* pred, const uint8_t* truth, size_t mask_bytes,
+                              const uwm_image_desc* descs /* device */, const int* radius /* device [N] */, int N,
+                              long long max_pixels, long long rows, long long* counts /* device [N][8] */,
+                              void* workspace, size_t workspace_bytes, uwm_stream stream);
 /* Mask enhancement on the device: the reference's enhance_mask (src/scripts/enhance_masks.py:16-67), which turns a tight
  * segmentation mask into the rounded, enlarged one people train on.  A ragged batch in ONE call, as above: image i is descs[i].h x
  * descs[i].w 8-bit grey pixels at in + descs[i].offset (any alignment), its result, in {0, 255}, goes to out + descs[i].offset; out

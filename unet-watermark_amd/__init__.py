@@ -29,3 +29,5 @@ from .extract import WatermarkExtractor, extract_regions, plan_cutouts, extract_
 from .textenh import enhance_text_features, text_enhance_ragged  # noqa: F401,E402
 from .train import FusedAdam, FusedAdamW  # noqa: F401,E402
 from .tiling import plan_tiles, plan_batch  # noqa: F401,E402
+from .scoring import score_masks_ragged, boundary_radius, metrics_from_counts, summarize  # noqa: F401,E402
+from .evaluate import Evaluator  # noqa: F401,E402

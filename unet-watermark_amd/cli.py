@@ -728,8 +728,57 @@ def extract_command(args):
     return res
 
 
+def _evaluate_dirs(args):
+    """the two input forms of `evaluate`: --input with --masks, or --data-dir D for D/watermarked and D/masks"""
+    pair = args.input is not None or args.masks is not None
+    if pair and args.data_dir is not None:
+        raise SystemExit("evaluate: give --input with --masks, or --data-dir, not both")
+    if not pair and args.data_dir is None:
+        raise SystemExit("evaluate: give --input with --masks, or --data-dir")
+    if pair and (args.input is None or args.masks is None):
+        raise SystemExit("evaluate: --input and --masks go together")
+    if pair:
+        return args.input, args.masks
+    return os.path.join(args.data_dir, "watermarked"), os.path.join(args.data_dir, "masks")
+
+
+def evaluate_command(args):
+    """Score the masks a checkpoint predicts for a labelled folder at each image's own size: the reference's five metrics and Boundary
+    IoU, micro (counts summed) and image-wise (values averaged); evaluate.py, DESIGN.md 8s.  Every refusal comes before anything is
+    created."""
+    from .evaluate import Evaluator, check_settings, format_summary, write_json
+    input_dir, masks_dir = _evaluate_dirs(args)
+    try:
+        check_settings(args.mask_type, args.text_enhance, args.tile, args.tile_overlap,
+                       0.02 if args.boundary_ratio is None and args.boundary_pixels is None else args.boundary_ratio, args.boundary_pixels,
+                       args.batch_size, args.limit)
+    except ValueError as e:
+        raise SystemExit(f"evaluate: {e}")
+    for flag, d in (("the image directory", input_dir), ("the mask directory", masks_dir)):
+        if not os.path.isdir(d):
+            raise SystemExit(f"evaluate: {flag} not found: {d}")
+    if not os.path.exists(args.model):
+        raise SystemExit(f"evaluate: model file not found: {args.model}")
+    if args.config and not os.path.exists(args.config):
+        raise SystemExit(f"evaluate: config file not found: {args.config}")
+    if not torch.cuda.is_available():
+        raise SystemExit("evaluate needs a HIP device (this path has no CPU fallback)")
+    cfg = get_cfg_defaults()
+    if args.config:
+        update_config(cfg, args.config)
+    ev = Evaluator(input_dir, masks_dir, args.model, None, args.mask_type, args.text_enhance, args.tile, args.tile_overlap, args.boundary_ratio,
+                   args.boundary_pixels, args.batch_size, args.limit, args.seed, config=cfg)
+    ev.settings["config"] = args.config
+    res = ev.run(per_image=args.per_image)
+    print(format_summary(res))
+    if args.output:
+        write_json(res, args.output)
+        print(f"wrote {args.output}")
+    return res
+
+
 def build_parser():
-    ap = argparse.ArgumentParser(description="MI355X-native U-Net watermark segmentation (train | masks | enhance-masks | extract | filter | select | predict)")
+    ap = argparse.ArgumentParser(description="MI355X-native U-Net watermark segmentation (train | masks | enhance-masks | extract | filter | select | evaluate | predict)")
     sub = ap.add_subparsers(dest="command")
     tp = sub.add_parser("train")
     tp.add_argument("--config", type=str, default=None)
@@ -867,6 +916,32 @@ def build_parser():
                     help="the _optimize_mask type every mask goes through (predict_mask's default: watermark)")
     lp.add_argument("--batch-size", type=int, default=None, help="images per captured call (default PREDICT.BATCH_SIZE)")
     lp.add_argument("--save-masks", action="store_true", help="also write <image>_<model>_mask.png for every image and model")
+    vp = sub.add_parser("evaluate", help="score the masks a checkpoint predicts against ground-truth masks, every image at its own size",
+                        description="Predict the mask of every image of --input (or DATA-DIR/watermarked) on the device-resize path, with "
+                                    "the post-processing, text enhancement or native-resolution tiling asked for, and count it against the "
+                                    "mask of the same stem in --masks (or DATA-DIR/masks; > 127 is foreground) on the device.  Prints the "
+                                    "reference's IoU, F1, accuracy, recall and precision (its get_metrics formulas; 0 / 0 gives 1) and "
+                                    "Boundary IoU (Cheng et al., CVPR 2021), micro (counts summed over the images) and image-wise (values "
+                                    "averaged).  An unreadable file, an image without a mask and a mask of another size count under "
+                                    "'errors' and stop nothing.  The reference has no such command.")
+    vp.add_argument("--input", type=str, default=None, help="the folder of images (jpg, jpeg, png, bmp, tiff, tif); with --masks")
+    vp.add_argument("--masks", type=str, default=None, help="the folder of ground-truth masks, paired with the images by file stem")
+    vp.add_argument("--data-dir", type=str, default=None, help="instead of --input and --masks: DIR/watermarked and DIR/masks")
+    vp.add_argument("--model", type=str, required=True); vp.add_argument("--config", type=str, default=None)
+    vp.add_argument("--mask-type", choices=["watermark", "text", "mixed"], default=None,
+                    help="post-process every mask as the reference's _optimize_mask does for this type before it is scored (absent: raw "
+                         "thresholded masks)")
+    vp.add_argument("--text-enhance", action="store_true", help="the reference's _enhance_text_features in front of the network, as predict's")
+    vp.add_argument("--tile", action="store_true", help="predict at native resolution from overlapping IMG_SIZE tiles, as predict's; not with --text-enhance")
+    vp.add_argument("--tile-overlap", type=int, default=64, help="pixels neighbouring tiles share, 0 .. IMG_SIZE / 2 (with --tile)")
+    vp.add_argument("--boundary-ratio", type=float, default=None,
+                    help="Boundary IoU's distance as a share of the image diagonal, at least one pixel (default 0.02, the paper's)")
+    vp.add_argument("--boundary-pixels", type=int, default=None, help="the same distance in pixels for every image, 0..32767 (0: no Boundary IoU); not with --boundary-ratio")
+    vp.add_argument("--batch-size", type=int, default=16, help="pairs per device call")
+    vp.add_argument("--limit", type=int, default=None, help="score a seeded random sample of this many pairs")
+    vp.add_argument("--seed", type=int, default=0, help="seed of the --limit sample")
+    vp.add_argument("--output", type=str, default=None, help="write settings, images, errors, micro and imagewise as JSON to this file")
+    vp.add_argument("--per-image", action="store_true", help="add per_image to the JSON: path, size, radius, the eight counts, the six metrics")
     pp = sub.add_parser("predict")
     pp.add_argument("--input", type=str, required=True); pp.add_argument("--output", type=str, required=True)
     pp.add_argument("--model", type=str, required=True); pp.add_argument("--config", type=str, default=None)
@@ -909,4 +984,6 @@ def main(argv=None):
         return enhance_masks_command(args)
     if args.command == "extract":
         return extract_command(args)
+    if args.command == "evaluate":
+        return evaluate_command(args)
     ap.print_help()

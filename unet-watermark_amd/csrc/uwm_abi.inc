@@ -785,6 +785,25 @@ int uwm_optimize_masks_ragged(const uint8_t* in, uint8_t* out, size_t mask_bytes
   LCHK(launch_optimize_masks_ragged(in, out, mask_bytes, (const ImageDesc*)descs, N, mask_type, max_pixels, rows, stats, ws, (hipStream_t)stream));
   return 0;
 }
+// ---- mask scoring (mask_score.hip): every argument is checked here, before any launch
+size_t uwm_score_masks_workspace_bytes(int N, size_t mask_bytes, long long rows) {
+  if (mask_ragged_caps_check("uwm_score_masks_workspace_bytes", N, mask_bytes, rows)) return 0;
+  return score_masks_workspace_bytes(N, mask_bytes, rows);
+}
+int uwm_score_masks_ragged(const uint8_t* pred, const uint8_t* truth, size_t mask_bytes, const uwm_image_desc* descs, const int* radius, int N,
+                           long long max_pixels, long long rows, long long* counts, void* ws, size_t ws_bytes, uwm_stream stream) {
+  const char* fn = "uwm_score_masks_ragged";
+  if (!pred || !truth || !descs || !radius || !counts || !ws) return fail("%s: null argument", fn);
+  if (mask_ragged_caps_check(fn, N, mask_bytes, rows)) return 1;
+  if (max_pixels < 1) return fail("%s: max_pixels must be >= 1 (got %lld)", fn, max_pixels);
+  if (max_pixels >= 2147483647ll) return fail("%s: max_pixels too large: it must be below 2^31 - 1 (got %lld)", fn, max_pixels);
+  if (((uintptr_t)descs | (uintptr_t)counts | (uintptr_t)ws) & 7) return fail("%s: descriptors, counts and the workspace must be 8-byte aligned", fn);
+  if ((uintptr_t)radius & 3) return fail("%s: radius must be 4-byte aligned", fn);
+  const size_t need = score_masks_workspace_bytes(N, mask_bytes, rows);
+  if (ws_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", fn, ws_bytes, need);
+  LCHK(launch_score_masks_ragged(pred, truth, mask_bytes, (const ImageDesc*)descs, radius, N, max_pixels, rows, counts, ws, (hipStream_t)stream));
+  return 0;
+}
 // ---- mask enhancement (mask_enhance.hip): every argument is checked here, before any launch
 static int enhance_caps_check(const char* fn, int N, size_t mask_bytes) {
   if (N < 1 || mask_bytes < 1) return fail("%s: N and mask_bytes must be >= 1 (got %d, %zu)", fn, N, mask_bytes);

@@ -695,6 +695,11 @@ hipError_t launch_optimize_mask(const uint8_t* in, uint8_t* out, int N, int H, i
 size_t mask_ragged_workspace_bytes(int N, size_t mask_bytes, long long rows);
 hipError_t launch_optimize_masks_ragged(const uint8_t* in, uint8_t* out, size_t mask_bytes, const ImageDesc* descs, int N, int mask_type,
                                         long long max_pixels, long long rows, long long* stats, void* ws, hipStream_t st);
+// region and Boundary-IoU counts of a ragged batch of mask pairs (mask_score.hip; the rule: include/uwm.h).
+// descs, radius: DEVICE memory; counts: [N][8]; ws: score_masks_workspace_bytes(N, mask_bytes, rows) bytes
+size_t score_masks_workspace_bytes(int N, size_t mask_bytes, long long rows);
+hipError_t launch_score_masks_ragged(const uint8_t* pred, const uint8_t* truth, size_t mask_bytes, const ImageDesc* descs, const int* radius,
+                                     int N, long long max_pixels, long long rows, long long* counts, void* ws, hipStream_t st);
 
 // mask enhancement (mask_enhance.hip): the reference's enhance_mask on a ragged batch, grey morphology + float blur + binary
 // smoothing (the rule: include/uwm.h).  ws: enhance_workspace_bytes(N, mask_bytes) bytes; stats (may be null): [N][4]

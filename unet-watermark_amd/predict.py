@@ -70,6 +70,7 @@ class WatermarkPredictor:
         self._cbuf = self._cws = None         # its static counts buffer and workspaces
         self._xgraphs = {}                    # predict_images_tiled: ONE graph per (images, chunk count, ...), beside the ones above
         self._xtiles = self._xplans = self._xlbuf = None      # its static tile table, per-image plans and ragged logit plane
+        self._gtbuf = None                    # score_images: the staged ground-truth masks, under _mbuf's descriptors
         self._hbuf = self._hevt = None        # pinned host staging of the packed bytes + the event of its last upload
         self.freeze = bool(freeze)
         if self.freeze:
@@ -329,6 +330,18 @@ class WatermarkPredictor:
         'text' | 'mixed': every blended mask then goes through the reference's _optimize_mask at its own size
         (uwm_optimize_masks_ragged), in place and inside the same graph.  return_logits: also the list of float32 (h_i, w_i) planes
         of blended logits the masks were thresholded from."""
+        descs, mdescs, areas, mask_bytes = self._run_tiled(images, overlap, apply_sigmoid, mask_type, return_logits, use_graph, tile_batch)
+        masks = self._mask_views(descs, mdescs, areas, mask_bytes)
+        if not return_logits:
+            return masks
+        lg = self._xlbuf[:mask_bytes].clone()
+        return masks, [lg[int(o): int(o) + int(a)].view(int(h), int(w)) for o, a, h, w in zip(mdescs["offset"], areas, descs["h"], descs["w"])]
+
+    def _run_tiled(self, images, overlap: int, apply_sigmoid: bool, mask_type: Optional[str], return_logits: bool, use_graph: bool,
+                   tile_batch: Optional[int]):
+        """stage `images` and run uwm_predict_tiled_u8 (and, with a mask_type, uwm_optimize_masks_ragged in place) as
+        predict_images_tiled describes -> (descs, mask descs, areas, mask bytes); the masks are in _mbuf, the blended logits, when
+        asked for, in _xlbuf"""
         from .tiling import check_overlap, plan_batch, table_tensor
         if mask_type is not None:
             mask_type_code(mask_type)
@@ -374,11 +387,55 @@ class WatermarkPredictor:
                     ws = (ws, ragged_workspace(self.device, n, self._mbuf.numel(), caps[2]))
                 self._xgraphs[key] = (g, ws)
             self._xgraphs[key][0].replay()
-        masks = self._mask_views(descs, mdescs, areas, mask_bytes)
-        if not return_logits:
-            return masks
-        lg = self._xlbuf[:mask_bytes].clone()
-        return masks, [lg[int(o): int(o) + int(a)].view(int(h), int(w)) for o, a, h, w in zip(mdescs["offset"], areas, descs["h"], descs["w"])]
+        return descs, mdescs, areas, mask_bytes
+
+    @torch.no_grad()
+    def score_images(self, images, truths, mask_type: Optional[str] = None, text_enhance: bool = False, tile: bool = False,
+                     overlap: int = 64, boundary_ratio: float = 0.02, boundary_pixels: Optional[int] = None, return_masks: bool = False):
+        """uint8 (h_i, w_i, C) images of ANY sizes and their ground-truth masks, uint8 (h_i, w_i) grey (binarised as > 127) -> the
+        int64 (N, 8) HOST array of scoring.COUNT_FIELDS for the masks that predict_images(images, mask_type=..., text_enhance=...)
+        or, with tile, predict_images_tiled(images, overlap, mask_type=...) returns: {tp, fp, fn, tn, |B(P) & B(G)|, |B(P)|, |B(G)|,
+        status}, B the Boundary-IoU band of distance boundary_pixels or, by default, scoring.boundary_radius(h_i, w_i,
+        boundary_ratio).  The prediction runs as it does there, through the same graphs; the truths are staged into
+        a buffer of their own under the same mask descriptors and uwm_score_masks_ragged runs behind the prediction on the same
+        stream, reading the predicted masks in place.  One device-to-host copy of 64 N bytes; no mask leaves the device unless
+        return_masks, which adds the list of device masks.  scoring.metrics_from_counts / summarize turn the rows into metrics."""
+        from .scoring import MAX_RADIUS, boundary_radius, score_masks_ragged
+        if self.device.type != "cuda" or not torch.cuda.is_available():
+            raise RuntimeError("score_images runs only on a HIP device (no CPU fallback)")
+        if tile and text_enhance:
+            raise ValueError("tile and text_enhance cannot be combined: the tiled path has no text enhancement")
+        if boundary_pixels is not None and not 0 <= int(boundary_pixels) <= MAX_RADIUS:
+            raise ValueError(f"boundary_pixels must be in 0..{MAX_RADIUS}, got {boundary_pixels!r}")
+        if boundary_pixels is None and not float(boundary_ratio) >= 0:
+            raise ValueError(f"boundary_ratio must not be negative, got {boundary_ratio!r}")
+        images, truths = list(images), [np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t) for t in truths]
+        if len(truths) != len(images):
+            raise ValueError(f"{len(images)} images but {len(truths)} truth masks")
+        for i, (im, t) in enumerate(zip(images, truths)):
+            if t.ndim == 3 and t.shape[2] == 1:
+                truths[i] = t = t[:, :, 0]
+            if t.ndim != 2 or t.dtype != np.uint8 or tuple(t.shape) != tuple(im.shape[:2]):
+                raise ValueError(f"truth {i} is {t.dtype} {tuple(t.shape)}: it must be a uint8 mask of its image's size {tuple(im.shape[:2])}")
+        if tile:
+            descs, mdescs, areas, mask_bytes = self._run_tiled(images, overlap, False, mask_type, False, True, None)
+        else:
+            if mask_type is not None:
+                mask_type_code(mask_type)
+            descs, mdescs, areas, mask_bytes, _ = self._run_images(images, False, mask_type, True, text_enhance)
+        n = len(descs)
+        radii = [min(boundary_radius(h, w, boundary_ratio), MAX_RADIUS) if boundary_pixels is None else int(boundary_pixels)
+                 for h, w in zip(descs["h"].tolist(), descs["w"].tolist())]
+        host = np.zeros(mask_bytes, np.uint8)
+        for t, o, a in zip(truths, mdescs["offset"], areas):
+            host[int(o): int(o) + int(a)] = t.reshape(-1)
+        if self._gtbuf is None or self._gtbuf.numel() != self._mbuf.numel():
+            self._gtbuf = torch.zeros_like(self._mbuf)
+        self._gtbuf[:mask_bytes].copy_(torch.from_numpy(host))
+        counts = score_masks_ragged(self._mbuf, self._gtbuf, self._mdesc, torch.tensor(radii, dtype=torch.int32, device=self.device), n=n,
+                                    max_pixels=int(areas.max()), rows=int(descs["h"].astype("int64").sum()))
+        out = counts.cpu().numpy()
+        return (out, self._mask_views(descs, mdescs, areas, mask_bytes)) if return_masks else out
 
     @torch.no_grad()
     def mask_stats(self, images, mask_type: str = "watermark", return_masks: bool = False, use_graph: bool = True,

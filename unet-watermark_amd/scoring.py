@@ -1,0 +1,119 @@
+"""Scoring predicted masks against ground truth (include/uwm.h): thin host wrappers over uwm_score_masks_ragged in
+csrc/mask_score.hip, which counts tp / fp / fn / tn and the three Boundary-IoU counts of a ragged batch of mask pairs on the
+device, and the formulas that turn those counts into the reference's five metrics (src/utils/metrics.py::get_metrics) plus
+Boundary IoU (Cheng et al., CVPR 2021).  No CPU fallback for the counting."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional
+
+import numpy as np
+
+from . import _lib as L
+
+COUNT_FIELDS = ("tp", "fp", "fn", "tn", "boundary_intersection", "boundary_pred", "boundary_truth", "status")
+METRIC_FIELDS = ("iou", "f1", "accuracy", "recall", "precision", "boundary_iou")
+MAX_RADIUS = 32767
+_sws = {}                                                 # device -> workspace tensor of the score call (grown on demand)
+
+
+def boundary_radius(h: int, w: int, ratio: float = 0.02) -> int:
+    """Boundary IoU's dilation distance for an h x w image: `ratio` of the diagonal, at least 1 (the paper's mask_to_boundary:
+    29 at 720 x 1280, 88 at 2160 x 3840)."""
+    return max(1, int(round(float(ratio) * math.sqrt(int(h) * int(h) + int(w) * int(w)))))
+
+
+def score_workspace(device, n: int, mask_bytes: int, rows: int):
+    """The score call's scratch for the capacities (n, mask_bytes, rows): one buffer per device, kept and grown like
+    postprocess.ragged_workspace; a captured graph holds the buffer it was captured with."""
+    import torch
+    need = L.lib().uwm_score_masks_workspace_bytes(int(n), int(mask_bytes), int(rows))
+    if need == 0:
+        raise RuntimeError(L.lib().uwm_last_error().decode(errors="replace"))
+    key = str(device)
+    ws = _sws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _sws[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws
+
+
+def score_masks_ragged(pred, truth, descs, radii, *, n: Optional[int] = None, max_pixels: Optional[int] = None,
+                       rows: Optional[int] = None, out=None):
+    """A ragged batch of mask pairs through ONE library call (uwm_score_masks_ragged).  pred, truth: uint8 1-d device tensors of
+    the same size; pair i is descs[i]'s (h, w), one byte per pixel, at [descs[i].offset:] of both, binarised as > 127 (pred may be
+    truth).  descs: a host record array with the fields offset / h / w (uploaded here), or a device tensor of uwm_image_desc bytes
+    — then n, max_pixels and rows must be given, nothing about the batch is read on the host, and the call can be captured.
+    radii: the Boundary-IoU distance of every pair (0 .. 32767; 0: no boundary counts), a host sequence or an int32 device tensor.
+    -> the int64 (n, 8) device tensor COUNT_FIELDS (`out`: a tensor to write them into).  max_pixels / rows: capacities, at least
+    the largest h*w and the sum of h; a pair beyond a capacity is a misfit (status 1, zeros)."""
+    import torch
+    if not isinstance(pred, torch.Tensor) or not isinstance(truth, torch.Tensor) or pred.device.type != "cuda" or truth.device != pred.device:
+        raise RuntimeError("uwm score_masks_ragged runs only on a HIP device (no CPU fallback)")
+    for t in (pred, truth):
+        if t.dtype != torch.uint8 or t.dim() != 1 or t.numel() == 0 or not t.is_contiguous():
+            raise RuntimeError(f"expected a non-empty contiguous 1-d uint8 buffer, got {t.dtype} {tuple(t.shape)}")
+    mask_bytes = min(pred.numel(), truth.numel())
+    if isinstance(descs, torch.Tensor):
+        if n is None or max_pixels is None or rows is None:
+            raise ValueError("score_masks_ragged: device descriptors need n, max_pixels and rows")
+        if descs.device != pred.device or descs.dtype != torch.uint8 or descs.numel() < 16 * int(n):
+            raise RuntimeError("score_masks_ragged: descs must be a uint8 tensor of 16 n bytes on the buffers' device")
+        d = descs
+    else:
+        from .data import descs_tensor
+        n = len(descs) if n is None else int(n)
+        if n < 1:
+            raise ValueError("score_masks_ragged: empty batch")
+        if max_pixels is None:
+            max_pixels = max(1, int((descs["h"].astype("int64") * descs["w"]).max()))
+        if rows is None:
+            rows = max(1, int(descs["h"].astype("int64").clip(min=0).sum()))
+        d = descs_tensor(descs).to(pred.device)
+    if isinstance(radii, torch.Tensor):
+        if radii.device != pred.device or radii.dtype != torch.int32 or radii.numel() < int(n) or not radii.is_contiguous():
+            raise RuntimeError("score_masks_ragged: radii must be a contiguous int32 tensor of n entries on the buffers' device")
+        r = radii
+    else:
+        host = np.ascontiguousarray(np.asarray(radii, dtype=np.int64).reshape(-1))
+        if host.size != int(n):
+            raise ValueError(f"score_masks_ragged: {host.size} radii for {n} pairs")
+        r = torch.from_numpy(host.clip(-1, 2 ** 31 - 1).astype(np.int32)).to(pred.device)
+    if out is None:
+        out = torch.empty((int(n), 8), dtype=torch.int64, device=pred.device)
+    elif out.dtype != torch.int64 or out.device != pred.device or out.numel() < 8 * int(n) or not out.is_contiguous():
+        raise RuntimeError("score_masks_ragged: out must be a contiguous int64 tensor of 8 n entries on the buffers' device")
+    with L.on_device(pred):
+        ws = score_workspace(pred.device, n, mask_bytes, rows)
+        L.check(L.lib().uwm_score_masks_ragged(C.c_void_p(pred.data_ptr()), C.c_void_p(truth.data_ptr()), mask_bytes, C.c_void_p(d.data_ptr()),
+                                               C.c_void_p(r.data_ptr()), int(n), int(max_pixels), int(rows), C.c_void_p(out.data_ptr()),
+                                               C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(L.stream_ptr(pred.device))))
+    return out
+
+
+def _ratio(num: float, den: float) -> float:
+    return float(num) / float(den) if den else 1.0
+
+
+def metrics_from_counts(row) -> dict:
+    """One COUNT_FIELDS row (or a sum of rows) -> {iou, f1, accuracy, recall, precision, boundary_iou}.  The first five are
+    segmentation_models_pytorch's formulas as the reference's get_metrics calls them (iou_score, f1_score, accuracy, recall,
+    precision), restated here, not run: smp is not installed with this project.
+        iou = tp / (tp + fp + fn)      f1 = 2 tp / (2 tp + fp + fn)      accuracy = (tp + tn) / (tp + fp + fn + tn)
+        recall = tp / (tp + fn)        precision = tp / (tp + fp)        boundary_iou = c4 / (c5 + c6 - c4)
+    0 / 0 gives 1.0: smp's default zero_division = 1.0, which get_metrics does not override."""
+    tp, fp, fn, tn, bi, bp, bt = (int(v) for v in list(row)[:7])
+    return {"iou": _ratio(tp, tp + fp + fn), "f1": _ratio(2 * tp, 2 * tp + fp + fn), "accuracy": _ratio(tp + tn, tp + fp + fn + tn),
+            "recall": _ratio(tp, tp + fn), "precision": _ratio(tp, tp + fp), "boundary_iou": _ratio(bi, bp + bt - bi)}
+
+
+def summarize(counts) -> dict:
+    """(n, 8) COUNT_FIELDS rows -> {"micro": the formulas on the counts summed over the images (the reference's
+    reduction="micro" over a batch), "imagewise": the mean over the images of each image's own values}.  Misfit rows (status != 0)
+    are left out; with no rows left every value is 1.0, as 0 / 0 is above."""
+    rows = np.asarray(counts, dtype=np.int64).reshape(-1, 8)
+    rows = rows[rows[:, 7] == 0]
+    micro = metrics_from_counts([int(v) for v in rows[:, :7].sum(axis=0)] if len(rows) else [0] * 7)
+    each = [metrics_from_counts(r) for r in rows]
+    imagewise = {k: (float(sum(m[k] for m in each) / len(each)) if each else 1.0) for k in METRIC_FIELDS}
+    return {"micro": micro, "imagewise": imagewise}
