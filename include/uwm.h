@@ -242,6 +242,64 @@ int    uwm_predict_tiled_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, 
                             uint8_t* mask, size_t mask_bytes, float* logits_out, void* workspace, size_t workspace_bytes, int N,
                             uwm_stream stream);
 
+/* Prediction with TEST-TIME AUGMENTATION (no counterpart in the reference): the network sees every image (or tile) under the views of
+ * a set, every logit plane is mapped back, and the planes are averaged before the threshold.  (the host side:
+ * unet_watermark_amd/tta.py.)
+ *   Views.  A view of an H x W plane is a code c = r + 4 f, r in 0..3, f in 0..1:  view_c(x) = rot90^r(hflip^f(x)) — the horizontal
+ *     flip first, then r counter-clockwise quarter turns as torch.rot90(x, r, (H, W)) makes them; one turn of a square of side S:
+ *     out[i][j] = in[j][S - 1 - i].  Code 0 is the identity, 4 the horizontal flip, 2 the half turn, 6 the vertical flip.  Codes 1, 3,
+ *     5 and 7 need H == W and are refused otherwise.
+ *   View sets.  A bitmask `views` in 1..255, bit c = view c, k = popcount(views).  hflip = 0x11, flips = 0x55, d4 = 0xFF, none = 0x01.
+ *   Slots.  The network inputs of B items (images, or tiles of a tile table) are slots: slot s = i * k + j is the j-th view of the set,
+ *     in ascending code order, of item i.  The forward runs them N at a time; the slot count is padded up to a multiple of N with
+ *     all-zero inputs whose logits are ignored.
+ *   Merge, at the network's resolution (before the resize back / the tile blend), per pixel:
+ *     acc = l'_{c0};  acc += l'_{cj} in ascending code order;  v = acc / (float)k        every operation rounded to fp32 on its own
+ *     with l'_c the logit plane of view c mapped back by view_c^-1.  k = 1 with code 0: v is that logit bit for bit (k = 1 does not
+ *     divide).  The order is fixed by the slot order, not by the chunking: a view set that straddles two forward chunks gives the same
+ *     bits as one that does not (the partial sum waits in the store).  No float atomics.  The sigmoid, where asked for, is applied
+ *     to v: this is the mean of the LOGITS, not of the probabilities.
+ * A slot range is [slot0, slot0 + num_slots).  The two input calls first write the base planes of the items the range touches into
+ *   `stage` (16-byte aligned, uwm_view_stage_bytes(views, num_slots, H, W): at most min(num_slots, (num_slots + k - 2) / k + 1) planes
+ *   of [H][W][4] floats — never k copies of a batch) with the existing kernel, then one launch writes every slot's view into out.
+ * uwm_op_resize_norm_view_u8_nhwc4: out[s - slot0] = view_c(uwm_op_resize_norm_u8_nhwc4's plane of image s / k), fp32 [num_slots][H][W][4]
+ *   (16-byte aligned, padding channel zero); a slot whose image is >= num_images is zeros.
+ * uwm_op_tile_norm_view_u8_nhwc4: the same over the K entries of a tile table, on uwm_op_tile_norm_u8_nhwc4's planes.
+ * uwm_op_view_merge: logits = the planes [num_slots][H][W] (element stride ld) of the range; store = one plane [H][W] per item,
+ *   [num_items] of them.  One thread owns a pixel of an item and walks the views of that item present in the range in slot order: the
+ *   first view of an item writes, later views add (to the store where the range starts inside the item), the last divides.  Slots of
+ *   items >= num_items are ignored.  A sequence of calls over consecutive ranges gives the same bits as one call over their union.
+ * uwm_predict_images_tta_u8: uwm_predict_images_u8 with num_images apart from the forward batch N: per chunk of N slots the viewed
+ *   resize + Normalize into the forward's input, the eval forward of (N, H, W) (frozen or not), the merge into the store
+ *   [num_images][H][W]; then uwm_resize_threshold_ragged of the store (ld = 1).  merged (may be NULL, 4-byte aligned): the store is
+ *   written there instead of the workspace's tail.  views = 0x01 gives uwm_predict_images_u8's masks.
+ * uwm_predict_tiled_tta_u8: uwm_predict_tiled_u8 with `views`: the store [K][T_h][T_w] (the workspace's tail) holds MERGED tile logits
+ *   and the existing blend runs on it unchanged.  K need not be a multiple of N: the slots K * k are padded instead.
+ * All: capturable — no host synchronisation, allocation or copy; ceil(items * k / N) chunks of {base planes, views, forward, merge}
+ *   launches and one closing launch, whatever the image sizes.  Every argument is checked before any launch.  An image whose
+ *   descriptor does not fit goes in as zeros / has its mask skipped, as in the calls without views, and costs only itself. */
+size_t uwm_view_stage_bytes(int views, int num_slots, int H, int W);
+int    uwm_op_resize_norm_view_u8_nhwc4(const uint8_t* src, size_t src_bytes, const uwm_image_desc* descs, int num_images, int C, int H,
+                                        int W, const float* mean, const float* std, int views, int slot0, int num_slots, float* stage,
+                                        size_t stage_bytes, float* out, uwm_stream stream);
+int    uwm_op_tile_norm_view_u8_nhwc4(const uint8_t* src, size_t src_bytes, const uwm_image_desc* descs, int num_images,
+                                      const uwm_tile_desc* tiles, int K, int C, int T_h, int T_w, const float* mean, const float* std,
+                                      int views, int slot0, int num_slots, float* stage, size_t stage_bytes, float* out,
+                                      uwm_stream stream);
+int    uwm_op_view_merge(const float* logits, int ld, int H, int W, int views, int slot0, int num_slots, int num_items, float* store,
+                         uwm_stream stream);
+size_t uwm_predict_images_tta_workspace_bytes(uwm_handle h, int N, int H, int W, int num_images, int views);
+int    uwm_predict_images_tta_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, const uwm_image_desc* in_descs, int num_images,
+                                 int views, const float* mean, const float* std, float threshold, int apply_sigmoid,
+                                 const uwm_image_desc* out_descs, uint8_t* mask, size_t mask_bytes, float* merged /* may be NULL */,
+                                 void* workspace, size_t workspace_bytes, int N, int H, int W, uwm_stream stream);
+size_t uwm_predict_tiled_tta_workspace_bytes(uwm_handle h, int N, int K, int T_h, int T_w, int views);
+int    uwm_predict_tiled_tta_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, const uwm_image_desc* in_descs, int num_images,
+                                const uwm_tile_desc* tiles, int K, const uwm_tile_image* plans, int T_h, int T_w, int overlap,
+                                const float* mean, const float* std, float threshold, int apply_sigmoid, const uwm_image_desc* out_descs,
+                                uint8_t* mask, size_t mask_bytes, float* logits_out, void* workspace, size_t workspace_bytes, int N,
+                                int views, uwm_stream stream);
+
 /* Masks from watermarked / clean pairs: the reference's WatermarkDataset._generate_mask with use_blurred_mask = False
  * (src/utils/dataset.py:197-211,277-278), which serves every image that has a clean counterpart and no mask file.  wm, clean and mask
  * are ragged batches as above (uint8 RGB interleaved, C = 3; masks one byte per pixel at any alignment); image i, at its OWN size:

@@ -31,3 +31,4 @@ from .train import FusedAdam, FusedAdamW  # noqa: F401,E402
 from .tiling import plan_tiles, plan_batch  # noqa: F401,E402
 from .scoring import score_masks_ragged, boundary_radius, metrics_from_counts, summarize  # noqa: F401,E402
 from .evaluate import Evaluator  # noqa: F401,E402
+from .tta import view_mask, view_codes, apply_view, invert_view, plan_slots, merge_views  # noqa: F401,E402

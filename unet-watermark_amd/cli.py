@@ -457,6 +457,10 @@ def predict_command(args):
     if tile and text_enhance:
         raise ValueError("--tile cannot be combined with --text-enhance: enhancing the images before they are cut into tiles is not "
                          "built yet; run one or the other")
+    tta = getattr(args, "tta", "none") or "none"
+    if tta != "none" and args.resize != "device":
+        raise ValueError("--tta needs --resize device: the views are made and their logits merged on the device, inside the ragged device "
+                         "path's one call (--resize host runs the plain forward)")
     cfg = get_cfg_defaults()
     if args.config and os.path.exists(args.config):
         update_config(cfg, args.config)
@@ -470,18 +474,20 @@ def predict_command(args):
     os.makedirs(args.output, exist_ok=True)
     files = sorted(f for f in os.listdir(args.input) if f.lower().endswith((".png", ".jpg", ".jpeg")))
     s, bs = int(cfg.DATA.IMG_SIZE), int(args.batch_size or cfg.PREDICT.BATCH_SIZE)
+    if tta != "none":
+        cfg.PREDICT.BATCH_SIZE = bs                            # the views of a batch go through the network --batch-size at a time
     for i in range(0, len(files), bs):
         chunk = files[i:i + bs]
         ims = [Image.open(os.path.join(args.input, f)).convert("RGB") for f in chunk]
         if tile:                                               # native resolution: overlapping IMG_SIZE tiles, blended on the device
             masks = pred.predict_images_tiled([np.asarray(im, dtype=np.uint8) for im in ims], int(args.tile_overlap), args.sigmoid,
-                                              args.mask_type, use_graph=len(chunk) == bs, tile_batch=bs)
+                                              args.mask_type, use_graph=len(chunk) == bs, tile_batch=bs, tta=tta)
             for f, m in zip(chunk, masks):
                 Image.fromarray(m.cpu().numpy()).save(os.path.join(args.output, os.path.splitext(f)[0] + "_mask.png"))
             continue
         if args.resize == "device":                            # cv2-convention resize on the device, both ways, in one call
             masks = pred.predict_images([np.asarray(im, dtype=np.uint8) for im in ims], args.sigmoid, args.mask_type,
-                                        use_graph=len(chunk) == bs, text_enhance=text_enhance)
+                                        use_graph=len(chunk) == bs, text_enhance=text_enhance, tta=tta)
             for f, m in zip(chunk, masks):
                 Image.fromarray(m.cpu().numpy()).save(os.path.join(args.output, os.path.splitext(f)[0] + "_mask.png"))
             continue
@@ -751,7 +757,7 @@ def evaluate_command(args):
     try:
         check_settings(args.mask_type, args.text_enhance, args.tile, args.tile_overlap,
                        0.02 if args.boundary_ratio is None and args.boundary_pixels is None else args.boundary_ratio, args.boundary_pixels,
-                       args.batch_size, args.limit)
+                       args.batch_size, args.limit, args.tta)
     except ValueError as e:
         raise SystemExit(f"evaluate: {e}")
     for flag, d in (("the image directory", input_dir), ("the mask directory", masks_dir)):
@@ -767,7 +773,7 @@ def evaluate_command(args):
     if args.config:
         update_config(cfg, args.config)
     ev = Evaluator(input_dir, masks_dir, args.model, None, args.mask_type, args.text_enhance, args.tile, args.tile_overlap, args.boundary_ratio,
-                   args.boundary_pixels, args.batch_size, args.limit, args.seed, config=cfg)
+                   args.boundary_pixels, args.batch_size, args.limit, args.seed, config=cfg, tta=args.tta)
     ev.settings["config"] = args.config
     res = ev.run(per_image=args.per_image)
     print(format_summary(res))
@@ -934,6 +940,8 @@ def build_parser():
     vp.add_argument("--text-enhance", action="store_true", help="the reference's _enhance_text_features in front of the network, as predict's")
     vp.add_argument("--tile", action="store_true", help="predict at native resolution from overlapping IMG_SIZE tiles, as predict's; not with --text-enhance")
     vp.add_argument("--tile-overlap", type=int, default=64, help="pixels neighbouring tiles share, 0 .. IMG_SIZE / 2 (with --tile)")
+    vp.add_argument("--tta", choices=["none", "hflip", "flips", "d4"], default="none",
+                    help="test-time augmentation as predict's --tta; the choice is recorded in the output JSON")
     vp.add_argument("--boundary-ratio", type=float, default=None,
                     help="Boundary IoU's distance as a share of the image diagonal, at least one pixel (default 0.02, the paper's)")
     vp.add_argument("--boundary-pixels", type=int, default=None, help="the same distance in pixels for every image, 0..32767 (0: no Boundary IoU); not with --boundary-ratio")
@@ -962,6 +970,12 @@ def build_parser():
                          "through the network --batch-size at a time and blend the tile logits into one mask at the image's own size "
                          "(no counterpart in the reference, which always resizes); needs --resize device, not with --text-enhance")
     pp.add_argument("--tile-overlap", type=int, default=64, help="pixels neighbouring tiles share, 0 .. IMG_SIZE / 2 (with --tile)")
+    pp.add_argument("--tta", choices=["none", "hflip", "flips", "d4"], default="none",
+                    help="test-time augmentation: the network sees every image (with --tile: every tile) under the views of the set -- "
+                         "hflip: identity + horizontal flip; flips: + vertical flip and half turn; d4: all 8 flips and quarter turns -- "
+                         "and the logit planes are mapped back and averaged on the device before the threshold (the mean of the logits, "
+                         "not of the probabilities); k forwards per image; needs --resize device; composes with --tile, --mask-type and "
+                         "--text-enhance where those compose")
     return ap
 
 

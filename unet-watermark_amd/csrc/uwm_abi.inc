@@ -525,6 +525,171 @@ int uwm_predict_tiled_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, con
                                           (const ImageDesc*)out_descs, threshold, apply_sigmoid, mask, mask_bytes, logits_out, st));
   return 0;
 }
+// ---- test-time augmentation (tta.hip): every argument is checked here, before any launch
+static int view_count(int views) { int k = 0; for (int c = 0; c < 8; ++c) k += (views >> c) & 1; return k; }
+static int view_set_check(const char* fn, int views, int H, int W) {
+  if (views < 1 || views > 255) return fail("%s: views must be 1..255 (got %d)", fn, views);
+  if ((views & 0xAA) && H != W) return fail("%s: a quarter-turn view (codes 1, 3, 5, 7) needs H == W (views 0x%02x, got %d x %d)", fn, views, H, W);
+  return 0;
+}
+static int view_range_check(const char* fn, int views, int H, int W, int slot0, int num_slots, int num_items) {
+  if (view_set_check(fn, views, H, W)) return 1;
+  if (H < 1 || W < 1) return fail("%s: H and W must be >= 1 (got %d x %d)", fn, H, W);
+  if (slot0 < 0 || num_slots < 1 || num_items < 1) return fail("%s: slot0 must be >= 0, num_slots and the item count >= 1 (got %d, %d, %d)", fn, slot0, num_slots, num_items);
+  if ((long long)slot0 + num_slots > 2147483647ll || (long long)num_items * view_count(views) + num_slots > 2147483647ll)
+    return fail("%s: slot range overflows (slot0 %d, num_slots %d, %d items of %d views)", fn, slot0, num_slots, num_items, view_count(views));
+  if ((long long)num_slots * ((H + 15) / 16) * ((W + 15) / 16) > 2147483647ll) return fail("%s: num_slots * H * W too large for one launch (%d x %d x %d)", fn, num_slots, H, W);
+  return 0;
+}
+size_t uwm_view_stage_bytes(int views, int num_slots, int H, int W) {
+  if (view_set_check("uwm_view_stage_bytes", views, H, W)) return 0;
+  if (num_slots < 1 || H < 1 || W < 1) { (void)fail("uwm_view_stage_bytes: num_slots, H and W must be >= 1 (got %d, %d, %d)", num_slots, H, W); return 0; }
+  return (size_t)view_stage_planes(views, num_slots) * H * W * 4 * sizeof(float);
+}
+static int view_stage_check(const char* fn, int views, int num_slots, int H, int W, const void* stage, size_t stage_bytes, const void* out) {
+  if (!stage || !out) return fail("%s: null argument", fn);
+  if (((uintptr_t)stage | (uintptr_t)out) & 15) return fail("%s: stage and out must be 16-byte aligned", fn);
+  const size_t need = uwm_view_stage_bytes(views, num_slots, H, W);
+  if (stage_bytes < need) return fail("%s: stage too small (%zu < %zu bytes, uwm_view_stage_bytes)", fn, stage_bytes, need);
+  return 0;
+}
+int uwm_op_resize_norm_view_u8_nhwc4(const uint8_t* src, size_t src_bytes, const uwm_image_desc* descs, int num_images, int C, int H, int W,
+                                     const float* mean, const float* std, int views, int slot0, int num_slots, float* stage, size_t stage_bytes,
+                                     float* out, uwm_stream stream) {
+  const char* fn = "uwm_op_resize_norm_view_u8_nhwc4";
+  if (!mean || !std) return fail("%s: null argument", fn);
+  if (resize_args_check(fn, src, src_bytes, descs, num_images, C, H, W, out)) return 1;
+  if (view_range_check(fn, views, H, W, slot0, num_slots, num_images)) return 1;
+  if (view_stage_check(fn, views, num_slots, H, W, stage, stage_bytes, out)) return 1;
+  for (int c = 0; c < C; ++c) if (!(std[c] > 0.f)) return fail("%s: std[%d] must be positive", fn, c);
+  LCHK(launch_resize_norm_view_u8_nhwc4(src, src_bytes, (const ImageDesc*)descs, num_images, C, H, W, mean, std, views, slot0, num_slots, stage, out,
+                                        (hipStream_t)stream));
+  return 0;
+}
+int uwm_op_tile_norm_view_u8_nhwc4(const uint8_t* src, size_t src_bytes, const uwm_image_desc* descs, int num_images, const uwm_tile_desc* tiles, int K,
+                                   int C, int T_h, int T_w, const float* mean, const float* std, int views, int slot0, int num_slots, float* stage,
+                                   size_t stage_bytes, float* out, uwm_stream stream) {
+  const char* fn = "uwm_op_tile_norm_view_u8_nhwc4";
+  if (!src || !descs || !tiles || !mean || !std) return fail("%s: null argument", fn);
+  if (tile_shape_check(fn, K, T_h, T_w, 0)) return 1;
+  if (C < 1 || C > 4) return fail("%s: C must be 1..4 (got %d)", fn, C);
+  if (num_images < 1 || src_bytes < 1) return fail("%s: num_images and src_bytes must be >= 1 (got %d, %zu)", fn, num_images, src_bytes);
+  if (view_range_check(fn, views, T_h, T_w, slot0, num_slots, K)) return 1;
+  if (view_stage_check(fn, views, num_slots, T_h, T_w, stage, stage_bytes, out)) return 1;
+  if ((uintptr_t)src & 3) return fail("%s: src must be 4-byte aligned", fn);
+  if (((uintptr_t)descs & 7) || ((uintptr_t)tiles & 3)) return fail("%s: descriptors must be 8-byte, tiles 4-byte aligned", fn);
+  for (int c = 0; c < C; ++c) if (!(std[c] > 0.f)) return fail("%s: std[%d] must be positive", fn, c);
+  LCHK(launch_tile_norm_view_u8_nhwc4(src, src_bytes, (const ImageDesc*)descs, num_images, (const TileDesc*)tiles, K, C, T_h, T_w, mean, std, views,
+                                      slot0, num_slots, stage, out, (hipStream_t)stream));
+  return 0;
+}
+int uwm_op_view_merge(const float* logits, int ld, int H, int W, int views, int slot0, int num_slots, int num_items, float* store,
+                      uwm_stream stream) {
+  const char* fn = "uwm_op_view_merge";
+  if (!logits || !store) return fail("%s: null argument", fn);
+  if (ld < 1) return fail("%s: ld must be >= 1 (got %d)", fn, ld);
+  if (view_range_check(fn, views, H, W, slot0, num_slots, num_items)) return 1;
+  if (((uintptr_t)logits | (uintptr_t)store) & 3) return fail("%s: logits and store must be 4-byte aligned", fn);
+  LCHK(launch_view_merge(logits, ld, H, W, views, slot0, num_slots, num_items, store, (hipStream_t)stream));
+  return 0;
+}
+// the workspace of the two model-level calls: the eval plan of (N, H, W) with the forward's logits behind it, then (256-byte aligned) the
+// staging planes of one chunk, then (256-byte aligned) the merged store [items][H][W], which is the workspace's tail
+static size_t tta_workspace_bytes(const char* fn, uwm_handle h, int N, int H, int W, int items, int views) {
+  if (!h) { (void)fail("%s: null argument", fn); return 0; }
+  if (view_set_check(fn, views, H, W)) return 0;
+  if (items < 1) { (void)fail("%s: the item count must be >= 1 (got %d)", fn, items); return 0; }
+  const size_t fwd = uwm_predict_workspace_bytes(h, N, H, W, 1);
+  if (!fwd) return 0;
+  const size_t stage = (size_t)view_stage_planes(views, N) * H * W * 4 * sizeof(float);
+  return ((fwd + 255) & ~(size_t)255) + ((stage + 255) & ~(size_t)255) + (size_t)items * H * W * sizeof(float);
+}
+size_t uwm_predict_images_tta_workspace_bytes(uwm_handle h, int N, int H, int W, int num_images, int views) {
+  return tta_workspace_bytes("uwm_predict_images_tta_workspace_bytes", h, N, H, W, num_images, views);
+}
+size_t uwm_predict_tiled_tta_workspace_bytes(uwm_handle h, int N, int K, int T_h, int T_w, int views) {
+  return tta_workspace_bytes("uwm_predict_tiled_tta_workspace_bytes", h, N, T_h, T_w, K, views);
+}
+int uwm_predict_images_tta_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, const uwm_image_desc* in_descs, int num_images, int views,
+                              const float* mean, const float* std, float threshold, int apply_sigmoid, const uwm_image_desc* out_descs,
+                              uint8_t* mask, size_t mask_bytes, float* merged, void* ws, size_t ws_bytes, int N, int H, int W, uwm_stream stream) {
+  const char* fn = "uwm_predict_images_tta_u8";
+  if (!h || !src || !in_descs || !mean || !std || !out_descs || !mask || !ws) return fail("%s: null argument", fn);
+  if (check_shape(N, H, W)) return 1;
+  if (view_range_check(fn, views, H, W, 0, N, num_images)) return 1;
+  if (num_images > (1 << 24)) return fail("%s: too many images for one launch (%d)", fn, num_images);
+  if (src_bytes < 1 || mask_bytes < 1) return fail("%s: src_bytes and mask_bytes must be >= 1", fn);
+  if (!std::isfinite(threshold)) return fail("%s: threshold must be finite", fn);
+  const int C = h->desc.in_channels;
+  if (C < 1 || C > 4) return fail("%s: the model takes %d channels; images have 1..4", fn, C);
+  for (int c = 0; c < C; ++c) if (!(std[c] > 0.f)) return fail("%s: std[%d] must be positive", fn, c);
+  if ((uintptr_t)src & 3) return fail("%s: src must be 4-byte aligned", fn);
+  if (((uintptr_t)in_descs | (uintptr_t)out_descs) & 7) return fail("%s: descriptors must be 8-byte aligned", fn);
+  if ((uintptr_t)ws & 15) return fail("%s: workspace must be 16-byte aligned", fn);
+  if ((uintptr_t)merged & 3) return fail("%s: merged must be 4-byte aligned", fn);
+  if (!h->params || !h->buffers) return fail("%s: call uwm_bind first", fn);
+  const size_t need = uwm_predict_images_tta_workspace_bytes(h, N, H, W, num_images, views);      // (also plans the eval forward of (N, H, W))
+  if (!need) return 1;
+  if (ws_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", fn, ws_bytes, need);
+  const size_t plane = (size_t)H * W, store_bytes = (size_t)num_images * plane * sizeof(float);
+  const size_t stage_bytes = ((size_t)view_stage_planes(views, N) * plane * 4 * sizeof(float) + 255) & ~(size_t)255;
+  float* lg = (float*)ws + h->plan.bytes / sizeof(float);                        // the forward's logits: behind the plan
+  float* stage = (float*)((char*)ws + (need - store_bytes - stage_bytes));
+  float* store = merged ? merged : (float*)((char*)ws + (need - store_bytes));
+  const long long slots = (long long)num_images * view_count(views);
+  h->have_fwd = false;
+  DeviceGuard guard(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  for (long long s0 = 0; s0 < slots; s0 += N) {
+    LCHK(launch_resize_norm_view_u8_nhwc4(src, src_bytes, (const ImageDesc*)in_descs, num_images, C, H, W, mean, std, views, (int)s0, N, stage,
+                                          (float*)ws + h->plan.x4, st));
+    if (do_forward(h, nullptr, lg, (float*)ws, N, H, W, 0, st)) return 1;
+    LCHK(launch_view_merge(lg, h->CP, H, W, views, (int)s0, N, num_images, store, st));
+  }
+  LCHK(launch_resize_threshold_ragged(store, 1, num_images, H, W, (const ImageDesc*)out_descs, threshold, apply_sigmoid, mask, mask_bytes, st));
+  return 0;
+}
+int uwm_predict_tiled_tta_u8(uwm_handle h, const uint8_t* src, size_t src_bytes, const uwm_image_desc* in_descs, int num_images,
+                             const uwm_tile_desc* tiles, int K, const uwm_tile_image* plans, int T_h, int T_w, int overlap, const float* mean,
+                             const float* std, float threshold, int apply_sigmoid, const uwm_image_desc* out_descs, uint8_t* mask, size_t mask_bytes,
+                             float* logits_out, void* ws, size_t ws_bytes, int N, int views, uwm_stream stream) {
+  const char* fn = "uwm_predict_tiled_tta_u8";
+  if (!h || !src || !in_descs || !tiles || !mean || !std || !ws) return fail("%s: null argument", fn);
+  if (check_shape(N, T_h, T_w)) return 1;
+  if (tile_blend_args_check(fn, K, plans, num_images, T_h, T_w, overlap, in_descs, h->desc.in_channels, out_descs, threshold, mask, mask_bytes,
+                            logits_out))
+    return 1;
+  if (view_range_check(fn, views, T_h, T_w, 0, N, K)) return 1;
+  if (src_bytes < 1) return fail("%s: src_bytes must be >= 1", fn);
+  const int C = h->desc.in_channels;
+  if (C < 1 || C > 4) return fail("%s: the model takes %d channels; images have 1..4", fn, C);
+  for (int c = 0; c < C; ++c) if (!(std[c] > 0.f)) return fail("%s: std[%d] must be positive", fn, c);
+  if ((uintptr_t)src & 3) return fail("%s: src must be 4-byte aligned", fn);
+  if ((uintptr_t)tiles & 3) return fail("%s: tiles must be 4-byte aligned", fn);
+  if ((uintptr_t)ws & 15) return fail("%s: workspace must be 16-byte aligned", fn);
+  if (!h->params || !h->buffers) return fail("%s: call uwm_bind first", fn);
+  const size_t need = uwm_predict_tiled_tta_workspace_bytes(h, N, K, T_h, T_w, views);      // (also plans the eval forward of (N, T_h, T_w))
+  if (!need) return 1;
+  if (ws_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", fn, ws_bytes, need);
+  const size_t plane = (size_t)T_h * T_w, store_bytes = (size_t)K * plane * sizeof(float);
+  const size_t stage_bytes = ((size_t)view_stage_planes(views, N) * plane * 4 * sizeof(float) + 255) & ~(size_t)255;
+  float* lg = (float*)ws + h->plan.bytes / sizeof(float);
+  float* stage = (float*)((char*)ws + (need - store_bytes - stage_bytes));
+  float* store = (float*)((char*)ws + (need - store_bytes));
+  const long long slots = (long long)K * view_count(views);
+  h->have_fwd = false;
+  DeviceGuard guard(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  for (long long s0 = 0; s0 < slots; s0 += N) {
+    LCHK(launch_tile_norm_view_u8_nhwc4(src, src_bytes, (const ImageDesc*)in_descs, num_images, (const TileDesc*)tiles, K, C, T_h, T_w, mean, std,
+                                        views, (int)s0, N, stage, (float*)ws + h->plan.x4, st));
+    if (do_forward(h, nullptr, lg, (float*)ws, N, T_h, T_w, 0, st)) return 1;
+    LCHK(launch_view_merge(lg, h->CP, T_h, T_w, views, (int)s0, N, K, store, st));
+  }
+  LCHK(launch_tile_blend_threshold_ragged(store, K, (const TileImage*)plans, num_images, T_h, T_w, overlap, (const ImageDesc*)in_descs, src_bytes, C,
+                                          (const ImageDesc*)out_descs, threshold, apply_sigmoid, mask, mask_bytes, logits_out, st));
+  return 0;
+}
 // ---- the dataset filter (filter_u8.hip): every argument is checked here, before any launch
 size_t uwm_filter_workspace_bytes(int N) {
   const size_t need = filter_workspace_bytes(N);

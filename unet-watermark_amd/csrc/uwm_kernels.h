@@ -518,6 +518,21 @@ hipError_t launch_tile_store(const float* logits, int ld, size_t npix, float* st
 hipError_t launch_tile_blend_threshold_ragged(const float* store, int K, const TileImage* plans, int num_images, int T_h, int T_w, int overlap,
                                               const ImageDesc* in_descs, size_t src_bytes, int C, const ImageDesc* out_descs, float thr,
                                               int apply_sigmoid, uint8_t* mask, size_t mask_bytes, float* logits_out, hipStream_t st);
+// ---- test-time augmentation: the D4 views of the network input, merged on the way back (tta.hip; the rule: include/uwm.h)
+// base planes a range of num_slots slots can touch at most: the staging buffer of the two calls below holds this many [H][W][4] planes (0: bad arguments)
+int view_stage_planes(int views, int num_slots);
+// slots [slot0, slot0 + num_slots) of the images (slot = image * k + j) -> out [num_slots][H][W][4]: launch_resize_norm_u8_nhwc4 of the
+// images the range touches into `stage`, then the views; a slot whose image is >= num_images is written as zeros
+hipError_t launch_resize_norm_view_u8_nhwc4(const uint8_t* src, size_t src_bytes, const ImageDesc* descs, int num_images, int C, int H, int W,
+                                            const float* mean, const float* std, int views, int slot0, int num_slots, float* stage, float* out,
+                                            hipStream_t st);
+// the same for the tiles of a tile table of K entries (slot = tile * k + j): launch_tile_norm_u8_nhwc4 into `stage`, then the views
+hipError_t launch_tile_norm_view_u8_nhwc4(const uint8_t* src, size_t src_bytes, const ImageDesc* descs, int num_images, const TileDesc* tiles, int K,
+                                          int C, int T_h, int T_w, const float* mean, const float* std, int views, int slot0, int num_slots,
+                                          float* stage, float* out, hipStream_t st);
+// logit planes [num_slots][H][W] (stride ld) of that slot range, mapped back, into store [num_items][H][W]: first view writes, later add, last divides
+hipError_t launch_view_merge(const float* logits, int ld, int H, int W, int views, int slot0, int num_slots, int num_items, float* store,
+                             hipStream_t st);
 // ---- masks from watermarked / clean pairs (pair_mask_u8.hip; the rule: include/uwm.h)
 constexpr int kPairMaskBlocks = 64;                 // workgroups per image, each walking that image's tiles: grid = N * this
 constexpr int kPairMaskTileW = 120, kPairMaskTileH = 32;      // mask pixels of one tile

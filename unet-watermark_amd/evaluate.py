@@ -46,8 +46,10 @@ def load_mask(path) -> np.ndarray:
 
 
 def check_settings(mask_type=None, text_enhance=False, tile=False, tile_overlap=64, boundary_ratio=0.02, boundary_pixels=None,
-                   batch_size=16, limit=None):
+                   batch_size=16, limit=None, tta=None):
     """the refusals of `evaluate`, before anything is created"""
+    from .tta import view_mask
+    view_mask(tta)
     if mask_type not in (None, "watermark", "text", "mixed"):
         raise ValueError(f"mask_type must be 'watermark', 'text' or 'mixed', got {mask_type!r}")
     if tile and text_enhance:
@@ -71,20 +73,21 @@ class Evaluator:
     def __init__(self, input_dir, masks_dir, model_path: Optional[str] = None, config_path: Optional[str] = None, mask_type: Optional[str] = None,
                  text_enhance: bool = False, tile: bool = False, tile_overlap: int = 64, boundary_ratio: Optional[float] = None,
                  boundary_pixels: Optional[int] = None, batch_size: int = 16, limit: Optional[int] = None, seed: int = 0, config=None,
-                 model=None, scorer=None, log=print):
+                 model=None, scorer=None, log=print, tta: Optional[str] = None):
         """input_dir / masks_dir: the images and their ground-truth masks, paired by stem.  model_path / config_path (or config /
         model: a ready config node / model) make the WatermarkPredictor that scores a batch; scorer(images, truths, radii) -> (n, 8)
         counts replaces it (tests).  mask_type / text_enhance / tile / tile_overlap: how the masks are predicted, as `predict
-        --resize device` takes them.  boundary_ratio (default 0.02 of the diagonal) or boundary_pixels: Boundary IoU's distance."""
+        --resize device` takes them.  boundary_ratio (default 0.02 of the diagonal) or boundary_pixels: Boundary IoU's distance.
+        tta: the test-time-augmentation view set ('none' | 'hflip' | 'flips' | 'd4'), as `predict --tta`; recorded in the settings."""
         if boundary_ratio is None and boundary_pixels is None:
             boundary_ratio = 0.02
-        check_settings(mask_type, text_enhance, tile, tile_overlap, boundary_ratio, boundary_pixels, batch_size, limit)
+        check_settings(mask_type, text_enhance, tile, tile_overlap, boundary_ratio, boundary_pixels, batch_size, limit, tta)
         self.input_dir, self.masks_dir = str(input_dir), str(masks_dir)
         self.settings = dict(input=self.input_dir, masks=self.masks_dir, model=model_path, config=config_path, mask_type=mask_type,
                              text_enhance=bool(text_enhance), tile=bool(tile), tile_overlap=int(tile_overlap),
                              boundary_ratio=None if boundary_ratio is None else float(boundary_ratio),
                              boundary_pixels=None if boundary_pixels is None else int(boundary_pixels), batch_size=int(batch_size),
-                             limit=None if limit is None else int(limit), seed=int(seed))
+                             limit=None if limit is None else int(limit), seed=int(seed), tta="none" if tta is None else tta)
         self.log = log or (lambda *a: None)
         self._scorer = scorer
         if scorer is None:
@@ -105,7 +108,7 @@ class Evaluator:
             return np.asarray(self._scorer(images, truths, radii), dtype=np.int64).reshape(len(images), 8)
         s = self.settings
         return self.predictor.score_images(images, truths, s["mask_type"], s["text_enhance"], s["tile"], s["tile_overlap"],
-                                           s["boundary_ratio"] if s["boundary_pixels"] is None else 0.02, s["boundary_pixels"])
+                                           s["boundary_ratio"] if s["boundary_pixels"] is None else 0.02, s["boundary_pixels"], tta=s["tta"])
 
     def run(self, per_image: bool = False) -> dict:
         """-> {'settings', 'images', 'errors', 'error_details' (per error {path, reason}), 'micro', 'imagewise'[, 'per_image']}: every pair of the

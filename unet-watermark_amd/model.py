@@ -530,6 +530,86 @@ class Unet(nn.Module):
                     SegmentationModelError)
         return mask
 
+    def _tta_call_setup(self, name: str, flat, n: int, in_descs, out_descs, batch: int, size, views: int, query, items: int):
+        """what the two test-time-augmentation calls share: the checks of their flat tensors, the bound / frozen state and the workspace
+        of `query`(handle, batch, ..., views) bytes -> (h, w, workspace, bytes)"""
+        if self.training:
+            raise RuntimeError(f"{name} is an eval-mode path: call .eval() first")
+        for t in flat:
+            self._require_gpu(t)
+            if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+                raise RuntimeError(f"{name} takes flat contiguous uint8 tensors (data.pack_images / data.descs_tensor / tiling.table_tensor)")
+        if n < 1 or in_descs.numel() < 16 * n or out_descs.numel() < 16 * n:
+            raise RuntimeError(f"{name}: {n} images need {16 * n} descriptor bytes each way")
+        if batch < 1 or items < 1:
+            raise RuntimeError(f"{name}: the forward batch and the item count must be >= 1 (got {batch}, {items})")
+        h, w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+        self.check_input_shape(torch.empty((0, self.in_channels, h, w)))
+        self._ensure_bound()
+        if self._frozen and not L.lib().uwm_is_frozen(self._h):
+            self._freeze_now(batch, h, w)
+        need = query(h, w)
+        if need == 0:
+            raise SegmentationModelError(L.lib().uwm_last_error().decode())
+        if self._ws is None or self._ws.numel() < need or self._ws.device != self.device:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)      # (a captured graph's owner keeps its own reference)
+        self._ws_key = (batch, h, w, False)
+        self._fwd_gen += 1
+        if self._n_mb:
+            self._set_drop_connect(batch, False, self.device)
+        return h, w, self._ws, need
+
+    @torch.no_grad()
+    def predict_images_tta_u8(self, packed: torch.Tensor, in_descs: torch.Tensor, out_descs: torch.Tensor, mask: torch.Tensor, n: int,
+                              batch: int, size, views: int, mean, std, threshold: float = 0.5, apply_sigmoid: bool = False):
+        """predict_images_u8 with test-time augmentation, in ONE library call (uwm_predict_images_tta_u8): every image goes through the
+        eval forward under each view of the bitmask `views` (tta.view_mask), `batch` slots at a time, and the logit planes are mapped
+        back and averaged (the mean of the logits, summed in ascending view order) before the resize back + threshold.  Nothing in
+        the call depends on the image sizes, so a graph captured around it serves every batch of n images.  Returns `mask`; the
+        merged planes (n, H, W) of the call stay readable as `self._merged_store` (a view of the workspace's tail)."""
+        n, batch, views = int(n), int(batch), int(views)
+        h, w, ws, need = self._tta_call_setup("predict_images_tta_u8", (packed, in_descs, out_descs, mask), n, in_descs, out_descs, batch, size, views,
+                                              lambda h, w: L.lib().uwm_predict_images_tta_workspace_bytes(self._h, batch, h, w, n, views), n)
+        self._merged_store = ws[need - 4 * n * h * w: need].view(torch.float32).view(n, h, w)
+        c = self.in_channels
+        mean_c = (C.c_float * c)(*[float(v) for v in mean[:c]]); std_c = (C.c_float * c)(*[float(v) for v in std[:c]])
+        with L.on_device(packed):
+            L.check(L.lib().uwm_predict_images_tta_u8(self._h, C.c_void_p(packed.data_ptr()), packed.numel(), C.c_void_p(in_descs.data_ptr()), n,
+                                                      views, mean_c, std_c, float(threshold), int(apply_sigmoid),
+                                                      C.c_void_p(out_descs.data_ptr()), C.c_void_p(mask.data_ptr()), mask.numel(), C.c_void_p(0),
+                                                      C.c_void_p(ws.data_ptr()), need, batch, h, w, C.c_void_p(L.stream_ptr(packed.device))),
+                    SegmentationModelError)
+        return mask
+
+    @torch.no_grad()
+    def predict_tiled_tta_u8(self, packed: torch.Tensor, in_descs: torch.Tensor, out_descs: torch.Tensor, mask: torch.Tensor, n: int,
+                             tiles: torch.Tensor, plans: torch.Tensor, k: int, batch: int, size, overlap: int, views: int, mean, std,
+                             threshold: float = 0.5, apply_sigmoid: bool = False, logits_out: Optional[torch.Tensor] = None):
+        """predict_tiled_u8 with test-time augmentation, in ONE library call (uwm_predict_tiled_tta_u8): every tile goes through the
+        eval forward under each view of the bitmask `views`, `batch` slots at a time; the store [k][T_h][T_w] (`self._tile_store`)
+        holds the merged tile logits and the blend runs on it as it does without views."""
+        n, k, batch, views = int(n), int(k), int(batch), int(views)
+        if plans.numel() < 16 * n or k < 1 or tiles.numel() < 16 * k:
+            raise RuntimeError(f"predict_tiled_tta_u8: {n} images need {16 * n} plan bytes and k = {k} tile entries {16 * k} table bytes")
+        if logits_out is not None:
+            self._require_gpu(logits_out)
+            if logits_out.dtype != torch.float32 or not logits_out.is_contiguous() or logits_out.numel() < mask.numel():
+                raise RuntimeError(f"predict_tiled_tta_u8: logits_out must be a contiguous float32 tensor of at least {mask.numel()} elements")
+        h, w, ws, need = self._tta_call_setup("predict_tiled_tta_u8", (packed, in_descs, out_descs, mask, tiles, plans), n, in_descs, out_descs, batch,
+                                              size, views, lambda h, w: L.lib().uwm_predict_tiled_tta_workspace_bytes(self._h, batch, k, h, w, views), k)
+        self._tile_store = ws[need - 4 * k * h * w: need].view(torch.float32).view(k, h, w)
+        c = self.in_channels
+        mean_c = (C.c_float * c)(*[float(v) for v in mean[:c]]); std_c = (C.c_float * c)(*[float(v) for v in std[:c]])
+        with L.on_device(packed):
+            L.check(L.lib().uwm_predict_tiled_tta_u8(self._h, C.c_void_p(packed.data_ptr()), packed.numel(), C.c_void_p(in_descs.data_ptr()), n,
+                                                     C.c_void_p(tiles.data_ptr()), k, C.c_void_p(plans.data_ptr()), h, w, int(overlap),
+                                                     mean_c, std_c, float(threshold), int(apply_sigmoid), C.c_void_p(out_descs.data_ptr()),
+                                                     C.c_void_p(mask.data_ptr()), mask.numel(),
+                                                     C.c_void_p(logits_out.data_ptr() if logits_out is not None else 0),
+                                                     C.c_void_p(ws.data_ptr()), need, batch, views, C.c_void_p(L.stream_ptr(packed.device))),
+                    SegmentationModelError)
+        return mask
+
     @torch.no_grad()
     def filter_images_u8(self, packed: torch.Tensor, in_descs: torch.Tensor, out_descs: torch.Tensor, counts: torch.Tensor, n: int,
                          size, mean, std, threshold: float = 0.5, post_process: bool = True, mask: Optional[torch.Tensor] = None,

@@ -20,6 +20,7 @@ from .data import descs_tensor, device_preprocess, pack_images
 from .metrics import threshold_mask
 from .model import create_model_from_config
 from .textenh import text_enhance_ragged, text_enhance_workspace
+from .tta import view_mask
 from .postprocess import RAGGED_TYPES, mask_type_code, optimize_mask, optimize_masks_ragged, ragged_workspace, workspace as mask_workspace
 
 
@@ -69,6 +70,8 @@ class WatermarkPredictor:
         self._ckey = None
         self._cbuf = self._cws = None         # its static counts buffer and workspaces
         self._xgraphs = {}                    # predict_images_tiled: ONE graph per (images, chunk count, ...), beside the ones above
+        self._agraphs = {}                    # predict_images(tta=...): ONE graph per (key of the plain call, view mask, forward batch), beside them
+        self._merged = None                   # ... and the merged logit planes (n, IMG_SIZE, IMG_SIZE) of the last such call
         self._xtiles = self._xplans = self._xlbuf = None      # its static tile table, per-image plans and ragged logit plane
         self._gtbuf = None                    # score_images: the staged ground-truth masks, under _mbuf's descriptors
         self._hbuf = self._hevt = None        # pinned host staging of the packed bytes + the event of its last upload
@@ -133,6 +136,7 @@ class WatermarkPredictor:
             self._graph = self._gkey = self._ugraph = self._ukey = self._pgraph = self._pkey = self._igraph = self._ikey = self._qgraph = self._qkey = self._cgraph = self._ckey = None
             self._tigraph = self._tikey = self._tqgraph = self._tqkey = None
             self._xgraphs = {}
+            self._agraphs = {}
 
     @torch.no_grad()
     def predict_mask_u8(self, images_u8_nhwc: torch.Tensor, out_size=None, apply_sigmoid: bool = False,
@@ -185,6 +189,7 @@ class WatermarkPredictor:
         self._igraph = self._ikey = self._qgraph = self._qkey = self._cgraph = self._ckey = None
         self._tigraph = self._tikey = self._tqgraph = self._tqkey = None
         self._xgraphs = {}
+        self._agraphs = {}
 
     def _stage_images(self, images):
         """pack `images` into the static staging buffers (_ibuf, _idesc, _mdesc; _mbuf sized for their masks) -> (n, IMG_SIZE, descs,
@@ -213,15 +218,19 @@ class WatermarkPredictor:
         self._mdesc[:16 * n].copy_(descs_tensor(mdescs))
         return n, s, descs, mdescs, areas, mask_bytes
 
-    def _run_images(self, images, apply_sigmoid: bool, mask_type: Optional[str], use_graph: bool, text_enhance: bool = False):
+    def _run_images(self, images, apply_sigmoid: bool, mask_type: Optional[str], use_graph: bool, text_enhance: bool = False, views: int = 1):
         """stage `images`, run uwm_predict_images_u8 and, with a mask_type, uwm_optimize_masks_ragged in place on _mbuf — one captured
         graph for both -> (descs, mask descs, areas, mask bytes, the int64 (n, 8) device stats or None).  The ragged call's
         capacities (the largest h*w, the sum of h) are kept and grown geometrically like the staging buffers; they and the buffer
         sizes are all the graph knows about a batch, so a batch that fits them replays it and one that exceeds one re-captures.
         text_enhance: the staged images first go through uwm_text_enhance_ragged into a second staging buffer (_ebuf), which the
         forward then reads — the same graph, kept in slots of its own, with the enhancement's two capacities (the largest h*w, the
-        sum of h*w) in its key."""
+        sum of h*w) in its key.
+        views != 1 (a tta.view_mask): uwm_predict_images_tta_u8 in place of uwm_predict_images_u8, PREDICT.BATCH_SIZE slots per forward;
+        its graphs live in a table of their own (_agraphs) under the plain call's key + (mask, batch), with the static stats and the
+        merged logit planes (n, IMG_SIZE, IMG_SIZE) of the graph beside it; `_merged` is the latter after the call."""
         n, s, descs, mdescs, areas, mask_bytes = self._stage_images(images)
+        batch = int(self.cfg.PREDICT.BATCH_SIZE)
         tcaps = ()
         if text_enhance:
             if self.model.in_channels != 3:
@@ -234,6 +243,7 @@ class WatermarkPredictor:
             if self._ebuf is None or self._ebuf.numel() != self._ibuf.numel():
                 self._ebuf = torch.zeros_like(self._ibuf)
                 self._tigraph = self._tikey = self._tqgraph = self._tqkey = None
+                self._agraphs = {}
             tcaps = ("text_enhance", self._tcap_pixels, self._tcap_total)
         if mask_type is not None:
             for name, need in (("_cap_pixels", int(areas.max())), ("_cap_rows", int(descs["h"].astype("int64").sum()))):
@@ -245,8 +255,12 @@ class WatermarkPredictor:
         def run():
             if text_enhance:
                 text_enhance_ragged(self._ibuf, self._idesc, out=self._ebuf, n=n, max_pixels=tcaps[1], total_pixels=tcaps[2])
-            self.model.predict_images_u8(self._ebuf if text_enhance else self._ibuf, self._idesc, self._mdesc, self._mbuf, n, (s, s),
-                                         IMAGENET_MEAN, IMAGENET_STD, self.threshold, apply_sigmoid)
+            if views != 1:
+                self.model.predict_images_tta_u8(self._ebuf if text_enhance else self._ibuf, self._idesc, self._mdesc, self._mbuf, n, batch,
+                                                 (s, s), views, IMAGENET_MEAN, IMAGENET_STD, self.threshold, apply_sigmoid)
+            else:
+                self.model.predict_images_u8(self._ebuf if text_enhance else self._ibuf, self._idesc, self._mdesc, self._mbuf, n, (s, s),
+                                             IMAGENET_MEAN, IMAGENET_STD, self.threshold, apply_sigmoid)
             if mask_type is not None:
                 optimize_masks_ragged(self._mbuf, self._mdesc, mask_type, True, out=self._mbuf, n=n, max_pixels=caps[1], rows=caps[2],
                                       stats=stats)
@@ -254,6 +268,27 @@ class WatermarkPredictor:
             if mask_type is not None:
                 stats = torch.empty((n, 8), dtype=torch.int64, device=self.device)
             run()
+            if views != 1:
+                self._merged = self.model._merged_store
+        elif views != 1:
+            key = (n, s, s, bool(apply_sigmoid), float(self.threshold)) + caps + tcaps + ("tta", views, batch)
+            if key not in self._agraphs:
+                self._refreeze_for(batch, s, s)
+                if mask_type is not None:
+                    stats = torch.empty((n, 8), dtype=torch.int64, device=self.device)
+                run()                                 # eager warm-up: plans the workspace, sets kernel attributes
+                torch.cuda.synchronize(self.device)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    run()
+                ws = self.model._ws                   # (the graph's workspaces stay alive with it)
+                if mask_type is not None:
+                    ws = (ws, ragged_workspace(self.device, n, self._mbuf.numel(), caps[2]))
+                if text_enhance:
+                    ws = (ws, text_enhance_workspace(self.device, tcaps[2], n))
+                self._agraphs[key] = (g, ws, stats, self.model._merged_store)
+            g, _, stats, self._merged = self._agraphs[key]
+            g.replay()
         else:
             key = (n, s, s, bool(apply_sigmoid), float(self.threshold)) + caps + tcaps      # (the threshold and the capacities are captured arguments)
             slot = "_i" if mask_type is None else "_q"      # the graph without post-processing stays when the other is captured
@@ -286,7 +321,7 @@ class WatermarkPredictor:
 
     @torch.no_grad()
     def predict_images(self, images, apply_sigmoid: bool = False, mask_type: Optional[str] = None, use_graph: bool = True,
-                       return_stats: bool = False, text_enhance: bool = False):
+                       return_stats: bool = False, text_enhance: bool = False, tta=None, return_logits: bool = False):
         """uint8 (h_i, w_i, C) images of ANY sizes (arrays or tensors) -> a list of uint8 {0,255} device masks, one per image at its
         own size: the reference's predict path (src/predict.py:327-335,614-625) device-resident from the image bytes on — cv2's
         INTER_LINEAR resize to IMG_SIZE (A.Resize) + Normalize, eval forward, bilinear resize of the logits back to (h_i, w_i) +
@@ -298,14 +333,25 @@ class WatermarkPredictor:
         return_stats (needs a mask_type): also the int64 (N, 8) HOST array of postprocess.STATS_FIELDS.
         text_enhance: every image first goes through the reference's _enhance_text_features at its own size
         (uwm_text_enhance_ragged, textenh.py) and the network sees the enhanced image; an image with a side below 16 goes in as it
-        is.  Independent of mask_type: mask_type='text', text_enhance=True is the reference's predict_text_watermark_mask."""
+        is.  Independent of mask_type: mask_type='text', text_enhance=True is the reference's predict_text_watermark_mask.
+        tta 'hflip' | 'flips' | 'd4' or a view mask (tta.view_mask): test-time augmentation — the network sees every (enhanced,
+        resized) image under each view of the set, PREDICT.BATCH_SIZE network inputs per forward, and the logit planes are mapped
+        back and averaged on the device before the resize back (uwm_predict_images_tta_u8; the mean of the LOGITS, DESIGN.md 8t);
+        one graph per view mask beside the others.  None / 'none': the call as it is without it.  return_logits (needs tta): also
+        the float32 (N, IMG_SIZE, IMG_SIZE) device tensor of merged logits, last in the result."""
+        views = view_mask(tta)
         if mask_type is not None:
             mask_type_code(mask_type)
         elif return_stats:
             raise ValueError("return_stats needs a mask_type ('watermark', 'text' or 'mixed')")
-        descs, mdescs, areas, mask_bytes, stats = self._run_images(images, apply_sigmoid, mask_type, use_graph, text_enhance)
+        if return_logits and views == 1:
+            raise ValueError("return_logits needs tta ('hflip', 'flips', 'd4' or a view mask other than 1)")
+        descs, mdescs, areas, mask_bytes, stats = self._run_images(images, apply_sigmoid, mask_type, use_graph, text_enhance, views)
         masks = self._mask_views(descs, mdescs, areas, mask_bytes)
-        return (masks, stats.cpu().numpy()) if return_stats else masks
+        out = (masks, stats.cpu().numpy()) if return_stats else masks
+        if return_logits:
+            out = (out if return_stats else (out,)) + (self._merged.clone(),)
+        return out
 
     def _tiled_static(self, name: str, need: int, dtype=torch.uint8):
         """the static device buffer `name` of predict_images_tiled holds at least `need` elements; grown geometrically, and the tiled
@@ -318,7 +364,7 @@ class WatermarkPredictor:
 
     @torch.no_grad()
     def predict_images_tiled(self, images, overlap: int = 64, apply_sigmoid: bool = False, mask_type: Optional[str] = None,
-                             return_logits: bool = False, use_graph: bool = True, tile_batch: Optional[int] = None):
+                             return_logits: bool = False, use_graph: bool = True, tile_batch: Optional[int] = None, tta=None):
         """uint8 (h_i, w_i, C) images of ANY sizes -> a list of uint8 {0,255} device masks, one per image at its own size, predicted at
         NATIVE resolution: instead of resizing an image to IMG_SIZE it is cut into IMG_SIZE x IMG_SIZE tiles that overlap by
         `overlap` pixels (tiling.plan_tiles; an image smaller than a tile is padded by reflection), the tiles of the whole batch go
@@ -329,8 +375,11 @@ class WatermarkPredictor:
         image sizes; it is re-captured when a staging buffer had to grow or the frozen arena was re-made.  mask_type 'watermark' |
         'text' | 'mixed': every blended mask then goes through the reference's _optimize_mask at its own size
         (uwm_optimize_masks_ragged), in place and inside the same graph.  return_logits: also the list of float32 (h_i, w_i) planes
-        of blended logits the masks were thresholded from."""
-        descs, mdescs, areas, mask_bytes = self._run_tiled(images, overlap, apply_sigmoid, mask_type, return_logits, use_graph, tile_batch)
+        of blended logits the masks were thresholded from.  tta (as predict_images): every TILE goes through the forward under each
+        view of the set and the tile-logit store holds the merged logits (uwm_predict_tiled_tta_u8); the blend, and so return_logits,
+        then work on those."""
+        descs, mdescs, areas, mask_bytes = self._run_tiled(images, overlap, apply_sigmoid, mask_type, return_logits, use_graph, tile_batch,
+                                                           view_mask(tta))
         masks = self._mask_views(descs, mdescs, areas, mask_bytes)
         if not return_logits:
             return masks
@@ -338,7 +387,7 @@ class WatermarkPredictor:
         return masks, [lg[int(o): int(o) + int(a)].view(int(h), int(w)) for o, a, h, w in zip(mdescs["offset"], areas, descs["h"], descs["w"])]
 
     def _run_tiled(self, images, overlap: int, apply_sigmoid: bool, mask_type: Optional[str], return_logits: bool, use_graph: bool,
-                   tile_batch: Optional[int]):
+                   tile_batch: Optional[int], views: int = 1):
         """stage `images` and run uwm_predict_tiled_u8 (and, with a mask_type, uwm_optimize_masks_ragged in place) as
         predict_images_tiled describes -> (descs, mask descs, areas, mask bytes); the masks are in _mbuf, the blended logits, when
         asked for, in _xlbuf"""
@@ -366,8 +415,12 @@ class WatermarkPredictor:
         lbuf = self._xlbuf if return_logits else None
 
         def run():
-            self.model.predict_tiled_u8(self._ibuf, self._idesc, self._mdesc, self._mbuf, n, self._xtiles, self._xplans, k, batch, (T, T),
-                                        overlap, IMAGENET_MEAN, IMAGENET_STD, self.threshold, apply_sigmoid, lbuf)
+            if views != 1:
+                self.model.predict_tiled_tta_u8(self._ibuf, self._idesc, self._mdesc, self._mbuf, n, self._xtiles, self._xplans, k, batch,
+                                                (T, T), overlap, views, IMAGENET_MEAN, IMAGENET_STD, self.threshold, apply_sigmoid, lbuf)
+            else:
+                self.model.predict_tiled_u8(self._ibuf, self._idesc, self._mdesc, self._mbuf, n, self._xtiles, self._xplans, k, batch, (T, T),
+                                            overlap, IMAGENET_MEAN, IMAGENET_STD, self.threshold, apply_sigmoid, lbuf)
             if mask_type is not None:
                 optimize_masks_ragged(self._mbuf, self._mdesc, mask_type, False, out=self._mbuf, n=n, max_pixels=caps[1], rows=caps[2])
         if not use_graph:
@@ -375,6 +428,8 @@ class WatermarkPredictor:
         else:
             # (the counts, the threshold, the capacities and the logit plane's pointer are captured arguments)
             key = (n, k // batch, batch, T, overlap, bool(apply_sigmoid), float(self.threshold), bool(return_logits)) + caps
+            if views != 1:
+                key += ("tta", views)                 # (a graph of its own per view mask; the keys without one are as they were)
             if key not in self._xgraphs:
                 self._refreeze_for(batch, T, T)
                 run()                                 # eager warm-up: plans the workspace, sets kernel attributes
@@ -391,7 +446,8 @@ class WatermarkPredictor:
 
     @torch.no_grad()
     def score_images(self, images, truths, mask_type: Optional[str] = None, text_enhance: bool = False, tile: bool = False,
-                     overlap: int = 64, boundary_ratio: float = 0.02, boundary_pixels: Optional[int] = None, return_masks: bool = False):
+                     overlap: int = 64, boundary_ratio: float = 0.02, boundary_pixels: Optional[int] = None, return_masks: bool = False,
+                     tta=None):
         """uint8 (h_i, w_i, C) images of ANY sizes and their ground-truth masks, uint8 (h_i, w_i) grey (binarised as > 127) -> the
         int64 (N, 8) HOST array of scoring.COUNT_FIELDS for the masks that predict_images(images, mask_type=..., text_enhance=...)
         or, with tile, predict_images_tiled(images, overlap, mask_type=...) returns: {tp, fp, fn, tn, |B(P) & B(G)|, |B(P)|, |B(G)|,
@@ -399,7 +455,9 @@ class WatermarkPredictor:
         boundary_ratio).  The prediction runs as it does there, through the same graphs; the truths are staged into
         a buffer of their own under the same mask descriptors and uwm_score_masks_ragged runs behind the prediction on the same
         stream, reading the predicted masks in place.  One device-to-host copy of 64 N bytes; no mask leaves the device unless
-        return_masks, which adds the list of device masks.  scoring.metrics_from_counts / summarize turn the rows into metrics."""
+        return_masks, which adds the list of device masks.  scoring.metrics_from_counts / summarize turn the rows into metrics.
+        tta: as predict_images / predict_images_tiled take it."""
+        views = view_mask(tta)
         from .scoring import MAX_RADIUS, boundary_radius, score_masks_ragged
         if self.device.type != "cuda" or not torch.cuda.is_available():
             raise RuntimeError("score_images runs only on a HIP device (no CPU fallback)")
@@ -418,11 +476,11 @@ class WatermarkPredictor:
             if t.ndim != 2 or t.dtype != np.uint8 or tuple(t.shape) != tuple(im.shape[:2]):
                 raise ValueError(f"truth {i} is {t.dtype} {tuple(t.shape)}: it must be a uint8 mask of its image's size {tuple(im.shape[:2])}")
         if tile:
-            descs, mdescs, areas, mask_bytes = self._run_tiled(images, overlap, False, mask_type, False, True, None)
+            descs, mdescs, areas, mask_bytes = self._run_tiled(images, overlap, False, mask_type, False, True, None, views)
         else:
             if mask_type is not None:
                 mask_type_code(mask_type)
-            descs, mdescs, areas, mask_bytes, _ = self._run_images(images, False, mask_type, True, text_enhance)
+            descs, mdescs, areas, mask_bytes, _ = self._run_images(images, False, mask_type, True, text_enhance, views)
         n = len(descs)
         radii = [min(boundary_radius(h, w, boundary_ratio), MAX_RADIUS) if boundary_pixels is None else int(boundary_pixels)
                  for h, w in zip(descs["h"].tolist(), descs["w"].tolist())]
