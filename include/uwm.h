@@ -959,6 +959,45 @@ int    uwm_score_masks_ragged(const uint8_t* pred, const uint8_t* truth, size_t 
                               const uwm_image_desc* descs /* device */, const int* radius /* device [N] */, int N,
                               long long max_pixels, long long rows, long long* counts /* device [N][8] */,
                               void* workspace, size_t workspace_bytes, uwm_stream stream);
+/* Exact Euclidean distance transforms and surface distances (mask_dist.hip).  Masks are one byte per pixel, binarised
+ * as > 127, under the descriptors of uwm_score_masks_ragged: image i is descs[i].h x descs[i].w at + descs[i].offset (any alignment).
+ * Everything outside an image is unset.
+ *   D2(M)[y][x]  = the minimum of (y - y')^2 + (x - x')^2 over the set pixels (y', x') of M: int32, 0 on set pixels, UWM_EDT_NONE
+ *                  everywhere when M has no set pixel.  Sides are 1 .. 32768, so every real value is below UWM_EDT_NONE.
+ *   dM           = M & ~erode(M), erode over the 4-neighbour cross: a set pixel with an unset 4-neighbour or on the image edge
+ *                  (scipy's binary_erosion(M, generate_binary_structure(2, 1), border_value=0): MedPy's hd, hd95, assd).
+ * uwm_edt_ragged writes D2 of image i's pixel k to d2[descs[i].offset + k]; d2 holds mask_bytes int32.  A misfit's entries are not
+ * written.  Three launches.
+ * uwm_surface_distances_ragged, with P = pred and G = truth of pair i (pred may alias truth):
+ *   a = D2(dG) read at the pixels of dP, b = D2(dP) read at the pixels of dG, v = a and b together, sorted, n = |v|
+ *   (lo, rem) = divmod(95 * (n - 1), 100), hi = lo + (rem > 0)
+ *   records[i] = long long [10]: 0 border_pred |dP|, 1 border_truth |dG|, 2 hd_d2_pred max a, 3 hd_d2_truth max b, 4 p95_d2_lo v[lo],
+ *                5 p95_d2_hi v[hi], 6 p95_rem rem, 7 cover_d2, 8 defined, 9 status: 0 done, 1 misfit
+ *   cover_d2   = the maximum over the set pixels of G of D2(P): the squared radius of the smallest Euclidean disc dilation of P that
+ *                covers G; 0 when G is empty, -1 when P is empty and G is not
+ *   sums[i]    = double [2]: the sum of sqrt(a), the sum of sqrt(b), added in a fixed order without float atomics: the same bits on
+ *                every run with the same capacities
+ *   defined    both masks empty: defined = 1 and every other entry 0.  Exactly one empty: defined = 0, entries 2..5 are -1, entry 6
+ *              and the sums are 0 (entries 0, 1 and 7 as above).  Otherwise defined = 1.
+ * From these on the host: hd = sqrt(max(record[2], record[3])); hd95 = sqrt(v[lo]) + (sqrt(v[hi]) - sqrt(v[lo])) * rem / 100 (numpy's
+ * linear percentile of sqrt(v)); assd = (sums[0] / |dP| + sums[1] / |dG|) / 2; cover_radius = ceil(sqrt(cover_d2)).
+ * Misfit: the rule of uwm_score_masks_ragged with sides limited to 32768 and no radius: a side outside 1 .. 32768, h_i * w_i >
+ * max_pixels, a region that leaves [0, mask_bytes), or, counting the images before it that pass those tests, a sum of rows above
+ * `rows` or of h_i * ceil(w_i / 64) above mask_bytes / 64 + rows.  A misfit's record is status 1 and zeros, its sums are 0 and it
+ * costs the others nothing.  Thirteen launches whatever N (N <= 65535) and the masks hold; max_pixels (1 .. 2^31 - 2) sizes the grids.
+ * Every per-pixel array of the workspace is indexed like the masks, so it grows with mask_bytes: 8 bytes per mask byte for the
+ * transform, 36 for the surface call.  Whatever the descriptors hold, no read leaves the masks / descs and no write leaves d2 +
+ * [0, mask_bytes), records, sums or the workspace; overlapping regions are the caller's error.  descs / records / sums / workspace
+ * 8-byte aligned, d2 4-byte.  Every argument is checked before any launch; no host synchronisation, allocation or copy. */
+#define UWM_EDT_NONE 2147483647
+size_t uwm_edt_workspace_bytes(int N, size_t mask_bytes, long long rows);
+int    uwm_edt_ragged(const uint8_t* masks, size_t mask_bytes, const uwm_image_desc* descs /* device */, int N, long long max_pixels,
+                      long long rows, int* d2 /* device [mask_bytes] */, void* workspace, size_t workspace_bytes, uwm_stream stream);
+size_t uwm_surface_distances_workspace_bytes(int N, size_t mask_bytes, long long rows);
+int    uwm_surface_distances_ragged(const uint8_t* pred, const uint8_t* truth, size_t mask_bytes,
+                                    const uwm_image_desc* descs /* device */, int N, long long max_pixels, long long rows,
+                                    long long* records /* device [N][10] */, double* sums /* device [N][2] */, void* workspace,
+                                    size_t workspace_bytes, uwm_stream stream);
 /* Mask enhancement on the device: the reference's enhance_mask (src/scripts/enhance_masks.py:16-67), which turns a tight
  * segmentation mask into the rounded, enlarged one people train on.  A ragged batch in ONE call, as above: image i is descs[i].h x
  * descs[i].w 8-bit grey pixels at in + descs[i].offset (any alignment), its result, in {0, 255}, goes to out + descs[i].offset; out

@@ -30,5 +30,6 @@ from .textenh import enhance_text_features, text_enhance_ragged  # noqa: F401,E4
 from .train import FusedAdam, FusedAdamW  # noqa: F401,E402
 from .tiling import plan_tiles, plan_batch  # noqa: F401,E402
 from .scoring import score_masks_ragged, boundary_radius, metrics_from_counts, summarize  # noqa: F401,E402
+from .scoring import distance_transform_ragged, surface_distances_ragged, surface_from_record, summarize_surface  # noqa: F401,E402
 from .evaluate import Evaluator  # noqa: F401,E402
 from .tta import view_mask, view_codes, apply_view, invert_view, plan_slots, merge_views  # noqa: F401,E402

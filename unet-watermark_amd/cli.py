@@ -773,7 +773,7 @@ def evaluate_command(args):
     if args.config:
         update_config(cfg, args.config)
     ev = Evaluator(input_dir, masks_dir, args.model, None, args.mask_type, args.text_enhance, args.tile, args.tile_overlap, args.boundary_ratio,
-                   args.boundary_pixels, args.batch_size, args.limit, args.seed, config=cfg, tta=args.tta)
+                   args.boundary_pixels, args.batch_size, args.limit, args.seed, config=cfg, tta=args.tta, surface=args.surface_distance)
     ev.settings["config"] = args.config
     res = ev.run(per_image=args.per_image)
     print(format_summary(res))
@@ -945,6 +945,10 @@ def build_parser():
     vp.add_argument("--boundary-ratio", type=float, default=None,
                     help="Boundary IoU's distance as a share of the image diagonal, at least one pixel (default 0.02, the paper's)")
     vp.add_argument("--boundary-pixels", type=int, default=None, help="the same distance in pixels for every image, 0..32767 (0: no Boundary IoU); not with --boundary-ratio")
+    vp.add_argument("--surface-distance", action="store_true",
+                    help="also measure, in pixels, the Hausdorff distance, its 95th percentile (HD95), the average symmetric surface "
+                         "distance and the covering radius (how far the predicted mask must be dilated by a Euclidean disc to cover "
+                         "the truth) from exact distance transforms on the device; adds 'surface' to the output")
     vp.add_argument("--batch-size", type=int, default=16, help="pairs per device call")
     vp.add_argument("--limit", type=int, default=None, help="score a seeded random sample of this many pairs")
     vp.add_argument("--seed", type=int, default=0, help="seed of the --limit sample")

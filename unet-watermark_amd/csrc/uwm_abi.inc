@@ -969,6 +969,46 @@ int uwm_score_masks_ragged(const uint8_t* pred, const uint8_t* truth, size_t mas
   LCHK(launch_score_masks_ragged(pred, truth, mask_bytes, (const ImageDesc*)descs, radius, N, max_pixels, rows, counts, ws, (hipStream_t)stream));
   return 0;
 }
+// ---- distance transforms and surface distances (mask_dist.hip): every argument is checked here, before any launch
+static int dist_args_check(const char* fn, int N, size_t mask_bytes, long long max_pixels, long long rows) {
+  if (mask_ragged_caps_check(fn, N, mask_bytes, rows)) return 1;
+  if (max_pixels < 1) return fail("%s: max_pixels must be >= 1 (got %lld)", fn, max_pixels);
+  if (max_pixels >= 2147483647ll) return fail("%s: max_pixels too large: it must be below 2^31 - 1 (got %lld)", fn, max_pixels);
+  return 0;
+}
+size_t uwm_edt_workspace_bytes(int N, size_t mask_bytes, long long rows) {
+  if (mask_ragged_caps_check("uwm_edt_workspace_bytes", N, mask_bytes, rows)) return 0;
+  return edt_workspace_bytes(N, mask_bytes, rows);
+}
+int uwm_edt_ragged(const uint8_t* masks, size_t mask_bytes, const uwm_image_desc* descs, int N, long long max_pixels, long long rows, int* d2,
+                   void* ws, size_t ws_bytes, uwm_stream stream) {
+  const char* fn = "uwm_edt_ragged";
+  if (!masks || !descs || !d2 || !ws) return fail("%s: null argument", fn);
+  if (dist_args_check(fn, N, mask_bytes, max_pixels, rows)) return 1;
+  if (((uintptr_t)descs | (uintptr_t)ws) & 7) return fail("%s: descriptors and the workspace must be 8-byte aligned", fn);
+  if ((uintptr_t)d2 & 3) return fail("%s: d2 must be 4-byte aligned", fn);
+  const size_t need = edt_workspace_bytes(N, mask_bytes, rows);
+  if (ws_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", fn, ws_bytes, need);
+  LCHK(launch_edt_ragged(masks, mask_bytes, (const ImageDesc*)descs, N, max_pixels, rows, d2, ws, (hipStream_t)stream));
+  return 0;
+}
+size_t uwm_surface_distances_workspace_bytes(int N, size_t mask_bytes, long long rows) {
+  if (mask_ragged_caps_check("uwm_surface_distances_workspace_bytes", N, mask_bytes, rows)) return 0;
+  return surface_distances_workspace_bytes(N, mask_bytes, rows);
+}
+int uwm_surface_distances_ragged(const uint8_t* pred, const uint8_t* truth, size_t mask_bytes, const uwm_image_desc* descs, int N,
+                                 long long max_pixels, long long rows, long long* records, double* sums, void* ws, size_t ws_bytes,
+                                 uwm_stream stream) {
+  const char* fn = "uwm_surface_distances_ragged";
+  if (!pred || !truth || !descs || !records || !sums || !ws) return fail("%s: null argument", fn);
+  if (dist_args_check(fn, N, mask_bytes, max_pixels, rows)) return 1;
+  if (((uintptr_t)descs | (uintptr_t)records | (uintptr_t)sums | (uintptr_t)ws) & 7)
+    return fail("%s: descriptors, records, sums and the workspace must be 8-byte aligned", fn);
+  const size_t need = surface_distances_workspace_bytes(N, mask_bytes, rows);
+  if (ws_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", fn, ws_bytes, need);
+  LCHK(launch_surface_distances_ragged(pred, truth, mask_bytes, (const ImageDesc*)descs, N, max_pixels, rows, records, sums, ws, (hipStream_t)stream));
+  return 0;
+}
 // ---- mask enhancement (mask_enhance.hip): every argument is checked here, before any launch
 static int enhance_caps_check(const char* fn, int N, size_t mask_bytes) {
   if (N < 1 || mask_bytes < 1) return fail("%s: N and mask_bytes must be >= 1 (got %d, %zu)", fn, N, mask_bytes);

@@ -715,6 +715,14 @@ hipError_t launch_optimize_masks_ragged(const uint8_t* in, uint8_t* out, size_t 
 size_t score_masks_workspace_bytes(int N, size_t mask_bytes, long long rows);
 hipError_t launch_score_masks_ragged(const uint8_t* pred, const uint8_t* truth, size_t mask_bytes, const ImageDesc* descs, const int* radius,
                                      int N, long long max_pixels, long long rows, long long* counts, void* ws, hipStream_t st);
+// exact squared Euclidean distance transforms of a ragged batch and the surface distances of mask pairs (mask_dist.hip; the rule:
+// include/uwm.h).  descs: DEVICE memory; d2: [mask_bytes] int32; records: [N][10]; sums: [N][2]
+size_t edt_workspace_bytes(int N, size_t mask_bytes, long long rows);
+hipError_t launch_edt_ragged(const uint8_t* masks, size_t mask_bytes, const ImageDesc* descs, int N, long long max_pixels, long long rows,
+                             int* d2, void* ws, hipStream_t st);
+size_t surface_distances_workspace_bytes(int N, size_t mask_bytes, long long rows);
+hipError_t launch_surface_distances_ragged(const uint8_t* pred, const uint8_t* truth, size_t mask_bytes, const ImageDesc* descs, int N,
+                                           long long max_pixels, long long rows, long long* records, double* sums, void* ws, hipStream_t st);
 
 // mask enhancement (mask_enhance.hip): the reference's enhance_mask on a ragged batch, grey morphology + float blur + binary
 // smoothing (the rule: include/uwm.h).  ws: enhance_workspace_bytes(N, mask_bytes) bytes; stats (may be null): [N][4]

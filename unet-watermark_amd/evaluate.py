@@ -14,7 +14,8 @@ from typing import Optional
 import numpy as np
 
 from .filter import IMAGE_EXTENSIONS, load_rgb
-from .scoring import COUNT_FIELDS, MAX_RADIUS, boundary_radius, metrics_from_counts, summarize
+from .scoring import (COUNT_FIELDS, MAX_RADIUS, SURFACE_FIELDS, boundary_radius, metrics_from_counts, summarize, summarize_surface,
+                      surface_from_record)
 
 
 def list_pairs(input_dir, masks_dir):
@@ -73,12 +74,15 @@ class Evaluator:
     def __init__(self, input_dir, masks_dir, model_path: Optional[str] = None, config_path: Optional[str] = None, mask_type: Optional[str] = None,
                  text_enhance: bool = False, tile: bool = False, tile_overlap: int = 64, boundary_ratio: Optional[float] = None,
                  boundary_pixels: Optional[int] = None, batch_size: int = 16, limit: Optional[int] = None, seed: int = 0, config=None,
-                 model=None, scorer=None, log=print, tta: Optional[str] = None):
+                 model=None, scorer=None, log=print, tta: Optional[str] = None, surface: bool = False, surface_scorer=None):
         """input_dir / masks_dir: the images and their ground-truth masks, paired by stem.  model_path / config_path (or config /
         model: a ready config node / model) make the WatermarkPredictor that scores a batch; scorer(images, truths, radii) -> (n, 8)
         counts replaces it (tests).  mask_type / text_enhance / tile / tile_overlap: how the masks are predicted, as `predict
         --resize device` takes them.  boundary_ratio (default 0.02 of the diagonal) or boundary_pixels: Boundary IoU's distance.
-        tta: the test-time-augmentation view set ('none' | 'hflip' | 'flips' | 'd4'), as `predict --tta`; recorded in the settings."""
+        tta: the test-time-augmentation view set ('none' | 'hflip' | 'flips' | 'd4'), as `predict --tta`; recorded in the settings.
+        surface: also measure the surface distances of every pair (Hausdorff, HD95, ASSD, covering radius): the result
+        gains 'surface' and the settings 'surface_distance'.  surface_scorer(images, truths) -> ((n, 10) records, (n, 2) sums) is the
+        test hook of that part, beside `scorer`."""
         if boundary_ratio is None and boundary_pixels is None:
             boundary_ratio = 0.02
         check_settings(mask_type, text_enhance, tile, tile_overlap, boundary_ratio, boundary_pixels, batch_size, limit, tta)
@@ -90,6 +94,10 @@ class Evaluator:
                              limit=None if limit is None else int(limit), seed=int(seed), tta="none" if tta is None else tta)
         self.log = log or (lambda *a: None)
         self._scorer = scorer
+        self._surface_scorer = surface_scorer
+        self.surface = bool(surface)
+        if self.surface:
+            self.settings["surface_distance"] = True
         if scorer is None:
             import torch
             from .predict import WatermarkPredictor
@@ -104,20 +112,32 @@ class Evaluator:
         return s["boundary_pixels"] if s["boundary_pixels"] is not None else min(boundary_radius(h, w, s["boundary_ratio"]), MAX_RADIUS)
 
     def _score(self, images, truths, radii):
+        """-> the (n, 8) counts and, with surface, the (n, 10) records and (n, 2) sums (else None, None)"""
+        n = len(images)
         if self._scorer is not None:
-            return np.asarray(self._scorer(images, truths, radii), dtype=np.int64).reshape(len(images), 8)
+            counts = np.asarray(self._scorer(images, truths, radii), dtype=np.int64).reshape(n, 8)
+            if not self.surface:
+                return counts, None, None
+            if self._surface_scorer is None:
+                raise RuntimeError("evaluate: a scorer hook with surface=True needs a surface_scorer hook")
+            records, sums = self._surface_scorer(images, truths)
+            return counts, np.asarray(records, dtype=np.int64).reshape(n, 10), np.asarray(sums, dtype=np.float64).reshape(n, 2)
         s = self.settings
-        return self.predictor.score_images(images, truths, s["mask_type"], s["text_enhance"], s["tile"], s["tile_overlap"],
-                                           s["boundary_ratio"] if s["boundary_pixels"] is None else 0.02, s["boundary_pixels"], tta=s["tta"])
+        got = self.predictor.score_images(images, truths, s["mask_type"], s["text_enhance"], s["tile"], s["tile_overlap"],
+                                          s["boundary_ratio"] if s["boundary_pixels"] is None else 0.02, s["boundary_pixels"], tta=s["tta"],
+                                          **(dict(surface=True) if self.surface else {}))
+        return (got[0], got[1][0], got[1][1]) if self.surface else (got, None, None)
 
     def run(self, per_image: bool = False) -> dict:
-        """-> {'settings', 'images', 'errors', 'error_details' (per error {path, reason}), 'micro', 'imagewise'[, 'per_image']}: every pair of the
+        """-> {'settings', 'images', 'errors', 'error_details' (per error {path, reason}), 'micro', 'imagewise'[, 'surface'][, 'per_image']}
+        ('surface': scoring.summarize_surface over the counted pairs, with the surface option; each per-image record then gains
+        'surface': the ten record fields, the two sums and the values of scoring.surface_from_record): every pair of the
         folders is decoded on the host, batched, predicted and counted; an unreadable file, an image without a mask and a mask whose
         size differs from its image's count under 'errors' and stop nothing."""
         s = self.settings
         pairs, orphans = list_pairs(self.input_dir, self.masks_dir)
         errors = [dict(path=p, reason="no mask with this stem") for _, p in orphans]
-        rows, records = [], []
+        rows, records, srows, ssums = [], [], [], []
         todo = sample_pairs(pairs, s["limit"], s["seed"])
         for b in range(0, len(todo), s["batch_size"]):
             paths, images, truths = [], [], []
@@ -134,19 +154,29 @@ class Evaluator:
             if not images:
                 continue
             radii = [self.radius(*im.shape[:2]) for im in images]
-            counts = self._score(images, truths, radii)
-            for p, im, d, row in zip(paths, images, radii, counts):
+            counts, srec, ssum = self._score(images, truths, radii)
+            for k, (p, im, d, row) in enumerate(zip(paths, images, radii, counts)):
                 if int(row[7]) != 0:
                     errors.append(dict(path=p, reason="not counted by the device (status %d)" % int(row[7])))
+                    continue
+                if self.surface and int(srec[k][9]) != 0:
+                    errors.append(dict(path=p, reason="surface distances not measured by the device (status %d)" % int(srec[k][9])))
                     continue
                 rows.append([int(v) for v in row])
                 if per_image:
                     records.append(dict(path=p, size=[int(im.shape[1]), int(im.shape[0])], radius=int(d),
                                         counts=dict(zip(COUNT_FIELDS, rows[-1])), metrics=metrics_from_counts(rows[-1])))
+                if self.surface:
+                    srows.append([int(v) for v in srec[k]]); ssums.append([float(v) for v in ssum[k]])
+                    if per_image:
+                        records[-1]["surface"] = dict(record=dict(zip(SURFACE_FIELDS, srows[-1])), sums=ssums[-1],
+                                                      **surface_from_record(srows[-1], ssums[-1]))
         for e in errors:
             self.log(f"error: {e['path']}: {e['reason']}")
         out = dict(settings=s, images=len(rows), errors=len(errors), error_details=errors)
         out.update(summarize(np.asarray(rows, dtype=np.int64).reshape(-1, 8)))
+        if self.surface:
+            out["surface"] = summarize_surface(np.asarray(srows, dtype=np.int64).reshape(-1, 10), np.asarray(ssums, dtype=np.float64).reshape(-1, 2))
         if per_image:
             out["per_image"] = records
         return out
@@ -156,6 +186,12 @@ def format_summary(result) -> str:
     lines = [f"images: {result['images']}  errors: {result['errors']}"]
     for name in ("micro", "imagewise"):
         lines.append(f"{name:>9}: " + "  ".join(f"{k} {v:.4f}" for k, v in result[name].items()))
+    if "surface" in result:
+        sf = result["surface"]
+        num = lambda v: "n/a" if v is None else f"{v:.3f}"      # noqa: E731
+        lines.append(f"{'surface':>9}: " + "  ".join(f"{k} {num(v)}" for k, v in sf["imagewise"].items())
+                     + f"  worst hd {num(sf['worst']['hd'])}  worst cover_radius {num(sf['worst']['cover_radius'])}"
+                     + f"  (pixels; {sf['images']} defined, {sf['undefined']} undefined)")
     return "\n".join(lines)
 
 

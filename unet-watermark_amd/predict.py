@@ -447,7 +447,7 @@ class WatermarkPredictor:
     @torch.no_grad()
     def score_images(self, images, truths, mask_type: Optional[str] = None, text_enhance: bool = False, tile: bool = False,
                      overlap: int = 64, boundary_ratio: float = 0.02, boundary_pixels: Optional[int] = None, return_masks: bool = False,
-                     tta=None):
+                     tta=None, surface: bool = False):
         """uint8 (h_i, w_i, C) images of ANY sizes and their ground-truth masks, uint8 (h_i, w_i) grey (binarised as > 127) -> the
         int64 (N, 8) HOST array of scoring.COUNT_FIELDS for the masks that predict_images(images, mask_type=..., text_enhance=...)
         or, with tile, predict_images_tiled(images, overlap, mask_type=...) returns: {tp, fp, fn, tn, |B(P) & B(G)|, |B(P)|, |B(G)|,
@@ -456,9 +456,11 @@ class WatermarkPredictor:
         a buffer of their own under the same mask descriptors and uwm_score_masks_ragged runs behind the prediction on the same
         stream, reading the predicted masks in place.  One device-to-host copy of 64 N bytes; no mask leaves the device unless
         return_masks, which adds the list of device masks.  scoring.metrics_from_counts / summarize turn the rows into metrics.
-        tta: as predict_images / predict_images_tiled take it."""
+        tta: as predict_images / predict_images_tiled take it.  surface: uwm_surface_distances_ragged runs behind the score call on
+        the same stream, reading the same two buffers; the return value gains (records, sums), the int64 (N, 10) HOST
+        array of scoring.SURFACE_FIELDS and the float64 (N, 2) HOST array of its sums, after the counts (and before the masks)"""
         views = view_mask(tta)
-        from .scoring import MAX_RADIUS, boundary_radius, score_masks_ragged
+        from .scoring import MAX_RADIUS, boundary_radius, score_masks_ragged, surface_distances_ragged
         if self.device.type != "cuda" or not torch.cuda.is_available():
             raise RuntimeError("score_images runs only on a HIP device (no CPU fallback)")
         if tile and text_enhance:
@@ -492,7 +494,13 @@ class WatermarkPredictor:
         self._gtbuf[:mask_bytes].copy_(torch.from_numpy(host))
         counts = score_masks_ragged(self._mbuf, self._gtbuf, self._mdesc, torch.tensor(radii, dtype=torch.int32, device=self.device), n=n,
                                     max_pixels=int(areas.max()), rows=int(descs["h"].astype("int64").sum()))
+        if surface:
+            records, sums = surface_distances_ragged(self._mbuf, self._gtbuf, self._mdesc, n=n, max_pixels=int(areas.max()),
+                                                     rows=int(descs["h"].astype("int64").sum()))
         out = counts.cpu().numpy()
+        if surface:
+            out = (out, (records.cpu().numpy(), sums.cpu().numpy()))
+            return out + (self._mask_views(descs, mdescs, areas, mask_bytes),) if return_masks else out
         return (out, self._mask_views(descs, mdescs, areas, mask_bytes)) if return_masks else out
 
     @torch.no_grad()

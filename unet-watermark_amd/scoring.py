@@ -1,7 +1,9 @@
 """Scoring predicted masks against ground truth (include/uwm.h): thin host wrappers over uwm_score_masks_ragged in
 csrc/mask_score.hip, which counts tp / fp / fn / tn and the three Boundary-IoU counts of a ragged batch of mask pairs on the
 device, and the formulas that turn those counts into the reference's five metrics (src/utils/metrics.py::get_metrics) plus
-Boundary IoU (Cheng et al., CVPR 2021).  No CPU fallback for the counting."""
+Boundary IoU (Cheng et al., CVPR 2021).  Below them the surface distances: wrappers over uwm_edt_ragged and
+uwm_surface_distances_ragged in csrc/mask_dist.hip, and the formulas that turn a record of squared distances into the Hausdorff
+distance, HD95, ASSD and the covering radius.  No CPU fallback for the counting or the distances."""
 from __future__ import annotations
 
 import ctypes as C
@@ -117,3 +119,142 @@ def summarize(counts) -> dict:
     each = [metrics_from_counts(r) for r in rows]
     imagewise = {k: (float(sum(m[k] for m in each) / len(each)) if each else 1.0) for k in METRIC_FIELDS}
     return {"micro": micro, "imagewise": imagewise}
+
+
+# ---------------------------------------------------------------- surface distances (csrc/mask_dist.hip)
+SURFACE_FIELDS = ("border_pred", "border_truth", "hd_d2_pred", "hd_d2_truth", "p95_d2_lo", "p95_d2_hi", "p95_rem", "cover_d2", "defined",
+                  "status")
+EDT_NONE = 2 ** 31 - 1                                    # UWM_EDT_NONE: D2 of an image without a set pixel
+MAX_SIDE = 32768
+_dws = {}                                                 # (device, call) -> workspace tensor of the two distance calls
+
+
+def _dist_workspace(device, call: str, n: int, mask_bytes: int, rows: int):
+    """the scratch of uwm_edt_ragged ('edt') or uwm_surface_distances_ragged ('surface'), kept and grown like score_workspace"""
+    import torch
+    need = getattr(L.lib(), f"uwm_{call}_workspace_bytes")(int(n), int(mask_bytes), int(rows))
+    if need == 0:
+        raise RuntimeError(L.lib().uwm_last_error().decode(errors="replace"))
+    key = (str(device), call)
+    ws = _dws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _dws[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws
+
+
+def _dist_args(name, buffers, descs, n, max_pixels, rows):
+    """the checks and descriptor handling the two distance wrappers share with score_masks_ragged -> (mask_bytes, descs tensor, n,
+    max_pixels, rows)"""
+    import torch
+    first = buffers[0]
+    if any(not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.device != first.device for t in buffers):
+        raise RuntimeError(f"uwm {name} runs only on a HIP device (no CPU fallback)")
+    for t in buffers:
+        if t.dtype != torch.uint8 or t.dim() != 1 or t.numel() == 0 or not t.is_contiguous():
+            raise RuntimeError(f"expected a non-empty contiguous 1-d uint8 buffer, got {t.dtype} {tuple(t.shape)}")
+    mask_bytes = min(t.numel() for t in buffers)
+    if isinstance(descs, torch.Tensor):
+        if n is None or max_pixels is None or rows is None:
+            raise ValueError(f"{name}: device descriptors need n, max_pixels and rows")
+        if descs.device != first.device or descs.dtype != torch.uint8 or descs.numel() < 16 * int(n):
+            raise RuntimeError(f"{name}: descs must be a uint8 tensor of 16 n bytes on the buffers' device")
+        d = descs
+    else:
+        from .data import descs_tensor
+        n = len(descs) if n is None else int(n)
+        if n < 1:
+            raise ValueError(f"{name}: empty batch")
+        if max_pixels is None:
+            max_pixels = max(1, int((descs["h"].astype("int64") * descs["w"]).max()))
+        if rows is None:
+            rows = max(1, int(descs["h"].astype("int64").clip(min=0).sum()))
+        d = descs_tensor(descs).to(first.device)
+    return mask_bytes, d, int(n), int(max_pixels), int(rows)
+
+
+def distance_transform_ragged(masks, descs, *, n: Optional[int] = None, max_pixels: Optional[int] = None, rows: Optional[int] = None,
+                              out=None):
+    """The exact squared Euclidean distance transform of a ragged batch of masks through ONE library call (uwm_edt_ragged).  masks: a
+    uint8 1-d device tensor; image i is descs[i]'s (h, w), one byte per pixel, at [descs[i].offset:], binarised as > 127.  descs: as
+    score_masks_ragged takes them (host records, or a device tensor with n, max_pixels and rows).  -> an int32 device tensor of
+    masks.numel() entries: D2 of image i's pixel k at [descs[i].offset + k], 0 on set pixels, EDT_NONE throughout an image without
+    one; entries no image covers, and those of a misfit (a side above 32768, a pair beyond a capacity), are not written (`out`: a
+    tensor to write into; a fresh one is zero-filled)."""
+    import torch
+    mask_bytes, d, n, max_pixels, rows = _dist_args("distance_transform_ragged", (masks,), descs, n, max_pixels, rows)
+    if out is None:
+        out = torch.zeros(mask_bytes, dtype=torch.int32, device=masks.device)
+    elif out.dtype != torch.int32 or out.device != masks.device or out.numel() < mask_bytes or not out.is_contiguous():
+        raise RuntimeError("distance_transform_ragged: out must be a contiguous int32 tensor of masks.numel() entries on the masks' device")
+    with L.on_device(masks):
+        ws = _dist_workspace(masks.device, "edt", n, mask_bytes, rows)
+        L.check(L.lib().uwm_edt_ragged(C.c_void_p(masks.data_ptr()), mask_bytes, C.c_void_p(d.data_ptr()), n, max_pixels, rows,
+                                       C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(L.stream_ptr(masks.device))))
+    return out
+
+
+def surface_distances_ragged(pred, truth, descs, *, n: Optional[int] = None, max_pixels: Optional[int] = None, rows: Optional[int] = None,
+                             out=None):
+    """The surface distances of a ragged batch of mask pairs through ONE library call (uwm_surface_distances_ragged): the buffers and
+    descriptors of score_masks_ragged (pred may be truth) -> (records, sums): the int64 (n, 10) device tensor SURFACE_FIELDS and the
+    float64 (n, 2) device tensor of the sums of sqrt over the two border-distance lists (`out`: a pair of tensors to write them
+    into).  surface_from_record / summarize_surface turn them into Hausdorff, HD95, ASSD and the covering radius."""
+    import torch
+    mask_bytes, d, n, max_pixels, rows = _dist_args("surface_distances_ragged", (pred, truth), descs, n, max_pixels, rows)
+    if out is None:
+        out = (torch.empty((n, 10), dtype=torch.int64, device=pred.device), torch.empty((n, 2), dtype=torch.float64, device=pred.device))
+    records, sums = out
+    for t, dt, k in ((records, torch.int64, 10), (sums, torch.float64, 2)):
+        if t.dtype != dt or t.device != pred.device or t.numel() < k * n or not t.is_contiguous():
+            raise RuntimeError("surface_distances_ragged: out must be contiguous int64 (n, 10) and float64 (n, 2) tensors on the buffers' device")
+    with L.on_device(pred):
+        ws = _dist_workspace(pred.device, "surface_distances", n, mask_bytes, rows)
+        L.check(L.lib().uwm_surface_distances_ragged(C.c_void_p(pred.data_ptr()), C.c_void_p(truth.data_ptr()), mask_bytes, C.c_void_p(d.data_ptr()),
+                                                     n, max_pixels, rows, C.c_void_p(records.data_ptr()), C.c_void_p(sums.data_ptr()),
+                                                     C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(L.stream_ptr(pred.device))))
+    return records, sums
+
+
+SURFACE_KEYS = ("hd", "hd95", "assd", "asd_pred_to_truth", "asd_truth_to_pred", "cover_radius")
+
+
+def surface_from_record(row, sums) -> dict:
+    """One SURFACE_FIELDS row and its two sums -> {hd, hd95, assd, asd_pred_to_truth, asd_truth_to_pred, cover_radius}, in pixels:
+        hd = sqrt(max(hd_d2_pred, hd_d2_truth))          hd95 = sqrt(lo) + (sqrt(hi) - sqrt(lo)) * rem / 100
+        asd_pred_to_truth = sums[0] / border_pred         asd_truth_to_pred = sums[1] / border_truth       assd = their mean
+        cover_radius = ceil(sqrt(cover_d2)): the radius of the smallest Euclidean disc dilation of the prediction that covers the truth
+    hd95 is numpy's linear 95th percentile of the two border-distance lists together (MedPy's hd95).  Both masks empty: every
+    value is 0.  Exactly one empty (defined == 0): the four distances are None; cover_radius is 0 when the truth is the empty one
+    and None when the prediction is.  A misfit row (status != 0): every value None."""
+    r = [int(v) for v in list(row)[:10]]
+    bp, bt, hp, ht, lo, hi, rem, cover, defined, status = r
+    out = dict.fromkeys(SURFACE_KEYS)
+    if status != 0:
+        return out
+    out["cover_radius"] = None if cover < 0 else int(math.isqrt(cover - 1) + 1 if cover > 0 else 0)
+    if not defined:
+        return out
+    if bp == 0 and bt == 0:
+        out.update(hd=0.0, hd95=0.0, assd=0.0, asd_pred_to_truth=0.0, asd_truth_to_pred=0.0)
+        return out
+    sa, sb = (float(v) for v in list(sums)[:2])
+    out["hd"] = math.sqrt(max(hp, ht))
+    out["hd95"] = math.sqrt(lo) + (math.sqrt(hi) - math.sqrt(lo)) * rem / 100
+    out["asd_pred_to_truth"], out["asd_truth_to_pred"] = sa / bp, sb / bt
+    out["assd"] = (out["asd_pred_to_truth"] + out["asd_truth_to_pred"]) / 2
+    return out
+
+
+def summarize_surface(records, sums) -> dict:
+    """(n, 10) SURFACE_FIELDS rows and their (n, 2) sums -> {"images": the defined pairs, "undefined": the pairs with exactly one empty
+    mask, "imagewise": the means of hd, hd95, assd and cover_radius over the defined pairs, "worst": the maxima of hd and
+    cover_radius over them}.  Misfit rows are left out; with no defined pair the means and maxima are None."""
+    rows = np.asarray(records, dtype=np.int64).reshape(-1, 10)
+    sm = np.asarray(sums, dtype=np.float64).reshape(-1, 2)
+    keep = rows[:, 9] == 0
+    rows, sm = rows[keep], sm[keep]
+    each = [surface_from_record(r, s) for r, s in zip(rows, sm) if int(r[8])]
+    names = ("hd", "hd95", "assd", "cover_radius")
+    return {"images": len(each), "undefined": int(len(rows) - len(each)),
+            "imagewise": {k: (float(sum(m[k] for m in each) / len(each)) if each else None) for k in names},
+            "worst": {k: (type(each[0][k])(max(m[k] for m in each)) if each else None) for k in ("hd", "cover_radius")}}
