@@ -1077,6 +1077,47 @@ int    uwm_text_enhance_ragged(const uint8_t* in, uint8_t* out, size_t bytes, co
                                int C /* 3 */, long long max_pixels, long long total_pixels,
                                uint8_t* edges /* may be NULL */, size_t edges_bytes, const uwm_image_desc* edge_descs /* device */,
                                void* workspace, size_t workspace_bytes, uwm_stream stream);
+/* Membrane (harmonic) fill on the device: what `repair` puts in the place of the predicted watermark.  A ragged batch in ONE call:
+ * image i is img_descs[i].h x img_descs[i].w x C interleaved bytes at images + img_descs[i].offset (any alignment), its mask is one
+ * byte per pixel at masks + mask_descs[i].offset (a byte != 0 is a hole pixel) and must have the image's size; the result goes to
+ * out + img_descs[i].offset; out may BE images (no other overlap).  Per image and channel, in float32, every operation rounded on
+ * its own and every division IEEE (tests/inpaint_ref.py is the numpy form the bytes are held to):
+ *   levels    level 0 is the image, level l + 1 has ((h_l + 1) >> 1) x ((w_l + 1) >> 1) cells, L = ceil(log2(max(h, w)));
+ *             children of (Y, X) in this order: (2Y, 2X), (2Y, 2X+1), (2Y+1, 2X), (2Y+1, 2X+1); neighbours of (y, x) in this order:
+ *             up, left, right, down; in both cases those inside the level only.  S(p) = the neighbours' sum in that order, cnt
+ *             their number.  up(c)(y, x) = ((9 c[py][px] + 3 c[py][qx]) + (3 c[qy][px] + c[qy][qx])) * 0.0625f, py = y >> 1,
+ *             qy = clamp(py + (y & 1 ? 1 : -1), 0, rows of c - 1), likewise in x
+ *   sweep     at level l with right-hand side b: the unknown cells with y + x even, then those with y + x odd, each u = (b + S) / cnt
+ *   1 pull    v_0 = the byte at known pixels (valid); a coarse cell with n > 0 valid children: v = their sum in children order / n
+ *   2 push    g_L = v_L; for l = L-1 .. 0: g_l = v_l where valid, else up(g_{l+1}), then one sweep with b = 0 over the non-valid
+ *             cells; u = g_0
+ *   3 cycles  `cycles` times V(0) on cnt * u - S = 0 over the hole pixels H_0.  H_{l+1} = the cells all of whose children are in
+ *             H_l; on levels >= 1 the values outside H_l are zero.  V(l): two sweeps; r = b - (cnt * u - S) on H_l; if l < L:
+ *             b_{l+1}(P) = the children's r in children order on H_{l+1}, e_{l+1} = 0, V(l+1), u += up(e_{l+1}) on H_l; two sweeps
+ *   4 store   hole pixels rint(min(max(u, 0), 255)), half to even; known pixels byte for byte
+ * stats (device, may be NULL): long long [N][4] = {hole pixels, status, levels that held unknowns, 0}; status 0 filled | 1 no hole
+ * pixel | 2 no known pixel (both: the output is the input, entry 2 is 0) | 3 misfit, nothing written, entries 0 and 2 zero.  The
+ * descriptors are read on the device; the host arguments are capacities, so one captured call serves every batch of N images that
+ * fits them: max_pixels (1 .. 2^30) bounds h_i * w_i, max_side (1 .. 32768) bounds every side and sets the number of levels, rows
+ * (1 .. 2^40) bounds the sum of h_i; grids are sized from N, max_pixels and max_side.  Misfit: a side outside 1 .. max_side, h_i * w_i
+ * > max_pixels, a region that leaves [0, image_bytes) or [0, mask_bytes), a mask of another size, or, counting the images before it
+ * that pass those tests, a sum of rows above `rows` or of cells above the workspace's planes (sized from image_bytes / C pixels).  A
+ * misfit costs the others nothing.  The launch count, uwm_inpaint_launch_count(cycles, max_side) = 5 + L + lc + cycles * (2 lc + 1)
+ * with L = ceil(log2(max_side)) and lc the first level whose sides fit 64 (from there on the levels run in LDS), depends on nothing
+ * else.  Work after the pull is done only in 32 x 32 tiles that hold a hole pixel (per level: an unknown).  Whatever the descriptors
+ * hold, no read leaves images / masks / the descriptors and no write leaves out + [0, image_bytes), stats or the workspace;
+ * overlapping regions are the caller's error.  workspace: uwm_inpaint_workspace_bytes(N, image_bytes, C, max_side) bytes (0 and a
+ * message on a bad argument): two float planes per channel at level 0 and three above (8 C + 4 C + 0.4 bytes per pixel of
+ * image_bytes / C, plus about 24 C max_side bytes per image).  Descriptors, stats and workspace 8-byte aligned.  Every argument is checked
+ * before any launch; no host synchronisation, allocation or copy.  Integer atomics only: runs are bit-identical. */
+enum { UWM_INPAINT_FILLED = 0, UWM_INPAINT_NO_HOLE = 1, UWM_INPAINT_NO_KNOWN = 2, UWM_INPAINT_MISFIT = 3 };
+size_t uwm_inpaint_workspace_bytes(int N, size_t image_bytes, int C, int max_side);
+int    uwm_inpaint_launch_count(int cycles /* 0..32 */, int max_side);        /* host only; 0 and a message on a bad argument */
+int    uwm_inpaint_ragged(const uint8_t* images, uint8_t* out /* may alias images */, size_t image_bytes,
+                          const uwm_image_desc* img_descs /* device */, const uint8_t* masks, size_t mask_bytes,
+                          const uwm_image_desc* mask_descs /* device */, int N, int C /* 1..4 */, int cycles /* 0..32 */,
+                          long long max_pixels, long long rows, int max_side, long long* stats /* device [N][4], may be NULL */,
+                          void* workspace, size_t workspace_bytes, uwm_stream stream);
 /* Watermark cut-outs from watermarked / clean pairs on the device: the reference's extract_watermarks.py (extract_watermark_from_pair,
  * _extract_single_watermark / _extract_combined_watermark, _create_transparent_watermark), whose transparent RGBA cut-outs are the logos
  * gen_data.py pastes.  Two calls with a small host plan between them (extract.plan_cutouts: centres, clustering, margins).

@@ -32,4 +32,5 @@ from .tiling import plan_tiles, plan_batch  # noqa: F401,E402
 from .scoring import score_masks_ragged, boundary_radius, metrics_from_counts, summarize  # noqa: F401,E402
 from .scoring import distance_transform_ragged, surface_distances_ragged, surface_from_record, summarize_surface  # noqa: F401,E402
 from .evaluate import Evaluator  # noqa: F401,E402
+from .inpaint import inpaint, inpaint_ragged, INPAINT_STATS_FIELDS  # noqa: F401,E402
 from .tta import view_mask, view_codes, apply_view, invert_view, plan_slots, merge_views  # noqa: F401,E402

@@ -18,7 +18,7 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 _PKG_DIR = Path(__file__).resolve().parent
 _CSRC = _PKG_DIR / "csrc"
 LIB_PATH = _PKG_DIR / "libuwm.so"
-SOURCES = ["uwm_route.hip", "conv_igemm.hip", "conv_patch.hip", "conv_patch16.hip", "conv_wino.hip", "conv_wino8.hip", "conv_wino_x3.hip", "conv_f16x3.hip", "conv_f16x3v2.hip", "conv_stem_f16x3.hip", "conv_up2.hip", "conv_up2_f16.hip", "conv_c16_f16.hip", "conv_gemm.hip", "conv_head.hip", "mbconv.hip", "wgrad_igemm.hip", "wgrad_patch.hip", "wgrad_wino.hip", "wgrad_f16x3.hip", "wgrad_c16.hip", "wgrad_gemm.hip", "wgrad_stem.hip", "elementwise.hip", "loss.hip", "loss_ext.hip", "mask_post.hip", "mask_score.hip", "mask_dist.hip", "mask_enhance.hip", "resize_u8.hip", "tile_u8.hip", "tta.hip", "pair_mask_u8.hip", "synth_u8.hip", "synth_text_u8.hip", "extract_u8.hip", "text_enhance.hip", "filter_u8.hip", "augment_u8.hip", "augment_ext_u8.hip", "jpeg_u8.hip", "jpeg_ragged_u8.hip", "uwm_model.hip"]
+SOURCES = ["uwm_route.hip", "conv_igemm.hip", "conv_patch.hip", "conv_patch16.hip", "conv_wino.hip", "conv_wino8.hip", "conv_wino_x3.hip", "conv_f16x3.hip", "conv_f16x3v2.hip", "conv_stem_f16x3.hip", "conv_up2.hip", "conv_up2_f16.hip", "conv_c16_f16.hip", "conv_gemm.hip", "conv_head.hip", "mbconv.hip", "wgrad_igemm.hip", "wgrad_patch.hip", "wgrad_wino.hip", "wgrad_f16x3.hip", "wgrad_c16.hip", "wgrad_gemm.hip", "wgrad_stem.hip", "elementwise.hip", "loss.hip", "loss_ext.hip", "mask_post.hip", "mask_score.hip", "mask_dist.hip", "mask_enhance.hip", "resize_u8.hip", "tile_u8.hip", "tta.hip", "pair_mask_u8.hip", "synth_u8.hip", "synth_text_u8.hip", "extract_u8.hip", "text_enhance.hip", "inpaint.hip", "filter_u8.hip", "augment_u8.hip", "augment_ext_u8.hip", "jpeg_u8.hip", "jpeg_ragged_u8.hip", "uwm_model.hip"]
 HIP_ARCH = "gfx950"
 # per-file compiler flags.  The fp16x3 kernels interleave their staging VALU work with MFMAs; hipcc turns the f4 arithmetic of that
 # work into packed v_pk_{fma,mul,add}_f32, which cost more than two plain VALU instructions beside MFMAs (MI355X_MICROARCH.md,
@@ -32,6 +32,7 @@ EXTRA_FLAGS["synth_u8.hip"] = ["-ffp-contract=off"]
 EXTRA_FLAGS["synth_text_u8.hip"] = ["-ffp-contract=off"]
 EXTRA_FLAGS["extract_u8.hip"] = ["-ffp-contract=off"]      # Pillow's SMOOTH filter and Image.blend, operation by operation
 EXTRA_FLAGS["text_enhance.hip"] = ["-ffp-contract=off"]    # CLAHE's blend, operation by operation (as augment_ext_u8.hip's pragma)
+EXTRA_FLAGS["inpaint.hip"] = ["-ffp-contract=off"]         # the membrane fill's sweeps, residuals and prolongation, operation by operation
 
 
 class uwm_unet_desc(C.Structure):
@@ -195,6 +196,9 @@ SIGNATURES = {
     "uwm_enhance_gauss_taps": (I, [I, C.POINTER(C.c_float)]),
     "uwm_text_enhance_workspace_bytes": (Z, [L, I]),
     "uwm_text_enhance_ragged": (I, [P, P, Z, P, I, I, L, L, P, Z, P, P, Z, P]),
+    "uwm_inpaint_workspace_bytes": (Z, [I, Z, I, I]),
+    "uwm_inpaint_launch_count": (I, [I, I]),
+    "uwm_inpaint_ragged": (I, [P, P, Z, P, P, Z, P, I, I, I, L, L, I, P, P, Z, P]),
     "uwm_extract_workspace_bytes": (Z, [I, L, I]),
     "uwm_extract_regions_ragged": (I, [P, Z, P, P, Z, P, I, I, I, I, L, L, P, Z, P, P, P, P, Z, P]),
     "uwm_extract_cutouts_ragged": (I, [P, Z, P, P, Z, P, I, P, I, L, P, Z, P, P, Z, P]),

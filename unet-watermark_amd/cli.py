@@ -1,8 +1,9 @@
-"""`python main.py train|predict|masks|filter|select|synth|extract ...` — counterpart of the reference's CLI for the model path
+"""`python main.py train|predict|repair|masks|filter|select|synth|extract ...` — counterpart of the reference's CLI for the model path
 (/root/reference/src/cli.py:368-395 flag names; train loop order /root/reference/src/train.py:207-499:
 epochs of train_epoch + validate (val batch = 2x train batch, :254), Adam | SGD (:265-279), ReduceLROnPlateau on the
 val loss | CosineAnnealingLR (:280-296,408-412), best / periodic checkpoints (:428-460), early stopping (:37-66,362-368)).
-`repair` / `auto` (IOPaint, OCR, video) are out of scope (SURVEY.md §2 rows 6,9,10); the data synthesis runs on the device (`train
+`repair` predicts the masks and fills them with the weight-free membrane fill of inpaint.py; the reference's IOPaint /
+LaMa, OCR, diffusion and video steps and its `auto` mode stay out of scope (SURVEY.md §2 rows 6,9,10: their weights do not ship); the data synthesis runs on the device (`train
 --synthesize`, `synth`): logo watermarks and, with --text-watermark-ratio / --mixed-watermark-ratio, text and mixed
 ones (§8o; the OCR mask is not served, masks come from pairs or from the pasted alpha planes).
 Multi-GPU: launch with torch.distributed.run; every rank trains its shard, gradients are all-reduced."""
@@ -783,6 +784,37 @@ def evaluate_command(args):
     return res
 
 
+def repair_command(args):
+    """Predict the watermark mask of every image of a folder and fill it on the device (or fill given masks): repair.py, DESIGN.md 8v.
+    Every refusal comes before anything is created."""
+    from .repair import check_settings, format_counts, repair_folder
+    try:
+        check_settings(args.model, args.masks, args.mask_type, args.text_enhance, args.tile, args.tile_overlap, args.tta, args.cycles,
+                       args.batch_size, args.limit)
+    except ValueError as e:
+        raise SystemExit(f"repair: {e}")
+    for what, d in (("the image directory", args.input), ("the mask directory", args.masks)):
+        if d is not None and not os.path.isdir(d):
+            raise SystemExit(f"repair: {what} not found: {d}")
+    if args.model is not None and not os.path.exists(args.model):
+        raise SystemExit(f"repair: model file not found: {args.model}")
+    if args.config and not os.path.exists(args.config):
+        raise SystemExit(f"repair: config file not found: {args.config}")
+    if not torch.cuda.is_available():
+        raise SystemExit("repair needs a HIP device (this path has no CPU fallback)")
+    pred = None
+    if args.model is not None:
+        cfg = get_cfg_defaults()
+        if args.config:
+            update_config(cfg, args.config)
+        cfg.PREDICT.BATCH_SIZE = int(args.batch_size)
+        pred = WatermarkPredictor(args.model, None, cfg, device="cuda")
+    res = repair_folder(args.input, args.output, pred, args.masks, args.mask_type, args.text_enhance, args.tile, args.tile_overlap, args.tta,
+                        args.cycles, args.save_masks, args.limit, args.seed, args.batch_size)
+    print(format_counts(res))
+    return res
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description="MI355X-native U-Net watermark segmentation (train | masks | enhance-masks | extract | filter | select | evaluate | predict)")
     sub = ap.add_subparsers(dest="command")
@@ -954,6 +986,28 @@ def build_parser():
     vp.add_argument("--seed", type=int, default=0, help="seed of the --limit sample")
     vp.add_argument("--output", type=str, default=None, help="write settings, images, errors, micro and imagewise as JSON to this file")
     vp.add_argument("--per-image", action="store_true", help="add per_image to the JSON: path, size, radius, the eight counts, the six metrics")
+    rp = sub.add_parser("repair", help="remove the watermarks of a folder: predict every mask and fill it on the device (the reference's repair)",
+                        description="Predict the watermark mask of every image of --input as predict's device path does and fill it with "
+                                    "the membrane (harmonic) interpolant on the device, or fill the masks of --masks (paired with the "
+                                    "images by file stem; a byte != 0 is filled).  A smooth fill: it removes a logo from sky, wall, paper or "
+                                    "skin and it smears texture; the reference's IOPaint / LaMa, OCR, diffusion and video steps are not "
+                                    "served.  Results are written as <stem>.png.  An unreadable file, an image without a mask and a mask "
+                                    "of another size count under 'errors' and stop nothing.")
+    rp.add_argument("--input", type=str, required=True); rp.add_argument("--output", type=str, required=True)
+    rp.add_argument("--model", type=str, default=None, help="the checkpoint that predicts the masks; or --masks")
+    rp.add_argument("--masks", type=str, default=None, help="instead of --model: a folder of masks, paired with the images by file stem")
+    rp.add_argument("--config", type=str, default=None)
+    rp.add_argument("--mask-type", choices=["watermark", "text", "mixed"], default="watermark",
+                    help="post-process every predicted mask as the reference's _optimize_mask does for this type (default watermark)")
+    rp.add_argument("--text-enhance", action="store_true", help="the reference's _enhance_text_features in front of the network, as predict's")
+    rp.add_argument("--tile", action="store_true", help="predict at native resolution from overlapping IMG_SIZE tiles, as predict's; not with --text-enhance")
+    rp.add_argument("--tile-overlap", type=int, default=64, help="pixels neighbouring tiles share, 0 .. IMG_SIZE / 2 (with --tile)")
+    rp.add_argument("--tta", choices=["none", "hflip", "flips", "d4"], default="none", help="test-time augmentation as predict's --tta")
+    rp.add_argument("--cycles", type=int, default=None, help="V-cycles of the fill's multigrid solver, 0..32 (default 7: within half a grey level of the exact membrane)")
+    rp.add_argument("--save-masks", type=str, default=None, help="also write the masks that were filled as DIR/<stem>.png")
+    rp.add_argument("--limit", type=int, default=None, help="repair a seeded random sample of this many images")
+    rp.add_argument("--seed", type=int, default=0, help="seed of the --limit sample")
+    rp.add_argument("--batch-size", type=int, default=16, help="images per device call")
     pp = sub.add_parser("predict")
     pp.add_argument("--input", type=str, required=True); pp.add_argument("--output", type=str, required=True)
     pp.add_argument("--model", type=str, required=True); pp.add_argument("--config", type=str, default=None)
@@ -1004,4 +1058,6 @@ def main(argv=None):
         return extract_command(args)
     if args.command == "evaluate":
         return evaluate_command(args)
+    if args.command == "repair":
+        return repair_command(args)
     ap.print_help()

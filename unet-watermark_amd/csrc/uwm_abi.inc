@@ -1077,6 +1077,44 @@ int uwm_text_enhance_ragged(const uint8_t* in, uint8_t* out, size_t bytes, const
                                   (const ImageDesc*)edge_descs, ws, (hipStream_t)stream));
   return 0;
 }
+// ---- membrane fill (inpaint.hip): every argument is checked here, before any launch
+static int inpaint_caps_check(const char* fn, int N, size_t image_bytes, int C, int max_side) {
+  if (N < 1 || N > 65535) return fail("%s: N must be 1 .. 65535 (got %d)", fn, N);
+  if (C < 1 || C > 4) return fail("%s: C must be 1 .. 4 (got %d)", fn, C);
+  if (image_bytes < 1 || image_bytes > ((size_t)1 << 40)) return fail("%s: image_bytes must be 1 .. 2^40 (got %zu)", fn, image_bytes);
+  if (max_side < 1 || max_side > 32768) return fail("%s: max_side must be 1 .. 32768 (got %d)", fn, max_side);
+  return 0;
+}
+size_t uwm_inpaint_workspace_bytes(int N, size_t image_bytes, int C, int max_side) {
+  if (inpaint_caps_check("uwm_inpaint_workspace_bytes", N, image_bytes, C, max_side)) return 0;
+  return inpaint_workspace_bytes(N, image_bytes, C, max_side);
+}
+int uwm_inpaint_launch_count(int cycles, int max_side) {
+  if (cycles < 0 || cycles > 32 || max_side < 1 || max_side > 32768) { fail("uwm_inpaint_launch_count: cycles 0 .. 32, max_side 1 .. 32768"); return 0; }
+  return inpaint_launch_count(cycles, max_side);
+}
+int uwm_inpaint_ragged(const uint8_t* images, uint8_t* out, size_t image_bytes, const uwm_image_desc* img_descs, const uint8_t* masks,
+                       size_t mask_bytes, const uwm_image_desc* mask_descs, int N, int C, int cycles, long long max_pixels, long long rows,
+                       int max_side, long long* stats, void* ws, size_t ws_bytes, uwm_stream stream) {
+  const char* fn = "uwm_inpaint_ragged";
+  if (!images || !out || !img_descs || !masks || !mask_descs || !ws) return fail("%s: null argument", fn);
+  if (inpaint_caps_check(fn, N, image_bytes, C, max_side)) return 1;
+  if (mask_bytes < 1 || mask_bytes > ((size_t)1 << 40)) return fail("%s: mask_bytes must be 1 .. 2^40 (got %zu)", fn, mask_bytes);
+  if (cycles < 0 || cycles > 32) return fail("%s: cycles %d outside 0..32", fn, cycles);
+  if (max_pixels < 1 || max_pixels > (1ll << 30)) return fail("%s: max_pixels must be 1 .. 2^30 (got %lld)", fn, max_pixels);
+  if (rows < 1 || rows > (1ll << 40)) return fail("%s: rows must be 1 .. 2^40 (got %lld)", fn, rows);
+  if (out != images && (uintptr_t)images < (uintptr_t)out + image_bytes && (uintptr_t)out < (uintptr_t)images + image_bytes)
+    return fail("%s: out must be images or must not overlap it", fn);
+  if ((uintptr_t)masks < (uintptr_t)out + image_bytes && (uintptr_t)out < (uintptr_t)masks + mask_bytes)
+    return fail("%s: out must not overlap masks", fn);
+  if (((uintptr_t)img_descs | (uintptr_t)mask_descs | (uintptr_t)stats | (uintptr_t)ws) & 7)
+    return fail("%s: descriptors, stats and the workspace must be 8-byte aligned", fn);
+  const size_t need = inpaint_workspace_bytes(N, image_bytes, C, max_side);
+  if (ws_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", fn, ws_bytes, need);
+  LCHK(launch_inpaint_ragged(images, out, image_bytes, (const ImageDesc*)img_descs, masks, mask_bytes, (const ImageDesc*)mask_descs, N, C, cycles,
+                             max_pixels, rows, max_side, stats, ws, (hipStream_t)stream));
+  return 0;
+}
 int uwm_op_morph(const uint8_t* in, uint8_t* out, int N, int H, int W, int dilate, int shape, int kw, int kh, int iterations,
                  void* ws, size_t ws_bytes, uwm_stream stream) {
   if (!in || !out) return fail("uwm_op_morph: null argument");

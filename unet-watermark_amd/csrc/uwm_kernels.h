@@ -762,4 +762,13 @@ hipError_t launch_text_enhance_ragged(const uint8_t* in, uint8_t* out, size_t by
                                       long long total_pixels, uint8_t* edges, size_t edges_bytes, const ImageDesc* edge_descs, void* ws,
                                       hipStream_t st);
 
+// membrane fill of the hole pixels of a ragged batch (inpaint.hip): pull-push, then `cycles` multigrid V-cycles on the hole (the
+// rule: include/uwm.h).  ws: inpaint_workspace_bytes(N, image_bytes, C, max_side) bytes; stats (may be null): [N][4].
+// The callers (uwm_abi.inc) have checked every argument
+size_t inpaint_workspace_bytes(int N, size_t image_bytes, int C, int max_side);
+int inpaint_launch_count(int cycles, int max_side);
+hipError_t launch_inpaint_ragged(const uint8_t* images, uint8_t* out, size_t image_bytes, const ImageDesc* img_descs, const uint8_t* masks,
+                                 size_t mask_bytes, const ImageDesc* mask_descs, int N, int C, int cycles, long long max_pixels, long long rows,
+                                 int max_side, long long* stats, void* ws, hipStream_t st);
+
 }  // namespace uwm

@@ -5,7 +5,8 @@ per image; here a whole batch goes through ONE hipGraph replay of the eval forwa
 The reference's mask post-processing (_optimize_mask, src/predict.py:161-301) is opt-in through `mask_type` and runs on the
 device inside the same graph (postprocess.py); its image enhancement for text watermarks (_enhance_text_features,
 src/predict.py:370-404) is opt-in through `text_enhance` and runs in front of the forward inside the same graph (textenh.py); its
-automatic type detection, IOPaint and OCR stay out of scope."""
+`repair` is served by remove_watermarks with the membrane fill of inpaint.py behind the prediction; its automatic type
+detection, IOPaint / LaMa, OCR and diffusion models stay out of scope."""
 from __future__ import annotations
 
 from typing import Optional
@@ -502,6 +503,50 @@ class WatermarkPredictor:
             out = (out, (records.cpu().numpy(), sums.cpu().numpy()))
             return out + (self._mask_views(descs, mdescs, areas, mask_bytes),) if return_masks else out
         return (out, self._mask_views(descs, mdescs, areas, mask_bytes)) if return_masks else out
+
+    @torch.no_grad()
+    def remove_watermarks(self, images, mask_type: Optional[str] = "watermark", text_enhance: bool = False, tile: bool = False,
+                          overlap: int = 64, tta=None, cycles: Optional[int] = None, return_masks: bool = False,
+                          return_stats: bool = False):
+        """uint8 (h_i, w_i, C) images of ANY sizes -> the list of uint8 (h_i, w_i, C) device tensors with the predicted watermark
+        filled in: the reference's `repair` with the membrane fill of inpaint.py in the place of IOPaint's LaMa.  The masks are those
+        predict_images(images, mask_type=..., text_enhance=..., tta=...) or, with tile, predict_images_tiled(images, overlap,
+        mask_type=..., tta=...) returns, predicted through the same graphs; uwm_inpaint_ragged then runs behind the prediction on the
+        same stream, reading the staged image bytes (the originals, not the text-enhanced ones) and the masks where they are.  Nothing
+        crosses to the host between prediction and fill.  An image without a predicted pixel, or predicted all over, comes back as
+        it is.  It is a smooth fill: it smears texture.  cycles: V-cycles of the solver (default
+        inpaint.DEFAULT_CYCLES).  return_masks: also the list of device masks; return_stats: also the int64 (N, 4) HOST array of
+        inpaint.INPAINT_STATS_FIELDS (after the masks)"""
+        from .inpaint import DEFAULT_CYCLES, MAX_SIDE, check_cycles, inpaint_buffers
+        if self.device.type != "cuda" or not torch.cuda.is_available():
+            raise RuntimeError("remove_watermarks runs only on a HIP device (no CPU fallback)")
+        if tile and text_enhance:
+            raise ValueError("tile and text_enhance cannot be combined: the tiled path has no text enhancement")
+        cycles = check_cycles(DEFAULT_CYCLES if cycles is None else cycles)
+        views = view_mask(tta)
+        images = list(images)
+        if tile:
+            descs, mdescs, areas, mask_bytes = self._run_tiled(images, overlap, False, mask_type, False, True, None, views)
+        else:
+            if mask_type is not None:
+                mask_type_code(mask_type)
+            descs, mdescs, areas, mask_bytes, _ = self._run_images(images, False, mask_type, True, text_enhance, views)
+        n, channels = len(descs), int(images[0].shape[2])
+        hs, ws = descs["h"].astype("int64"), descs["w"].astype("int64")
+        side = int(max(hs.max(), ws.max()))
+        if side > MAX_SIDE or int(areas.max()) > 2 ** 30:
+            raise ValueError(f"remove_watermarks: an image with a side above {MAX_SIDE} or more than 2^30 pixels")
+        stats = torch.empty((n, 4), dtype=torch.int64, device=self.device) if return_stats else None
+        nbytes = int(descs["offset"][-1]) + channels * int(areas[-1])
+        out = inpaint_buffers(self._ibuf, self._idesc, self._mbuf, self._mdesc, n, channels, max_pixels=int(areas.max()), rows=int(hs.sum()),
+                              max_side=side, cycles=cycles, stats=stats)[:nbytes]
+        res = [out[int(o): int(o) + channels * int(a)].view(int(h), int(w), channels) for o, a, h, w in zip(descs["offset"], areas, hs, ws)]
+        ret = (res,)
+        if return_masks:
+            ret += (self._mask_views(descs, mdescs, areas, mask_bytes),)
+        if return_stats:
+            ret += (stats.cpu().numpy(),)
+        return ret[0] if len(ret) == 1 else ret
 
     @torch.no_grad()
     def mask_stats(self, images, mask_type: str = "watermark", return_masks: bool = False, use_graph: bool = True,
