@@ -129,7 +129,7 @@ def main():
     say(f"(b) whole call, text_enhance=True                        {fmt(r['enhanced'])}")
     say(f"    the flag adds {np.median(r['enhanced']) - np.median(r['plain']):.3f} ms to a call of {np.median(r['plain']):.3f} ms "
         f"(host packing, upload, graph replay, clone of the masks)")
-    g = windows({"plain": (pred._qgraph.replay, 5), "enhanced": (pred._tqgraph.replay, 5)}, a.windows, event_ms)
+    g = windows({"plain": (pred._graphs["images_post"].graph.replay, 5), "enhanced": (pred._graphs["text_images_post"].graph.replay, 5)}, a.windows, event_ms)
     say(f"(c) graph replay alone, text_enhance=False               {fmt(g['plain'])}")
     say(f"(c) graph replay alone, text_enhance=True                {fmt(g['enhanced'])}")
     say(f"    the enhancement is {np.median(g['enhanced']) - np.median(g['plain']):.3f} ms beside {np.median(g['plain']):.3f} ms of resize, forward, "

@@ -76,14 +76,14 @@ def main():
         f"{plans[0]['ny']} x {plans[0]['nx']} tiles per image, {real} tiles in {K} entries, {chunks} chunks")
     # the call: captured by the predictor; its replay is what is timed
     masks = pred.predict_images_tiled(imgs, a.overlap)
-    key = [k for k in pred._xgraphs if k[:3] == (a.images, chunks, N)]
-    assert len(key) == 1
-    graph = pred._xgraphs[key[0]][0]
+    entry = [e for e in pred._graphs.values() if e.group == "tiled" and e.key[:3] == (a.images, chunks, N)]
+    assert len(entry) == 1
+    graph = entry[0].graph
     store = pred.model._tile_store                      # the store of the call (a view of the graph's workspace)
     # its forwards alone: the plain batch forward at the same N
     x = torch.randn(N, 3, T, T, device=dev)
     pred.logits(x)
-    fgraph = pred._graph
+    fgraph = pred._graphs["logits"].graph
     # gather and blend alone, on the call's own buffers
     lib = L.lib()
     st = C.c_void_p(L.stream_ptr(dev))

@@ -51,17 +51,18 @@ def run_case(title, pred, imgs, tiled, overlap, windows):
     dev = pred.device
     T, N, n = int(pred.cfg.DATA.IMG_SIZE), int(pred.cfg.PREDICT.BATCH_SIZE), len(imgs)
     call = (lambda **kw: pred.predict_images_tiled(imgs, overlap, **kw)) if tiled else (lambda **kw: pred.predict_images(imgs, **kw))
-    table = lambda: pred._xgraphs if tiled else pred._agraphs      # (looked up anew: a grown buffer replaces the table)
+    group = "tiled" if tiled else "tta"
+    table = lambda: {e.key: e.graph for e in pred._graphs.values() if e.group == group}      # (looked up anew: a grown buffer drops entries)
     items, k_of = {}, {}
     call()
-    plain_graph = [g for key, g in pred._xgraphs.items() if "tta" not in key][-1][0] if tiled else pred._igraph
+    plain_graph = [g for key, g in table().items() if "tta" not in key][-1] if tiled else pred._graphs["images"].graph
     items["plain"] = plain_graph.replay
     for name in ("d4", "flips", "hflip"):
         before = set(table())
         call(tta=name)
         key = [key for key in table() if key not in before]
         assert len(key) == 1
-        items[name] = table()[key[0]][0].replay
+        items[name] = table()[key[0]].replay
         k_of[name] = len(tta.view_codes(name))
     if tiled:
         sizes = [tuple(im.shape[:2]) for im in imgs]

@@ -297,11 +297,11 @@ def test_one_captured_graph_serves_batches_of_other_sizes(cuda):
     eager = {k: pred.watermark_counts(x, return_masks=True, use_graph=False) for k, x in (("a", a), ("b", b))}
     assert 0 < eager["a"][0][:, 0].sum() < eager["a"][0][:, 1].sum()
     got = pred.watermark_counts(a, return_masks=True)
-    graph = pred._cgraph
+    graph = pred._graphs["counts"].graph
     assert graph is not None
     for k, x in (("a", a), ("b", b), ("a", a)):
         counts, masks = pred.watermark_counts(x, return_masks=True)
-        assert pred._cgraph is graph, k                      # replayed, not re-captured
+        assert pred._graphs["counts"].graph is graph, k                      # replayed, not re-captured
         assert counts.dtype == np.int64 and counts.shape == (3, 2) and counts.tolist() == eager[k][0].tolist(), k
         for m, e, im in zip(masks, eager[k][1], x):
             assert m.shape == im.shape[:2] and torch.equal(m, e), k

@@ -181,9 +181,9 @@ def test_cli_writes_optimised_masks(U, cuda, tmp_path):
 
 def test_graph_survives_a_larger_eager_call(U, cuda):
     """the post-processing workspace is one buffer per device that grows; a captured graph keeps the buffer it was captured with"""
-    from unet_watermark_amd import postprocess as PP
+    from unet_watermark_amd import _device as D, postprocess as PP
     pred = _predictor(U, cuda)
-    PP._ws.clear()                            # (earlier tests have grown the buffer: start from none)
+    D._WORKSPACE.pop(("mask", D.resolve(cuda)), None)      # (earlier tests have grown the buffer: start from none)
     g = torch.Generator().manual_seed(4)
     im = torch.randint(0, 256, (1, 64, 64, 3), dtype=torch.uint8, generator=g).to(cuda)
     first, s_first = pred.predict_mask_u8(im, mask_type="mixed", return_summary=True)

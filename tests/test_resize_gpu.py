@@ -225,14 +225,14 @@ def test_predict_images_equals_resize_then_predict_mask_u8_per_image(cuda, froze
             assert len(got) == len(imgs)
             for a, g, m in zip(imgs, got, want):
                 assert g.dtype == torch.uint8 and tuple(g.shape) == a.shape[:2] and torch.equal(g, m), a.shape
-        graphs.append(pred._igraph)
+        graphs.append(pred._graphs["images"].graph)
         want = expected(imgs, "text")
         for g, m in zip(pred.predict_images(imgs, mask_type="text"), want):
             assert torch.equal(g, m)
         assert pred.model.frozen == frozen
-    assert graphs[0] is not None and graphs[1] is graphs[0] and pred._igraph is graphs[0]
+    assert graphs[0] is not None and graphs[1] is graphs[0] and pred._graphs["images"].graph is graphs[0]
     # a batch that does not fit the staging buffers is still right (buffers grow, the graph is captured again)
     big = R.images(3, [(300, 400), (64, 64), (10, 10), (200, 50)], seed=4)
     for g, m in zip(pred.predict_images(big), expected(big, None)):
         assert torch.equal(g, m)
-    assert pred._igraph is not graphs[0]
+    assert pred._graphs["images"].graph is not graphs[0]

@@ -117,22 +117,22 @@ def test_one_graph_serves_batches_that_fit_and_a_larger_one_recaptures(cuda):
     assert max(h * w for h, w in SIZES_B) <= max(h * w for h, w in SIZES_A)
     pred.predict_images(a)
     pred.predict_images(a, mask_type="watermark")
-    graph, plain = pred._qgraph, pred._igraph
+    graph, plain = pred._graphs["images_post"].graph, pred._graphs["images"].graph
     assert graph is not None and plain is not None
     for imgs in (b, a, b):
         got = pred.predict_images(imgs, mask_type="watermark")
-        assert pred._qgraph is graph                                               # replayed, not re-captured
+        assert pred._graphs["images_post"].graph is graph                                               # replayed, not re-captured
         for g, w in zip(got, _parent_route(pred, imgs, "watermark")):
             assert torch.equal(g, w)
-    assert pred._igraph is plain                                                   # (the graph without post-processing is left alone)
+    assert pred._graphs["images"].graph is plain                                                   # (the graph without post-processing is left alone)
     got = pred.predict_images(big, mask_type="watermark")                          # 500 x 700 exceeds every capacity
-    assert pred._qgraph is not graph and pred._qgraph is not None
+    assert pred._graphs["images_post"].graph is not graph and pred._graphs["images_post"].graph is not None
     for g, w in zip(got, _parent_route(pred, big, "watermark")):
         assert torch.equal(g, w)
-    graph = pred._qgraph
+    graph = pred._graphs["images_post"].graph
     for g, w in zip(pred.predict_images(a, mask_type="watermark"), _parent_route(pred, a, "watermark")):      # fits the grown capacities
         assert torch.equal(g, w)
-    assert pred._qgraph is graph
+    assert pred._graphs["images_post"].graph is graph
 
 
 @pytest.mark.parametrize("mask_type", R.MASK_TYPES)

@@ -192,7 +192,7 @@ def test_predict_images_with_text_enhance_equals_predicting_the_enhanced_images(
         if mask_type is None:
             assert all(0.02 < float((m > 0).float().mean()) < 0.98 for m in want)
         assert any(not torch.equal(a, b) for a, b in zip(before, want))                               # the enhancement matters to the masks
-        default_graph = pred._qgraph if mask_type else pred._igraph
+        default_graph = pred._graphs["images_post"].graph if mask_type else pred._graphs["images"].graph
         assert default_graph is not None
         for use_graph in (True, False, True):
             got = pred.predict_images(imgs, mask_type=mask_type, text_enhance=True, use_graph=use_graph)
@@ -202,7 +202,43 @@ def test_predict_images_with_text_enhance_equals_predicting_the_enhanced_images(
         for use_graph in (True, False):
             again = pred.predict_images(imgs, mask_type=mask_type, use_graph=use_graph)
             assert all(torch.equal(a, b) for a, b in zip(again, before))
-        assert (pred._qgraph if mask_type else pred._igraph) is default_graph
-        assert (pred._tqgraph if mask_type else pred._tigraph) is not None
+        assert (pred._graphs["images_post"].graph if mask_type else pred._graphs["images"].graph) is default_graph
+        assert (pred._graphs["text_images_post"].graph if mask_type else pred._graphs["text_images"].graph) is not None
     stats = pred.mask_stats(imgs, "text", text_enhance=True)
     assert np.array_equal(stats, pred.mask_stats(ref_enhanced, "text"))
+
+
+def test_a_graph_captured_on_an_index_less_device_pins_the_workspaces_it_replays_on(cuda):
+    """WatermarkPredictor(device="cuda"): the captured calls took their workspaces under their buffers' device, cuda:0.  The entry's
+    keep must hold those very tensors, so that a larger eager call, which replaces them in the store, leaves the graph replaying on
+    memory it owns."""
+    import unet_watermark_amd as U
+    from unet_watermark_amd import _device as D
+    from unet_watermark_amd.constants import IMAGENET_MEAN as MEAN, IMAGENET_STD as STD
+    from unet_watermark_amd.postprocess import optimize_masks_ragged
+    pred = _predictor("cuda")
+    rng = np.random.default_rng(11)
+    imgs = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for h, w in ((40, 56), (72, 48))]
+    packed, descs, _ = U.pack_images(imgs)
+    _, lg = pred.model.predict_u8(U.device_resize(packed, descs, 64, 3), MEAN[:3], STD[:3], 0.0, return_logits=True)
+    pred.threshold = float(lg.median())
+    for name in ("mask_ragged", "text_enhance"):                   # (earlier tests have grown the buffers: start from none)
+        D._WORKSPACE.pop((name, cuda), None)
+    kw = dict(mask_type="watermark", text_enhance=True, return_stats=True)
+    eager, eager_stats = pred.predict_images(imgs, use_graph=False, **kw)
+    first, first_stats = pred.predict_images(imgs, **kw)          # the capture
+    pred.predict_images(imgs, **kw)                                # a replay
+    entry = pred._graphs["text_images_post"]
+    for name in ("mask_ragged", "text_enhance"):
+        assert any(t is D._WORKSPACE[(name, cuda)] for t in entry.keep), name
+    pinned = D._WORKSPACE[("mask_ragged", cuda)]
+    big = np.zeros(1, DESC)
+    big[0] = (0, 900, 1100)
+    optimize_masks_ragged(torch.zeros(900 * 1100, dtype=torch.uint8, device=cuda), big)
+    assert D._WORKSPACE[("mask_ragged", cuda)] is not pinned      # the store moved on to a larger buffer
+    again, again_stats = pred.predict_images(imgs, **kw)          # a replay, on the pinned one
+    assert pred._graphs["text_images_post"] is entry
+    assert first_stats[:, 6].tolist() == [40 * 56, 72 * 48] and not first_stats[:, 7].any()      # every image was served
+    assert np.array_equal(again_stats, first_stats) and np.array_equal(first_stats, eager_stats)
+    for a, f, e in zip(again, first, eager):
+        assert torch.equal(a, f) and torch.equal(f, e)

@@ -212,19 +212,24 @@ def test_blended_planes_and_masks_equal_the_restatement(cuda, apply_sigmoid):
         pred.threshold = old
 
 
+def _graphs_of(pred, group):
+    """key -> captured graph of the predictor's entries of one group ('tiled', 'tta')"""
+    return {e.key: e.graph for e in pred._graphs.values() if e.group == group}
+
+
 def test_a_captured_call_replays_on_another_batch_with_the_same_chunk_count(cuda):
     c = _case(cuda)
     pred = c["pred"]
     pred.threshold = float(np.median(np.concatenate([b.reshape(-1) for b in c["blended"]])))
     try:
         first = pred.predict_images_tiled(c["imgs"], OVERLAP)
-        graphs = dict(pred._xgraphs)
+        graphs = _graphs_of(pred, "tiled")
         key = [k for k in graphs if len(k) == 8 and k[:3] == (len(SIZES), c["K"] // N, N) and k[5] is False and k[7] is False and k[6] == pred.threshold]
         assert len(key) == 1
         other = _images([(w, h) for h, w in SIZES], 2)                       # other sizes, the same number of tiles and bytes
         eager = pred.predict_images_tiled(other, OVERLAP, use_graph=False)
         replay = pred.predict_images_tiled(other, OVERLAP)
-        assert pred._xgraphs[key[0]][0] is graphs[key[0]][0]                 # replayed, not captured again
+        assert _graphs_of(pred, "tiled")[key[0]] is graphs[key[0]]                # replayed, not captured again
         for a, b, (h, w) in zip(eager, replay, SIZES):
             assert tuple(b.shape) == (w, h) and torch.equal(a, b)
         assert any(0.05 < float((m > 0).float().mean()) < 0.95 for m in replay)
@@ -296,9 +301,9 @@ def test_predict_images_is_unchanged_by_a_tiled_call(cuda):
     c = _case(cuda)
     pred = c["pred"]
     before = [m.clone() for m in pred.predict_images(c["imgs"])]
-    graph = pred._igraph
+    graph = pred._graphs["images"].graph
     pred.predict_images_tiled(c["imgs"], OVERLAP)
     pred.predict_images_tiled(c["imgs"], OVERLAP, mask_type="text", use_graph=False)
     after = pred.predict_images(c["imgs"])
-    assert pred._igraph is graph                                             # the default path's graph stays as captured
+    assert pred._graphs["images"].graph is graph                                             # the default path's graph stays as captured
     assert all(torch.equal(a, b) for a, b in zip(before, after))

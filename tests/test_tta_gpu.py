@@ -291,6 +291,11 @@ def test_merge_alone_equals_the_host_restatement_whatever_the_chunking(cuda, mas
 
 
 # ------------------------------------------------------------------------------------------------ the model
+def _graphs_of(pred, group):
+    """key -> captured graph of the predictor's entries of one group ('tiled', 'tta')"""
+    return {e.key: e.graph for e in pred._graphs.values() if e.group == group}
+
+
 @pytest.mark.parametrize("name", ["hflip", "d4"])
 def test_predict_images_merges_the_plain_forwards_of_the_viewed_inputs(cuda, name):
     c = _case(cuda)
@@ -307,11 +312,11 @@ def test_predict_images_merges_the_plain_forwards_of_the_viewed_inputs(cuda, nam
             for m, w, s in zip(masks, want_masks, c["sizes"]):
                 assert m.dtype == torch.uint8 and tuple(m.shape) == s and torch.equal(m, w), (name, use_graph, s)
         # another batch of other sizes with the same counts replays the same graph
-        graphs = dict(pred._agraphs)
+        graphs = _graphs_of(pred, "tta")
         other = _images([(33, 90), (80, 80), (64, 17)], 22)
         ref_other, _ = _ref_merged(pred, _resize_norm(other, cuda), name)
         masks, merged = pred.predict_images(other, tta=name, return_logits=True)
-        assert set(pred._agraphs) == set(graphs) and all(pred._agraphs[k][0] is graphs[k][0] for k in graphs)
+        assert _graphs_of(pred, "tta") == graphs                # replayed: the same keys, the same graph objects
         assert torch.equal(_bits(merged), _bits(ref_other))
         for m, w in zip(masks, _ragged_masks(ref_other, [(33, 90), (80, 80), (64, 17)], c["thr"], cuda)):
             assert torch.equal(m, w)
@@ -463,7 +468,7 @@ def test_nothing_changes_without_the_flag(cuda):
             s = pred.score_images(c["imgs"], truths, **kw)
             return a, [m.clone() for m in b], [x.clone() for x in bl], s
         before = snapshot()
-        graph, xkeys = pred._igraph, set(pred._xgraphs)
+        graph, xkeys = pred._graphs["images"].graph, set(_graphs_of(pred, "tiled"))
         pred.predict_images(c["imgs"], tta="d4")
         pred.predict_images_tiled(c["imgs"], OVERLAP, tta="flips")
         pred.score_images(c["imgs"], truths, tta="hflip")
@@ -473,7 +478,7 @@ def test_nothing_changes_without_the_flag(cuda):
             assert all(torch.equal(x, y) for x, y in zip(before[1], after[1])), kw
             assert all(torch.equal(_bits(x), _bits(y)) for x, y in zip(before[2], after[2])), kw
             assert np.array_equal(before[3], after[3]), kw
-        assert pred._igraph is graph and xkeys <= set(pred._xgraphs)          # the default paths' graphs stay as captured
+        assert pred._graphs["images"].graph is graph and xkeys <= set(_graphs_of(pred, "tiled"))          # the default paths' graphs stay as captured
         # the plain call is what views = 0x01 computes through the new entry: the same masks
         eager = pred.predict_images(c["imgs"], use_graph=False)
         assert all(torch.equal(x, y) for x, y in zip(eager, before[0]))

@@ -20,7 +20,7 @@ import torch  # noqa: F401
 from torch.utils.data import Dataset  # noqa: F401
 
 from ..constants import IMAGENET_MEAN, IMAGENET_STD  # noqa: F401
-from ._common import _WORKSPACE, workspace  # noqa: F401
+from .._device import _WORKSPACE, workspace  # noqa: F401
 from .ragged import DESC_DTYPE, INTERP, descs_tensor, device_resize, mask_descs_for, pack_images  # noqa: F401
 from .augment import (AUG_DESC_DTYPE, AUG_EXT_DTYPE, AUG_HFLIP, AUG_RECIPES, AUG_RECIPES_EXT, AUG_VFLIP, BLUR_GAUSS, BLUR_MOTION,  # noqa: F401
                       BLUR_NONE, IDENTITY_MINV, JPEG_QUALITY_RANGE, NOISE_SIGMA_MAX, RECIPES, TONE_CLAHE, TONE_NONE, TONE_TABLE,
@@ -40,6 +40,6 @@ from .datasets import (LOGO_EXTENSIONS, LOGO_SUBDIRS, PAIR_IMAGE_EXTENSIONS, Dev
                        RawPairDataset, RawSynthDataset, SyntheticWatermarkDataset, list_collate, list_logos)
 from .pipeline import DeviceInputPipeline  # noqa: F401
 
-# the per-feature cache names of the single-file module: the three caches are the one dict of _common now, keyed by (name, device)
+# the per-feature cache names of the single-file module: the three caches are the one dict of _device, keyed by (name, device)
 _EXT_WORKSPACE = _JPEG_WORKSPACE = _SYNTH_WORKSPACE = _WORKSPACE
 _ext_workspace, _jpeg_workspace = _partial(workspace, "augment_ext"), _partial(workspace, "jpeg")

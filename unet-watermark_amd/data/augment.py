@@ -9,7 +9,7 @@ import torch
 
 from .. import _lib as L
 from ..constants import IMAGENET_MEAN, IMAGENET_STD
-from ._common import device_u8, norm_arrays, ptr, upload_records, workspace
+from .._device import device_u8, norm_arrays, ptr, upload_records, workspace
 
 AUG_HFLIP, AUG_VFLIP = 1, 2
 
@@ -362,7 +362,7 @@ def device_augment(images_u8: torch.Tensor, masks_u8, params, mean=IMAGENET_MEAN
                                            ptr(u8), st), ValueError)
         else:
             ed = upload_records(ex, x.device)
-            ws = workspace("augment_ext", x.device, int(L.lib().uwm_augment_ext_workspace_bytes(n, h, w, c)))
+            ws = workspace("augment_ext", x.device, L.lib().uwm_augment_ext_workspace_bytes(n, h, w, c), ValueError)
             L.check(L.lib().uwm_augment_ext_u8(ptr(x), ptr(m), ptr(dd), ptr(ed), n, h, w, c, mean_c, std_c, int(mask_threshold), ptr(ws),
                                                ws.numel(), ptr(out), ptr(mo), ptr(u8), st), ValueError)
     res = (out,) + ((mo,) if m is not None else ()) + ((u8,) if return_u8 else ())
@@ -399,7 +399,7 @@ def device_jpeg(images_u8: torch.Tensor, quality, mean=IMAGENET_MEAN, std=IMAGEN
     u8 = torch.empty((n, h, w, 3), dtype=torch.uint8, device=x.device) if return_u8 else None
     mean_c, std_c = norm_arrays(mean, std, 3)
     with L.on_device(x):
-        ws = workspace("jpeg", x.device, int(L.lib().uwm_jpeg_workspace_bytes(n, h, w)))
+        ws = workspace("jpeg", x.device, L.lib().uwm_jpeg_workspace_bytes(n, h, w), ValueError)
         L.check(L.lib().uwm_jpeg_u8(ptr(x), ptr(qd), n, h, w, mean_c, std_c, ptr(ws), ws.numel(), ptr(out), ptr(u8),
                                     C.c_void_p(L.stream_ptr(x.device))), ValueError)
     return (out, u8) if return_u8 else out

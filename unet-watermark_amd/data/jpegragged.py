@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from ._common import device_u8, ptr, upload_records, workspace
+from .._device import device_u8, ptr, upload_records, workspace
 from .ragged import DESC_DTYPE, descs_tensor
 
 SYNTH_JPEG_QUALITY = 95                   # gen_data.py:908 (and the temporary file of a mixed sample, gen_data.py:402-410)
@@ -50,10 +50,7 @@ def device_jpeg_ragged(packed: torch.Tensor, descs, quality, inplace=False) -> t
     dd = descs_tensor(d, src.device)
     qd = upload_records(q.astype(np.int32), src.device)
     with L.on_device(src):
-        need = int(L.lib().uwm_jpeg_ragged_workspace_bytes(n, src.numel()))
-        if need == 0:
-            L.check(1, ValueError)
-        ws = workspace("jpeg_ragged", src.device, need)
+        ws = workspace("jpeg_ragged", src.device, L.lib().uwm_jpeg_ragged_workspace_bytes(n, src.numel()), ValueError)
         L.check(L.lib().uwm_jpeg_ragged_u8(ptr(src), ptr(out), src.numel(), ptr(dd), ptr(qd), n, 3, int(pixels.max()), ptr(ws), ws.numel(),
                                            C.c_void_p(L.stream_ptr(src.device))), ValueError)
     return out

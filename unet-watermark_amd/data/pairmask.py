@@ -5,7 +5,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from ._common import device_u8, ptr
+from .._device import device_u8, ptr
 from .ragged import DESC_DTYPE, INTERP, descs_tensor, mask_descs_for, pack_images
 
 

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from ._common import device_u8, ptr
+from .._device import device_u8, ptr
 
 DESC_DTYPE = np.dtype([("offset", "<i8"), ("h", "<i4"), ("w", "<i4")])      # = uwm_image_desc (include/uwm.h), 16 bytes
 INTERP = {"nearest": 0, "linear": 1}                                        # UWM_INTER_* = cv2's values

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from ._common import device_u8, ptr, upload_records, workspace
+from .._device import device_u8, ptr, upload_records, workspace
 from .augment import IDENTITY_MINV
 from .ragged import DESC_DTYPE, descs_tensor, mask_descs_for
 
@@ -274,10 +274,7 @@ def device_synth(packed_images, image_descs, packed_logos, logo_descs, jobs, wit
     jd = upload_records(j, out.device)
     step = DESC_DTYPE.itemsize
     with L.on_device(out):
-        need = int(L.lib().uwm_synth_workspace_bytes(n, k, P, T))
-        if need == 0:
-            L.check(1, ValueError)
-        ws = workspace("synth", out.device, need)
+        ws = workspace("synth", out.device, L.lib().uwm_synth_workspace_bytes(n, k, P, T), ValueError)
         L.check(L.lib().uwm_synth_u8(ptr(out), out.numel(), ptr(dd), ptr(mask), mask.numel() if with_mask else 0,
                                      C.c_void_p(dd.data_ptr() + n * step), ptr(logos), logos.numel(),
                                      C.c_void_p(dd.data_ptr() + 2 * n * step), len(ldesc), ptr(jd), n, k, P, T,

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from ._common import device_u8, ptr, upload_records, workspace
+from .._device import device_u8, ptr, upload_records, workspace
 from .augment import IDENTITY_MINV
 from .ragged import DESC_DTYPE, descs_tensor, mask_descs_for
 from .synth import SYNTH_MAX_SLOTS, synth_blur_params, synth_opacity_lut, synth_rotate_setup
@@ -334,10 +334,7 @@ def device_synth_text(packed_images, image_descs, packed_planes, plane_descs, jo
     jd = upload_records(j, out.device)
     step = DESC_DTYPE.itemsize
     with L.on_device(out):
-        need = int(L.lib().uwm_synth_text_workspace_bytes(n, k, P, T))
-        if need == 0:
-            L.check(1, ValueError)
-        ws = workspace("synth_text", out.device, need)
+        ws = workspace("synth_text", out.device, L.lib().uwm_synth_text_workspace_bytes(n, k, P, T), ValueError)
         L.check(L.lib().uwm_synth_text_u8(ptr(out), out.numel(), ptr(dd), ptr(mask), mask.numel() if mask is not None else 0,
                                           C.c_void_p(dd.data_ptr() + n * step), int(mask_mode), ptr(planes), planes.numel(),
                                           C.c_void_p(dd.data_ptr() + 2 * n * step), len(pdesc), ptr(jd), n, k, P, T,

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib as L
 from .data import DESC_DTYPE, PAIR_IMAGE_EXTENSIONS, descs_tensor, device_resize, mask_descs_for, pack_images
-from .data._common import ptr, upload_records, workspace
+from ._device import ptr, ragged_capacities, upload_records, workspace
 
 MAX_REGIONS = 254                                          # UWM_EXTRACT_MAX_REGIONS: kept regions of one image
 ROW_FIELDS = ("id", "a00", "a10", "a01", "x0", "y0", "x1", "y1", "pixels")
@@ -59,9 +59,9 @@ def extract_regions(wm_buf, clean_buf, descs, threshold=30, min_area=100, clean_
     n = len(wd)
     cd = wd if clean_descs is None else _descs(clean_descs, n)
     pd = mask_descs_for(wd) if plane_descs is None else _descs(plane_descs, n)
-    sizes = np.clip(wd["h"].astype(np.int64), 0, None) * np.clip(wd["w"].astype(np.int64), 0, None)
-    max_pixels = max(1, int(sizes.max())) if max_pixels is None else int(max_pixels)
-    total_pixels = max(1, int(sizes.sum())) if total_pixels is None else int(total_pixels)
+    caps = ragged_capacities(wd)
+    max_pixels = caps["max_pixels"] if max_pixels is None else int(max_pixels)
+    total_pixels = caps["total_pixels"] if total_pixels is None else int(total_pixels)
     nplane = max(1, int((pd["offset"].astype(np.int64) + pd["h"].astype(np.int64) * pd["w"]).max()))
     plane = torch.full((nplane,), 255, dtype=torch.uint8, device=wm.device)
     stats = torch.empty((n, 4), dtype=torch.int64, device=wm.device)
@@ -70,10 +70,7 @@ def extract_regions(wm_buf, clean_buf, descs, threshold=30, min_area=100, clean_
     step = n * DESC_DTYPE.itemsize
     lib = L.lib()
     with L.on_device(wm):
-        need = lib.uwm_extract_workspace_bytes(n, total_pixels, 0)
-        if need == 0:
-            L.check(1, ValueError)
-        ws = workspace("extract", wm.device, need)
+        ws = workspace("extract", wm.device, lib.uwm_extract_workspace_bytes(n, total_pixels, 0), ValueError)
         L.check(lib.uwm_extract_regions_ragged(ptr(wm), wm.numel(), ptr(dd), ptr(cl), cl.numel(), C.c_void_p(dd.data_ptr() + step), n, 3, t, a,
                                                max_pixels, total_pixels, ptr(plane), plane.numel(), C.c_void_p(dd.data_ptr() + 2 * step),
                                                ptr(stats), ptr(table), ptr(ws), ws.numel(), C.c_void_p(L.stream_ptr(wm.device))), ValueError)
@@ -195,10 +192,7 @@ def extract_cutouts(wm_buf, descs, plane, plane_descs, jobs, out_bytes=None, max
     dj = upload_records(jb, wm.device)
     lib = L.lib()
     with L.on_device(wm):
-        need = lib.uwm_extract_workspace_bytes(0, 0, len(jb))
-        if need == 0:
-            L.check(1, ValueError)
-        ws = workspace("extract", wm.device, need)
+        ws = workspace("extract", wm.device, lib.uwm_extract_workspace_bytes(0, 0, len(jb)), ValueError)
         L.check(lib.uwm_extract_cutouts_ragged(ptr(wm), wm.numel(), ptr(dd), ptr(pl), pl.numel(), C.c_void_p(dd.data_ptr() + n * DESC_DTYPE.itemsize),
                                                n, ptr(dj), len(jb), max_crop_pixels, ptr(out), out.numel(), ptr(status), ptr(ws), ws.numel(),
                                                C.c_void_p(L.stream_ptr(wm.device))), ValueError)

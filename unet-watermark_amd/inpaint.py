@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib as L
+from . import _device as D, _lib as L
 
 # the smallest count at which every case of tests/test_inpaint.py's convergence table is within 0.5 grey levels of the exact membrane
 # before rounding (the corner hole at 97 x 131 is the slowest, 0.51 after six cycles, 0.26 after seven)
@@ -22,7 +22,6 @@ MAX_CYCLES = 32
 MAX_SIDE = 32768
 INPAINT_STATS_FIELDS = ("hole_pixels", "status", "levels", "reserved")
 STATUS = {"filled": 0, "no_hole": 1, "no_known": 2, "misfit": 3}          # UWM_INPAINT_*
-_ws = {}                                                                  # device -> workspace tensor (grown on demand)
 
 
 def check_cycles(cycles) -> int:
@@ -34,14 +33,7 @@ def check_cycles(cycles) -> int:
 def inpaint_workspace(device, n: int, image_bytes: int, channels: int, max_side: int) -> torch.Tensor:
     """uwm_inpaint_ragged's scratch for the capacities (n, image_bytes, channels, max_side): one buffer per device, kept and grown on
     demand; a captured graph holds the buffer it was captured with"""
-    need = L.lib().uwm_inpaint_workspace_bytes(int(n), int(image_bytes), int(channels), int(max_side))
-    if need == 0:
-        raise RuntimeError(L.lib().uwm_last_error().decode(errors="replace"))
-    key = str(device)
-    ws = _ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _ws[key] = torch.empty(need, dtype=torch.uint8, device=device)
-    return ws
+    return D.workspace("inpaint", device, L.lib().uwm_inpaint_workspace_bytes(int(n), int(image_bytes), int(channels), int(max_side)))
 
 
 def launch_count(cycles: int, max_side: int) -> int:
@@ -59,28 +51,18 @@ def inpaint_buffers(buf: torch.Tensor, descs: torch.Tensor, mbuf: torch.Tensor, 
     uwm_image_desc bytes on the same device.  Nothing about the batch is read on the host, so the call can be captured; max_pixels,
     rows and max_side are capacities (the largest h*w, the sum of h, the largest side).  out: buf itself (in place) or a tensor of
     its size (default: a new one; bytes outside the images are zero); stats: an int64 (n, 4) device tensor (INPAINT_STATS_FIELDS)"""
-    if not isinstance(buf, torch.Tensor) or buf.device.type != "cuda":
-        raise RuntimeError("uwm inpaint runs only on a HIP device (no CPU fallback)")
-    for t, what in ((buf, "buf"), (mbuf, "mbuf")):
-        if t.dtype != torch.uint8 or t.dim() != 1 or t.numel() == 0 or not t.is_contiguous() or t.device != buf.device:
-            raise RuntimeError(f"inpaint: {what} must be a non-empty contiguous 1-d uint8 tensor on the images' device")
-    for d, what in ((descs, "descs"), (mdescs, "mdescs")):
-        if not isinstance(d, torch.Tensor) or d.device != buf.device or d.dtype != torch.uint8 or d.numel() < 16 * int(n):
-            raise RuntimeError(f"inpaint: {what} must be a uint8 tensor of 16 n bytes on the images' device")
+    descs, n, caps = D.ragged_args("inpaint", (buf, mbuf), descs, n, max_pixels=max_pixels, rows=rows)
+    if not isinstance(mdescs, torch.Tensor) or mdescs.device != buf.device or mdescs.dtype != torch.uint8 or mdescs.numel() < 16 * n:
+        raise RuntimeError("inpaint: mdescs must be a uint8 tensor of 16 n bytes on the images' device")
     cycles = check_cycles(cycles)
-    if out is None:
-        out = torch.zeros_like(buf)
-    elif out.dtype != torch.uint8 or out.device != buf.device or out.numel() != buf.numel() or not out.is_contiguous():
-        raise RuntimeError("inpaint: out must be a contiguous uint8 tensor of the buffer's size on the same device")
-    if stats is not None and (stats.dtype != torch.int64 or stats.device != buf.device or stats.numel() < 4 * int(n) or not stats.is_contiguous()):
-        raise RuntimeError("inpaint: stats must be a contiguous int64 tensor of 4 n entries on the images' device")
+    out = D.out_like("inpaint", out, buf)
+    if stats is not None:
+        stats = D.stats_like("inpaint", stats, n, 4, buf.device)
     with L.on_device(buf):
         ws = workspace if workspace is not None else inpaint_workspace(buf.device, n, buf.numel(), channels, max_side)
-        L.check(L.lib().uwm_inpaint_ragged(C.c_void_p(buf.data_ptr()), C.c_void_p(out.data_ptr()), buf.numel(), C.c_void_p(descs.data_ptr()),
-                                           C.c_void_p(mbuf.data_ptr()), mbuf.numel(), C.c_void_p(mdescs.data_ptr()), int(n), int(channels),
-                                           cycles, int(max_pixels), int(rows), int(max_side),
-                                           C.c_void_p(stats.data_ptr() if stats is not None else 0), C.c_void_p(ws.data_ptr()), ws.numel(),
-                                           C.c_void_p(L.stream_ptr(buf.device))), ValueError)
+        L.check(L.lib().uwm_inpaint_ragged(D.ptr(buf), D.ptr(out), buf.numel(), D.ptr(descs), D.ptr(mbuf), mbuf.numel(), D.ptr(mdescs), n,
+                                           int(channels), cycles, caps["max_pixels"], caps["rows"], int(max_side), D.ptr(stats), D.ptr(ws),
+                                           ws.numel(), C.c_void_p(L.stream_ptr(buf.device))), ValueError)
     return out
 
 
@@ -119,7 +101,7 @@ def inpaint_ragged(images, masks, cycles: int = DEFAULT_CYCLES, return_stats: bo
     stats = torch.empty((n, 4), dtype=torch.int64, device=dev) if return_stats else None
     out = inpaint_buffers(buf, descs_tensor(descs).to(dev), mbuf, descs_tensor(mdescs).to(dev), n, channels, max_pixels=int(areas.max()),
                           rows=int(hs.sum()), max_side=int(max(hs.max(), ws_.max())), cycles=cycles, stats=stats)
-    res = [out[int(o): int(o) + channels * int(a)].view(int(h), int(w), channels) for o, a, h, w in zip(descs["offset"], areas, hs, ws_)]
+    res = D.ragged_views(out, descs, channels)
     return (res, stats.cpu().numpy()) if return_stats else res
 
 

@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from ._device import norm_arrays, ptr
 
 
 class _Node(nn.Module):
@@ -356,18 +357,46 @@ class Unet(nn.Module):
             L.check(L.lib().uwm_bind(self._h, C.c_void_p(key[0]), C.c_void_p(key[1]), C.c_void_p(key[2])))
             self._bound = key
 
-    def _workspace(self, n, h, w, training, logits_inside=None):
-        key = (n, h, w, bool(training))
-        if logits_inside is None:
-            need = L.lib().uwm_workspace_bytes(self._h, n, h, w, int(training))
-        else:                                 # predict_u8: the eval plan [+ the logits behind it]
-            need = L.lib().uwm_predict_workspace_bytes(self._h, n, h, w, int(logits_inside))
+    def _workspace(self, need, key):
+        """the model's one workspace with at least `need` bytes, what a uwm_*_workspace_bytes query of this handle answered (0: its
+        refusal), for the plan `key` = (forward batch, h, w, training); grown when it is too small.  A captured graph's owner keeps
+        its own reference."""
         if need == 0:
             raise SegmentationModelError(L.lib().uwm_last_error().decode())
         if self._ws is None or self._ws.numel() < need or self._ws.device != self.device:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         self._ws_key = key
         return self._ws
+
+    def _eval_call_setup(self, name: str, flat, n: int, batch: int, size, query, mean, std):
+        """what the eval entry points share: eval mode, the checks of their flat tensors (packed bytes, descriptors in and out first: n
+        images need 16 n bytes of each), the input size, the bound / frozen state for the forward batch, the workspace of `query`(h, w)
+        bytes, the forward generation and drop-connect -> (h, w, workspace, bytes, mean array, std array)"""
+        if self.training:
+            raise RuntimeError(f"{name} is an eval-mode path: call .eval() first")
+        for t in flat:
+            self._require_gpu(t)
+            if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+                raise RuntimeError(f"{name} takes flat contiguous uint8 tensors (data.pack_images / data.descs_tensor / tiling.table_tensor)")
+        if flat and (n < 1 or flat[1].numel() < 16 * n or flat[2].numel() < 16 * n):
+            raise RuntimeError(f"{name}: {n} images need {16 * n} descriptor bytes each way")
+        if batch < 1:
+            raise RuntimeError(f"{name}: the forward batch must be >= 1 (got {batch})")
+        h, w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+        self.check_input_shape(torch.empty((0, self.in_channels, h, w)))
+        self._ensure_bound()
+        if self._frozen and not L.lib().uwm_is_frozen(self._h):
+            self._freeze_now(batch, h, w)
+        need = query(h, w)
+        ws = self._workspace(need, (batch, h, w, False))
+        self._fwd_gen += 1
+        if self._n_mb:
+            self._set_drop_connect(batch, False, self.device)
+        return (h, w, ws, need) + norm_arrays(mean, std, self.in_channels)
+
+    def _predict_bytes(self, n, return_logits):
+        """the workspace query of the calls around ONE eval forward of n images: the eval plan [+ the logits behind it]"""
+        return lambda h, w: L.lib().uwm_predict_workspace_bytes(self._h, n, h, w, int(not return_logits))
 
     def check_input_shape(self, x):
         h, w = x.shape[-2:]
@@ -391,7 +420,7 @@ class Unet(nn.Module):
         self._ensure_bound()
         if self._frozen and not training and not L.lib().uwm_is_frozen(self._h):
             self._freeze_now(n, h, w)        # freeze(batch_shape=None): this forward fixes the forms (also after a re-bind)
-        ws = self._workspace(n, h, w, training)
+        ws = self._workspace(L.lib().uwm_workspace_bytes(self._h, n, h, w, int(training)), (n, h, w, bool(training)))
         logits = torch.empty((n, h, w, self._cp), dtype=torch.float32, device=x.device)
         self._fwd_gen += 1
         if self._n_mb:
@@ -410,30 +439,18 @@ class Unet(nn.Module):
         Normalize(mean, std) of x/255 written straight into the forward's input layout, eval forward (frozen or not), bilinear
         resize to `out_size` (default: the input size) + threshold.  Bit-identical to device_preprocess -> forward ->
         resize_threshold.  return_logits: also the logits (N,classes,H,W)."""
-        if self.training:
-            raise RuntimeError("predict_u8 is an eval-mode path: call .eval() first")
         self._require_gpu(images_u8)
         if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[3] != self.in_channels:
             raise RuntimeError(f"expected uint8 images of shape (N,H,W,{self.in_channels}), got {images_u8.dtype} {tuple(images_u8.shape)}")
         x = images_u8.contiguous()
-        n, h, w, c = x.shape
-        self.check_input_shape(x.permute(0, 3, 1, 2))
+        n = x.shape[0]
+        h, w, ws, _, mean_c, std_c = self._eval_call_setup("predict_u8", (), n, n, x.shape[1:3], self._predict_bytes(n, return_logits), mean, std)
         oh, ow = (h, w) if out_size is None else (int(out_size[0]), int(out_size[1]))
-        self._ensure_bound()
-        if self._frozen and not L.lib().uwm_is_frozen(self._h):
-            self._freeze_now(n, h, w)
-        ws = self._workspace(n, h, w, False, logits_inside=not return_logits)
         mask = torch.empty((n, oh, ow), dtype=torch.uint8, device=x.device)
         logits = torch.empty((n, h, w, self._cp), dtype=torch.float32, device=x.device) if return_logits else None
-        self._fwd_gen += 1
-        if self._n_mb:
-            self._set_drop_connect(n, False, x.device)
-        mean_c = (C.c_float * c)(*[float(v) for v in mean[:c]]); std_c = (C.c_float * c)(*[float(v) for v in std[:c]])
         with L.on_device(x):
-            L.check(L.lib().uwm_predict_u8(self._h, C.c_void_p(x.data_ptr()), mean_c, std_c, float(threshold), int(apply_sigmoid),
-                                           oh, ow, C.c_void_p(mask.data_ptr()), C.c_void_p(logits.data_ptr() if logits is not None else 0),
-                                           C.c_void_p(ws.data_ptr()), ws.numel(), n, h, w, C.c_void_p(L.stream_ptr(x.device))),
-                    SegmentationModelError)
+            L.check(L.lib().uwm_predict_u8(self._h, ptr(x), mean_c, std_c, float(threshold), int(apply_sigmoid), oh, ow, ptr(mask), ptr(logits),
+                                           ptr(ws), ws.numel(), n, h, w, C.c_void_p(L.stream_ptr(x.device))), SegmentationModelError)
         return (mask, self._logits_view(logits)) if return_logits else mask
 
     @torch.no_grad()
@@ -445,34 +462,14 @@ class Unet(nn.Module):
         `size` = (H, W) + Normalize into the forward's input, eval forward (frozen or not), resize back + threshold.  Nothing in the
         call depends on the image sizes, so a graph captured around it serves every batch of n images.  Returns `mask`
         [, logits (n,classes,H,W)]."""
-        if self.training:
-            raise RuntimeError("predict_images_u8 is an eval-mode path: call .eval() first")
-        for t in (packed, in_descs, out_descs, mask):
-            self._require_gpu(t)
-            if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
-                raise RuntimeError("predict_images_u8 takes flat contiguous uint8 tensors (data.pack_images / data.descs_tensor)")
         n = int(n)
-        if n < 1 or in_descs.numel() < 16 * n or out_descs.numel() < 16 * n:
-            raise RuntimeError(f"predict_images_u8: {n} images need {16 * n} descriptor bytes each way")
-        h, w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
-        self.check_input_shape(torch.empty((0, self.in_channels, h, w)))
-        self._ensure_bound()
-        if self._frozen and not L.lib().uwm_is_frozen(self._h):
-            self._freeze_now(n, h, w)
-        ws = self._workspace(n, h, w, False, logits_inside=not return_logits)
+        h, w, ws, _, mean_c, std_c = self._eval_call_setup("predict_images_u8", (packed, in_descs, out_descs, mask), n, n, size,
+                                                           self._predict_bytes(n, return_logits), mean, std)
         logits = torch.empty((n, h, w, self._cp), dtype=torch.float32, device=packed.device) if return_logits else None
-        self._fwd_gen += 1
-        if self._n_mb:
-            self._set_drop_connect(n, False, packed.device)
-        c = self.in_channels
-        mean_c = (C.c_float * c)(*[float(v) for v in mean[:c]]); std_c = (C.c_float * c)(*[float(v) for v in std[:c]])
         with L.on_device(packed):
-            L.check(L.lib().uwm_predict_images_u8(self._h, C.c_void_p(packed.data_ptr()), packed.numel(), C.c_void_p(in_descs.data_ptr()),
-                                                  mean_c, std_c, float(threshold), int(apply_sigmoid), C.c_void_p(out_descs.data_ptr()),
-                                                  C.c_void_p(mask.data_ptr()), mask.numel(),
-                                                  C.c_void_p(logits.data_ptr() if logits is not None else 0),
-                                                  C.c_void_p(ws.data_ptr()), ws.numel(), n, h, w, C.c_void_p(L.stream_ptr(packed.device))),
-                    SegmentationModelError)
+            L.check(L.lib().uwm_predict_images_u8(self._h, ptr(packed), packed.numel(), ptr(in_descs), mean_c, std_c, float(threshold),
+                                                  int(apply_sigmoid), ptr(out_descs), ptr(mask), mask.numel(), ptr(logits), ptr(ws), ws.numel(),
+                                                  n, h, w, C.c_void_p(L.stream_ptr(packed.device))), SegmentationModelError)
         return (mask, self._logits_view(logits)) if return_logits else mask
 
     @torch.no_grad()
@@ -487,77 +484,28 @@ class Unet(nn.Module):
         floats, the same offsets).  Nothing in the call depends on the image sizes beyond k, so a graph captured around it serves every
         batch of n images with k tile entries.  Returns `mask`; the store [k][T_h][T_w] of the call stays readable as
         `self._tile_store` (a view of the workspace's tail)."""
-        if self.training:
-            raise RuntimeError("predict_tiled_u8 is an eval-mode path: call .eval() first")
-        for t in (packed, in_descs, out_descs, mask, tiles, plans):
-            self._require_gpu(t)
-            if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
-                raise RuntimeError("predict_tiled_u8 takes flat contiguous uint8 tensors (data.pack_images / data.descs_tensor / tiling.table_tensor)")
         n, k, batch = int(n), int(k), int(batch)
-        if n < 1 or in_descs.numel() < 16 * n or out_descs.numel() < 16 * n or plans.numel() < 16 * n:
-            raise RuntimeError(f"predict_tiled_u8: {n} images need {16 * n} descriptor bytes each way and as many plan bytes")
+        if plans.numel() < 16 * n:
+            raise RuntimeError(f"predict_tiled_u8: {n} images need {16 * n} plan bytes")
         if k < 1 or batch < 1 or k % batch or tiles.numel() < 16 * k:
             raise RuntimeError(f"predict_tiled_u8: k = {k} tile entries must be a multiple of the batch {batch} and need {16 * k} table bytes")
-        if logits_out is not None:
-            self._require_gpu(logits_out)
-            if logits_out.dtype != torch.float32 or not logits_out.is_contiguous() or logits_out.numel() < mask.numel():
-                raise RuntimeError(f"predict_tiled_u8: logits_out must be a contiguous float32 tensor of at least {mask.numel()} elements")
-        h, w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
-        self.check_input_shape(torch.empty((0, self.in_channels, h, w)))
-        self._ensure_bound()
-        if self._frozen and not L.lib().uwm_is_frozen(self._h):
-            self._freeze_now(batch, h, w)
-        need = L.lib().uwm_predict_tiled_workspace_bytes(self._h, batch, k, h, w)
-        if need == 0:
-            raise SegmentationModelError(L.lib().uwm_last_error().decode())
-        if self._ws is None or self._ws.numel() < need or self._ws.device != self.device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)      # (a captured graph's owner keeps its own reference)
-        self._ws_key = (batch, h, w, False)
-        ws = self._ws
+        self._check_logits_out("predict_tiled_u8", logits_out, mask)
+        h, w, ws, need, mean_c, std_c = self._eval_call_setup(
+            "predict_tiled_u8", (packed, in_descs, out_descs, mask, tiles, plans), n, batch, size,
+            lambda h, w: L.lib().uwm_predict_tiled_workspace_bytes(self._h, batch, k, h, w), mean, std)
         self._tile_store = ws[need - 4 * k * h * w: need].view(torch.float32).view(k, h, w)
-        self._fwd_gen += 1
-        if self._n_mb:
-            self._set_drop_connect(batch, False, packed.device)
-        c = self.in_channels
-        mean_c = (C.c_float * c)(*[float(v) for v in mean[:c]]); std_c = (C.c_float * c)(*[float(v) for v in std[:c]])
         with L.on_device(packed):
-            L.check(L.lib().uwm_predict_tiled_u8(self._h, C.c_void_p(packed.data_ptr()), packed.numel(), C.c_void_p(in_descs.data_ptr()), n,
-                                                 C.c_void_p(tiles.data_ptr()), k, C.c_void_p(plans.data_ptr()), h, w, int(overlap),
-                                                 mean_c, std_c, float(threshold), int(apply_sigmoid), C.c_void_p(out_descs.data_ptr()),
-                                                 C.c_void_p(mask.data_ptr()), mask.numel(),
-                                                 C.c_void_p(logits_out.data_ptr() if logits_out is not None else 0),
-                                                 C.c_void_p(ws.data_ptr()), need, batch, C.c_void_p(L.stream_ptr(packed.device))),
+            L.check(L.lib().uwm_predict_tiled_u8(self._h, ptr(packed), packed.numel(), ptr(in_descs), n, ptr(tiles), k, ptr(plans), h, w,
+                                                 int(overlap), mean_c, std_c, float(threshold), int(apply_sigmoid), ptr(out_descs), ptr(mask),
+                                                 mask.numel(), ptr(logits_out), ptr(ws), need, batch, C.c_void_p(L.stream_ptr(packed.device))),
                     SegmentationModelError)
         return mask
 
-    def _tta_call_setup(self, name: str, flat, n: int, in_descs, out_descs, batch: int, size, views: int, query, items: int):
-        """what the two test-time-augmentation calls share: the checks of their flat tensors, the bound / frozen state and the workspace
-        of `query`(handle, batch, ..., views) bytes -> (h, w, workspace, bytes)"""
-        if self.training:
-            raise RuntimeError(f"{name} is an eval-mode path: call .eval() first")
-        for t in flat:
-            self._require_gpu(t)
-            if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
-                raise RuntimeError(f"{name} takes flat contiguous uint8 tensors (data.pack_images / data.descs_tensor / tiling.table_tensor)")
-        if n < 1 or in_descs.numel() < 16 * n or out_descs.numel() < 16 * n:
-            raise RuntimeError(f"{name}: {n} images need {16 * n} descriptor bytes each way")
-        if batch < 1 or items < 1:
-            raise RuntimeError(f"{name}: the forward batch and the item count must be >= 1 (got {batch}, {items})")
-        h, w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
-        self.check_input_shape(torch.empty((0, self.in_channels, h, w)))
-        self._ensure_bound()
-        if self._frozen and not L.lib().uwm_is_frozen(self._h):
-            self._freeze_now(batch, h, w)
-        need = query(h, w)
-        if need == 0:
-            raise SegmentationModelError(L.lib().uwm_last_error().decode())
-        if self._ws is None or self._ws.numel() < need or self._ws.device != self.device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)      # (a captured graph's owner keeps its own reference)
-        self._ws_key = (batch, h, w, False)
-        self._fwd_gen += 1
-        if self._n_mb:
-            self._set_drop_connect(batch, False, self.device)
-        return h, w, self._ws, need
+    def _check_logits_out(self, name: str, logits_out, mask):
+        if logits_out is not None:
+            self._require_gpu(logits_out)
+            if logits_out.dtype != torch.float32 or not logits_out.is_contiguous() or logits_out.numel() < mask.numel():
+                raise RuntimeError(f"{name}: logits_out must be a contiguous float32 tensor of at least {mask.numel()} elements")
 
     @torch.no_grad()
     def predict_images_tta_u8(self, packed: torch.Tensor, in_descs: torch.Tensor, out_descs: torch.Tensor, mask: torch.Tensor, n: int,
@@ -568,17 +516,14 @@ class Unet(nn.Module):
         the call depends on the image sizes, so a graph captured around it serves every batch of n images.  Returns `mask`; the
         merged planes (n, H, W) of the call stay readable as `self._merged_store` (a view of the workspace's tail)."""
         n, batch, views = int(n), int(batch), int(views)
-        h, w, ws, need = self._tta_call_setup("predict_images_tta_u8", (packed, in_descs, out_descs, mask), n, in_descs, out_descs, batch, size, views,
-                                              lambda h, w: L.lib().uwm_predict_images_tta_workspace_bytes(self._h, batch, h, w, n, views), n)
+        h, w, ws, need, mean_c, std_c = self._eval_call_setup(
+            "predict_images_tta_u8", (packed, in_descs, out_descs, mask), n, batch, size,
+            lambda h, w: L.lib().uwm_predict_images_tta_workspace_bytes(self._h, batch, h, w, n, views), mean, std)
         self._merged_store = ws[need - 4 * n * h * w: need].view(torch.float32).view(n, h, w)
-        c = self.in_channels
-        mean_c = (C.c_float * c)(*[float(v) for v in mean[:c]]); std_c = (C.c_float * c)(*[float(v) for v in std[:c]])
         with L.on_device(packed):
-            L.check(L.lib().uwm_predict_images_tta_u8(self._h, C.c_void_p(packed.data_ptr()), packed.numel(), C.c_void_p(in_descs.data_ptr()), n,
-                                                      views, mean_c, std_c, float(threshold), int(apply_sigmoid),
-                                                      C.c_void_p(out_descs.data_ptr()), C.c_void_p(mask.data_ptr()), mask.numel(), C.c_void_p(0),
-                                                      C.c_void_p(ws.data_ptr()), need, batch, h, w, C.c_void_p(L.stream_ptr(packed.device))),
-                    SegmentationModelError)
+            L.check(L.lib().uwm_predict_images_tta_u8(self._h, ptr(packed), packed.numel(), ptr(in_descs), n, views, mean_c, std_c, float(threshold),
+                                                      int(apply_sigmoid), ptr(out_descs), ptr(mask), mask.numel(), ptr(None), ptr(ws), need, batch, h, w,
+                                                      C.c_void_p(L.stream_ptr(packed.device))), SegmentationModelError)
         return mask
 
     @torch.no_grad()
@@ -591,23 +536,16 @@ class Unet(nn.Module):
         n, k, batch, views = int(n), int(k), int(batch), int(views)
         if plans.numel() < 16 * n or k < 1 or tiles.numel() < 16 * k:
             raise RuntimeError(f"predict_tiled_tta_u8: {n} images need {16 * n} plan bytes and k = {k} tile entries {16 * k} table bytes")
-        if logits_out is not None:
-            self._require_gpu(logits_out)
-            if logits_out.dtype != torch.float32 or not logits_out.is_contiguous() or logits_out.numel() < mask.numel():
-                raise RuntimeError(f"predict_tiled_tta_u8: logits_out must be a contiguous float32 tensor of at least {mask.numel()} elements")
-        h, w, ws, need = self._tta_call_setup("predict_tiled_tta_u8", (packed, in_descs, out_descs, mask, tiles, plans), n, in_descs, out_descs, batch,
-                                              size, views, lambda h, w: L.lib().uwm_predict_tiled_tta_workspace_bytes(self._h, batch, k, h, w, views), k)
+        self._check_logits_out("predict_tiled_tta_u8", logits_out, mask)
+        h, w, ws, need, mean_c, std_c = self._eval_call_setup(
+            "predict_tiled_tta_u8", (packed, in_descs, out_descs, mask, tiles, plans), n, batch, size,
+            lambda h, w: L.lib().uwm_predict_tiled_tta_workspace_bytes(self._h, batch, k, h, w, views), mean, std)
         self._tile_store = ws[need - 4 * k * h * w: need].view(torch.float32).view(k, h, w)
-        c = self.in_channels
-        mean_c = (C.c_float * c)(*[float(v) for v in mean[:c]]); std_c = (C.c_float * c)(*[float(v) for v in std[:c]])
         with L.on_device(packed):
-            L.check(L.lib().uwm_predict_tiled_tta_u8(self._h, C.c_void_p(packed.data_ptr()), packed.numel(), C.c_void_p(in_descs.data_ptr()), n,
-                                                     C.c_void_p(tiles.data_ptr()), k, C.c_void_p(plans.data_ptr()), h, w, int(overlap),
-                                                     mean_c, std_c, float(threshold), int(apply_sigmoid), C.c_void_p(out_descs.data_ptr()),
-                                                     C.c_void_p(mask.data_ptr()), mask.numel(),
-                                                     C.c_void_p(logits_out.data_ptr() if logits_out is not None else 0),
-                                                     C.c_void_p(ws.data_ptr()), need, batch, views, C.c_void_p(L.stream_ptr(packed.device))),
-                    SegmentationModelError)
+            L.check(L.lib().uwm_predict_tiled_tta_u8(self._h, ptr(packed), packed.numel(), ptr(in_descs), n, ptr(tiles), k, ptr(plans), h, w,
+                                                     int(overlap), mean_c, std_c, float(threshold), int(apply_sigmoid), ptr(out_descs), ptr(mask),
+                                                     mask.numel(), ptr(logits_out), ptr(ws), need, batch, views,
+                                                     C.c_void_p(L.stream_ptr(packed.device))), SegmentationModelError)
         return mask
 
     @torch.no_grad()
@@ -620,24 +558,12 @@ class Unet(nn.Module):
         count.  `counts`: an int64 (n, 2) device tensor that receives {foreground pixels, h_i * w_i}; `mask`: absent, no mask is
         written at all; else the flat uint8 buffer that receives every mask at out_descs' offsets.  Capturable like
         predict_images_u8.  Returns `counts` [, logits (n,classes,H,W)]."""
-        if self.training:
-            raise RuntimeError("filter_images_u8 is an eval-mode path: call .eval() first")
-        for t in (packed, in_descs, out_descs) + (() if mask is None else (mask,)):
-            self._require_gpu(t)
-            if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
-                raise RuntimeError("filter_images_u8 takes flat contiguous uint8 tensors (data.pack_images / data.descs_tensor)")
         n = int(n)
-        if n < 1 or in_descs.numel() < 16 * n or out_descs.numel() < 16 * n:
-            raise RuntimeError(f"filter_images_u8: {n} images need {16 * n} descriptor bytes each way")
         self._require_gpu(counts)
         if counts.dtype != torch.int64 or counts.numel() < 2 * n or not counts.is_contiguous():
             raise RuntimeError(f"filter_images_u8: counts must be a contiguous int64 tensor of at least ({n}, 2)")
-        h, w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
-        self.check_input_shape(torch.empty((0, self.in_channels, h, w)))
-        self._ensure_bound()
-        if self._frozen and not L.lib().uwm_is_frozen(self._h):
-            self._freeze_now(n, h, w)
-        ws = self._workspace(n, h, w, False, logits_inside=not return_logits)
+        h, w, ws, _, mean_c, std_c = self._eval_call_setup("filter_images_u8", (packed, in_descs, out_descs) + (() if mask is None else (mask,)), n, n,
+                                                           size, self._predict_bytes(n, return_logits), mean, std)
         need = L.lib().uwm_filter_workspace_bytes(n)
         if need == 0:
             raise SegmentationModelError(L.lib().uwm_last_error().decode(errors="replace"))
@@ -645,20 +571,11 @@ class Unet(nn.Module):
         if fws is None or fws.numel() < need or fws.device != packed.device:
             fws = self._filter_ws = torch.empty(need, dtype=torch.uint8, device=packed.device)      # (a captured graph's owner keeps its own reference)
         logits = torch.empty((n, h, w, self._cp), dtype=torch.float32, device=packed.device) if return_logits else None
-        self._fwd_gen += 1
-        if self._n_mb:
-            self._set_drop_connect(n, False, packed.device)
-        c = self.in_channels
-        mean_c = (C.c_float * c)(*[float(v) for v in mean[:c]]); std_c = (C.c_float * c)(*[float(v) for v in std[:c]])
         with L.on_device(packed):
-            L.check(L.lib().uwm_filter_images_u8(self._h, C.c_void_p(packed.data_ptr()), packed.numel(), C.c_void_p(in_descs.data_ptr()),
-                                                 mean_c, std_c, float(threshold), int(bool(post_process)), C.c_void_p(out_descs.data_ptr()),
-                                                 C.c_void_p(mask.data_ptr() if mask is not None else 0), mask.numel() if mask is not None else 0,
-                                                 C.c_void_p(counts.data_ptr()),
-                                                 C.c_void_p(logits.data_ptr() if logits is not None else 0),
-                                                 C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(fws.data_ptr()), fws.numel(), n, h, w,
-                                                 C.c_void_p(L.stream_ptr(packed.device))),
-                    SegmentationModelError)
+            L.check(L.lib().uwm_filter_images_u8(self._h, ptr(packed), packed.numel(), ptr(in_descs), mean_c, std_c, float(threshold),
+                                                 int(bool(post_process)), ptr(out_descs), ptr(mask), mask.numel() if mask is not None else 0,
+                                                 ptr(counts), ptr(logits), ptr(ws), ws.numel(), ptr(fws), fws.numel(), n, h, w,
+                                                 C.c_void_p(L.stream_ptr(packed.device))), SegmentationModelError)
         return (counts, self._logits_view(logits)) if return_logits else counts
 
     def _set_drop_connect(self, n: int, training: bool, device):

@@ -17,13 +17,11 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib as L
+from . import _device as D, _lib as L
 
 MASK_TYPES = {"watermark": 0, "text": 1, "mixed": 2}
 SHAPES = {"rect": 0, "ellipse": 2, 0: 0, 2: 2}          # cv2.MORPH_RECT / cv2.MORPH_ELLIPSE
 _OPS = {"dilate": 1, "erode": 0}
-
-_ws = {}                                                  # device -> workspace tensor (grown on demand)
 
 
 def mask_type_code(mask_type) -> int:
@@ -66,14 +64,7 @@ def workspace(device, n: int, h: int, w: int) -> torch.Tensor:
     """The calls' scratch (bit planes, labels, areas): one buffer per device, kept and grown on demand like the model's workspace.
     A captured graph holds the buffer it was captured with (WatermarkPredictor keeps that reference), so growing it later for a
     larger shape leaves the graph valid."""
-    need = L.lib().uwm_mask_workspace_bytes(n, h, w)
-    if need == 0:
-        raise RuntimeError(L.lib().uwm_last_error().decode(errors="replace"))
-    key = str(device)
-    ws = _ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _ws[key] = torch.empty(need, dtype=torch.uint8, device=device)
-    return ws
+    return D.workspace("mask", device, L.lib().uwm_mask_workspace_bytes(n, h, w))
 
 
 def optimize_mask(mask_u8: torch.Tensor, mask_type: str = "watermark", return_summary: bool = False, out=None):
@@ -104,20 +95,12 @@ def optimize_mask(mask_u8: torch.Tensor, mask_type: str = "watermark", return_su
 
 RAGGED_TYPES = {**MASK_TYPES, "none": 3}                 # 'none' (UWM_MASK_NONE): binarise, no morphology, every component kept
 STATS_FIELDS = ("components", "largest_area", "foreground", "largest_id", "kept_components", "largest_kept_area", "pixels", "status")
-_rws = {}                                                 # device -> workspace tensor of the ragged call (grown on demand)
 
 
 def ragged_workspace(device, n: int, mask_bytes: int, rows: int) -> torch.Tensor:
     """The ragged call's scratch for the capacities (n, mask_bytes, rows): one buffer per device, kept and grown like `workspace`; a
     captured graph holds the buffer it was captured with."""
-    need = L.lib().uwm_mask_ragged_workspace_bytes(int(n), int(mask_bytes), int(rows))
-    if need == 0:
-        raise RuntimeError(L.lib().uwm_last_error().decode(errors="replace"))
-    key = str(device)
-    ws = _rws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _rws[key] = torch.empty(need, dtype=torch.uint8, device=device)
-    return ws
+    return D.workspace("mask_ragged", device, L.lib().uwm_mask_ragged_workspace_bytes(int(n), int(mask_bytes), int(rows)))
 
 
 def optimize_masks_ragged(buf: torch.Tensor, descs, mask_type: str = "watermark", return_stats: bool = False, out=None, *,
@@ -131,58 +114,25 @@ def optimize_masks_ragged(buf: torch.Tensor, descs, mask_type: str = "watermark"
     max_pixels / rows: capacities, at least the largest h*w and the sum of h; an image beyond a capacity is a misfit (status 1)."""
     if mask_type not in RAGGED_TYPES:
         raise ValueError(f"mask_type must be one of 'watermark', 'text', 'mixed', 'none', got {mask_type!r}")
-    if not isinstance(buf, torch.Tensor) or buf.device.type != "cuda":
-        raise RuntimeError("uwm optimize_masks_ragged runs only on a HIP device (no CPU fallback)")
-    if buf.dtype != torch.uint8 or buf.dim() != 1 or buf.numel() == 0 or not buf.is_contiguous():
-        raise RuntimeError(f"expected a non-empty contiguous 1-d uint8 buffer, got {buf.dtype} {tuple(buf.shape)}")
-    if isinstance(descs, torch.Tensor):
-        if n is None or max_pixels is None or rows is None:
-            raise ValueError("optimize_masks_ragged: device descriptors need n, max_pixels and rows")
-        if descs.device != buf.device or descs.dtype != torch.uint8 or descs.numel() < 16 * int(n):
-            raise RuntimeError("optimize_masks_ragged: descs must be a uint8 tensor of 16 n bytes on the buffer's device")
-        d = descs
-    else:
-        from .data import descs_tensor
-        n = len(descs) if n is None else int(n)
-        if n < 1:
-            raise ValueError("optimize_masks_ragged: empty batch")
-        if max_pixels is None:
-            max_pixels = max(1, int((descs["h"].astype("int64") * descs["w"]).max()))
-        if rows is None:
-            rows = max(1, int(descs["h"].astype("int64").clip(min=0).sum()))
-        d = descs_tensor(descs).to(buf.device)
-    if out is None:
-        o = torch.zeros_like(buf)
-    else:
-        if out.dtype != torch.uint8 or out.device != buf.device or out.numel() != buf.numel() or not out.is_contiguous():
-            raise RuntimeError("optimize_masks_ragged: out must be a contiguous uint8 tensor of the buffer's size on the same device")
-        o = out
-    if return_stats and stats is None:
-        stats = torch.empty((int(n), 8), dtype=torch.int64, device=buf.device)
+    d, n, caps = D.ragged_args("optimize_masks_ragged", (buf,), descs, n, max_pixels=max_pixels, rows=rows)
+    o = D.out_like("optimize_masks_ragged", out, buf)
+    if return_stats:
+        stats = D.stats_like("optimize_masks_ragged", stats, n, 8, buf.device)
     with L.on_device(buf):
-        ws = ragged_workspace(buf.device, n, buf.numel(), rows)
-        L.check(L.lib().uwm_optimize_masks_ragged(C.c_void_p(buf.data_ptr()), C.c_void_p(o.data_ptr()), buf.numel(), C.c_void_p(d.data_ptr()),
-                                                  int(n), RAGGED_TYPES[mask_type], int(max_pixels), int(rows),
-                                                  C.c_void_p(stats.data_ptr() if return_stats else 0), C.c_void_p(ws.data_ptr()), ws.numel(),
+        ws = ragged_workspace(buf.device, n, buf.numel(), caps["rows"])
+        L.check(L.lib().uwm_optimize_masks_ragged(D.ptr(buf), D.ptr(o), buf.numel(), D.ptr(d), n, RAGGED_TYPES[mask_type], caps["max_pixels"],
+                                                  caps["rows"], D.ptr(stats if return_stats else None), D.ptr(ws), ws.numel(),
                                                   C.c_void_p(L.stream_ptr(buf.device))))
     return (o, stats) if return_stats else o
 
 
 ENHANCE_STATS_FIELDS = ("foreground_in", "foreground_out", "pixels", "status")
-_ews = {}                                                 # device -> workspace tensor of the enhancement (grown on demand)
 
 
 def enhance_workspace(device, n: int, mask_bytes: int) -> torch.Tensor:
     """uwm_enhance_masks_ragged's scratch for the capacities (n, mask_bytes): one buffer per device, kept and grown like `workspace`;
     a captured graph holds the buffer it was captured with."""
-    need = L.lib().uwm_enhance_masks_workspace_bytes(int(n), int(mask_bytes))
-    if need == 0:
-        raise RuntimeError(L.lib().uwm_last_error().decode(errors="replace"))
-    key = str(device)
-    ws = _ews.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _ews[key] = torch.empty(need, dtype=torch.uint8, device=device)
-    return ws
+    return D.workspace("enhance", device, L.lib().uwm_enhance_masks_workspace_bytes(int(n), int(mask_bytes)))
 
 
 def _enhance_params(expand_pixels, blur_kernel, smooth_iterations):
@@ -205,37 +155,15 @@ def enhance_masks_ragged(buf: torch.Tensor, descs, expand_pixels: int = 10, blur
     the int64 (n, 4) device tensor ENHANCE_STATS_FIELDS (`stats`: a tensor to write them into).  The rules are restated from
     OpenCV's documented behaviour, not run against it (include/uwm.h)."""
     e, k, s = _enhance_params(expand_pixels, blur_kernel, smooth_iterations)
-    if not isinstance(buf, torch.Tensor) or buf.device.type != "cuda":
-        raise RuntimeError("uwm enhance_masks_ragged runs only on a HIP device (no CPU fallback)")
-    if buf.dtype != torch.uint8 or buf.dim() != 1 or buf.numel() == 0 or not buf.is_contiguous():
-        raise RuntimeError(f"expected a non-empty contiguous 1-d uint8 buffer, got {buf.dtype} {tuple(buf.shape)}")
-    if isinstance(descs, torch.Tensor):
-        if n is None or max_pixels is None:
-            raise ValueError("enhance_masks_ragged: device descriptors need n and max_pixels")
-        if descs.device != buf.device or descs.dtype != torch.uint8 or descs.numel() < 16 * int(n):
-            raise RuntimeError("enhance_masks_ragged: descs must be a uint8 tensor of 16 n bytes on the buffer's device")
-        d = descs
-    else:
-        from .data import descs_tensor
-        n = len(descs) if n is None else int(n)
-        if n < 1:
-            raise ValueError("enhance_masks_ragged: empty batch")
-        if max_pixels is None:
-            max_pixels = max(1, int((descs["h"].astype("int64") * descs["w"]).max()))
-        d = descs_tensor(descs).to(buf.device)
-    if out is None:
-        o = torch.zeros_like(buf)
-    else:
-        if out.dtype != torch.uint8 or out.device != buf.device or out.numel() != buf.numel() or not out.is_contiguous():
-            raise RuntimeError("enhance_masks_ragged: out must be a contiguous uint8 tensor of the buffer's size on the same device")
-        o = out
-    if return_stats and stats is None:
-        stats = torch.empty((int(n), 4), dtype=torch.int64, device=buf.device)
+    d, n, caps = D.ragged_args("enhance_masks_ragged", (buf,), descs, n, max_pixels=max_pixels)
+    o = D.out_like("enhance_masks_ragged", out, buf)
+    if return_stats:
+        stats = D.stats_like("enhance_masks_ragged", stats, n, 4, buf.device)
     with L.on_device(buf):
         ws = enhance_workspace(buf.device, n, buf.numel())
-        L.check(L.lib().uwm_enhance_masks_ragged(C.c_void_p(buf.data_ptr()), C.c_void_p(o.data_ptr()), buf.numel(), C.c_void_p(d.data_ptr()),
-                                                 int(n), e, k, s, int(max_pixels), C.c_void_p(stats.data_ptr() if return_stats else 0),
-                                                 C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(L.stream_ptr(buf.device))))
+        L.check(L.lib().uwm_enhance_masks_ragged(D.ptr(buf), D.ptr(o), buf.numel(), D.ptr(d), n, e, k, s, caps["max_pixels"],
+                                                 D.ptr(stats if return_stats else None), D.ptr(ws), ws.numel(),
+                                                 C.c_void_p(L.stream_ptr(buf.device))))
     return (o, stats) if return_stats else o
 
 

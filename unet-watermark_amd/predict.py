@@ -9,6 +9,7 @@ src/predict.py:370-404) is opt-in through `text_enhance` and runs in front of th
 detection, IOPaint / LaMa, OCR and diffusion models stay out of scope."""
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import Optional
 
 import numpy as np
@@ -20,9 +21,14 @@ from .constants import IMAGENET_MEAN, IMAGENET_STD  # noqa: F401   (predict.IMAG
 from .data import descs_tensor, device_preprocess, pack_images
 from .metrics import threshold_mask
 from .model import create_model_from_config
-from .textenh import text_enhance_ragged, text_enhance_workspace
+from ._device import ragged_views, recording
+from .textenh import text_enhance_ragged
 from .tta import view_mask
-from .postprocess import RAGGED_TYPES, mask_type_code, optimize_mask, optimize_masks_ragged, ragged_workspace, workspace as mask_workspace
+from .postprocess import RAGGED_TYPES, mask_type_code, optimize_mask, optimize_masks_ragged
+
+# the groups of captured graphs, by what a graph replays on beside the model's arena (WatermarkPredictor._drop): a cloned input of its
+# own; the staging buffers; those and the enhanced images; the same under test-time augmentation; the staging buffers and the tile tables
+GRAPH_GROUPS = ("input", "images", "text", "tta", "tiled")
 
 
 class WatermarkPredictor:
@@ -46,34 +52,16 @@ class WatermarkPredictor:
             # the kernel choice does not depend on the batch size: an image's logits stay bit-identical whatever batch it rides in
             self.model.set_precision(precision, min_workgroups=1 if precision.startswith("f16x3") else None)
         self.threshold = float(self.cfg.PREDICT.THRESHOLD)
-        self._graph = None
-        self._gkey = None
-        self._gin = self._gout = self._gws = None
-        self._ugraph = None
-        self._ukey = None
-        self._uin = self._uout = self._uws = None
-        self._pgraph = None                   # predict_mask(mask_type=...): the forward + threshold + post-processing graph
-        self._pkey = None
-        self._pin = self._pout = self._pws = None
-        self._igraph = None                   # predict_images: ONE graph per (N, H, W, apply_sigmoid, threshold), whatever the image sizes
-        self._ikey = None
-        self._ibuf = self._idesc = self._mdesc = self._mbuf = self._iws = None      # its static staging buffers
-        self._qgraph = None                   # predict_images(mask_type=...) / mask_stats: the same with the ragged post-processing
-        self._qkey = None
-        self._qws = self._sbuf = None         # ... its static (N, 8) stats, and the capacities of the post-processing in it
-        self._cap_pixels = self._cap_rows = 0
-        self._tigraph = self._tqgraph = None  # the same two with text_enhance: graphs of their own, so the default ones stay as captured
-        self._tikey = self._tqkey = None
-        self._tiws = self._tqws = self._tsbuf = None
-        self._ebuf = None                     # ... the enhanced images: a second staging buffer of _ibuf's size
-        self._tcap_pixels = self._tcap_total = 0      # ... and the capacities of the enhancement in them
-        self._cgraph = None                   # watermark_counts: ONE graph per (N, IMG_SIZE, threshold, post_process, with masks)
-        self._ckey = None
-        self._cbuf = self._cws = None         # its static counts buffer and workspaces
-        self._xgraphs = {}                    # predict_images_tiled: ONE graph per (images, chunk count, ...), beside the ones above
-        self._agraphs = {}                    # predict_images(tta=...): ONE graph per (key of the plain call, view mask, forward batch), beside them
-        self._merged = None                   # ... and the merged logit planes (n, IMG_SIZE, IMG_SIZE) of the last such call
-        self._xtiles = self._xplans = self._xlbuf = None      # its static tile table, per-image plans and ragged logit plane
+        # slot -> entry(key, graph, static, out, keep, group) of every captured graph (_captured).  One entry per kind for 'logits',
+        # 'mask', 'mask_u8', 'images', 'images_post' (with a mask_type), 'text_images', 'text_images_post' (the same two with
+        # text_enhance: graphs of their own, so the default ones stay as captured) and 'counts', where a new key replaces the graph;
+        # one entry per key under ('tiled', key) and ('tta', key)
+        self._graphs = {}
+        self._ibuf = self._idesc = self._mdesc = self._mbuf = None      # predict_images' static staging buffers
+        self._ebuf = None                     # text_enhance: the enhanced images, a second staging buffer of _ibuf's size
+        self._caps = {}                       # the capacities captured ragged calls were given, grown geometrically (_capacity)
+        self._merged = None                   # tta: the merged logit planes (n, IMG_SIZE, IMG_SIZE) of the last such call
+        self._xtiles = self._xplans = self._xlbuf = None      # predict_images_tiled's static tile table, per-image plans and ragged logit plane
         self._gtbuf = None                    # score_images: the staged ground-truth masks, under _mbuf's descriptors
         self._hbuf = self._hevt = None        # pinned host staging of the packed bytes + the event of its last upload
         self.freeze = bool(freeze)
@@ -90,19 +78,11 @@ class WatermarkPredictor:
         batch shape is captured once into a hipGraph and replayed (static input/output buffers)."""
         if not use_graph:
             return self.model(x)
-        key = tuple(x.shape)
-        if self._gkey != key:
-            self._refreeze_for(x.shape[0], x.shape[2], x.shape[3])
-            self._gin = x.clone()
-            self.model(self._gin)                     # eager warm-up: plans the workspace, sets kernel attributes
-            torch.cuda.synchronize(self.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._gout = self.model(self._gin)
-            self._graph, self._gkey, self._gws = g, key, self.model._ws      # (the graph's workspace stays alive with it)
-        self._gin.copy_(x)
-        self._graph.replay()
-        return self._gout
+        e = self._captured("logits", tuple(x.shape), (x.shape[0], x.shape[2], x.shape[3]), lambda st: self.model(st["x"]),
+                           lambda: {"x": x.clone()}, "input")
+        e.static["x"].copy_(x)
+        e.graph.replay()
+        return e.out
 
     @torch.no_grad()
     def predict_mask(self, x: torch.Tensor, apply_sigmoid: bool = False, use_graph: bool = True, mask_type: Optional[str] = None) -> torch.Tensor:
@@ -114,30 +94,50 @@ class WatermarkPredictor:
         run = lambda t: optimize_mask(threshold_mask(self.model(t), self.threshold, apply_sigmoid), mask_type)
         if not use_graph:
             return run(x)
-        key = (tuple(x.shape), bool(apply_sigmoid), mask_type)
-        if self._pkey != key:
-            self._refreeze_for(x.shape[0], x.shape[2], x.shape[3])
-            self._pin = x.clone()
-            run(self._pin)                            # eager warm-up (also allocates the post-processing workspace)
-            torch.cuda.synchronize(self.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._pout = run(self._pin)
-            self._pgraph, self._pkey = g, key
-            self._pws = (self.model._ws, mask_workspace(x.device, *self._pout.shape))      # (the graph's workspaces stay alive with it)
-        self._pin.copy_(x)
-        self._pgraph.replay()
-        return self._pout
+        e = self._captured("mask", (tuple(x.shape), bool(apply_sigmoid), mask_type), (x.shape[0], x.shape[2], x.shape[3]),
+                           lambda st: run(st["x"]), lambda: {"x": x.clone()}, "input")
+        e.static["x"].copy_(x)
+        e.graph.replay()
+        return e.out
+
+    def _captured(self, slot, key, shape, run, statics=dict, group="images"):
+        """the entry of `slot`, captured now when the slot is empty or holds another key: the arena re-made for the forward batch
+        `shape` = (n, h, w) where it must be, the static tensors allocated (`statics`() -> dict), one eager run(static) as warm-up (it
+        plans the workspaces and sets kernel attributes), then the capture of run(static), whose result is the entry's `out`.  `keep`
+        pins what the graph replays on beside the statics: the model's workspaces and every workspace the store handed out during
+        warm-up and capture.  The caller copies its inputs into entry.static and replays entry.graph."""
+        e = self._graphs.get(slot)
+        if e is None or e.key != key:
+            self._refreeze_for(*shape)
+            static = statics()
+            with recording() as used:
+                run(static)
+                torch.cuda.synchronize(self.device)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    out = run(static)
+            keep = (self.model._ws, getattr(self.model, "_filter_ws", None), *used)
+            e = self._graphs[slot] = SimpleNamespace(key=key, graph=g, static=static, out=out, keep=keep, group=group)
+        return e
+
+    def _drop(self, *groups):
+        """the captured graphs of `groups` (GRAPH_GROUPS) go: what they replay on was replaced"""
+        self._graphs = {slot: e for slot, e in self._graphs.items() if e.group not in groups}
+
+    def _capacity(self, name: str, need: int, limit: int) -> int:
+        """the capacity `name` of the captured ragged calls covers `need`: kept, and grown geometrically up to `limit` when it does not;
+        the capacities are in the graphs' keys, so a batch that fits them replays and one that exceeds one re-captures"""
+        have = self._caps.get(name, 0)
+        if have < need:
+            have = self._caps[name] = min(max(need, 2 * have), limit)
+        return have
 
     def _refreeze_for(self, n: int, h: int, w: int):
         """freeze=True: a new graph shape whose bank forms differ from the frozen ones gets the arena re-made for it; the graphs
         captured on the old arena contents go."""
         if self.freeze and not self.model.frozen_serves(n, h, w):
             self.model.freeze(batch_shape=(n, h, w))
-            self._graph = self._gkey = self._ugraph = self._ukey = self._pgraph = self._pkey = self._igraph = self._ikey = self._qgraph = self._qkey = self._cgraph = self._ckey = None
-            self._tigraph = self._tikey = self._tqgraph = self._tqkey = None
-            self._xgraphs = {}
-            self._agraphs = {}
+            self._drop(*GRAPH_GROUPS)
 
     @torch.no_grad()
     def predict_mask_u8(self, images_u8_nhwc: torch.Tensor, out_size=None, apply_sigmoid: bool = False,
@@ -164,20 +164,10 @@ class WatermarkPredictor:
         if not use_graph:
             return pick(run(x))
         key = (tuple(x.shape), None if out_size is None else tuple(out_size), bool(apply_sigmoid)) + (() if mask_type is None else (mask_type,))
-        if self._ukey != key:
-            self._refreeze_for(x.shape[0], x.shape[1], x.shape[2])
-            self._uin = x.clone()
-            run(self._uin)                            # eager warm-up
-            torch.cuda.synchronize(self.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._uout = run(self._uin)
-            self._ugraph, self._ukey, self._uws = g, key, self.model._ws
-            if mask_type is not None:
-                self._uws = (self._uws, mask_workspace(x.device, *self._uout[0].shape))
-        self._uin.copy_(x)
-        self._ugraph.replay()
-        return pick(self._uout)
+        e = self._captured("mask_u8", key, x.shape[:3], lambda st: run(st["x"]), lambda: {"x": x.clone()}, "input")
+        e.static["x"].copy_(x)
+        e.graph.replay()
+        return pick(e.out)
 
     def _staging(self, name: str, need: int):
         """the static device buffer `name` holds at least `need` bytes; grown geometrically.  A graph captured on the old buffer
@@ -187,10 +177,7 @@ class WatermarkPredictor:
             return
         cap = max(need, 256 if buf is None else 2 * buf.numel())
         setattr(self, name, torch.zeros(cap, dtype=torch.uint8, device=self.device))
-        self._igraph = self._ikey = self._qgraph = self._qkey = self._cgraph = self._ckey = None
-        self._tigraph = self._tikey = self._tqgraph = self._tqkey = None
-        self._xgraphs = {}
-        self._agraphs = {}
+        self._drop("images", "text", "tta", "tiled")
 
     def _stage_images(self, images):
         """pack `images` into the static staging buffers (_ibuf, _idesc, _mdesc; _mbuf sized for their masks) -> (n, IMG_SIZE, descs,
@@ -228,8 +215,8 @@ class WatermarkPredictor:
         forward then reads — the same graph, kept in slots of its own, with the enhancement's two capacities (the largest h*w, the
         sum of h*w) in its key.
         views != 1 (a tta.view_mask): uwm_predict_images_tta_u8 in place of uwm_predict_images_u8, PREDICT.BATCH_SIZE slots per forward;
-        its graphs live in a table of their own (_agraphs) under the plain call's key + (mask, batch), with the static stats and the
-        merged logit planes (n, IMG_SIZE, IMG_SIZE) of the graph beside it; `_merged` is the latter after the call."""
+        its graphs have a slot each, ('tta', the plain call's key + (mask, batch)), with the static stats and the merged logit planes
+        (n, IMG_SIZE, IMG_SIZE) of the graph in the entry; `_merged` is the latter after the call."""
         n, s, descs, mdescs, areas, mask_bytes = self._stage_images(images)
         batch = int(self.cfg.PREDICT.BATCH_SIZE)
         tcaps = ()
@@ -238,22 +225,13 @@ class WatermarkPredictor:
                 raise RuntimeError(f"text_enhance takes RGB images; the model takes {self.model.in_channels} channels")
             if int(areas.max()) > 2 ** 30:
                 raise ValueError("text_enhance: an image of more than 2^30 pixels")
-            for name, need in (("_tcap_pixels", int(areas.max())), ("_tcap_total", int(areas.sum()))):
-                if getattr(self, name) < need:
-                    setattr(self, name, min(max(need, 2 * getattr(self, name)), 2 ** 30 if name == "_tcap_pixels" else 2 ** 40))
+            tcaps = ("text_enhance", self._capacity("text_pixels", int(areas.max()), 2 ** 30), self._capacity("text_total", int(areas.sum()), 2 ** 40))
             if self._ebuf is None or self._ebuf.numel() != self._ibuf.numel():
                 self._ebuf = torch.zeros_like(self._ibuf)
-                self._tigraph = self._tikey = self._tqgraph = self._tqkey = None
-                self._agraphs = {}
-            tcaps = ("text_enhance", self._tcap_pixels, self._tcap_total)
-        if mask_type is not None:
-            for name, need in (("_cap_pixels", int(areas.max())), ("_cap_rows", int(descs["h"].astype("int64").sum()))):
-                if getattr(self, name) < need:
-                    setattr(self, name, min(max(need, 2 * getattr(self, name)), 2 ** 31 - 2 if name == "_cap_pixels" else 2 ** 40))
-        caps = () if mask_type is None else (mask_type, self._cap_pixels, self._cap_rows)
-        stats = None
+                self._drop("text", "tta")
+        caps = () if mask_type is None else (mask_type,) + self._mask_capacities(descs, areas)
 
-        def run():
+        def run(static):
             if text_enhance:
                 text_enhance_ragged(self._ibuf, self._idesc, out=self._ebuf, n=n, max_pixels=tcaps[1], total_pixels=tcaps[2])
             if views != 1:
@@ -264,61 +242,34 @@ class WatermarkPredictor:
                                              IMAGENET_MEAN, IMAGENET_STD, self.threshold, apply_sigmoid)
             if mask_type is not None:
                 optimize_masks_ragged(self._mbuf, self._mdesc, mask_type, True, out=self._mbuf, n=n, max_pixels=caps[1], rows=caps[2],
-                                      stats=stats)
-        if not use_graph:
-            if mask_type is not None:
-                stats = torch.empty((n, 8), dtype=torch.int64, device=self.device)
-            run()
-            if views != 1:
-                self._merged = self.model._merged_store
-        elif views != 1:
-            key = (n, s, s, bool(apply_sigmoid), float(self.threshold)) + caps + tcaps + ("tta", views, batch)
-            if key not in self._agraphs:
-                self._refreeze_for(batch, s, s)
-                if mask_type is not None:
-                    stats = torch.empty((n, 8), dtype=torch.int64, device=self.device)
-                run()                                 # eager warm-up: plans the workspace, sets kernel attributes
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    run()
-                ws = self.model._ws                   # (the graph's workspaces stay alive with it)
-                if mask_type is not None:
-                    ws = (ws, ragged_workspace(self.device, n, self._mbuf.numel(), caps[2]))
-                if text_enhance:
-                    ws = (ws, text_enhance_workspace(self.device, tcaps[2], n))
-                self._agraphs[key] = (g, ws, stats, self.model._merged_store)
-            g, _, stats, self._merged = self._agraphs[key]
-            g.replay()
-        else:
-            key = (n, s, s, bool(apply_sigmoid), float(self.threshold)) + caps + tcaps      # (the threshold and the capacities are captured arguments)
-            slot = "_i" if mask_type is None else "_q"      # the graph without post-processing stays when the other is captured
-            sbuf = "_sbuf"
-            if text_enhance:
-                slot, sbuf = "_t" + slot[1:], "_tsbuf"
-            if getattr(self, slot + "key") != key or getattr(self, slot + "graph") is None:
-                self._refreeze_for(n, s, s)
-                if mask_type is not None:
-                    stats = torch.empty((n, 8), dtype=torch.int64, device=self.device)
-                    setattr(self, sbuf, stats)
-                run()                                 # eager warm-up: plans the workspace, sets kernel attributes
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    run()
-                ws = self.model._ws                   # (the graph's workspaces stay alive with it)
-                if mask_type is not None:
-                    ws = (ws, ragged_workspace(self.device, n, self._mbuf.numel(), caps[2]))
-                if text_enhance:
-                    ws = (ws, text_enhance_workspace(self.device, tcaps[2], n))
-                setattr(self, slot + "graph", g); setattr(self, slot + "key", key); setattr(self, slot + "ws", ws)
-            stats = getattr(self, sbuf) if mask_type is not None else None
-            getattr(self, slot + "graph").replay()
-        return descs, mdescs, areas, mask_bytes, stats
+                                      stats=static["stats"])
+            return self.model._merged_store if views != 1 else None
 
-    def _mask_views(self, descs, mdescs, areas, mask_bytes):
-        out = self._mbuf[:mask_bytes].clone()         # (the staging buffer is overwritten by the next call)
-        return [out[int(o): int(o) + int(a)].view(int(h), int(w)) for o, a, h, w in zip(mdescs["offset"], areas, descs["h"], descs["w"])]
+        def statics():
+            return {"stats": torch.empty((n, 8), dtype=torch.int64, device=self.device)} if mask_type is not None else {}
+        key = (n, s, s, bool(apply_sigmoid), float(self.threshold)) + caps + tcaps      # (the threshold and the capacities are captured arguments)
+        if not use_graph:
+            static = statics()
+            merged = run(static)
+        else:
+            if views != 1:
+                key += ("tta", views, batch)
+                e = self._captured(("tta", key), key, (batch, s, s), run, statics, "tta")
+            else:                                     # (the graph without post-processing stays when the other is captured)
+                slot = ("text_images" if text_enhance else "images") + ("" if mask_type is None else "_post")
+                e = self._captured(slot, key, (n, s, s), run, statics, "text" if text_enhance else "images")
+            e.graph.replay()
+            static, merged = e.static, e.out
+        if views != 1:
+            self._merged = merged
+        return descs, mdescs, areas, mask_bytes, static.get("stats")
+
+    def _mask_capacities(self, descs, areas):
+        """-> the capacities (max_pixels, rows) a captured uwm_optimize_masks_ragged gets for this batch: the largest h*w, the sum of h"""
+        return (self._capacity("pixels", int(areas.max()), 2 ** 31 - 2), self._capacity("rows", int(descs["h"].astype("int64").sum()), 2 ** 40))
+
+    def _mask_views(self, mdescs, mask_bytes):
+        return ragged_views(self._mbuf[:mask_bytes].clone(), mdescs)      # (the staging buffer is overwritten by the next call)
 
     @torch.no_grad()
     def predict_images(self, images, apply_sigmoid: bool = False, mask_type: Optional[str] = None, use_graph: bool = True,
@@ -348,7 +299,7 @@ class WatermarkPredictor:
         if return_logits and views == 1:
             raise ValueError("return_logits needs tta ('hflip', 'flips', 'd4' or a view mask other than 1)")
         descs, mdescs, areas, mask_bytes, stats = self._run_images(images, apply_sigmoid, mask_type, use_graph, text_enhance, views)
-        masks = self._mask_views(descs, mdescs, areas, mask_bytes)
+        masks = self._mask_views(mdescs, mask_bytes)
         out = (masks, stats.cpu().numpy()) if return_stats else masks
         if return_logits:
             out = (out if return_stats else (out,)) + (self._merged.clone(),)
@@ -361,7 +312,7 @@ class WatermarkPredictor:
         if buf is not None and buf.numel() >= need:
             return
         setattr(self, name, torch.zeros(max(need, 256 if buf is None else 2 * buf.numel()), dtype=dtype, device=self.device))
-        self._xgraphs = {}
+        self._drop("tiled")
 
     @torch.no_grad()
     def predict_images_tiled(self, images, overlap: int = 64, apply_sigmoid: bool = False, mask_type: Optional[str] = None,
@@ -381,11 +332,10 @@ class WatermarkPredictor:
         then work on those."""
         descs, mdescs, areas, mask_bytes = self._run_tiled(images, overlap, apply_sigmoid, mask_type, return_logits, use_graph, tile_batch,
                                                            view_mask(tta))
-        masks = self._mask_views(descs, mdescs, areas, mask_bytes)
+        masks = self._mask_views(mdescs, mask_bytes)
         if not return_logits:
             return masks
-        lg = self._xlbuf[:mask_bytes].clone()
-        return masks, [lg[int(o): int(o) + int(a)].view(int(h), int(w)) for o, a, h, w in zip(mdescs["offset"], areas, descs["h"], descs["w"])]
+        return masks, ragged_views(self._xlbuf[:mask_bytes].clone(), mdescs)
 
     def _run_tiled(self, images, overlap: int, apply_sigmoid: bool, mask_type: Optional[str], return_logits: bool, use_graph: bool,
                    tile_batch: Optional[int], views: int = 1):
@@ -408,14 +358,10 @@ class WatermarkPredictor:
             self._tiled_static("_xlbuf", self._mbuf.numel(), torch.float32)
         self._xtiles[:16 * k].copy_(table_tensor(tiles))
         self._xplans[:16 * n].copy_(table_tensor(plans))
-        if mask_type is not None:
-            for name, need in (("_cap_pixels", int(areas.max())), ("_cap_rows", int(descs["h"].astype("int64").sum()))):
-                if getattr(self, name) < need:
-                    setattr(self, name, min(max(need, 2 * getattr(self, name)), 2 ** 31 - 2 if name == "_cap_pixels" else 2 ** 40))
-        caps = () if mask_type is None else (mask_type, self._cap_pixels, self._cap_rows)
+        caps = () if mask_type is None else (mask_type,) + self._mask_capacities(descs, areas)
         lbuf = self._xlbuf if return_logits else None
 
-        def run():
+        def run(static=None):
             if views != 1:
                 self.model.predict_tiled_tta_u8(self._ibuf, self._idesc, self._mdesc, self._mbuf, n, self._xtiles, self._xplans, k, batch,
                                                 (T, T), overlap, views, IMAGENET_MEAN, IMAGENET_STD, self.threshold, apply_sigmoid, lbuf)
@@ -430,19 +376,8 @@ class WatermarkPredictor:
             # (the counts, the threshold, the capacities and the logit plane's pointer are captured arguments)
             key = (n, k // batch, batch, T, overlap, bool(apply_sigmoid), float(self.threshold), bool(return_logits)) + caps
             if views != 1:
-                key += ("tta", views)                 # (a graph of its own per view mask; the keys without one are as they were)
-            if key not in self._xgraphs:
-                self._refreeze_for(batch, T, T)
-                run()                                 # eager warm-up: plans the workspace, sets kernel attributes
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    run()
-                ws = self.model._ws                   # (the graph's workspaces stay alive with it)
-                if mask_type is not None:
-                    ws = (ws, ragged_workspace(self.device, n, self._mbuf.numel(), caps[2]))
-                self._xgraphs[key] = (g, ws)
-            self._xgraphs[key][0].replay()
+                key += ("tta", views)                 # (a graph of its own per view mask)
+            self._captured(("tiled", key), key, (batch, T, T), run, group="tiled").graph.replay()
         return descs, mdescs, areas, mask_bytes
 
     @torch.no_grad()
@@ -501,8 +436,8 @@ class WatermarkPredictor:
         out = counts.cpu().numpy()
         if surface:
             out = (out, (records.cpu().numpy(), sums.cpu().numpy()))
-            return out + (self._mask_views(descs, mdescs, areas, mask_bytes),) if return_masks else out
-        return (out, self._mask_views(descs, mdescs, areas, mask_bytes)) if return_masks else out
+            return out + (self._mask_views(mdescs, mask_bytes),) if return_masks else out
+        return (out, self._mask_views(mdescs, mask_bytes)) if return_masks else out
 
     @torch.no_grad()
     def remove_watermarks(self, images, mask_type: Optional[str] = "watermark", text_enhance: bool = False, tile: bool = False,
@@ -540,10 +475,9 @@ class WatermarkPredictor:
         nbytes = int(descs["offset"][-1]) + channels * int(areas[-1])
         out = inpaint_buffers(self._ibuf, self._idesc, self._mbuf, self._mdesc, n, channels, max_pixels=int(areas.max()), rows=int(hs.sum()),
                               max_side=side, cycles=cycles, stats=stats)[:nbytes]
-        res = [out[int(o): int(o) + channels * int(a)].view(int(h), int(w), channels) for o, a, h, w in zip(descs["offset"], areas, hs, ws)]
-        ret = (res,)
+        ret = (ragged_views(out, descs, channels),)
         if return_masks:
-            ret += (self._mask_views(descs, mdescs, areas, mask_bytes),)
+            ret += (self._mask_views(mdescs, mask_bytes),)
         if return_stats:
             ret += (stats.cpu().numpy(),)
         return ret[0] if len(ret) == 1 else ret
@@ -561,7 +495,7 @@ class WatermarkPredictor:
             raise ValueError(f"mask_type must be one of 'watermark', 'text', 'mixed', 'none', got {mask_type!r}")
         descs, mdescs, areas, mask_bytes, stats = self._run_images(images, False, mask_type, use_graph, text_enhance)
         host = stats.cpu().numpy()
-        return (host, self._mask_views(descs, mdescs, areas, mask_bytes)) if return_masks else host
+        return (host, self._mask_views(mdescs, mask_bytes)) if return_masks else host
 
     @torch.no_grad()
     def watermark_counts(self, images, post_process: Optional[bool] = None, return_masks: bool = False, use_graph: bool = True):
@@ -574,29 +508,19 @@ class WatermarkPredictor:
         return_masks, which adds the list of uint8 {0,255} device masks."""
         post = bool(self.cfg.PREDICT.POST_PROCESS if post_process is None else post_process)
         n, s, descs, mdescs, areas, mask_bytes = self._stage_images(images)
-        counts = None
 
-        def run():
-            return self.model.filter_images_u8(self._ibuf, self._idesc, self._mdesc, counts, n, (s, s), IMAGENET_MEAN, IMAGENET_STD,
+        def run(static):
+            return self.model.filter_images_u8(self._ibuf, self._idesc, self._mdesc, static["counts"], n, (s, s), IMAGENET_MEAN, IMAGENET_STD,
                                                self.threshold, post, self._mbuf if return_masks else None)
+
+        def statics():
+            return {"counts": torch.zeros((n, 2), dtype=torch.int64, device=self.device)}
         if not use_graph:
-            counts = torch.zeros((n, 2), dtype=torch.int64, device=self.device)
-            run()
+            counts = run(statics())
         else:
             key = (n, s, s, float(self.threshold), post, bool(return_masks))      # (threshold, post_process and the mask pointer are captured arguments)
-            if self._ckey != key or self._cgraph is None:
-                self._refreeze_for(n, s, s)
-                counts = self._cbuf = torch.zeros((n, 2), dtype=torch.int64, device=self.device)
-                run()                                 # eager warm-up: plans the workspace, sets kernel attributes
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    run()
-                self._cgraph, self._ckey, self._cws = g, key, (self.model._ws, self.model._filter_ws)
-            counts = self._cbuf
-            self._cgraph.replay()
+            e = self._captured("counts", key, (n, s, s), run, statics)
+            e.graph.replay()
+            counts = e.static["counts"]
         host = counts.cpu().numpy()
-        if not return_masks:
-            return host
-        out = self._mbuf[:mask_bytes].clone()         # (the staging buffer is overwritten by the next call)
-        return host, [out[int(o): int(o) + int(a)].view(int(h), int(w)) for o, a, h, w in zip(mdescs["offset"], areas, descs["h"], descs["w"])]
+        return (host, self._mask_views(mdescs, mask_bytes)) if return_masks else host

@@ -11,13 +11,13 @@ import math
 from typing import Optional
 
 import numpy as np
+import torch
 
-from . import _lib as L
+from . import _device as D, _lib as L
 
 COUNT_FIELDS = ("tp", "fp", "fn", "tn", "boundary_intersection", "boundary_pred", "boundary_truth", "status")
 METRIC_FIELDS = ("iou", "f1", "accuracy", "recall", "precision", "boundary_iou")
 MAX_RADIUS = 32767
-_sws = {}                                                 # device -> workspace tensor of the score call (grown on demand)
 
 
 def boundary_radius(h: int, w: int, ratio: float = 0.02) -> int:
@@ -29,15 +29,7 @@ def boundary_radius(h: int, w: int, ratio: float = 0.02) -> int:
 def score_workspace(device, n: int, mask_bytes: int, rows: int):
     """The score call's scratch for the capacities (n, mask_bytes, rows): one buffer per device, kept and grown like
     postprocess.ragged_workspace; a captured graph holds the buffer it was captured with."""
-    import torch
-    need = L.lib().uwm_score_masks_workspace_bytes(int(n), int(mask_bytes), int(rows))
-    if need == 0:
-        raise RuntimeError(L.lib().uwm_last_error().decode(errors="replace"))
-    key = str(device)
-    ws = _sws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _sws[key] = torch.empty(need, dtype=torch.uint8, device=device)
-    return ws
+    return D.workspace("score", device, L.lib().uwm_score_masks_workspace_bytes(int(n), int(mask_bytes), int(rows)))
 
 
 def score_masks_ragged(pred, truth, descs, radii, *, n: Optional[int] = None, max_pixels: Optional[int] = None,
@@ -49,29 +41,8 @@ def score_masks_ragged(pred, truth, descs, radii, *, n: Optional[int] = None, ma
     radii: the Boundary-IoU distance of every pair (0 .. 32767; 0: no boundary counts), a host sequence or an int32 device tensor.
     -> the int64 (n, 8) device tensor COUNT_FIELDS (`out`: a tensor to write them into).  max_pixels / rows: capacities, at least
     the largest h*w and the sum of h; a pair beyond a capacity is a misfit (status 1, zeros)."""
-    import torch
-    if not isinstance(pred, torch.Tensor) or not isinstance(truth, torch.Tensor) or pred.device.type != "cuda" or truth.device != pred.device:
-        raise RuntimeError("uwm score_masks_ragged runs only on a HIP device (no CPU fallback)")
-    for t in (pred, truth):
-        if t.dtype != torch.uint8 or t.dim() != 1 or t.numel() == 0 or not t.is_contiguous():
-            raise RuntimeError(f"expected a non-empty contiguous 1-d uint8 buffer, got {t.dtype} {tuple(t.shape)}")
+    d, n, caps = D.ragged_args("score_masks_ragged", (pred, truth), descs, n, max_pixels=max_pixels, rows=rows)
     mask_bytes = min(pred.numel(), truth.numel())
-    if isinstance(descs, torch.Tensor):
-        if n is None or max_pixels is None or rows is None:
-            raise ValueError("score_masks_ragged: device descriptors need n, max_pixels and rows")
-        if descs.device != pred.device or descs.dtype != torch.uint8 or descs.numel() < 16 * int(n):
-            raise RuntimeError("score_masks_ragged: descs must be a uint8 tensor of 16 n bytes on the buffers' device")
-        d = descs
-    else:
-        from .data import descs_tensor
-        n = len(descs) if n is None else int(n)
-        if n < 1:
-            raise ValueError("score_masks_ragged: empty batch")
-        if max_pixels is None:
-            max_pixels = max(1, int((descs["h"].astype("int64") * descs["w"]).max()))
-        if rows is None:
-            rows = max(1, int(descs["h"].astype("int64").clip(min=0).sum()))
-        d = descs_tensor(descs).to(pred.device)
     if isinstance(radii, torch.Tensor):
         if radii.device != pred.device or radii.dtype != torch.int32 or radii.numel() < int(n) or not radii.is_contiguous():
             raise RuntimeError("score_masks_ragged: radii must be a contiguous int32 tensor of n entries on the buffers' device")
@@ -81,15 +52,11 @@ def score_masks_ragged(pred, truth, descs, radii, *, n: Optional[int] = None, ma
         if host.size != int(n):
             raise ValueError(f"score_masks_ragged: {host.size} radii for {n} pairs")
         r = torch.from_numpy(host.clip(-1, 2 ** 31 - 1).astype(np.int32)).to(pred.device)
-    if out is None:
-        out = torch.empty((int(n), 8), dtype=torch.int64, device=pred.device)
-    elif out.dtype != torch.int64 or out.device != pred.device or out.numel() < 8 * int(n) or not out.is_contiguous():
-        raise RuntimeError("score_masks_ragged: out must be a contiguous int64 tensor of 8 n entries on the buffers' device")
+    out = D.stats_like("score_masks_ragged", out, n, 8, pred.device, what="out")
     with L.on_device(pred):
-        ws = score_workspace(pred.device, n, mask_bytes, rows)
-        L.check(L.lib().uwm_score_masks_ragged(C.c_void_p(pred.data_ptr()), C.c_void_p(truth.data_ptr()), mask_bytes, C.c_void_p(d.data_ptr()),
-                                               C.c_void_p(r.data_ptr()), int(n), int(max_pixels), int(rows), C.c_void_p(out.data_ptr()),
-                                               C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(L.stream_ptr(pred.device))))
+        ws = score_workspace(pred.device, n, mask_bytes, caps["rows"])
+        L.check(L.lib().uwm_score_masks_ragged(D.ptr(pred), D.ptr(truth), mask_bytes, D.ptr(d), D.ptr(r), n, caps["max_pixels"], caps["rows"],
+                                               D.ptr(out), D.ptr(ws), ws.numel(), C.c_void_p(L.stream_ptr(pred.device))))
     return out
 
 
@@ -126,50 +93,11 @@ SURFACE_FIELDS = ("border_pred", "border_truth", "hd_d2_pred", "hd_d2_truth", "p
                   "status")
 EDT_NONE = 2 ** 31 - 1                                    # UWM_EDT_NONE: D2 of an image without a set pixel
 MAX_SIDE = 32768
-_dws = {}                                                 # (device, call) -> workspace tensor of the two distance calls
 
 
 def _dist_workspace(device, call: str, n: int, mask_bytes: int, rows: int):
-    """the scratch of uwm_edt_ragged ('edt') or uwm_surface_distances_ragged ('surface'), kept and grown like score_workspace"""
-    import torch
-    need = getattr(L.lib(), f"uwm_{call}_workspace_bytes")(int(n), int(mask_bytes), int(rows))
-    if need == 0:
-        raise RuntimeError(L.lib().uwm_last_error().decode(errors="replace"))
-    key = (str(device), call)
-    ws = _dws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _dws[key] = torch.empty(need, dtype=torch.uint8, device=device)
-    return ws
-
-
-def _dist_args(name, buffers, descs, n, max_pixels, rows):
-    """the checks and descriptor handling the two distance wrappers share with score_masks_ragged -> (mask_bytes, descs tensor, n,
-    max_pixels, rows)"""
-    import torch
-    first = buffers[0]
-    if any(not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.device != first.device for t in buffers):
-        raise RuntimeError(f"uwm {name} runs only on a HIP device (no CPU fallback)")
-    for t in buffers:
-        if t.dtype != torch.uint8 or t.dim() != 1 or t.numel() == 0 or not t.is_contiguous():
-            raise RuntimeError(f"expected a non-empty contiguous 1-d uint8 buffer, got {t.dtype} {tuple(t.shape)}")
-    mask_bytes = min(t.numel() for t in buffers)
-    if isinstance(descs, torch.Tensor):
-        if n is None or max_pixels is None or rows is None:
-            raise ValueError(f"{name}: device descriptors need n, max_pixels and rows")
-        if descs.device != first.device or descs.dtype != torch.uint8 or descs.numel() < 16 * int(n):
-            raise RuntimeError(f"{name}: descs must be a uint8 tensor of 16 n bytes on the buffers' device")
-        d = descs
-    else:
-        from .data import descs_tensor
-        n = len(descs) if n is None else int(n)
-        if n < 1:
-            raise ValueError(f"{name}: empty batch")
-        if max_pixels is None:
-            max_pixels = max(1, int((descs["h"].astype("int64") * descs["w"]).max()))
-        if rows is None:
-            rows = max(1, int(descs["h"].astype("int64").clip(min=0).sum()))
-        d = descs_tensor(descs).to(first.device)
-    return mask_bytes, d, int(n), int(max_pixels), int(rows)
+    """the scratch of uwm_edt_ragged ('edt') or uwm_surface_distances_ragged ('surface_distances'), kept and grown like score_workspace"""
+    return D.workspace(call, device, getattr(L.lib(), f"uwm_{call}_workspace_bytes")(int(n), int(mask_bytes), int(rows)))
 
 
 def distance_transform_ragged(masks, descs, *, n: Optional[int] = None, max_pixels: Optional[int] = None, rows: Optional[int] = None,
@@ -180,16 +108,16 @@ def distance_transform_ragged(masks, descs, *, n: Optional[int] = None, max_pixe
     masks.numel() entries: D2 of image i's pixel k at [descs[i].offset + k], 0 on set pixels, EDT_NONE throughout an image without
     one; entries no image covers, and those of a misfit (a side above 32768, a pair beyond a capacity), are not written (`out`: a
     tensor to write into; a fresh one is zero-filled)."""
-    import torch
-    mask_bytes, d, n, max_pixels, rows = _dist_args("distance_transform_ragged", (masks,), descs, n, max_pixels, rows)
+    d, n, caps = D.ragged_args("distance_transform_ragged", (masks,), descs, n, max_pixels=max_pixels, rows=rows)
+    mask_bytes = masks.numel()
     if out is None:
         out = torch.zeros(mask_bytes, dtype=torch.int32, device=masks.device)
     elif out.dtype != torch.int32 or out.device != masks.device or out.numel() < mask_bytes or not out.is_contiguous():
         raise RuntimeError("distance_transform_ragged: out must be a contiguous int32 tensor of masks.numel() entries on the masks' device")
     with L.on_device(masks):
-        ws = _dist_workspace(masks.device, "edt", n, mask_bytes, rows)
-        L.check(L.lib().uwm_edt_ragged(C.c_void_p(masks.data_ptr()), mask_bytes, C.c_void_p(d.data_ptr()), n, max_pixels, rows,
-                                       C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(L.stream_ptr(masks.device))))
+        ws = _dist_workspace(masks.device, "edt", n, mask_bytes, caps["rows"])
+        L.check(L.lib().uwm_edt_ragged(D.ptr(masks), mask_bytes, D.ptr(d), n, caps["max_pixels"], caps["rows"], D.ptr(out), D.ptr(ws), ws.numel(),
+                                       C.c_void_p(L.stream_ptr(masks.device))))
     return out
 
 
@@ -199,19 +127,15 @@ def surface_distances_ragged(pred, truth, descs, *, n: Optional[int] = None, max
     descriptors of score_masks_ragged (pred may be truth) -> (records, sums): the int64 (n, 10) device tensor SURFACE_FIELDS and the
     float64 (n, 2) device tensor of the sums of sqrt over the two border-distance lists (`out`: a pair of tensors to write them
     into).  surface_from_record / summarize_surface turn them into Hausdorff, HD95, ASSD and the covering radius."""
-    import torch
-    mask_bytes, d, n, max_pixels, rows = _dist_args("surface_distances_ragged", (pred, truth), descs, n, max_pixels, rows)
-    if out is None:
-        out = (torch.empty((n, 10), dtype=torch.int64, device=pred.device), torch.empty((n, 2), dtype=torch.float64, device=pred.device))
-    records, sums = out
-    for t, dt, k in ((records, torch.int64, 10), (sums, torch.float64, 2)):
-        if t.dtype != dt or t.device != pred.device or t.numel() < k * n or not t.is_contiguous():
-            raise RuntimeError("surface_distances_ragged: out must be contiguous int64 (n, 10) and float64 (n, 2) tensors on the buffers' device")
+    d, n, caps = D.ragged_args("surface_distances_ragged", (pred, truth), descs, n, max_pixels=max_pixels, rows=rows)
+    mask_bytes = min(pred.numel(), truth.numel())
+    out = (None, None) if out is None else out
+    records = D.stats_like("surface_distances_ragged", out[0], n, 10, pred.device, what="out[0]")
+    sums = D.stats_like("surface_distances_ragged", out[1], n, 2, pred.device, torch.float64, what="out[1]")
     with L.on_device(pred):
-        ws = _dist_workspace(pred.device, "surface_distances", n, mask_bytes, rows)
-        L.check(L.lib().uwm_surface_distances_ragged(C.c_void_p(pred.data_ptr()), C.c_void_p(truth.data_ptr()), mask_bytes, C.c_void_p(d.data_ptr()),
-                                                     n, max_pixels, rows, C.c_void_p(records.data_ptr()), C.c_void_p(sums.data_ptr()),
-                                                     C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(L.stream_ptr(pred.device))))
+        ws = _dist_workspace(pred.device, "surface_distances", n, mask_bytes, caps["rows"])
+        L.check(L.lib().uwm_surface_distances_ragged(D.ptr(pred), D.ptr(truth), mask_bytes, D.ptr(d), n, caps["max_pixels"], caps["rows"],
+                                                     D.ptr(records), D.ptr(sums), D.ptr(ws), ws.numel(), C.c_void_p(L.stream_ptr(pred.device))))
     return records, sums
 
 

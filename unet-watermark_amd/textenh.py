@@ -11,24 +11,16 @@ from typing import Optional
 
 import torch
 
-from . import _lib as L
+from . import _device as D, _lib as L
 
 STATUS = {"done": 0, "misfit": 1, "copied": 2}            # UWM_TEXT_ENHANCE_*: per image; `copied`: a side below MIN_SIDE, left unchanged
 MIN_SIDE = 16
-_ws = {}                                                  # device -> workspace tensor (grown on demand)
 
 
 def text_enhance_workspace(device, total_pixels: int, n: int) -> torch.Tensor:
     """uwm_text_enhance_ragged's scratch for the capacities (total_pixels, n): one buffer per device, kept and grown on demand; a
     captured graph holds the buffer it was captured with.  Its first n int32 are the per-image status after a call."""
-    need = L.lib().uwm_text_enhance_workspace_bytes(int(total_pixels), int(n))
-    if need == 0:
-        raise RuntimeError(L.lib().uwm_last_error().decode(errors="replace"))
-    key = str(device)
-    ws = _ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _ws[key] = torch.empty(need, dtype=torch.uint8, device=device)
-    return ws
+    return D.workspace("text_enhance", device, L.lib().uwm_text_enhance_workspace_bytes(int(total_pixels), int(n)))
 
 
 def text_enhance_ragged(buf: torch.Tensor, descs, out=None, *, n: Optional[int] = None, max_pixels: Optional[int] = None,
@@ -41,51 +33,19 @@ def text_enhance_ragged(buf: torch.Tensor, descs, out=None, *, n: Optional[int] 
     a flat uint8 device buffer that receives every image's dilated edge plane, one byte per pixel in {0, 255}.  return_status: also
     the int32 (n,) device tensor of STATUS values (a view of the workspace: read it before the next call).  max_pixels /
     total_pixels: capacities, at least the largest h*w and the sum of h*w; an image beyond one is a misfit (status 1)."""
-    if not isinstance(buf, torch.Tensor) or buf.device.type != "cuda":
-        raise RuntimeError("uwm text_enhance_ragged runs only on a HIP device (no CPU fallback)")
-    if buf.dtype != torch.uint8 or buf.dim() != 1 or buf.numel() == 0 or not buf.is_contiguous():
-        raise RuntimeError(f"expected a non-empty contiguous 1-d uint8 buffer, got {buf.dtype} {tuple(buf.shape)}")
     if (edges is None) != (edge_descs is None):
         raise ValueError("text_enhance_ragged: edges and edge_descs go together")
-
-    def device_descs(d, what):
-        if isinstance(d, torch.Tensor):
-            if n is None or max_pixels is None or total_pixels is None:
-                raise ValueError("text_enhance_ragged: device descriptors need n, max_pixels and total_pixels")
-            if d.device != buf.device or d.dtype != torch.uint8 or d.numel() < 16 * int(n):
-                raise RuntimeError(f"text_enhance_ragged: {what} must be a uint8 tensor of 16 n bytes on the buffer's device")
-            return d
-        from .data import descs_tensor
-        return descs_tensor(d).to(buf.device)
-
-    if not isinstance(descs, torch.Tensor):
-        n = len(descs) if n is None else int(n)
-        if n < 1:
-            raise ValueError("text_enhance_ragged: empty batch")
-        areas = descs["h"].astype("int64").clip(min=0) * descs["w"].astype("int64").clip(min=0)
-        if max_pixels is None:
-            max_pixels = max(1, int(areas.max()))
-        if total_pixels is None:
-            total_pixels = max(1, int(areas.sum()))
-    d = device_descs(descs, "descs")
-    ed = None if edge_descs is None else device_descs(edge_descs, "edge_descs")
-    if edges is not None and (not isinstance(edges, torch.Tensor) or edges.device != buf.device or edges.dtype != torch.uint8
-                              or edges.dim() != 1 or edges.numel() == 0 or not edges.is_contiguous()):
-        raise RuntimeError("text_enhance_ragged: edges must be a non-empty contiguous 1-d uint8 tensor on the buffer's device")
-    if out is None:
-        o = torch.zeros_like(buf)
-    else:
-        if out.dtype != torch.uint8 or out.device != buf.device or out.numel() != buf.numel() or not out.is_contiguous():
-            raise RuntimeError("text_enhance_ragged: out must be a contiguous uint8 tensor of the buffer's size on the same device")
-        o = out
+    d, n, caps = D.ragged_args("text_enhance_ragged", (buf,), descs, n, max_pixels=max_pixels, total_pixels=total_pixels)
+    ed = None
+    if edges is not None:
+        ed = D.ragged_args("text_enhance_ragged", (buf, edges), edge_descs, n, **caps)[0]
+    o = D.out_like("text_enhance_ragged", out, buf)
     with L.on_device(buf):
-        ws = text_enhance_workspace(buf.device, total_pixels, n)
-        L.check(L.lib().uwm_text_enhance_ragged(C.c_void_p(buf.data_ptr()), C.c_void_p(o.data_ptr()), buf.numel(), C.c_void_p(d.data_ptr()),
-                                                int(n), 3, int(max_pixels), int(total_pixels),
-                                                C.c_void_p(edges.data_ptr() if edges is not None else 0), edges.numel() if edges is not None else 0,
-                                                C.c_void_p(ed.data_ptr() if ed is not None else 0), C.c_void_p(ws.data_ptr()), ws.numel(),
+        ws = text_enhance_workspace(buf.device, caps["total_pixels"], n)
+        L.check(L.lib().uwm_text_enhance_ragged(D.ptr(buf), D.ptr(o), buf.numel(), D.ptr(d), n, 3, caps["max_pixels"], caps["total_pixels"],
+                                                D.ptr(edges), edges.numel() if edges is not None else 0, D.ptr(ed), D.ptr(ws), ws.numel(),
                                                 C.c_void_p(L.stream_ptr(buf.device))))
-    return (o, ws[:4 * int(n)].view(torch.int32)) if return_status else o
+    return (o, ws[:4 * n].view(torch.int32)) if return_status else o
 
 
 def enhance_text_features(images, device="cuda", return_edges: bool = False, return_status: bool = False):
@@ -104,10 +64,9 @@ def enhance_text_features(images, device="cuda", return_edges: bool = False, ret
     areas = descs["h"].astype("int64") * descs["w"]
     edges = torch.zeros(int(areas.sum()), dtype=torch.uint8, device=dev) if return_edges else None
     out, status = text_enhance_ragged(buf, descs, edges=edges, edge_descs=mdescs if return_edges else None, return_status=True)
-    res = [out[int(o): int(o) + 3 * int(a)].view(int(h), int(w), 3) for o, a, h, w in zip(descs["offset"], areas, descs["h"], descs["w"])]
-    ret = [res]
+    ret = [D.ragged_views(out, descs, 3)]
     if return_edges:
-        ret.append([edges[int(o): int(o) + int(a)].view(int(h), int(w)) for o, a, h, w in zip(mdescs["offset"], areas, descs["h"], descs["w"])])
+        ret.append(D.ragged_views(edges, mdescs))
     if return_status:
         ret.append(status.cpu().numpy().copy())
     return ret[0] if len(ret) == 1 else tuple(ret)
